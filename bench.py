@@ -19,7 +19,9 @@ matching.  When K is not a multiple of B the shorter lanes idle in the last lock
 says how many slots): that time is part of `value`.  `single_lane` is what ONE stream consumed strictly in order gets
 (no batching across windows): rows/s and p50 window latency.
 
-    python bench.py                       # 1 GPU, K = 20, W = 5 (what the driver runs)
+    python bench.py                       # 1 GPU, K = 20, W = 5 (what the driver runs): the headline figure only
+    python bench.py --full                # + live kernel timing, single lane, stage times, rooflines, CPU baseline, golden labels
+    python bench.py --dump-outputs DIR    # + DIR/<name>.npy: what the timed path computed in its last step
     python bench.py --gpus N              # starts N ranks itself (a child `python -m torch.distributed.run`, one rank per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W     # the driver's form: used as launched
@@ -98,7 +100,36 @@ def parse():
                          "from 6 lanes, 2 from 4): their launches interleave on the GPU, so the Gram / rotate GEMMs of one "
                          "group overlap the Jacobi rounds of the others and partly filled workgroup rounds are shared.  More "
                          "than 3 groups + the main stream exceed the hardware queues HIP hands out and serialise.")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: live per-kernel timing of the timed region, the "
+                         "in-order single lane, stand-alone stage times, rooflines, the CPU baseline and the labels against "
+                         "the reference golden (a plain run sets up, warms up, times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path computed in its last step to DIR/<name>.npy "
+                         "(float64, at most 64 MB in all; same arguments -> same inputs)")
     return ap.parse_args()
+
+
+DUMP_BYTES = (64 << 20) - (64 << 10)   # (64 MB less room for the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float64) per array.  The budget of DUMP_BYTES is dealt out smallest array first;
+    an array larger than its share keeps a fixed, seeded sample of its last axis, whose indices go to <name>_index.npy, so
+    that the files of two runs with the same arguments compare entry for entry."""
+    os.makedirs(path, exist_ok=True)
+    items = sorted(((n, np.ascontiguousarray(a, dtype=np.float64)) for n, a in arrays.items()), key=lambda x: x[1].nbytes)
+    left = DUMP_BYTES
+    for i, (name, a) in enumerate(items):
+        share = left // (len(items) - i)
+        if a.nbytes > share and a.size:
+            n = a.shape[-1]
+            idx = np.sort(np.random.default_rng(0).choice(n, size=max(1, (share - 8 * n) // (a.nbytes // n)), replace=False))
+            np.save(os.path.join(path, f"{name}_index.npy"), idx.astype(np.float64))
+            left -= 8 * len(idx)
+            a = np.ascontiguousarray(a[..., idx])
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        left -= a.nbytes
 
 
 def hip_event_ms(fn, stream, reps=1):
@@ -330,11 +361,11 @@ def run_swfdmc(args, cfg):
         return float(tm.item())
 
     for gr in groups:
-        gr.sk.profile(True)
+        gr.sk.profile(args.full)
     t_halo = bracket(lambda: run_steps(0, 1))            # the halo lock-step (also the warm-up: plans, graphs, caches)
     n_warm = [len(gr.pipe.latencies) for gr in groups]
     for gr in groups:
-        gr.sk.profile(True)
+        gr.sk.profile(args.full)
     elapsed = bracket(lambda: run_steps(1, 1 + blk))
     raw = {}
     for gr in groups:
@@ -344,12 +375,21 @@ def run_swfdmc(args, cfg):
     raw_all = mdist.gather_raw_labels(raw_local, [K] * world, device=coll_dev)
     all_labels = mdist.replay_label_chain(raw_all, mo.match_clusters)
     if rank == 0:
-        reads = [gr.sk.profile_read_direct() for gr in groups]
-        direct = all(r[0] for r in reads)
-        t_ms, n_launch, solved = sum(r[1] for r in reads), sum(r[2] for r in reads), sum(r[3] for r in reads)
         lat = np.concatenate([np.array(gr.pipe.latencies[n0:]) for gr, n0 in zip(groups, n_warm)])
-        fl = 4.0 * 256 ** 3 / 3 + 2.0 * 256 * 256 * 128 + 20 * 512 * 255 * 5.0 + 128 * 4.0 * 255 * 6.0
+        if args.dump_outputs:
+            # the last lock-step: every lane whose block is that long sketches, clusters and labels its last window
+            last = [g0 + b1 - 1 for b0, b1 in blocks if b1 - b0 == blk]
+            trace = {tr["trigger"]: tr for gr in groups for tr in gr.pipe.trace}
+            dump_outputs(args.dump_outputs, {
+                "labels": all_labels,
+                "labels_last_step": np.stack([trace[gi]["raw"] for gi in last]),
+                "sketch_sigma_last_step": np.stack([trace[gi]["sigma"] for gi in last]),
+            })
         roof = None
+        reads = [gr.sk.profile_read_direct() for gr in groups] if args.full else []
+        direct = bool(reads) and all(r[0] for r in reads)
+        t_ms, n_launch, solved = sum(r[1] for r in reads), sum(r[2] for r in reads), sum(r[3] for r in reads)
+        fl = 4.0 * 256 ** 3 / 3 + 2.0 * 256 * 256 * 128 + 20 * 512 * 255 * 5.0 + 128 * 4.0 * 255 * 6.0
         if direct and n_launch:
             us = 1e3 * t_ms / n_launch
             tfl = (solved / n_launch) * fl / (us * 1e-6) / 1e12
@@ -577,14 +617,16 @@ def main():
         for th in ths:
             th.join()
 
-    for sk in sketches:
-        sk.profile(True)        # (whole-script launch average, for comparison with rocprofv3 --stats of this command)
+    if args.full:
+        for sk in sketches:
+            sk.profile(True)    # (whole-script launch average, for comparison with rocprofv3 --stats of this command)
     run_range(0, Wu)
-    other_reads = [sk.profile_read() for sk in sketches]   # warm-up windows
+    other_reads = [sk.profile_read() for sk in sketches] if args.full else []   # warm-up windows
     n_warm_lat = len(pipe.latencies)
-    pipe.eng.score_events = []  # HIP events around every similarity-GEMM launch of the timed region
-    for sk in sketches:
-        sk.profile(True)        # HIP events around every Jacobi sweep graph of the timed region
+    if args.full:
+        pipe.eng.score_events = []  # HIP events around every similarity-GEMM launch of the timed region
+        for sk in sketches:
+            sk.profile(True)    # HIP events around every Jacobi sweep graph of the timed region
 
     if world > 1:
         dist.barrier()
@@ -599,6 +641,9 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
+    # what the sketches handed back in the last timed lock-step (the halo lock-step below appends to them again)
+    last_sketch = ([[x.cpu().numpy() for x in sk_out[(g, T - 1)]] for g in range(len(sketches))]
+                   if args.dump_outputs and rank == 0 else None)
 
     # ---- the halo: every lane first sketches ONE window it does not own (SWFD MAIN(t) continues AUX(t - 1)); in the layout
     # above the warm-up windows play that role.  One sketch-only lock-step of all lanes is timed here, with the same
@@ -632,6 +677,7 @@ def main():
     raw_all = mdist.gather_raw_labels(raw_local, [K] * world, device=coll_dev)
     all_labels = mdist.replay_label_chain(raw_all, mo.match_clusters)
 
+    res = None
     if rank == 0:
         lat = np.array(pipe.latencies[n_warm_lat:])
         if sketches and all(r["ev"] is not None for r in refs):
@@ -643,6 +689,70 @@ def main():
             sk_lat = np.array([sk_done[(gof[p], t)] - sk_events[(gof[p], t)][1]
                                for t in range(Wu, T) for p in range(B) if t < Wu + blks[p]])
             lat = np.maximum(lat, sk_lat) if len(lat) == len(sk_lat) else lat
+        value_excl_halo = world * K * W / elapsed
+        halo_share = t_halo * K / 100.0          # K of the 100 windows a GPU owns in BASELINE config 2
+        value = world * K * W / (elapsed + halo_share)
+        L_sk = sketch.L if sketch is not None else 0
+        sha16 = hashlib.sha256(all_labels.astype(np.int64).tobytes()).hexdigest()[:16]
+        res = {
+            "metric": ("stream rows/sec, d=1024 l=128 window=10k synthetic (SWFD + kNN similarity + eigenstep + labels)"
+                       if args.workload in ("c2", "c4") else f"stream rows/sec, {cfg['name']} (SWFD + kNN similarity + eigenstep + labels)"),
+            "value": value,
+            "unit": "rows/s",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": Wu,
+            "ms_per_step": 1e3 * (elapsed + halo_share) / K,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {
+                "workload": cfg["name"],
+                "stream": args.kind,
+                "W": W, "d": D, "l": ell, "k": k, "modalities": M,
+                "swfd_levels": L_sk,
+                "parallelism": f"windows sharded in contiguous blocks over {world} GPU(s) x {B} lock-step lane(s) per GPU",
+                "rccl_ranks": (dist.get_world_size() if world > 1 else 1),
+                "collective_backend": (dist.get_backend() if world > 1 else None),
+                "lanes_per_gpu": B,
+                "padded_window_slots": padded_slots,
+                "labels_sha16": sha16,
+                "labels_match_reference_golden": None,
+            },
+            "p50_window_latency_ms": float(np.median(lat) * 1e3) if len(lat) else None,
+            "single_lane": None,
+            # every lane re-sketches ONE window it does not own (its halo: SWFD MAIN(t) continues AUX(t-1)); the warm-up
+            # windows play that role here and are not timed.  On the 100-window-per-GPU stream of BASELINE config 2
+            # (1M rows) B lanes cost B extra sketch windows:
+            "value_excl_halo": value_excl_halo,
+            "halo": {"lock_step_s": t_halo, "share_charged_s": halo_share, "timed_s": elapsed,
+                     "rule": "value = rows / (timed + halo lock-step x K / 100): every lane sketches one window it does not own "
+                             "before its block; on the 100-window-per-GPU stream of BASELINE config 2 the K timed windows "
+                             "carry K / 100 of that lock-step (measured here: all lanes, sketch only, same bracket)"},
+            "stages_ms": None,
+            "roofline": None,
+            "roofline_hbm": None,
+            "roofline_mfma": None,
+            "roofline_8d": None,
+            "cpu_baseline": None,
+        }
+        if args.dump_outputs:
+            # the last timed lock-step: lanes whose block is that long label their last window (the others idle in it)
+            trig = [trigger_of(p, T - 1) for p in range(B) if T - 1 < Wu + blks[p]]
+            out = {"labels": all_labels,
+                   "labels_last_step": np.stack([by_trigger[tg] for tg in trig]),
+                   "eigenstep_sigma_last_step": np.stack([next(tr["sigma"] for tr in pipe.trace if tr["trigger"] == tg)
+                                                          for tg in trig])}
+            if last_sketch:
+                ell_ = last_sketch[0][1].shape[-1]
+                out["sketch"] = np.concatenate([b.reshape(-1, ell_, D) for b, _, _ in last_sketch])
+                out["sketch_sigma"] = np.concatenate([s_.reshape(-1, ell_) for _, s_, _ in last_sketch])
+                out["sketch_level_delta"] = np.concatenate([i_.reshape(-1, 2) for _, _, i_ in last_sketch])
+            dump_outputs(args.dump_outputs, out)
+
+    if rank == 0 and args.full:
         ev_pairs = pipe.eng.score_events
         pipe.eng.score_events = None
         gemm_live_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_pairs])) if ev_pairs else None
@@ -919,9 +1029,6 @@ def main():
             roof["launches_whole_script"] = n_all
         if roof is None:
             roof = roof_gemm
-        value_excl_halo = world * K * W / elapsed
-        halo_share = t_halo * K / 100.0          # K of the 100 windows a GPU owns in BASELINE config 2
-        value = world * K * W / (elapsed + halo_share)
         # (3) the whole path in SURVEY 8(d) units: algorithmic flop per row (SWFD 12 l d per FD instance, similarity
         #     2 W d per modality, eigenstep 13 * 2 W (l + 10), dense variant) x rows/s against the fp64 peak
         per_row = 0.0
@@ -941,7 +1048,6 @@ def main():
                           "achieved": eig_bytes / (stages["rsvd_ms"] * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                           "frac": eig_bytes / (stages["rsvd_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS},
         }
-        sha16 = hashlib.sha256(all_labels.astype(np.int64).tobytes()).hexdigest()[:16]
         golden_ok = None
         try:   # event labels of the REFERENCE's own window loop over the same windows (tests/golden/make_golden.py)
             gp = os.path.join(ROOT, "tests", "golden", f"bench_{args.workload}_{args.kind}_s{args.seed}.npz")
@@ -951,53 +1057,12 @@ def main():
                     golden_ok = bool(str(gg["cumulative_sha16"][world * K - 1]) == sha16)
         except Exception:
             golden_ok = None
-        res = {
-            "metric": ("stream rows/sec, d=1024 l=128 window=10k synthetic (SWFD + kNN similarity + eigenstep + labels)"
-                       if args.workload in ("c2", "c4") else f"stream rows/sec, {cfg['name']} (SWFD + kNN similarity + eigenstep + labels)"),
-            "value": value,
-            "unit": "rows/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": Wu,
-            "ms_per_step": 1e3 * (elapsed + halo_share) / K,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": cfg["name"],
-                "stream": args.kind,
-                "W": W, "d": D, "l": ell, "k": k, "modalities": M,
-                "swfd_levels": L_sk,
-                "parallelism": f"windows sharded in contiguous blocks over {world} GPU(s) x {B} lock-step lane(s) per GPU",
-                "rccl_ranks": (dist.get_world_size() if world > 1 else 1),
-                "collective_backend": (dist.get_backend() if world > 1 else None),
-                "lanes_per_gpu": B,
-                "padded_window_slots": padded_slots,
-                "labels_sha16": sha16,
-                "labels_match_reference_golden": golden_ok,
-            },
-            "p50_window_latency_ms": float(np.median(lat) * 1e3) if len(lat) else None,
-            "single_lane": single,
-            # every lane re-sketches ONE window it does not own (its halo: SWFD MAIN(t) continues AUX(t-1)); the warm-up
-            # windows play that role here and are not timed.  On the 100-window-per-GPU stream of BASELINE config 2
-            # (1M rows) B lanes cost B extra sketch windows:
-            "value_excl_halo": value_excl_halo,
-            "halo": {"lock_step_s": t_halo, "share_charged_s": halo_share, "timed_s": elapsed,
-                     "rule": "value = rows / (timed + halo lock-step x K / 100): every lane sketches one window it does not own "
-                             "before its block; on the 100-window-per-GPU stream of BASELINE config 2 the K timed windows "
-                             "carry K / 100 of that lock-step (measured here: all lanes, sketch only, same bracket)"},
-            "stages_ms": stages,
-            "roofline": roof,
-            "roofline_hbm": roof_hbm,
-            "roofline_mfma": roof_gemm,
-            "roofline_8d": roof_8d,
-        }
+        res["config"]["labels_match_reference_golden"] = golden_ok
+        res.update({"single_lane": single, "stages_ms": stages, "roofline": roof, "roofline_hbm": roof_hbm,
+                    "roofline_mfma": roof_gemm, "roofline_8d": roof_8d})
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(cfg, args.kind, args.seed, with_swfd=not args.no_swfd)
-        else:
-            res["cpu_baseline"] = None
+    if rank == 0:
         print(json.dumps(res))
     pipe.close()
     for sk in sketches:

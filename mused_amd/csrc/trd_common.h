@@ -17,8 +17,9 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 // (measured: ~1e-16), a cosine <= TRD_COS_MAX with each of its 4 neighbours in the spectrum, and no 6 significant eigenvalues
 // may lie within max(1e-7 lam_0, TRD_GAP_PER_RES rmax |T|) (rmax = largest residual of the matrix): pairs 5 or more apart are
 // then separated by more than that width, which bounds their mutual contamination 2 rmax |T| / gap by 1e-8 -- the level the
-// neighbours are tested at and the parity tests assert (1e-8 sigma_1).
-constexpr double TRD_RES_MAX = 1e-13, TRD_COS_MAX = 1e-8, TRD_GAP_PER_RES = 2e8;
+// neighbours are tested at and the parity tests assert (1e-8 sigma_1).  The blocked solver (trdx.hip) re-orthogonalises the
+// certified neighbours whose cosine lies above TRD_COS_REORTH.
+constexpr double TRD_RES_MAX = 1e-13, TRD_COS_MAX = 1e-8, TRD_GAP_PER_RES = 2e8, TRD_COS_REORTH = 1e-10;
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the wave's GLOBAL stores (s_waitcnt
 // vmcnt(0)): inside the step loops that would put the latency of a store nobody reads before a later phase (the

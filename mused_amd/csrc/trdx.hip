@@ -477,21 +477,23 @@ __global__ __launch_bounds__(256) void trdx_cert_kernel(const int* __restrict__ 
                                                         const TrdShape sh) {
   constexpr int TNX = LY::TNX, TMX = LY::TMX;
   __shared__ double lam[TMX], zs[TMX], rs[TMX];
-  __shared__ int bad;
-  __shared__ double rmax_s;
+  __shared__ int near[TMX];  // bit q of near[c]: vectors c - q - 1 and c have a cosine above TRD_COS_REORTH
+  __shared__ int bad, nnear;
+  __shared__ double rmax_s, red[4];
   const int bm = blockIdx.x, t = threadIdx.x;
   if (rep && rep[bm] != bm) {  // (the Jacobi skips it too)
     if (t == 0) { done[bm] = 1; act[bm] = -1; jrep[bm] = rep[bm]; }
     return;
   }
   double* wsm = ws + (long)bm * LY::W_PER;
-  const double* Zg = wsm + LY::W_ZG;
+  double* Zg = wsm + LY::W_ZG;
   for (int c = t; c < sh.nvec; c += 256) {
     lam[c] = wsm[LY::W_LG + c];
     zs[c] = wsm[LY::W_LG + TMX + c];
     rs[c] = wsm[LY::W_LG + 2 * TMX + c];
+    near[c] = 0;
   }
-  if (t == 0) bad = reinterpret_cast<const int*>(wsm + LY::W_MI + 2)[0];
+  if (t == 0) { bad = reinterpret_cast<const int*>(wsm + LY::W_MI + 2)[0]; nnear = 0; }
   __syncthreads();
   const double lam0 = lam[0], lamcut = lam[sh.need - 1];
   auto significant = [&](int c) -> bool { return c < sh.nvec && trd_significant(lam[c], c, lam0, lamcut, sh); };
@@ -515,12 +517,46 @@ __global__ __launch_bounds__(256) void trdx_cert_kernel(const int* __restrict__ 
       for (int q = 0; q < 4; ++q) dt[q] = fma(z0, q < nn ? zr[q + 1] : 0.0, dt[q]);
     }
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (q < nn && significant(c + q + 1) && !(fabs(dt[q]) * zs[c] * zs[c + q + 1] <= TRD_COS_MAX)) atomicOr(&bad, 2);
+    for (int q = 0; q < 4; ++q) {
+      if (!(q < nn && significant(c + q + 1))) continue;
+      const double cs = fabs(dt[q]) * zs[c] * zs[c + q + 1];
+      if (!(cs <= TRD_COS_MAX)) atomicOr(&bad, 2);
+      else if (cs > TRD_COS_REORTH) { atomicOr(&near[c + q + 1], 1 << q); atomicAdd(&nnear, 1); }
+    }
     if (c + 5 < sh.nvec && significant(c + 5) && (lam[c] - lam[c + 5]) <= width) atomicOr(&bad, 4);
   }
   __syncthreads();
   const bool ok = bad == 0;
+  if (ok && nnear > 0) {
+    // Certified, but some neighbours are closer than their spectral gap lets twisted factorisation separate (contamination
+    // ~ eps |T| / gap): take z_p out of z_c for those pairs, in ascending order of c (modified Gram-Schmidt, z_p final
+    // before z_c).  Thread t owns rows t, t + 256, ..: the updates of Zg never cross threads, only the sums go through LDS.
+    auto block_sum = [&](double v) -> double {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      __syncthreads();  // (red is free: the previous sum has been read)
+      if ((t & 63) == 0) red[t >> 6] = v;
+      __syncthreads();
+      return (red[0] + red[1]) + (red[2] + red[3]);
+    };
+    for (int c = 1; c < sh.nvec; ++c) {
+      const int nb = near[c];
+      if (nb == 0) continue;
+      for (int q = 3; q >= 0; --q) {  // nearest-first would not matter: the coefficients are <= TRD_COS_MAX
+        if (!(nb >> q & 1)) continue;
+        const int p = c - q - 1;
+        double d = 0.0;
+        for (int i = t; i < TNX; i += 256) d = fma(Zg[(long)i * TMX + c], Zg[(long)i * TMX + p], d);
+        const double f = block_sum(d) * zs[p] * zs[p];
+        for (int i = t; i < TNX; i += 256) Zg[(long)i * TMX + c] = fma(-f, Zg[(long)i * TMX + p], Zg[(long)i * TMX + c]);
+      }
+      double ss = 0.0;
+      for (int i = t; i < TNX; i += 256) { const double z = Zg[(long)i * TMX + c]; ss = fma(z, z, ss); }
+      const double zc = 1.0 / sqrt(block_sum(ss));
+      if (t == 0) { zs[c] = zc; wsm[LY::W_LG + TMX + c] = zc; }
+      __syncthreads();  // (zs[c] is read as zs[p] by the next vectors)
+    }
+  }
   if (t == 0) {
     done[bm] = ok ? 1 : 0;
     act[bm] = ok ? bm : -1;
