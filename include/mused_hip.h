@@ -180,6 +180,28 @@ long mused_kmeans_ws_bytes(int n, int d, int k);
 int mused_kmeans_lloyd(const double* X, long ld, int n, int d, int k, const double* mean, double* centers, double tol,
                        int max_iter, int* labels_out, int* info_out, void* ws, long ws_bytes, void* stream);
 
+/* ---- sSVDMC_mini: MiniBatchKMeans(n_clusters_total, random_state=seed, batch_size=W).partial_fit(X).predict(X) --------
+ * (main.py:82-86; sklearn 1.7 cluster/_kmeans.py).  The arithmetic only: the RandomState stays on the host (k-means++ on the
+ * first batch, _random_reassign, the trim and rows of the reassignment, mused_amd/cluster.py), which keeps a copy of the
+ * k counts.  X: n x d fp64, pitch ld, UNCENTRED; centers: k x d fp64 (pitch d); counts: k fp64.  k <= 1024, d <= 512, no
+ * k * d bound.  ws: mused_mbkm_ws_bytes(n, d, k) bytes.  Enqueue-only.
+ * mused_mbkm_step: labels (n int32, out) = the E step of _mini_batch_step (:1624, _labels_inertia; csq - 2 x.c with the
+ *   fma-chain dot of mused_kmeans_lloyd, first minimum on ties), then _minibatch_update_dense (:1632-1640,
+ *   _k_means_minibatch.pyx update_center_dense): per cluster with rows c <- c * counts, + rows in sample order,
+ *   counts += rows, c *= 1 / counts -- bit-identical to scikit-learn's centres and counts wherever the labels agree.
+ * mused_mbkm_reassign: centers[dst_centers[i]] <- X[src_rows[i]] for i < m, counts <- new_counts (k fp64): the device half
+ *   of :1643-1673 (centers_new[to_reassign] = X[new_centers]; weight_sums[to_reassign] = min(...)).  Pairs outside
+ *   [0, n) x [0, k) are skipped.  m <= k.
+ * mused_kmeans_assign: labels (n int32) of X against the centres, the same E step (predict, :1066; labels_ after
+ *   partial_fit, :2293). */
+long mused_mbkm_ws_bytes(int n, int d, int k);
+int mused_mbkm_step(const double* X, long ld, int n, int d, int k, double* centers, double* counts, int* labels, void* ws,
+                    long ws_bytes, void* stream);
+int mused_mbkm_reassign(const double* X, long ld, int n, int d, int k, const int* src_rows, const int* dst_centers, int m,
+                        const double* new_counts, double* centers, double* counts, void* stream);
+int mused_kmeans_assign(const double* X, long ld, int n, int d, int k, const double* centers, int* labels, void* ws,
+                        long ws_bytes, void* stream);
+
 /* ---- a5-a7: SeqBasedSWFD (swfd submodule; call sites main.py:62,65-67,70) ---------------------- */
 
 /* SeqBasedSWFD(N=, R=, d=, sketch_dim=) */

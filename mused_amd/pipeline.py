@@ -3,10 +3,11 @@ built on the device engine.
 
 Per full window (trigger rule of main.py:32):
     per-modality kNN adjacency (device bitmask)  ->  OR-fusion  ->
-        approach "sSVDMC"/"sSVDMC_hung": randomized-SVD embedding            (main.py:79)
+        approach "sSVDMC"/"sSVDMC_hung"/"sSVDMC_mini": randomized-SVD embedding (main.py:79)
         approach "SWFDMC"             : SeqBasedSWFD over the rows of the fused matrix, R from the
                                         first window only, sketch transposed to (W, l)  (main.py:58-76)
-    -> k-means with n_clusters = #distinct true labels in the window (main.py:41,97)
+    -> k-means with n_clusters = #distinct true labels in the window (main.py:41,97); "sSVDMC_mini": one MiniBatchKMeans
+       (n_clusters_total) for the whole stream, partial_fit + predict per window IN WINDOW ORDER (main.py:82-86)
     -> Hungarian matching against the previous window, min_overlap = 3 (main.py:110)
     -> labels appended (main.py:118-119).
 
@@ -33,9 +34,18 @@ from .swfd import SeqBasedSWFD
 class StreamPipeline:
     def __init__(self, window_size, reduced_dim, k_basis, seed, approach="sSVDMC", modality_types=None,
                  step_window_ratio=1, engine=None, async_labels=True, feature_sketch=False, stream=None,
-                 assume_finite=False, window_slots=1):
-        if approach not in ("sSVDMC", "sSVDMC_hung", "SWFDMC"):
+                 assume_finite=False, window_slots=1, n_clusters_total=None):
+        if approach not in ("sSVDMC", "sSVDMC_hung", "sSVDMC_mini", "SWFDMC"):
             raise ValueError(f"approach {approach!r} is not on the device hot path")
+        if approach == "sSVDMC_mini" and n_clusters_total is None:
+            raise ValueError("approach 'sSVDMC_mini' needs n_clusters_total (MiniBatchKMeans(n_clusters=n_clusters_total), "
+                             "main.py:84)")
+        # "sSVDMC_mini": ONE clusterer for the stream (mused_amd.cluster.MiniBatchKMeans, built at the first window on the
+        # thread that clusters).  Its state is a chain over windows, so its clustering runs on the chain worker, in window
+        # order, not in the parallel k-means pool; the device work of later windows (slots included) still overlaps it.
+        self._mini = approach == "sSVDMC_mini"
+        self.n_clusters_total = None if n_clusters_total is None else int(n_clusters_total)
+        self.clusterer = None
         self.W, self.ell, self.k, self.seed = int(window_size), int(reduced_dim), int(k_basis), int(seed)
         self.approach = approach
         self.types = modality_types
@@ -255,7 +265,9 @@ class StreamPipeline:
                 reduced_host, sigma_host = reduced_dev.cpu().numpy(), sigma_dev.cpu().numpy()
             WindowEngine.check_rsvd_flags(flags_host)  # raised on the label worker, surfaces in flush()
         t0 = time.perf_counter()
-        if self._km_device and reduced_dev is not None and reduced_dev.dtype == torch.float64:
+        if self._mini:
+            clusters = self._minibatch(reduced_dev, reduced_host)
+        elif self._km_device and reduced_dev is not None and reduced_dev.dtype == torch.float64:
             st = getattr(self._km_local, "stream", None)
             if st is None:
                 st = self._km_local.stream = torch.cuda.Stream(priority=-1)
@@ -266,6 +278,36 @@ class StreamPipeline:
             clusters = mo.perform_clustering(reduced_host, n_clusters, self.seed)
         self.host_ms["kmeans"].append(1e3 * (time.perf_counter() - t0))
         return clusters, sigma_host
+
+    def _minibatch(self, reduced_dev, reduced_host):
+        """main.py:82-86: clusterer.partial_fit(reduced).predict(reduced) on the stream's one MiniBatchKMeans.  Called in
+        window order (chain worker, or the caller without async labels).  labels_ after partial_fit IS predict on the same
+        rows: the same E step on the same centres (compute_labels=True)."""
+        if not self._km_device:   # MUSED_KMEANS=host: scikit-learn's own class
+            if self.clusterer is None:
+                from sklearn.cluster import MiniBatchKMeans as SkMiniBatchKMeans
+
+                self.clusterer = SkMiniBatchKMeans(n_clusters=self.n_clusters_total, random_state=self.seed, batch_size=self.W)
+            return self.clusterer.partial_fit(reduced_host).predict(reduced_host)
+        from .cluster import MiniBatchKMeans
+
+        st = getattr(self._km_local, "stream", None)
+        if st is None:
+            st = self._km_local.stream = torch.cuda.Stream(priority=-1)
+        if self.clusterer is None:
+            self.clusterer = MiniBatchKMeans(n_clusters=self.n_clusters_total, random_state=self.seed, batch_size=self.W,
+                                             stream=st)
+        if reduced_dev is not None and reduced_dev.dtype == torch.float64:
+            reduced_dev.record_stream(st)  # produced on the pipeline's stream, complete (ev), consumed on the worker's
+            X = reduced_dev
+        else:
+            X = np.ascontiguousarray(reduced_host, dtype=np.float64)
+        self.km_device_windows += 1
+        return self.clusterer.partial_fit(X).labels_
+
+    def _cluster_chain(self, job):
+        """sSVDMC_mini: the clustering and the matching of one window, both on the chain worker (window order)."""
+        self._chain(self._cluster(job), job)
 
     def _optimistic_nnz(self):
         return any(mo.edges_per_row(t, self.k) is None for t in (self.types or []))
@@ -350,6 +392,15 @@ class StreamPipeline:
         # (slot -> hop-state key of this window's deferred flag words: the engine has moved on by the time a worker reads them)
         return (ev, red_pin, sig_pin, n_clusters, trigger, t_start, flag_pin, reduced, mods, list(eng.slot_keys), eng)
 
+    def _submit(self, job):
+        """Hand a window to the label workers (async mode)."""
+        if self._mini:
+            return self._pool.submit(self._cluster_chain, job)
+        return self._pool.submit(self._chain, self._kpool.submit(self._cluster, job), job)
+
+    def _cluster_chain_after(self, fut_job):
+        return self._cluster_chain(fut_job.result())
+
     def _cluster_after(self, fut_job):
         return self._cluster(fut_job.result())
 
@@ -397,13 +448,16 @@ class StreamPipeline:
             if self._pool is None:
                 self._chain(self._cluster(job), job)
             else:
-                self._pending.append(self._pool.submit(self._chain, self._kpool.submit(self._cluster, job), job))
+                self._pending.append(self._submit(job))
             return
         while len(self._pending) >= self._max_inflight + self._nslots:  # back-pressure (pinned buffers, engines)
             self._pending.popleft().result()
         wait_ev = torch.cuda.Event()
         wait_ev.record(caller)
         fut_job = self._dpools[slot].submit(self._device_side, mods, n_clusters, trigger, t_start, eng, st, wait_ev)
+        if self._mini:
+            self._pending.append(self._pool.submit(self._cluster_chain_after, fut_job))
+            return
         fut_cluster = self._kpool.submit(self._cluster_after, fut_job)
         self._pending.append(self._pool.submit(self._chain_after, fut_cluster, fut_job))
 
@@ -422,7 +476,7 @@ class StreamPipeline:
         if self._pool is None:
             self._chain(self._cluster(job), job)
         else:
-            self._pending.append(self._pool.submit(self._chain, self._kpool.submit(self._cluster, job), job))
+            self._pending.append(self._submit(job))
 
     def flush(self):
         """Wait for every window handed in so far; re-raises the first error a worker met (the remaining windows are
@@ -529,7 +583,7 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
     # modality types go through unchanged: "" / anything the reference does not special-case = Euclidean kNN
     # (matrix_operations.py:112), "text" and "cosine" = the cosine kernel, the other SED2012 metadata types raise
     with StreamPipeline(window_size, reduced_dim, k_basis, seed, approach, list(modality_types), step_window_ratio,
-                        window_slots=int(os.environ.get("MUSED_WINDOW_SLOTS", "1"))) as pipe:
+                        window_slots=int(os.environ.get("MUSED_WINDOW_SLOTS", "1")), n_clusters_total=n_clusters_total) as pipe:
         clusters = pipe.run(data_modalities, np.asarray(complete_true_labels))
     results = dict(results or {})
     results["all_clusters"] = clusters
