@@ -169,6 +169,23 @@ int mused_gemm_f64(int a_kc, int b_kc, const double* A, long lda, const double* 
 int mused_gemm_f64_batched(int a_kc, int b_kc, const double* A, long lda, long strideA, const double* B, long ldb,
                            long strideB, double* C, long ldc, long strideC, int M, int N, int K, int batch,
                            double alpha, void* stream);
+/* Diagnostic entries for the launch modes the library uses inside (unit tests).  A == B with equal layouts, leading
+ * dimensions and strides and M == N selects the symmetric launch (tiles on or above the diagonal, mirrored stores) in
+ * every GEMM entry, as inside the library.
+ * mused_gemm_f64_batched_rep: mused_gemm_f64_batched, but entry z is computed only if rep[z] == z (rep: batch device
+ *   ints; the C of the other entries is not written).
+ * mused_gemm_f64_splitk: partial (nsplit x M x N, pitch N) = the products over k in [s kchunk, (s + 1) kchunk), then C (M x N,
+ *   pitch N, alpha = 1) = their sum in split order.  kchunk > 0 a multiple of 16, nsplit >= 1, kchunk * nsplit >= K.
+ * mused_gemm_f64_batched_splitk: the same per batch entry (partial: batch x nsplit x M x N, C: batch x M x N), entries with
+ *   rep[z] != z skipped in both steps (rep may be NULL). */
+int mused_gemm_f64_batched_rep(int a_kc, int b_kc, const double* A, long lda, long strideA, const double* B, long ldb,
+                               long strideB, double* C, long ldc, long strideC, int M, int N, int K, int batch,
+                               double alpha, const int* rep, void* stream);
+int mused_gemm_f64_splitk(int a_kc, int b_kc, const double* A, long lda, const double* B, long ldb, double* partial,
+                          double* C, int M, int N, int K, int kchunk, int nsplit, void* stream);
+int mused_gemm_f64_batched_splitk(int a_kc, int b_kc, const double* A, long lda, long strideA, const double* B, long ldb,
+                                  long strideB, double* partial, double* C, int M, int N, int K, int batch, int kchunk,
+                                  int nsplit, const int* rep, void* stream);
 
 /* ---- a10 / f2: the Lloyd iterations of perform_clustering (matrix_operations.py:149-153, sklearn KMeans) ------------
  * The k-means++ seeding stays on the host (scikit-learn's own routine on the same RandomState stream); E / M steps and

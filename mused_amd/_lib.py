@@ -60,6 +60,9 @@ _PROTOS = {
     "mused_syevj_batched": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "mused_gemm_f64": (_i, [_i, _i, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _d, _vp]),
     "mused_gemm_f64_batched": (_i, [_i, _i, _vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _d, _vp]),
+    "mused_gemm_f64_batched_rep": (_i, [_i, _i, _vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _d, _vp, _vp]),
+    "mused_gemm_f64_splitk": (_i, [_i, _i, _vp, _l, _vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "mused_gemm_f64_batched_splitk": (_i, [_i, _i, _vp, _l, _l, _vp, _l, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "mused_kmeans_ws_bytes": (_l, [_i, _i, _i]),
     "mused_kmeans_lloyd": (_i, [_vp, _l, _i, _i, _i, _vp, _vp, _d, _i, _vp, C.POINTER(_i), _vp, _l, _vp]),
     "mused_mbkm_ws_bytes": (_l, [_i, _i, _i]),

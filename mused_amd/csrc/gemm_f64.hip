@@ -46,8 +46,8 @@ int gemm_f64(bool a_kc, bool b_kc, const double* A, long lda, long strideA, cons
 
 int gemm_f64_splitk(bool a_kc, bool b_kc, const double* A, long lda, const double* B, long ldb, double* partial,
                     int M, int N, int K, int kchunk, int nsplit, hipStream_t stream) {
-  MUSED_REQUIRE(kchunk % GEMM_BK == 0 && (long)kchunk * nsplit >= K, "gemm_f64_splitk: bad kchunk %d x %d for K=%d",
-                kchunk, nsplit, K);
+  MUSED_REQUIRE(kchunk > 0 && kchunk % GEMM_BK == 0 && nsplit >= 1 && (long)kchunk * nsplit >= K,
+                "gemm_f64_splitk: bad kchunk %d x %d for K=%d", kchunk, nsplit, K);
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   g.A = A; g.B = B; g.lda = lda; g.ldb = ldb;
@@ -75,7 +75,7 @@ __global__ void splitk_reduce_kernel(const double* __restrict__ partial, int nsp
 int gemm_f64_batched_splitk(bool a_kc, bool b_kc, const double* A, long lda, long strideA, const double* B, long ldb, long strideB,
                             double* partial, int M, int N, int K, int batch, int kchunk, int nsplit, hipStream_t stream,
                             const int* rep) {
-  MUSED_REQUIRE(kchunk % GEMM_BK == 0 && nsplit >= 1 && (long)kchunk * nsplit >= K,
+  MUSED_REQUIRE(kchunk > 0 && kchunk % GEMM_BK == 0 && nsplit >= 1 && (long)kchunk * nsplit >= K,
                 "gemm_f64_batched_splitk: bad kchunk %d x %d for K=%d", kchunk, nsplit, K);
   GemmArgs g;
   memset(&g, 0, sizeof(g));
@@ -145,6 +145,34 @@ int mused_gemm_f64_batched(int a_kc, int b_kc, const double* A, long lda, long s
                            double alpha, void* stream) {
   return mused::gemm_f64(a_kc != 0, b_kc != 0, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, M, N, K, batch,
                          alpha, (hipStream_t)stream);
+}
+
+// Test/diagnostic entries for the launch modes the library uses internally (split-K, duplicate skipping).
+int mused_gemm_f64_batched_rep(int a_kc, int b_kc, const double* A, long lda, long strideA, const double* B, long ldb,
+                               long strideB, double* C, long ldc, long strideC, int M, int N, int K, int batch,
+                               double alpha, const int* rep, void* stream) {
+  return mused::gemm_f64(a_kc != 0, b_kc != 0, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, M, N, K, batch,
+                         alpha, (hipStream_t)stream, rep);
+}
+
+int mused_gemm_f64_splitk(int a_kc, int b_kc, const double* A, long lda, const double* B, long ldb, double* partial,
+                          double* C, int M, int N, int K, int kchunk, int nsplit, void* stream) {
+  MUSED_REQUIRE(A && B && partial && C && M >= 0 && N >= 0 && K >= 0, "mused_gemm_f64_splitk: bad arguments");
+  int rc = mused::gemm_f64_splitk(a_kc != 0, b_kc != 0, A, lda, B, ldb, partial, M, N, K, kchunk, nsplit,
+                                  (hipStream_t)stream);
+  if (rc != MUSED_OK || M == 0 || N == 0) return rc;
+  return mused::gemm_splitk_reduce(partial, nsplit, (long)M * N, C, (hipStream_t)stream);
+}
+
+int mused_gemm_f64_batched_splitk(int a_kc, int b_kc, const double* A, long lda, long strideA, const double* B, long ldb,
+                                  long strideB, double* partial, double* C, int M, int N, int K, int batch, int kchunk,
+                                  int nsplit, const int* rep, void* stream) {
+  MUSED_REQUIRE(A && B && partial && C && M >= 0 && N >= 0 && K >= 0 && batch >= 1,
+                "mused_gemm_f64_batched_splitk: bad arguments");
+  int rc = mused::gemm_f64_batched_splitk(a_kc != 0, b_kc != 0, A, lda, strideA, B, ldb, strideB, partial, M, N, K, batch,
+                                          kchunk, nsplit, (hipStream_t)stream, rep);
+  if (rc != MUSED_OK || M == 0 || N == 0) return rc;
+  return mused::gemm_batched_splitk_reduce(partial, nsplit, (long)M * N, C, batch, rep, (hipStream_t)stream);
 }
 
 }  // extern "C"

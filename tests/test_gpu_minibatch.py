@@ -60,6 +60,16 @@ def test_device_minibatch_bitwise_sklearn(n, d, k):
     _against_sklearn(_blob_batches(6, n, d, 0), k, 0, _cuda, batch_size=n)
 
 
+@pytest.mark.parametrize("n,d,k,steps", [(3000, 512, 64, 3), (4096, 32, 1024, 2)])
+def test_device_minibatch_bitwise_sklearn_at_limits(n, d, k, steps):
+    """At the declared limits of the device kernels (d = 512: 16-row tiles with 16 lanes per row and a second feature
+    accumulator; k = 1024: the centres in three LDS tiles of the E step) on k well-separated blobs."""
+    rng = np.random.default_rng(n + d + k)
+    mu = 10.0 * rng.normal(size=(k, d))
+    batches = [mu[rng.integers(0, k, n)] + 0.1 * rng.normal(size=(n, d)) for _ in range(steps)]
+    _against_sklearn(batches, k, 0, _cuda, batch_size=n)
+
+
 def test_device_minibatch_trim_branch():
     """n = 64, k = 48, reassignment_ratio = 0.5: the argsort trim of the reassignment (tests/test_minibatch_host.py)."""
     rng = np.random.default_rng(1)
