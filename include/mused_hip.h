@@ -84,7 +84,7 @@ int mused_knn_fused(const void* X, int dtype, long n, int d, long ld, int k, int
  *   posting lists (postptr[n_tags + 1], postrow[]); S[i][j] = -|Ti & Tj| / |Ti | Tj| (0 if either set is empty,
  *   jaccard_similarity :245-248), S[i][i] = +1 (the reference scores a row against itself with -1 and sorts
  *   descending, :87-88).  n <= 65536.
- * mused_group_mask: ids[n] (< 0: no user name) -> adjacency bitmask of "same id, other row" (:56-71, 123-130). */
+ * mused_group_mask: ids[n] (< 0: no user name) -> adjacency bitmask of "same id, other row" (:56-71, 123-130); any n. */
 #define MUSED_REC_LOCATION 0
 #define MUSED_REC_TIME 1
 int mused_record_scores(const double* rec, int n, int kind, double* S, void* stream);
@@ -99,6 +99,32 @@ int mused_record_knn(const double* rec, int n, int kind, int k, int* out_idx, un
                      void* stream);
 int mused_jaccard_knn(const int* rowptr, const int* tags, const int* postptr, const int* postrow, int n, int n_tags, int k,
                       int* out_idx, unsigned long long* out_mask, int mask_words, void* stream);
+
+/* Batch scale (process_batch_data, main.py:132-167: the whole subset as one window, 150,000 rows by default): the same
+ * selections for ANY n, with no n x n matrix and no global scratch.  One workgroup per row walks the columns in chunks of
+ * at most `chunk` (0: the largest that fits, <= 16384) and keeps the row's k smallest (score, column) pairs in LDS;
+ * ties to the smaller column.  Wherever mused_record_knn / mused_jaccard_knn apply the neighbour lists are identical.
+ * out_idx (n x k int32, ascending columns) is required; out_mask (may be NULL; mask_words <= 8192) is built from it
+ * (own column cleared).  k <= 1024.
+ * mused_sparse_cosine_knn: the k_basis + 1 most similar rows of the "text" modality (matrix_operations.py:101-108) from
+ *   the L2-normalised TF-IDF rows as CSR (rowptr[n + 1], terms[], vals[]: entries in the order scikit-learn stores them,
+ *   NOT sorted) plus the per-term posting lists (postptr[n_terms + 1], postrow[] ascending, postval[]).  Similarity =
+ *   sum over row i's entries in stored order of x_it * x_jt from 0, no FMA: SciPy's csr_matmat order behind
+ *   cosine_similarity on sparse input, so the scores equal the reference's text_sim bit for bit; selected by the key
+ *   0 - similarity (rows sharing no term score 0 and are taken in index order). */
+int mused_record_knn_chunked(const double* rec, int n, int kind, int k, int chunk, int* out_idx,
+                             unsigned long long* out_mask, int mask_words, void* stream);
+int mused_jaccard_knn_chunked(const int* rowptr, const int* tags, const int* postptr, const int* postrow, int n, int n_tags,
+                              int k, int chunk, int* out_idx, unsigned long long* out_mask, int mask_words, void* stream);
+int mused_sparse_cosine_knn(const int* rowptr, const int* terms, const double* vals, const int* postptr, const int* postrow,
+                            const double* postval, int n, int n_terms, int k, int chunk, int* out_idx,
+                            unsigned long long* out_mask, int mask_words, void* stream);
+/* Neighbour lists -> adjacency bitmask in window coordinates: list row r (idx: n_rows x k int32) becomes window row
+ * row_map[r] with the bits row_map[idx[r][j]], the row's own column cleared (matrix_operations.py:123-130).  With a row
+ * map every other row is empty (the mask is zero-filled first); row_map NULL: the identity, n_rows == n.
+ * mask_words <= 8192 (n <= 524,288). */
+int mused_lists_to_mask(const int* idx, int n_rows, int k, const int* row_map, int n, unsigned long long* out_mask,
+                        int mask_words, void* stream);
 
 /* ---- a3 / a4: adjacency bitmasks -------------------------------------------------------------
  * An adjacency is n rows x words uint64 (words >= ceil(n/64)); bit j of row i <=> A[i][j] = 1. */

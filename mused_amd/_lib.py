@@ -40,6 +40,10 @@ _PROTOS = {
     "mused_record_knn": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     "mused_jaccard_knn": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     "mused_jaccard_scores": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "mused_record_knn_chunked": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "mused_jaccard_knn_chunked": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "mused_sparse_cosine_knn": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "mused_lists_to_mask": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp]),
     "mused_adj_fuse": (_i, [C.POINTER(_vp), _i, _i, _i, _vp, _vp]),
     "mused_adj_degrees": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mused_adj_csr_fill": (_i, [_vp, _i, _i, _vp, _vp, _vp]),

@@ -379,7 +379,8 @@ __global__ __launch_bounds__(256) void cand_select_kernel(CandArgs c, int n, int
     int rank = 0;
     for (int m = 0; m < kk; ++m) rank += fcols[m] < fcols[j];
     if (out_idx) out_idx[(long)wrow * k + rank] = cj;
-    if (cj != wrow && cj >= 0 && cj < n) atomicOr(&bits[cj >> 5], 1u << (cj & 31));
+    // (no bit row without out_mask: with mask_words = 0 `bits` would alias fcols)
+    if (out_mask && cj != wrow && cj >= 0 && cj < n) atomicOr(&bits[cj >> 5], 1u << (cj & 31));
   }
   wave_lds_fence();
   if (out_mask) {

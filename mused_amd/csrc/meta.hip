@@ -43,16 +43,18 @@ __global__ __launch_bounds__(256) void record_scores_kernel(const double* __rest
 __global__ __launch_bounds__(256) void group_mask_kernel(const int* __restrict__ ids, int n, int words,
                                                          unsigned long long* __restrict__ mask) {
   const int w = blockIdx.x * 256 + threadIdx.x;
-  const int i = blockIdx.y;
   if (w >= words) return;
-  const int me = ids[i];
-  unsigned long long bits = 0;
-  if (me >= 0) {
-    const int j0 = w * 64;
-    for (int b = 0; b < 64 && j0 + b < n; ++b)
-      if (ids[j0 + b] == me && j0 + b != i) bits |= 1ull << b;
+  // rows i = blockIdx.y, blockIdx.y + gridDim.y, ...: grid.y is capped at 65,535, n is not
+  for (int i = blockIdx.y; i < n; i += gridDim.y) {
+    const int me = ids[i];
+    unsigned long long bits = 0;
+    if (me >= 0) {
+      const int j0 = w * 64;
+      for (int b = 0; b < 64 && j0 + b < n; ++b)
+        if (ids[j0 + b] == me && j0 + b != i) bits |= 1ull << b;
+    }
+    mask[(long)i * words + w] = bits;
   }
-  mask[(long)i * words + w] = bits;
 }
 
 // ---- tags: S[i][j] = -|T_i & T_j| / |T_i | T_j| (0 when either set is empty), S[i][i] = +1 ---------------------------
@@ -104,9 +106,9 @@ int mused_record_scores(const double* rec, int n, int kind, double* S, void* str
 }
 
 int mused_group_mask(const int* ids, int n, unsigned long long* out_mask, int mask_words, void* stream) {
-  MUSED_REQUIRE(ids && out_mask && n > 0 && mask_words >= cdiv(n, 64) && n <= 65535,
+  MUSED_REQUIRE(ids && out_mask && n > 0 && mask_words >= cdiv(n, 64),
                 "mused_group_mask: bad arguments (n=%d words=%d)", n, mask_words);
-  dim3 grid(cdiv(mask_words, 256), n);
+  dim3 grid(cdiv(mask_words, 256), n < 65535 ? n : 65535);
   group_mask_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(ids, n, mask_words, out_mask);
   MUSED_LAUNCH_CHECK();
   return MUSED_OK;

@@ -28,6 +28,8 @@ from ._lib import F32, F64, I64, METRIC_COSINE, METRIC_L2, MusedError, call
 
 _DT = {torch.float32: F32, torch.float64: F64, torch.int64: I64}
 _FUSED_META_ROWS = 15000  # mused_record_knn (<= 16384) / mused_jaccard_knn (<= 15000) keep one row of scores in LDS
+# beyond it the metadata selections walk the columns in chunks (csrc/meta_stream.hip) instead of an n x n score matrix
+_MAX_LIST_K = 1024
 
 
 def _require_gpu():
@@ -351,7 +353,10 @@ class WindowEngine:
         if n > self.n_max or rec.shape[1] != 2:
             raise ValueError(f"{kind}: need (n <= {self.n_max}) x 2 records, got {tuple(rec.shape)}")
         kcode = {"location": 0, "time": 1}[kind]
-        if n <= _FUSED_META_ROWS and self.knn_mode != "classic":
+        if n > _FUSED_META_ROWS:
+            # beyond one row of scores in LDS: chunked selection, no n x n score matrix (csrc/meta_stream.hip)
+            return self.lists_to_adjacency(self.record_lists(rec, kind, kk), n)
+        if self.knn_mode != "classic":
             # scores of a row computed into LDS by the selection kernel itself: no n x n score matrix
             w = words_for(n)
             mask = torch.empty((n, w), dtype=torch.int64, device=self.device)
@@ -359,6 +364,129 @@ class WindowEngine:
             return Adjacency(mask, n)
         call("mused_record_scores", ptr(rec), n, kcode, ptr(self.scores), stream_ptr())
         return self._select(n, kk)
+
+    # ---- batch scale (process_batch_data): neighbour lists for any n, no n x n matrix (csrc/meta_stream.hip) ----------
+    def _lists_out(self, n: int, kk: int) -> torch.Tensor:
+        if not 1 <= kk <= min(n, _MAX_LIST_K):
+            raise ValueError(f"need 1 <= k <= min(n, {_MAX_LIST_K}) neighbours per row (k={kk}, n={n})")
+        return torch.empty((n, kk), dtype=torch.int32, device=self.device)
+
+    def record_lists(self, records, kind: str, kk: int, chunk: int = 0) -> torch.Tensor:
+        """(n, kk) int32 device tensor: per row the kk closest rows of `record_adjacency` (self included when it is among
+        them), ascending columns, for any n.  `chunk` (0: the largest that fits LDS) only changes how the columns are
+        walked, never the result."""
+        rec = records if isinstance(records, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(records, dtype=np.float64))
+        rec = rec.to(self.device, torch.float64).contiguous()
+        n = rec.shape[0]
+        if rec.dim() != 2 or rec.shape[1] != 2:
+            raise ValueError(f"{kind}: need n x 2 records, got {tuple(rec.shape)}")
+        idx = self._lists_out(n, kk)
+        call("mused_record_knn_chunked", ptr(rec), n, {"location": 0, "time": 1}[kind], kk, int(chunk), ptr(idx), None, 0,
+             stream_ptr())
+        self._keep = rec
+        return idx
+
+    @staticmethod
+    def _postings(rowptr, cols, n_cols: int, vals=None):
+        """Posting lists of a CSR (rows ascending inside a list); the CSR itself is left in its stored order."""
+        n = len(rowptr) - 1
+        rows = np.repeat(np.arange(n, dtype=np.int32), np.diff(rowptr))
+        order = np.argsort(cols, kind="stable")
+        postptr = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=max(n_cols, 1)))]).astype(np.int32)
+        return postptr, rows[order], (None if vals is None else np.ascontiguousarray(vals[order], dtype=np.float64))
+
+    def _dev_arrays(self, *arrays):
+        out = []
+        for a in arrays:
+            a = np.ascontiguousarray(a)
+            out.append(torch.from_numpy(a if len(a) else np.zeros(1, a.dtype)).to(self.device))
+        return out
+
+    def jaccard_lists(self, rowptr, tags, n_tags: int, kk: int, chunk: int = 0) -> torch.Tensor:
+        """(n, kk) int32: per row the kk rows of `jaccard_adjacency`, ascending columns, for any n."""
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
+        tags = np.ascontiguousarray(tags, dtype=np.int32)
+        n = len(rowptr) - 1
+        postptr, postrow, _ = self._postings(rowptr, tags, n_tags)
+        dev = self._dev_arrays(rowptr, tags, postptr, postrow)
+        idx = self._lists_out(n, kk)
+        call("mused_jaccard_knn_chunked", ptr(dev[0]), ptr(dev[1]), ptr(dev[2]), ptr(dev[3]), n, int(n_tags), kk, int(chunk),
+             ptr(idx), None, 0, stream_ptr())
+        self._keep = dev  # alive until the stream has consumed them (the next call replaces them)
+        return idx
+
+    def sparse_cosine_lists(self, csr, kk: int, chunk: int = 0) -> torch.Tensor:
+        """(n, kk) int32: per row the kk most similar rows by cosine of the L2-normalised sparse rows `csr` (SciPy CSR as
+        scikit-learn's normalize returns it, entries in stored order), ties to the smaller row.  The similarities are
+        the ones cosine_similarity computes on the host, bit for bit."""
+        n, n_terms = csr.shape
+        rowptr = np.asarray(csr.indptr, dtype=np.int32)
+        terms = np.asarray(csr.indices, dtype=np.int32)
+        vals = np.asarray(csr.data, dtype=np.float64)
+        postptr, postrow, postval = self._postings(rowptr, terms, n_terms, vals)
+        dev = self._dev_arrays(rowptr, terms, vals, postptr, postrow, postval)
+        idx = self._lists_out(n, kk)
+        call("mused_sparse_cosine_knn", *[ptr(t) for t in dev], n, int(n_terms), kk, int(chunk), ptr(idx), None, 0,
+             stream_ptr())
+        self._keep = dev
+        return idx
+
+    def knn_lists(self, rows, k: int, metric: str = "l2") -> torch.Tensor:
+        """(n, kk) int32 neighbour lists of `knn_adjacency` (fused similarity + selection, no bit rows: any n the candidate
+        workspace allows).  A candidate-list overflow is retried once with 1024 candidates per row, then raised -- never
+        the n x n score matrix."""
+        X = to_device_rows(rows, self.device)
+        n, d = X.shape
+        if metric == "l2":
+            kk, m = max(1, int(k)), METRIC_L2
+            if kk > n:
+                raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = {kk}, "
+                                 f"n_samples_fit = {n}, n_samples = {n}")
+        elif metric == "cosine":
+            kk, m = min(int(k) + 1, n), METRIC_COSINE
+        else:
+            raise ValueError(f"unknown metric {metric!r}")
+        if 4 * kk + 128 > 1024:
+            raise MusedError(f"knn_lists: {kk} neighbours per row exceed the candidate lists of the fused kernel (k <= 224)")
+        idx = torch.empty((n, kk), dtype=torch.int32, device=self.device)
+        cap = max(704, ((4 * kk + 128 + 63) // 64) * 64)
+        for attempt in (0, 1):
+            nbytes = int(_lib.lib().mused_knn_fused_ws_bytes(n, cap))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            call("mused_knn_fused", ptr(X), _DT[X.dtype], n, d, X.stride(0), kk, m, ptr(ws), nbytes, cap, ptr(idx), None, 0,
+                 ptr(self._ovf), stream_ptr())
+            if int(self._ovf.item()) == 0:
+                return idx
+            del ws
+            if cap == 1024:
+                break
+            cap = 1024
+        raise MusedError(f"knn_lists: a candidate list overflowed {cap} entries (thousands of equal scores in a row of "
+                         f"{n}); there is no n x n fallback at this size")
+
+    def lists_to_adjacency(self, idx: torch.Tensor, n: int, valid=None) -> Adjacency:
+        """Window-coordinate bitmask of neighbour lists: list row r is window row valid[r] (r without `valid`), its
+        entries map through `valid` the same way; own column cleared, rows without a list empty."""
+        w = words_for(n)
+        mask = torch.empty((n, w), dtype=torch.int64, device=self.device)
+        rmap = None
+        if valid is not None:
+            rmap = valid if isinstance(valid, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(valid))
+            rmap = rmap.to(self.device, torch.int32).contiguous()
+        n_rows, kk = (idx.shape[0], idx.shape[1]) if idx is not None else (0, 0)
+        call("mused_lists_to_mask", ptr(idx) if idx is not None and idx.numel() else None, n_rows, kk,
+             ptr(rmap) if rmap is not None else None, n, ptr(mask), w, stream_ptr())
+        self._keep_map = (rmap, idx)
+        return Adjacency(mask, n)
+
+    def fuse_into(self, dst: Adjacency, src: Adjacency) -> Adjacency:
+        """dst |= src in place (one modality mask at a time beside the fused one); dst becomes a fused adjacency."""
+        if src.n != dst.n or src.words != dst.words:
+            raise ValueError("adjacency shapes differ")
+        arr = (C.c_void_p * 2)(dst.mask.data_ptr(), src.mask.data_ptr())
+        call("mused_adj_fuse", arr, 2, dst.n, dst.words, ptr(dst.mask), stream_ptr())
+        dst.fused = True
+        return dst
 
     def jaccard_adjacency(self, rowptr, tags, n_tags: int, kk: int) -> Adjacency:
         """The kk rows with the largest Jaccard similarity of tag sets per row (matrix_operations.py:73-89); sets as CSR
@@ -368,13 +496,15 @@ class WindowEngine:
         n = len(rowptr) - 1
         if n > self.n_max:
             raise ValueError(f"window of {n} rows exceeds the engine capacity {self.n_max}")
+        if n > _FUSED_META_ROWS:
+            return self.lists_to_adjacency(self.jaccard_lists(rowptr, tags, n_tags, kk), n)
         rows = np.repeat(np.arange(n, dtype=np.int32), np.diff(rowptr))
         order = np.argsort(tags, kind="stable")  # posting lists: rows of a tag in ascending order
         postrow = rows[order]
         postptr = np.concatenate([[0], np.cumsum(np.bincount(tags, minlength=max(n_tags, 1)))]).astype(np.int32)
         dev = [torch.from_numpy(a).to(self.device) for a in (rowptr, tags if len(tags) else np.zeros(1, np.int32),
                                                               postptr, postrow if len(postrow) else np.zeros(1, np.int32))]
-        if n <= _FUSED_META_ROWS and self.knn_mode != "classic":
+        if self.knn_mode != "classic":
             w = words_for(n)
             mask = torch.empty((n, w), dtype=torch.int64, device=self.device)
             call("mused_jaccard_knn", ptr(dev[0]), ptr(dev[1]), ptr(dev[2]), ptr(dev[3]), n, int(n_tags), kk, None, ptr(mask),

@@ -34,6 +34,9 @@ import numpy as np
 from . import engine as _eng
 
 _METADATA_TYPES = ("location", "time", "username", "tags")
+# "text": the dense TF-IDF (n x vocabulary fp64) goes to the device while it stays below this many bytes; beyond it (or
+# when the caller asks for it) the sparse rows are used as they are (csrc/meta_stream.hip, SPCOS source)
+TEXT_DENSE_BYTES = 1 << 30
 
 
 def _metric_for(modality_type) -> str:
@@ -57,15 +60,32 @@ def edges_per_row(modality_type, k_basis):
     return max(k, 1)
 
 
-def adjacency_on_device(data, modality_type="", k_basis=50, engine=None) -> _eng.Adjacency:
+def _bit_rows_fit(n: int, kk: int) -> bool:
+    """mused_knn_fused keeps one bit row per wave in 64 KiB of LDS (csrc/knn_fused.hip)."""
+    return 4 * (8 * _eng.words_for(n) + 4 * kk) + 16 <= 64 * 1024
+
+
+def _dense_knn(eng, X, k_basis, metric, n, valid_idx) -> _eng.Adjacency:
+    """kNN adjacency of device rows X (the valid rows of a window of n; valid_idx None: all of them)."""
+    kk = max(1, int(k_basis)) if metric == "l2" else min(int(k_basis) + 1, X.shape[0])
+    if valid_idx is None and _bit_rows_fit(n, kk):
+        return eng.knn_adjacency(X, k_basis, metric)
+    if valid_idx is None or n > _eng._FUSED_META_ROWS:
+        # beyond the LDS bit rows, or invalid rows at batch scale: neighbour lists, then the mask through the row map
+        return eng.lists_to_adjacency(eng.knn_lists(X, k_basis, metric), n, valid_idx)
+    return _scatter_valid(eng.knn_adjacency(X, k_basis, metric), valid_idx, n)
+
+
+def adjacency_on_device(data, modality_type="", k_basis=50, engine=None, text_sparse=None) -> _eng.Adjacency:
     """Device-resident result of create_adjacency_matrix (matrix_operations.py:14-132, `case _`).
 
     Rows with a non-finite entry are excluded from the kNN and get empty rows / columns
-    (matrix_operations.py:114-115, 126-127)."""
+    (matrix_operations.py:114-115, 126-127).  `text_sparse` ("text" only): True = sparse TF-IDF rows on the device,
+    False = dense, None = dense unless it exceeds TEXT_DENSE_BYTES."""
     import torch
 
     if modality_type == "text":
-        return _text_adjacency(data, k_basis, engine)
+        return _text_adjacency(data, k_basis, engine, sparse=text_sparse)
     if modality_type in _METADATA_TYPES:
         return _metadata_adjacency(data, modality_type, k_basis, engine)
     metric = _metric_for(modality_type)
@@ -88,13 +108,13 @@ def adjacency_on_device(data, modality_type="", k_basis=50, engine=None) -> _eng
     n = len(data)
     eng = engine or _eng.default_engine(n)
     if all_valid:
-        return eng.knn_adjacency(X, k_basis, metric)
+        return _dense_knn(eng, X, k_basis, metric, n, None)
     if isinstance(data, torch.Tensor):
         X = X[valid_idx].contiguous()
     if X.shape[0] == 0:
         w = _eng.words_for(n)
         return _eng.Adjacency(torch.zeros((n, w), dtype=torch.int64, device=eng.device), n)
-    return _scatter_valid(eng.knn_adjacency(X, k_basis, metric), valid_idx, n)
+    return _dense_knn(eng, X, k_basis, metric, n, valid_idx)
 
 
 def _scatter_valid(sub: _eng.Adjacency, valid_idx, n: int) -> _eng.Adjacency:
@@ -106,10 +126,12 @@ def _scatter_valid(sub: _eng.Adjacency, valid_idx, n: int) -> _eng.Adjacency:
     return _eng.Adjacency.from_dense(dense)
 
 
-def _text_adjacency(data, k_basis, engine=None) -> _eng.Adjacency:
+def _text_adjacency(data, k_basis, engine=None, sparse=None) -> _eng.Adjacency:
     """matrix_operations.py:91-110: rows with a non-empty title or description are valid; TF-IDF of
     "title description" on the host (same TfidfVectorizer call), then cosine similarity and the k_basis + 1 most
-    similar rows per row on the device (`MUSED_METRIC_COSINE`)."""
+    similar rows per row on the device: dense rows through `MUSED_METRIC_COSINE`, or (`sparse`, or a dense TF-IDF beyond
+    TEXT_DENSE_BYTES) the rows scikit-learn's normalize returns, as they are stored, through mused_sparse_cosine_knn --
+    the similarities of cosine_similarity on sparse input bit for bit."""
     import torch
     from sklearn.feature_extraction.text import TfidfVectorizer
 
@@ -124,11 +146,17 @@ def _text_adjacency(data, k_basis, engine=None) -> _eng.Adjacency:
     text = np.where(vd[:, 0] != "", vd[:, 0], " ") + " " + np.where(vd[:, 1] != "", vd[:, 1], " ")
     if not np.any(text != " "):
         return empty()
-    V = np.asarray(TfidfVectorizer().fit_transform(text).todense(), dtype=np.float64)
-    sub = eng.knn_adjacency(_eng.to_device_rows(V), k_basis, "cosine")
-    if len(valid) == n:
-        return sub
-    return _scatter_valid(sub, torch.from_numpy(valid).to(eng.device), n)
+    T = TfidfVectorizer().fit_transform(text)
+    if sparse is None:
+        sparse = T.shape[0] * T.shape[1] * 8 > TEXT_DENSE_BYTES
+    valid_idx = None if len(valid) == n else torch.from_numpy(valid).to(eng.device)
+    if sparse:
+        from sklearn.preprocessing import normalize
+
+        Tn = normalize(T, copy=True)  # what cosine_similarity does to its input (the stored order is kept)
+        return eng.lists_to_adjacency(eng.sparse_cosine_lists(Tn, min(int(k_basis) + 1, Tn.shape[0])), n, valid_idx)
+    V = np.asarray(T.todense(), dtype=np.float64)
+    return _dense_knn(eng, _eng.to_device_rows(V), k_basis, "cosine", n, valid_idx)
 
 
 def _metadata_adjacency(data, modality_type, k_basis, engine=None) -> _eng.Adjacency:
@@ -143,21 +171,34 @@ def _metadata_adjacency(data, modality_type, k_basis, engine=None) -> _eng.Adjac
     eng = engine or _eng.default_engine(max(n, 1))
     empty = lambda: _eng.Adjacency(torch.zeros((n, _eng.words_for(n)), dtype=torch.int64, device=eng.device), n)
     k = int(k_basis)
+    # batch scale (beyond one row of scores in LDS): neighbour lists of the valid rows, mapped straight into the window's
+    # mask (no n x n round trip)
+    lists = n > _eng._FUSED_META_ROWS
     if modality_type == "location":  # 'latitude', 'longitude'; k + 1 because a row is its own nearest neighbour
         valid = np.where(~np.isnan(data.astype(np.float64)).any(axis=1))[0]
         if len(valid) == 0:
             return empty()
-        sub = eng.record_adjacency(data[valid], "location", min(k + 1, len(valid)))
+        rec, kk = data[valid], min(k + 1, len(valid))
+        if lists:
+            return eng.lists_to_adjacency(eng.record_lists(rec, "location", kk), n, _map(valid, n))
+        sub = eng.record_adjacency(rec, "location", kk)
     elif modality_type == "time":  # 'datetaken', 'dateupload'; 0.0 marks a missing stamp
         valid = np.where(~((data[:, 0] == 0.0) | (data[:, 1] == 0.0)))[0]
         if len(valid) == 0 or 3 * k + 1 <= 0:
             return empty()
-        sub = eng.record_adjacency(data[valid], "time", min(3 * k + 1, len(valid)))
+        rec, kk = data[valid], min(3 * k + 1, len(valid))
+        if lists:
+            return eng.lists_to_adjacency(eng.record_lists(rec, "time", kk), n, _map(valid, n))
+        sub = eng.record_adjacency(rec, "time", kk)
     elif modality_type == "username":
         valid = np.where(data[:, 0] != "")[0]
         if len(valid) == 0:
             return empty()
         _, ids = np.unique(data[valid, 0].astype(str), return_inverse=True)
+        if lists:  # id -1 for rows without a name: no edges in their rows or columns
+            full = np.full(n, -1, dtype=np.int32)
+            full[valid] = ids
+            return eng.group_adjacency(full)
         sub = eng.group_adjacency(ids)
     else:  # "tags"
         valid = np.where(data[:, 0] != "")[0]
@@ -168,10 +209,18 @@ def _metadata_adjacency(data, modality_type, k_basis, engine=None) -> _eng.Adjac
             tag_set = set(tags) if tags else set()
             ids.extend(sorted(vocab.setdefault(t, len(vocab)) for t in tag_set))
             rowptr.append(len(ids))
-        sub = eng.jaccard_adjacency(rowptr, np.asarray(ids, dtype=np.int32), len(vocab), min(k, len(valid)))
+        ids, kk = np.asarray(ids, dtype=np.int32), min(k, len(valid))
+        if lists:
+            return eng.lists_to_adjacency(eng.jaccard_lists(rowptr, ids, len(vocab), kk), n, _map(valid, n))
+        sub = eng.jaccard_adjacency(rowptr, ids, len(vocab), kk)
     if len(valid) == n:
         return sub
     return _scatter_valid(sub, torch.from_numpy(valid).to(eng.device), n)
+
+
+def _map(valid, n):
+    """Row map of lists_to_adjacency: None when every row is valid."""
+    return None if len(valid) == n else valid
 
 
 def create_adjacency_matrix(data, modality_type, k_basis=50):

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import matrix_operations as mo
+from ._lib import MusedError
 from .engine import WindowEngine
 from .swfd import SeqBasedSWFD
 
@@ -587,6 +588,83 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
         clusters = pipe.run(data_modalities, np.asarray(complete_true_labels))
     results = dict(results or {})
     results["all_clusters"] = clusters
+    results["processing_time"] = (time.time_ns() - t0) / 1e9
+    return results
+
+
+BATCH_APPROACHES = ("SVDMC_batch", "DBSCAN_batch", "HDBSCAN_batch")
+
+
+def batch_embedding(data_modalities, modality_types, reduced_dim, k_basis, seed, engine=None, timings=None):
+    """Device part of process_batch_data (main.py:138-147): per-modality kNN adjacency of all rows, OR-fused into one
+    bitmask as it arrives (one modality mask alive beside the fused one), then the randomized-SVD embedding at n = subset
+    size.  Returns (embedding (n, m) fp64 CUDA tensor, sigma, number of fused edges).  `timings`: a dict that receives
+    the seconds of every phase (synchronised) and, as "peak_bytes", the most device memory in use beyond what was in
+    use on entry at the end of any phase."""
+    n = len(data_modalities[0])
+    base = torch.cuda.mem_get_info()[1] - torch.cuda.mem_get_info()[0] if timings is not None else 0
+    eng = engine or WindowEngine(max(n, 2))
+
+    def tick(name, t):
+        if timings is not None:
+            torch.cuda.synchronize()
+            timings[name] = timings.get(name, 0.0) + time.perf_counter() - t
+            free, total = torch.cuda.mem_get_info()  # device memory in use beyond what was in use on entry
+            timings["peak_bytes"] = max(timings.get("peak_bytes", 0), total - free - base)
+        return time.perf_counter()
+
+    try:
+        fused = None
+        t = time.perf_counter()
+        for i, (m, ty) in enumerate(zip(data_modalities, modality_types)):
+            if len(m) != n:
+                raise ValueError(f"modality {i} has {len(m)} rows, modality 0 has {n}")
+            adj = mo.adjacency_on_device(m, ty, k_basis, engine=eng)
+            t = tick(f"knn[{i}:{ty or 'l2'}]", t)
+            fused = adj if fused is None else eng.fuse_into(fused, adj)
+            del adj
+            t = tick("fusion", t)
+        deg, _, _ = fused.degrees()
+        nnz = int(deg.to(torch.int64).sum().item())
+        if nnz >= 2 ** 31:
+            raise MusedError(f"the fused adjacency has {nnz} edges: the eigenstep's neighbour lists are int32 (< 2^31)")
+        t = tick("fusion", t)
+        emb, sig, flags = eng.svd_reduce(fused, reduced_dim, seed, nnz_cap=max(nnz, 1), want_flags=True)
+        WindowEngine.check_rsvd_flags(flags.cpu().numpy())
+        tick("eigenstep", t)
+        return emb, sig, nnz
+    finally:
+        if engine is None:
+            eng.close()
+
+
+def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_basis, n_clusters, seed, approach,
+                       complete_true_labels, noise_rate, label_mode, sorting, eps, min_samples, min_cluster_size,
+                       window_size, timings=None):
+    """Same positional parameters as main.py:132: the whole subset as one window -- kNN adjacency per modality, fusion,
+    randomized-SVD embedding on the device (`batch_embedding`), then "SVDMC_batch": k-means with n_clusters on the device
+    (perform_clustering_on_device: scikit-learn's labels); "DBSCAN_batch" / "HDBSCAN_batch": the host wrappers on the
+    embedding, as the reference does.  Returns `results` with the labels ("all_clusters") and the wall time
+    ("processing_time"), like process_streaming_data.  `timings`: see batch_embedding (plus "clustering" and "edges")."""
+    if approach not in BATCH_APPROACHES:
+        raise ValueError(f"approach {approach!r} is not a batch approach {BATCH_APPROACHES}")
+    if approach == "HDBSCAN_batch":
+        import hdbscan  # noqa: F401  (the reference imports it at module level: without it nothing runs)
+    t0 = time.time_ns()
+    emb, _, nnz = batch_embedding(data_modalities, list(modality_types), reduced_dim, k_basis, seed, timings=timings)
+    t1 = time.perf_counter()
+    if approach == "HDBSCAN_batch":
+        clusters = mo.perform_hdbscan_clustering(emb.cpu().numpy(), min_cluster_size=min_cluster_size,
+                                                 min_samples=min_samples)
+    elif approach == "DBSCAN_batch":
+        clusters = mo.perform_dbscan_clustering(emb.cpu().numpy(), eps=eps, min_samples=min_samples)
+    else:
+        clusters = mo.perform_clustering_on_device(emb, n_clusters, seed)
+    if timings is not None:
+        timings["clustering"] = time.perf_counter() - t1
+        timings["edges"] = nnz
+    results = dict(results or {})
+    results["all_clusters"] = np.asarray(clusters)
     results["processing_time"] = (time.time_ns() - t0) / 1e9
     return results
 

@@ -80,6 +80,37 @@ def text_stream(n: int, seed: int = 0, vocab: int = 120, topics: int = 4, blank_
     return data.astype(str), labels.astype(np.int64)
 
 
+def sparse_text_stream(n: int, seed: int = 0, vocab: int = 20000, zipf: float = 1.1, dup_rate: float = 0.05,
+                       blank_rate: float = 0.04):
+    """Synthetic ('title', 'description') string records with a LARGE Zipf vocabulary (the TF-IDF rows are sparse), for
+    the sparse path of the "text" modality: short documents, so that many pairs share no word (similarity exactly 0,
+    ties filled by index order), a share `dup_rate` of exact copies of earlier documents (equal similarities) and blank
+    rows as text_stream has them.  Returns ((n, 2) array of str, labels: the index of the document a row copies, else
+    its own)."""
+    rng = np.random.default_rng([seed, 0x5BA7])
+    p = 1.0 / np.arange(1, vocab + 1) ** zipf
+    p /= p.sum()
+    words = np.array([f"v{i:05d}" for i in range(vocab)])
+    data = np.empty((n, 2), dtype=object)
+    labels = np.arange(n, dtype=np.int64)
+    for i in range(n):
+        if i > 0 and rng.random() < dup_rate:
+            j = int(rng.integers(0, i))
+            data[i] = data[j]
+            labels[i] = labels[j]
+            continue
+        data[i, 0] = " ".join(rng.choice(words, size=int(rng.integers(1, 5)), p=p))
+        data[i, 1] = " ".join(rng.choice(words, size=int(rng.integers(3, 12)), p=p))
+        u = rng.random()
+        if u < blank_rate:
+            data[i, 0] = ""
+        elif u < 2 * blank_rate:
+            data[i, 1] = ""
+        elif u < 2.5 * blank_rate:
+            data[i, 0] = data[i, 1] = ""
+    return data.astype(str), labels
+
+
 def metadata_stream(n: int, seed: int = 0, events: int = 5, users: int = 24, vocab: int = 60, missing: float = 0.05,
                     integer_time: bool = False):
     """Synthetic SED2012-style metadata columns, in the layout data_loader.py:87-99 hands to the reference:
