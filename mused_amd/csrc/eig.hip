@@ -24,55 +24,75 @@ struct OsjqCtl {
   int pad;
 };
 
+// Which kernels a plan launches.  Decided once, by eig_choose(), from the shape, the flags and the environment; everything
+// that allocates, launches, profiles or releases switches on these two enums.
+enum class EigDirect {
+  None,  // the Jacobi solves every matrix
+  Trd,   // orders <= 256 (trd.hip, register resident): runs first, the Jacobi (always the queue) takes the matrices it rejected
+  Trdx,  // orders 320 .. 1024 (trdx.hip, blocked): runs first, the sweep graph runs on its rejects -- when there are any
+};
+enum class EigJacobi {
+  Queue,      // orders <= 256: one persistent work-queue launch per solve (osjq_kernel)
+  WaveGraph,  // orders <= 512: launch-per-round sweeps of the wave-private kernel (osjw_kernel; orders 320 .. 512: the pairs
+              // inside the blocks by the row-per-thread kernel first)
+  RowGraph,   // orders 640 .. 1024: launch-per-round sweeps of the row-per-thread kernel (osj_round_kernel)
+};
+struct EigChoice {
+  EigDirect direct;
+  EigJacobi jacobi;
+  int ldn;        // padded order (multiple of 64; of 128 above 512) = rows of the working copy
+  int rps;        // launch rounds per sweep: nb - 1 (orders <= 256: round 0 carries the pairs inside the blocks) or nb
+  int need;       // leading eigenpairs the caller reads (0: all): what the direct solver delivers
+  bool cert_all;  // every one of them must pass the certificate (eigenstep) / those that survive the FD shrink
+  bool sort;      // store columns by descending norm inside each block pair
+  bool adaptive;  // per-matrix convergence flags: `sweeps` is a cap
+};
+// The environment switches of this layer, read once per eig_plan_create
+struct EigEnv {
+  bool trd;        // MUSED_EIG_TRD=0 turns the direct solvers off
+  int queue;       // MUSED_EIG_QUEUE=1 / anything else / unset: 1 / 0 / -1 (the batch decides)
+  bool graph;      // MUSED_NO_GRAPH=1: no private hipGraph
+  unsigned long long queue_timeout;  // MUSED_EIG_QUEUE_TIMEOUT_TICKS
+};
+
 struct EigPlan {
-  int n, batch, sweeps;
-  int method;  // 0 = two-sided, one launch per rotation set; 1 = one-sided block Jacobi (default)
-  int ldn;     // OSJ: padded order (multiple of 64) = threads per workgroup
-  double* Gc;  // OSJ: batch x ldn x ldn, column-major working copy
-  double* lam; // OSJ: batch x ldn column norms
-  int* notconv;  // OSJ: (sweeps * rps) x batch flags: a pair that still matters was met in that launch round
-  int rps;       // launch rounds per sweep: nb - 1 (orders <= 256: round 0 carries the pairs inside the blocks) or nb
-  int* qclean;   // queue solver: consecutive clean rounds per matrix
-  int wavek;     // OSJ: 1 = wave-private kernel (orders <= 256)
-  bool direct;   // OSJ: the caller fills Gc itself (n == ldn): no pack pass
-  const int* rep; // optional: matrix b is a duplicate of matrix rep[b] != b and is not solved
-  int sortcols;  // OSJ: store columns by descending norm inside each block pair
-  int sort_from; // OSJ wave kernel: first sweep that sorts
-  // persistent work-queue solver (orders <= 256, see osjq_kernel): one launch per solve instead of sweeps x (nb - 1)
-  int use_queue;
-  unsigned* q;        // unit ring: 0 = empty, else 1 + ((matrix * 256 + global round) * 4 + block pair)
-  unsigned qcap;
-  struct OsjqCtl* qctl;
-  // direct solver for the leading pairs only: runs first, the Jacobi then takes the matrices it rejected.
-  // 1: orders <= 256 (trd.hip; fallback = the persistent queue Jacobi); 2: orders 320 .. 1024 (trdx.hip; fallback = the sweep graph)
-  int trd;
-  const int* jrep;     // what the Jacobi's launch-per-round kernels test (matrix b runs when jrep[b] == b): rep, or -- behind the
-                       // direct solver of orders 320 .. 1024 (trdx.hip) -- the per-solve list of the matrices it rejected
-  int *trdx_act, *trdx_jrep;  // trdx: matrices that passed (act[b] == b) / that the Jacobi must solve (jrep[b] == b)
-  int* trdx_nrej;             // trdx: device count of the matrices the last solve rejected
-  int* trdx_nrej_host;        // ... its pinned host copy: the Jacobi's sweep graph (hundreds of launches that would find nothing
-  hipEvent_t trdx_ev;         //     to do) is only launched when the count is not zero
-  int trd_need;        // leading eigenpairs the caller reads
-  int trd_cert_all;    // every one of them must pass the certificate (eigenstep) / those that survive the FD shrink
-  double* trd_ws;
-  int* trd_done;       // per matrix: 1 = solved by the direct solver (the Jacobi skips it)
-  unsigned long long q_timeout;  // ticks of s_memrealtime (100 MHz) a consumer waits for its ticket (3 s; MUSED_EIG_QUEUE_TIMEOUT_TICKS)
-  int* err_out;                  // optional device word the caller reads back: set when the queue solver gave up (results invalid)
-  int* qdone;         // per matrix: units of its current round that have finished
-  double* trace; // OSJ adaptive: trace(G) per matrix (owns the allocation notconv / work point into)
-  unsigned long long* work;  // OSJ adaptive, profiling: (matrix, sweep) pairs that did work
-  // live profiling (off by default): HIP events around every replay of the sweep graph
-  bool prof;
-  int prof_n;
-  std::vector<hipEvent_t>* ev0;
-  std::vector<hipEvent_t>* ev1;
-  std::vector<hipEvent_t>* evm;  // direct solver: after its first kernel (the tridiagonalisation)
-  double* G[2];
-  double* V[2];
-  hipGraph_t graph;
-  hipGraphExec_t exec;
-  hipStream_t cap_stream;
-  bool have_graph;
+  int n = 0, batch = 0, sweeps = 0;
+  EigChoice c{};
+  double* G = nullptr;    // n != ldn only: batch x n x n staging buffer the caller fills (the pack pass pads it into Gc)
+  double* Gc = nullptr;   // batch x ldn x ldn, column-major working copy
+  double* lam = nullptr;  // batch x ldn column norms
+  const int* rep = nullptr;  // optional: matrix b is a duplicate of matrix rep[b] != b and is not solved
+  const int* jrep = nullptr;  // what the Jacobi's launch-per-round kernels test (matrix b runs when jrep[b] == b): rep, or -- behind
+                              // the blocked direct solver (trdx.hip) -- the per-solve list of the matrices it rejected
+  int* err_out = nullptr;  // optional device word the caller reads back: set when the queue solver gave up (results invalid)
+  // adaptive sweeps: [trace (batch doubles) | work counter (1 x u64) | flags]; trace owns the allocation
+  double* trace = nullptr;             // trace(G) per matrix
+  unsigned long long* work = nullptr;  // profiling: (matrix, round) pairs that did work / matrices the direct solver solved
+  int* notconv = nullptr;  // (sweeps * rps) x batch flags: a pair that still matters was met in that launch round
+  // EigJacobi::Queue (see osjq_kernel)
+  unsigned* q = nullptr;  // unit ring: 0 = empty, else 1 + ((matrix * 256 + global round) * 4 + block pair)
+  unsigned qcap = 0;
+  OsjqCtl* qctl = nullptr;
+  int* qdone = nullptr;   // per matrix: units of its current round that have finished
+  int* qclean = nullptr;  // per matrix: consecutive clean rounds
+  unsigned long long q_timeout = 0;  // ticks of s_memrealtime (100 MHz) a consumer waits for its ticket (3 s)
+  // EigDirect::Trd / Trdx
+  double* trd_ws = nullptr;
+  int* trd_done = nullptr;  // per matrix: 1 = solved by the direct solver (the Jacobi skips it)
+  int *trdx_act = nullptr, *trdx_jrep = nullptr;  // trdx: matrices that passed (act[b] == b) / that the Jacobi must solve (jrep[b] == b)
+  int* trdx_nrej = nullptr;       // trdx: device count of the matrices the last solve rejected
+  int* trdx_nrej_host = nullptr;  // ... its pinned host copy: the Jacobi's sweep graph (hundreds of launches that would find nothing
+  hipEvent_t trdx_ev = nullptr;   //     to do) is only launched when the count is not zero
+  // live profiling (off by default): HIP events around every solve
+  bool prof = false;
+  int prof_n = 0;
+  std::vector<hipEvent_t> ev0, ev1;
+  std::vector<hipEvent_t> evm;  // direct solver: after its first kernel (the tridiagonalisation)
+  // private hipGraph of the Jacobi launches (exec != nullptr: there is one)
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  hipStream_t cap_stream = nullptr;
+  bool capturing = false;  // a capture on cap_stream was begun and not ended
 };
 
 // ======================= one-sided block Jacobi (register resident) =========================
@@ -301,7 +321,7 @@ __host__ __device__ constexpr int osj_sched_q(int c2, int step, int k) {
   return CROSS ? (c2 / 2 + (k + step) % (c2 / 2)) : osj_pair_q(c2, step, k);
 }
 
-template <int CB, int NT, int MODE, int DBG = 0>
+template <int CB, int NT, int MODE>
 __global__ __launch_bounds__(NT) void osj_round_kernel(double* __restrict__ Gc, int n, int ldn, int nb, int round,
                                                       int* __restrict__ notconv, int fr, int rps,
                                                       const double* __restrict__ trace, int sortcols,
@@ -320,7 +340,6 @@ __global__ __launch_bounds__(NT) void osj_round_kernel(double* __restrict__ Gc, 
   }
   // MODE 1: block pair (bp, bq) of the round-robin, cross pairs only; MODE 2: ONE block of 2*CB
   // consecutive columns (blockIdx.x), all pairs inside it; MODE 0: block pair, all pairs.
-  // DBG != 0: timing-only ablations (results are wrong): 2 no rotation maths, 3 no barrier, 4 no apply.
   //
   // FAST (scaled) ROTATIONS: column j is held as d_j * x_j with a per-column scale d_j (LDS, starts at
   // 1).  A rotation (c, s, t = s/c) of the true columns becomes
@@ -330,7 +349,7 @@ __global__ __launch_bounds__(NT) void osj_round_kernel(double* __restrict__ Gc, 
   // rotations per column per launch: d >= 2^-16, no underflow).
   constexpr bool CROSS = (MODE == 1);
   constexpr int C2 = 2 * CB;
-  constexpr int NSTEP = (DBG == 5 || DBG == 6) ? 0 : (DBG == 7 ? 4 : (CROSS ? CB : C2 - 1));
+  constexpr int NSTEP = CROSS ? CB : C2 - 1;
   constexpr int NW = NT / 64;
   __shared__ double part[2][NW][C2];  // double-buffered cross-wave partial sums
   __shared__ double nrm[NW][C2];      // per-wave private copies: true squared column norms,
@@ -387,7 +406,7 @@ __global__ __launch_bounds__(NT) void osj_round_kernel(double* __restrict__ Gc, 
     int idx;
     const double t = wave_treduce<CB>(dv, lane, idx);
     if ((lane & ((64 / CB) - 1)) == 0) part[buf][wave][idx] = t;
-    if constexpr (DBG != 3) __syncthreads();
+    __syncthreads();
     if (lane < CB) {  // every wave computes all CB rotations redundantly: no second barrier
       double raw = 0.0;
 #pragma unroll
@@ -407,11 +426,7 @@ __global__ __launch_bounds__(NT) void osj_round_kernel(double* __restrict__ Gc, 
       const double pq = raw * dp * dq;
       active |= osj_pair_active(pq * pq, nrm[wave][p], nrm[wave][q], small2, OSJ_CONV_COS2_ROW);
       double c = 1.0, tt = 0.0, npp, nqq;
-      if constexpr (DBG == 2) {
-        c = 0.8; tt = 0.75; npp = nrm[wave][p] + pq; nqq = nrm[wave][q];
-      } else {
-        osj_rotation_t(nrm[wave][p], nrm[wave][q], pq, c, tt, npp, nqq);
-      }
+      osj_rotation_t(nrm[wave][p], nrm[wave][q], pq, c, tt, npp, nqq);
       double tp = 0.0, tq = 0.0;
       if (tt != 0.0) {
         const double ip = isc[wave][p], iq = isc[wave][q];
@@ -433,12 +448,8 @@ __global__ __launch_bounds__(NT) void osj_round_kernel(double* __restrict__ Gc, 
       const double2 t2 = tau[wave][k];
       const int p = osj_sched_p<CROSS>(C2, step, k), q = osj_sched_q<CROSS>(C2, step, k);
       const double xp = x[p], xq = x[q];
-      if constexpr (DBG == 4) {
-        x[p] = xp + t2.x;
-      } else {
-        x[p] = fma(-t2.x, xq, xp);
-        x[q] = fma(t2.y, xp, xq);
-      }
+      x[p] = fma(-t2.x, xq, xp);
+      x[q] = fma(t2.y, xp, xq);
     }
   }
   // de Rijk at block level: store the columns by descending norm (large columns first speeds up the
@@ -953,10 +964,11 @@ __global__ __launch_bounds__(1024) void osjq_prep_direct_kernel(OsjqCtl* __restr
 
 template <int RP>
 static void osjq_launch(EigPlan* p, hipStream_t st) {
-  const int nb = p->ldn / OSJ_CB, upr = nb / 2;
-  if (p->trd) {
+  const int ldn = p->c.ldn, nb = ldn / OSJ_CB, upr = nb / 2;
+  const bool behind_direct = p->c.direct == EigDirect::Trd;
+  if (behind_direct) {
     hipLaunchKernelGGL(osjq_prep_direct_kernel, dim3(1), dim3(1024), 0, st, p->qctl, p->q, p->qcap, p->qdone, p->qclean, p->batch,
-                       upr, p->rep, p->trd_done, p->Gc, p->ldn, p->notconv ? p->sweeps * p->rps : 0, p->notconv ? p->trace : nullptr,
+                       upr, p->rep, p->trd_done, p->Gc, ldn, p->notconv ? p->sweeps * p->c.rps : 0, p->notconv ? p->trace : nullptr,
                        p->notconv);
   } else {
     hipLaunchKernelGGL(osjq_zero_kernel, dim3(cdiv(p->qcap, 1024)), dim3(1024), 0, st, p->q, p->qcap, p->qctl);
@@ -968,22 +980,22 @@ static void osjq_launch(EigPlan* p, hipStream_t st) {
   // 2 resident workgroups per CU; fewer than that is fine too (nobody waits for a particular workgroup to be resident).
   // Behind the direct solver the queue only ever holds the few matrices its certificate rejected: a small grid then, so that
   // the usual launch -- which finds nothing to do -- does not make 512 workgroups wait for 64 KB of LDS each
-  const long cap = p->trd ? 64 : 512;
+  const long cap = behind_direct ? 64 : 512;
   const int grid = (int)(units < cap ? units : cap);
-  hipLaunchKernelGGL((osjq_kernel<RP>), dim3(grid), dim3(256), 0, st, p->Gc, p->ldn, nb, p->batch, p->sweeps, p->sort_from,
-                     p->notconv, p->trace, p->q, p->qcap, p->qctl, p->qdone, p->qclean, p->q_timeout, p->err_out);
+  hipLaunchKernelGGL((osjq_kernel<RP>), dim3(grid), dim3(256), 0, st, p->Gc, ldn, nb, p->batch, p->sweeps,
+                     p->c.sort ? 0 : 1 << 30 /* first sweep that sorts */, p->notconv, p->trace, p->q, p->qcap, p->qctl, p->qdone, p->qclean, p->q_timeout, p->err_out);
 }
 
 // orders <= 256: round 0 carries the pairs inside the blocks, nb - 1 launches per sweep
 template <int RP>
 static void osjw_launch_sweep(EigPlan* p, int sweep, hipStream_t st) {
-  const int nb = p->ldn / OSJ_CB;
-  const int so = sweep >= p->sort_from ? 1 : 0;
-  const int rps = p->rps;  // nb - 1
-  hipLaunchKernelGGL((osjw_kernel<RP, 8, true>), dim3(nb / 2, p->batch), dim3(256), 0, st, p->Gc, p->ldn, nb, 0,
+  const int ldn = p->c.ldn, nb = ldn / OSJ_CB;
+  const int so = p->c.sort ? 1 : 0;
+  const int rps = p->c.rps;  // nb - 1
+  hipLaunchKernelGGL((osjw_kernel<RP, 8, true>), dim3(nb / 2, p->batch), dim3(256), 0, st, p->Gc, ldn, nb, 0,
                      p->notconv, sweep * rps, rps, p->trace, so, p->jrep);
   for (int round = 1; round < nb - 1; ++round)
-    hipLaunchKernelGGL((osjw_kernel<RP, 8, false>), dim3(nb / 2, p->batch), dim3(256), 0, st, p->Gc, p->ldn, nb,
+    hipLaunchKernelGGL((osjw_kernel<RP, 8, false>), dim3(nb / 2, p->batch), dim3(256), 0, st, p->Gc, ldn, nb,
                        round, p->notconv, sweep * rps + round, rps, p->trace, so, p->jrep);
 }
 
@@ -1060,13 +1072,13 @@ __global__ void osj_extract_kernel(const double* __restrict__ Gc, const double* 
 template <int NT>
 static void osjw4_launch_sweep(EigPlan* p, int sweep, hipStream_t st) {
   constexpr int RP = NT / 64;
-  const int nb = p->ldn / OSJ_CB;
-  const int rps = p->rps;  // nb: the intra-block launch + nb - 1 block-pair rounds
-  hipLaunchKernelGGL((osj_round_kernel<OSJ_CB / 2, NT, 2>), dim3(nb, p->batch), dim3(NT), 0, st, p->Gc, p->n, p->ldn,
-                     2 * nb, 0, p->notconv, sweep * rps, rps, p->trace, p->sortcols, p->jrep);
-  const int so = sweep >= p->sort_from ? 1 : 0;
+  const int ldn = p->c.ldn, nb = ldn / OSJ_CB;
+  const int rps = p->c.rps;  // nb: the intra-block launch + nb - 1 block-pair rounds
+  const int so = p->c.sort ? 1 : 0;
+  hipLaunchKernelGGL((osj_round_kernel<OSJ_CB / 2, NT, 2>), dim3(nb, p->batch), dim3(NT), 0, st, p->Gc, p->n, ldn,
+                     2 * nb, 0, p->notconv, sweep * rps, rps, p->trace, so, p->jrep);
   for (int round = 0; round < nb - 1; ++round)
-    hipLaunchKernelGGL((osjw_kernel<RP, 4, false>), dim3(nb / 2, p->batch), dim3(512), 0, st, p->Gc, p->ldn, nb, round,
+    hipLaunchKernelGGL((osjw_kernel<RP, 4, false>), dim3(nb / 2, p->batch), dim3(512), 0, st, p->Gc, ldn, nb, round,
                        p->notconv, sweep * rps + 1 + round, rps, p->trace, so, p->jrep);
 }
 
@@ -1075,58 +1087,55 @@ static void osj_launch_sweep(EigPlan* p, int sweep, hipStream_t st) {
   // one sweep = every column pair exactly once: one INTRA launch (pairs inside each group of 2*CB
   // columns... i.e. inside each block pair (2b, 2b+1)) followed by the block-pair rounds; the pair
   // (2b, 2b+1) itself meets in the round-robin too, where only its CROSS pairs are left to do.
-  const int nb = p->ldn / OSJ_CB;
+  const int ldn = p->c.ldn, nb = ldn / OSJ_CB;
   // INTRA: pairs within each single block.  Run as MODE 2 on "super blocks" of 2*CB columns would also
   // rotate the cross pairs of (2b, 2b+1); instead launch MODE 2 with half-size blocks: CB/2 columns per
   // block -> 2*(CB/2) = CB columns per workgroup = exactly one block.
-  const int rps = p->rps;  // nb
-  hipLaunchKernelGGL((osj_round_kernel<OSJ_CB / 2, NT, 2>), dim3(nb, p->batch), dim3(NT), 0, st, p->Gc, p->n, p->ldn,
-                     2 * nb, 0, p->notconv, sweep * rps, rps, p->trace, p->sortcols, p->jrep);
+  const int rps = p->c.rps;  // nb
+  const int so = p->c.sort ? 1 : 0;
+  hipLaunchKernelGGL((osj_round_kernel<OSJ_CB / 2, NT, 2>), dim3(nb, p->batch), dim3(NT), 0, st, p->Gc, p->n, ldn,
+                     2 * nb, 0, p->notconv, sweep * rps, rps, p->trace, so, p->jrep);
   for (int round = 0; round < nb - 1; ++round)
-    hipLaunchKernelGGL((osj_round_kernel<OSJ_CB, NT, 1>), dim3(nb / 2, p->batch), dim3(NT), 0, st, p->Gc, p->n, p->ldn,
-                       nb, round, p->notconv, sweep * rps + 1 + round, rps, p->trace, p->sortcols, p->jrep);
+    hipLaunchKernelGGL((osj_round_kernel<OSJ_CB, NT, 1>), dim3(nb / 2, p->batch), dim3(NT), 0, st, p->Gc, p->n, ldn,
+                       nb, round, p->notconv, sweep * rps + 1 + round, rps, p->trace, so, p->jrep);
 }
 
+// The Jacobi's launches of one solve: the queue's few kernels, or `sweeps` sweeps of launch-per-round kernels
 static int osj_enqueue_sweeps(EigPlan* p, hipStream_t st) {
-  if (p->use_queue) {
-    switch (p->ldn) {
-      case 64: osjq_launch<1>(p, st); break;
-      case 128: osjq_launch<2>(p, st); break;
-      case 192: osjq_launch<3>(p, st); break;
-      default: osjq_launch<4>(p, st); break;
-    }
-    MUSED_LAUNCH_CHECK();
-    return MUSED_OK;
-  }
-  for (int sw = 0; sw < p->sweeps; ++sw) {
-    if (p->wavek) {
-      switch (p->ldn) {
-        case 64: osjw_launch_sweep<1>(p, sw, st); break;
-        case 128: osjw_launch_sweep<2>(p, sw, st); break;
-        case 192: osjw_launch_sweep<3>(p, sw, st); break;
-        case 256: osjw_launch_sweep<4>(p, sw, st); break;
-        case 320: osjw4_launch_sweep<320>(p, sw, st); break;
-        case 384: osjw4_launch_sweep<384>(p, sw, st); break;
-        case 448: osjw4_launch_sweep<448>(p, sw, st); break;
-        default: osjw4_launch_sweep<512>(p, sw, st); break;
+  const int ldn = p->c.ldn;
+  switch (p->c.jacobi) {
+    case EigJacobi::Queue:
+      switch (ldn) {
+        case 64: osjq_launch<1>(p, st); break;
+        case 128: osjq_launch<2>(p, st); break;
+        case 192: osjq_launch<3>(p, st); break;
+        default: osjq_launch<4>(p, st); break;
       }
-      continue;
-    }
-    switch (p->ldn) {
-      case 64: osj_launch_sweep<64>(p, sw, st); break;
-      case 128: osj_launch_sweep<128>(p, sw, st); break;
-      case 192: osj_launch_sweep<192>(p, sw, st); break;
-      case 256: osj_launch_sweep<256>(p, sw, st); break;
-      case 320: osj_launch_sweep<320>(p, sw, st); break;
-      case 384: osj_launch_sweep<384>(p, sw, st); break;
-      case 448: osj_launch_sweep<448>(p, sw, st); break;
-      case 512: osj_launch_sweep<512>(p, sw, st); break;
-      case 640: osj_launch_sweep<640>(p, sw, st); break;
-      case 768: osj_launch_sweep<768>(p, sw, st); break;
-      case 896: osj_launch_sweep<896>(p, sw, st); break;
-      case 1024: osj_launch_sweep<1024>(p, sw, st); break;
-      default: set_error("osj: unsupported padded order %d", p->ldn); return MUSED_ERR_UNSUPPORTED;
-    }
+      break;
+    case EigJacobi::WaveGraph:
+      for (int sw = 0; sw < p->sweeps; ++sw) {
+        switch (ldn) {
+          case 64: osjw_launch_sweep<1>(p, sw, st); break;
+          case 128: osjw_launch_sweep<2>(p, sw, st); break;
+          case 192: osjw_launch_sweep<3>(p, sw, st); break;
+          case 256: osjw_launch_sweep<4>(p, sw, st); break;
+          case 320: osjw4_launch_sweep<320>(p, sw, st); break;
+          case 384: osjw4_launch_sweep<384>(p, sw, st); break;
+          case 448: osjw4_launch_sweep<448>(p, sw, st); break;
+          default: osjw4_launch_sweep<512>(p, sw, st); break;
+        }
+      }
+      break;
+    case EigJacobi::RowGraph:
+      for (int sw = 0; sw < p->sweeps; ++sw) {
+        switch (ldn) {
+          case 640: osj_launch_sweep<640>(p, sw, st); break;
+          case 768: osj_launch_sweep<768>(p, sw, st); break;
+          case 896: osj_launch_sweep<896>(p, sw, st); break;
+          default: osj_launch_sweep<1024>(p, sw, st); break;
+        }
+      }
+      break;
   }
   MUSED_LAUNCH_CHECK();
   return MUSED_OK;
@@ -1137,179 +1146,170 @@ static int osj_padded_order(int n) {
   return ((n + 127) / 128) * 128;
 }
 
-int eig_plan_create(int n, int batch, int sweeps, bool own_graph, EigPlan** out, const int* rep, int flags, int* err_out,
-                    int need) {
-  MUSED_REQUIRE(n >= 2 && n % 2 == 0 && n <= 1024 && batch >= 1 && sweeps >= 1,
-                "eig_plan_create: the order must be even and <= 1024 (n=%d)", n);
-  CaptureLock resource_guard(capture_mutex());  // allocations + capture: not beside another thread's capture
-  EigPlan* p = new EigPlan();
-  memset(p, 0, sizeof(*p));
-  p->n = n; p->batch = batch; p->sweeps = sweeps;
-  p->rep = rep;
-  p->jrep = rep;
-  p->err_out = err_out;
-  p->method = 1;
-  const size_t bytes = sizeof(double) * (size_t)batch * n * n;
-  if (p->method == 1) {
-    p->ldn = osj_padded_order(n);
-    MUSED_CHECK_HIP(hipMalloc(&p->G[0], bytes));
-    MUSED_CHECK_HIP(hipMalloc(&p->Gc, sizeof(double) * (size_t)batch * p->ldn * p->ldn));
-    MUSED_CHECK_HIP(hipMalloc(&p->lam, sizeof(double) * (size_t)batch * p->ldn));
-    const char* sf = getenv("MUSED_OSJ_SORT_FROM");
-    p->sort_from = sf ? atoi(sf) : 0;
-    const char* wk = getenv("MUSED_OSJ_WAVE");  // 0: row-per-thread kernel for every order
-    p->wavek = (p->ldn <= 512 && !(wk && wk[0] == '0')) ? 1 : 0;
-    const char* so = getenv("MUSED_OSJ_SORT");
-    p->sortcols = (so && so[0] == '0') ? 0 : 1;  // row-per-thread kernel only: helps on rank-deficient matrices
-    if (flags & EIG_PLAN_NO_SORT) {  // columns stay where they are (the caller reads parts of them by position)
-      p->sort_from = 1 << 30;
-      p->sortcols = 0;
-    }
-    {
-      const int nb0 = p->ldn / OSJ_CB;
-      p->rps = (p->wavek && p->ldn <= 256) ? (nb0 > 1 ? nb0 - 1 : 1) : nb0;
-    }
-    {
-      // persistent work-queue solver: wave-private kernel orders (<= 256), at most 255 global rounds per solve
-      // Default (MUSED_EIG_QUEUE unset): batches of at most 224 units per round (one sketch lane: 28 matrices x 4) --
-      // the persistent workgroups then occupy at most one slot on fewer than all CUs, so kernels of other streams
-      // (the adjacency / eigenstep chain, whose one-workgroup panel kernels need a whole CU) still find room.  Larger
-      // batches keep the launch-per-round graph: a persistent grid that fills the GPU for milliseconds would starve them.
-      // MUSED_EIG_QUEUE=1 / 0 forces it on / off.
-      const char* qe = getenv("MUSED_EIG_QUEUE");
-      const int nbq = p->ldn / OSJ_CB;
-      const bool fits = p->wavek && p->ldn <= 256 && nbq >= 2 && sweeps * (nbq - 1) <= 255 && batch <= (1 << 21);
-      bool want = qe ? (qe[0] == '1') : ((long)batch * (nbq / 2) <= 224);
-      {
-        // direct solver (MUSED_EIG_TRD=0 turns it off): orders up to 256, callers that read the leading pairs only -- the
-        // top half (FD rotation: those that survive the shrink are certified) or the `need` largest, all certified (eigenstep)
-        const char* te = getenv("MUSED_EIG_TRD");
-        p->trd_need = (flags & (EIG_PLAN_TOP_NEED | EIG_PLAN_TOP_FD)) ? need : ((flags & EIG_PLAN_TOP_HALF) ? n / 2 : 0);
-        p->trd_cert_all = (flags & EIG_PLAN_TOP_NEED) ? 1 : 0;
-        p->trd = (p->trd_need > 0 && trd_supports(n, p->ldn, p->trd_need) && fits && !(te && te[0] == '0')) ? 1 : 0;
-        if (p->trd) want = true;  // its rare rejects go through the one-launch queue solver (nothing queued: it exits at once)
-      }
-      p->use_queue = (fits && want) ? 1 : 0;
-      if (p->use_queue) {
-        p->qcap = (unsigned)((long)batch * (nbq / 2) * (nbq - 1) * sweeps);
-        MUSED_CHECK_HIP(hipMalloc(&p->q, sizeof(unsigned) * (size_t)p->qcap));
-        MUSED_CHECK_HIP(hipMalloc(&p->qctl, sizeof(OsjqCtl)));
-        MUSED_CHECK_HIP(hipMalloc(&p->qdone, sizeof(int) * (size_t)batch));
-        MUSED_CHECK_HIP(hipMalloc(&p->qclean, sizeof(int) * (size_t)batch));
-        MUSED_CHECK_HIP(hipMemset(p->qctl, 0, sizeof(OsjqCtl)));
-        MUSED_CHECK_HIP(hipMemset(p->q, 0, sizeof(unsigned) * (size_t)p->qcap));  // (cleared from now on only after use)
-        const char* tq = getenv("MUSED_EIG_QUEUE_TIMEOUT_TICKS");  // test knob: 1 forces the give-up path
-        p->q_timeout = tq ? strtoull(tq, nullptr, 10) : 300000000ull;
-      }
-      if (p->trd) {
-        int rc_t = trd_prepare();
-        if (rc_t) return rc_t;
-        MUSED_CHECK_HIP(hipMalloc(&p->trd_ws, sizeof(double) * trd_workspace_doubles(batch)));
-        MUSED_CHECK_HIP(hipMalloc(&p->trd_done, sizeof(int) * (size_t)batch));
-      } else if (p->trd_need > 0 && trdx_supports(p->ldn, p->trd_need) &&
-                 !(getenv("MUSED_EIG_TRD") && getenv("MUSED_EIG_TRD")[0] == '0')) {
-        // orders 320 .. 1024: blocked direct solver; the sweep graph below runs on the matrices it rejects (jrep)
-        p->trd = 2;
-        int rc_t = trdx_prepare(p->ldn);
-        if (rc_t) return rc_t;
-        MUSED_CHECK_HIP(hipMalloc(&p->trd_ws, sizeof(double) * trdx_workspace_doubles(p->ldn, batch)));
-        MUSED_CHECK_HIP(hipMalloc(&p->trd_done, sizeof(int) * (size_t)batch));
-        MUSED_CHECK_HIP(hipMalloc(&p->trdx_act, sizeof(int) * (size_t)batch));
-        MUSED_CHECK_HIP(hipMalloc(&p->trdx_jrep, sizeof(int) * (size_t)batch));
-        MUSED_CHECK_HIP(hipMalloc(&p->trdx_nrej, sizeof(int)));
-        MUSED_CHECK_HIP(hipHostMalloc((void**)&p->trdx_nrej_host, sizeof(int), hipHostMallocDefault));
-        MUSED_CHECK_HIP(hipEventCreateWithFlags(&p->trdx_ev, hipEventDisableTiming));
-        p->jrep = p->trdx_jrep;
-      }
-    }
-    // Adaptive sweep count (default; MUSED_EIG_ADAPTIVE=0: always `sweeps` sweeps): `sweeps` is the cap, a matrix
-    // stops after the first sweep that met no column pair with cos^2 above the threshold (osj_pair_active).  How many sweeps
-    // that takes depends on the matrix (full-rank sketch buffers ~10 at order 256, rank-deficient ones up to 16).
-    const char* ad = getenv("MUSED_EIG_ADAPTIVE");
-    if (!(ad && ad[0] == '0') && !(flags & EIG_PLAN_FIXED_SWEEPS)) {
-      // [trace (batch doubles) | work counter (1 x u64) | flags (batch * sweeps ints)]
-      MUSED_CHECK_HIP(hipMalloc(&p->trace, sizeof(double) * ((size_t)batch + 1) + sizeof(int) * (size_t)batch * sweeps * p->rps));
-      p->work = (unsigned long long*)(p->trace + batch);
-      p->notconv = (int*)(p->trace + batch + 1);
-      MUSED_CHECK_HIP(hipMemset(p->work, 0, 8));
-    }
-  }
-  p->have_graph = false;
+static EigEnv eig_read_env() {
+  EigEnv e;
+  const char* te = getenv("MUSED_EIG_TRD");
+  e.trd = !(te && te[0] == '0');
+  const char* qe = getenv("MUSED_EIG_QUEUE");
+  e.queue = qe ? (qe[0] == '1' ? 1 : 0) : -1;
   const char* ng = getenv("MUSED_NO_GRAPH");
-  if (own_graph && !(ng && ng[0] == '1')) {
+  e.graph = !(ng && ng[0] == '1');
+  const char* tq = getenv("MUSED_EIG_QUEUE_TIMEOUT_TICKS");  // test knob: 1 forces the give-up path
+  e.queue_timeout = tq ? strtoull(tq, nullptr, 10) : 300000000ull;
+  return e;
+}
+
+// THE decision: which solvers a plan of order n runs.  Pure (no HIP call, no allocation, no getenv).
+static EigChoice eig_choose(int n, int batch, int sweeps, int flags, int need, const EigEnv& env) {
+  EigChoice c;
+  c.ldn = osj_padded_order(n);
+  const int nb = c.ldn / OSJ_CB;  // >= 2
+  c.sort = !(flags & EIG_PLAN_NO_SORT);  // off: columns stay where they are (the caller reads parts of them by position)
+  // Adaptive sweep count (default): `sweeps` is the cap, a matrix stops after a sweep's worth of launch rounds that met no
+  // column pair with cos^2 above the threshold (osj_pair_active).  How many sweeps that takes depends on the matrix
+  // (full-rank sketch buffers ~10 at order 256, rank-deficient ones up to 16).
+  c.adaptive = !(flags & EIG_PLAN_FIXED_SWEEPS);
+  // callers that read the leading pairs only -- the top half (FD rotation: those that survive the shrink are certified) or the
+  // `need` largest, all certified (eigenstep)
+  c.need = (flags & (EIG_PLAN_TOP_NEED | EIG_PLAN_TOP_FD)) ? need : ((flags & EIG_PLAN_TOP_HALF) ? n / 2 : 0);
+  c.cert_all = (flags & EIG_PLAN_TOP_NEED) != 0;
+  // persistent work-queue solver: wave-private kernel orders (<= 256), at most 255 global rounds per solve
+  const bool queue_fits = c.ldn <= 256 && sweeps * (nb - 1) <= 255 && batch <= (1 << 21);
+  c.direct = EigDirect::None;
+  if (env.trd && c.need > 0) {
+    if (queue_fits && trd_supports(n, c.ldn, c.need))
+      c.direct = EigDirect::Trd;
+    else if (trdx_supports(c.ldn, c.need))
+      c.direct = EigDirect::Trdx;
+  }
+  // Default (MUSED_EIG_QUEUE unset): batches of at most 224 units per round (one sketch lane: 28 matrices x 4) --
+  // the persistent workgroups then occupy at most one slot on fewer than all CUs, so kernels of other streams
+  // (the adjacency / eigenstep chain, whose one-workgroup panel kernels need a whole CU) still find room.  Larger
+  // batches keep the launch-per-round graph: a persistent grid that fills the GPU for milliseconds would starve them.
+  // MUSED_EIG_QUEUE=1 / 0 forces it on / off.  Behind the register-resident direct solver it is always the queue: the
+  // rare rejects go through its one launch (nothing queued: it exits at once).
+  const bool want_queue =
+      c.direct == EigDirect::Trd || (env.queue >= 0 ? env.queue == 1 : (long)batch * (nb / 2) <= 224);
+  c.jacobi = (queue_fits && want_queue) ? EigJacobi::Queue : (c.ldn <= 512 ? EigJacobi::WaveGraph : EigJacobi::RowGraph);
+  c.rps = c.ldn <= 256 ? nb - 1 : nb;
+  return c;
+}
+
+static int eig_plan_create_impl(EigPlan* p, const EigEnv& env, bool own_graph) {
+  const EigChoice& c = p->c;
+  const size_t batch = (size_t)p->batch, ldn = (size_t)c.ldn;
+  if (p->n != c.ldn) MUSED_CHECK_HIP(hipMalloc(&p->G, sizeof(double) * batch * p->n * p->n));
+  MUSED_CHECK_HIP(hipMalloc(&p->Gc, sizeof(double) * batch * ldn * ldn));
+  MUSED_CHECK_HIP(hipMalloc(&p->lam, sizeof(double) * batch * ldn));
+  if (c.jacobi == EigJacobi::Queue) {
+    const int nb = c.ldn / OSJ_CB;
+    p->qcap = (unsigned)((long)p->batch * (nb / 2) * (nb - 1) * p->sweeps);
+    p->q_timeout = env.queue_timeout;
+    MUSED_CHECK_HIP(hipMalloc(&p->q, sizeof(unsigned) * (size_t)p->qcap));
+    MUSED_CHECK_HIP(hipMalloc(&p->qctl, sizeof(OsjqCtl)));
+    MUSED_CHECK_HIP(hipMalloc(&p->qdone, sizeof(int) * batch));
+    MUSED_CHECK_HIP(hipMalloc(&p->qclean, sizeof(int) * batch));
+    MUSED_CHECK_HIP(hipMemset(p->qctl, 0, sizeof(OsjqCtl)));
+    MUSED_CHECK_HIP(hipMemset(p->q, 0, sizeof(unsigned) * (size_t)p->qcap));  // (cleared from now on only after use)
+  }
+  int rc;
+  switch (c.direct) {
+    case EigDirect::None: break;
+    case EigDirect::Trd:
+      if ((rc = trd_prepare())) return rc;
+      MUSED_CHECK_HIP(hipMalloc(&p->trd_ws, sizeof(double) * trd_workspace_doubles(p->batch)));
+      MUSED_CHECK_HIP(hipMalloc(&p->trd_done, sizeof(int) * batch));
+      break;
+    case EigDirect::Trdx:  // the sweep graph below runs on the matrices it rejects (jrep)
+      if ((rc = trdx_prepare(c.ldn))) return rc;
+      MUSED_CHECK_HIP(hipMalloc(&p->trd_ws, sizeof(double) * trdx_workspace_doubles(c.ldn, p->batch)));
+      MUSED_CHECK_HIP(hipMalloc(&p->trd_done, sizeof(int) * batch));
+      MUSED_CHECK_HIP(hipMalloc(&p->trdx_act, sizeof(int) * batch));
+      MUSED_CHECK_HIP(hipMalloc(&p->trdx_jrep, sizeof(int) * batch));
+      MUSED_CHECK_HIP(hipMalloc(&p->trdx_nrej, sizeof(int)));
+      MUSED_CHECK_HIP(hipHostMalloc((void**)&p->trdx_nrej_host, sizeof(int), hipHostMallocDefault));
+      MUSED_CHECK_HIP(hipEventCreateWithFlags(&p->trdx_ev, hipEventDisableTiming));
+      p->jrep = p->trdx_jrep;
+      break;
+  }
+  if (c.adaptive) {
+    // [trace (batch doubles) | work counter (1 x u64) | flags (batch * sweeps * rps ints)]
+    MUSED_CHECK_HIP(hipMalloc(&p->trace, sizeof(double) * (batch + 1) + sizeof(int) * batch * p->sweeps * c.rps));
+    p->work = (unsigned long long*)(p->trace + batch);
+    p->notconv = (int*)(p->trace + batch + 1);
+    MUSED_CHECK_HIP(hipMemset(p->work, 0, 8));
+  }
+  if (own_graph && env.graph) {
     MUSED_CHECK_HIP(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));
     MUSED_CHECK_HIP(hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = osj_enqueue_sweeps(p, p->cap_stream);
-    hipError_t e = hipStreamEndCapture(p->cap_stream, &p->graph);
-    if (rc < 0 || e != hipSuccess) {
-      set_error("eig_plan_create: graph capture failed (%s)", hipGetErrorString(e));
-      return MUSED_ERR_HIP;
-    }
+    p->capturing = true;  // (a failure from here on: eig_plan_destroy ends the capture)
+    if ((rc = osj_enqueue_sweeps(p, p->cap_stream))) return rc;
+    p->capturing = false;
+    MUSED_CHECK_HIP(hipStreamEndCapture(p->cap_stream, &p->graph));
     MUSED_CHECK_HIP(hipGraphInstantiate(&p->exec, p->graph, nullptr, nullptr, 0));
-    p->have_graph = true;
     // the capture stream has done its job: every live HIP stream competes for the few hardware queues the user's
     // streams are mapped onto (two sketch groups + the main path need three of them undisturbed)
     (void)hipStreamDestroy(p->cap_stream);
     p->cap_stream = nullptr;
   }
+  return MUSED_OK;
+}
+
+int eig_plan_create(int n, int batch, int sweeps, bool own_graph, EigPlan** out, const int* rep, int flags, int* err_out,
+                    int need) {
+  MUSED_REQUIRE(n >= 2 && n % 2 == 0 && n <= 1024 && batch >= 1 && sweeps >= 1,
+                "eig_plan_create: the order must be even and <= 1024 (n=%d)", n);
+  CaptureLock resource_guard(capture_mutex());  // allocations + capture: not beside another thread's capture
+  const EigEnv env = eig_read_env();
+  EigPlan* p = new EigPlan();
+  p->n = n; p->batch = batch; p->sweeps = sweeps;
+  p->rep = p->jrep = rep;
+  p->err_out = err_out;
+  p->c = eig_choose(n, batch, sweeps, flags, need, env);
+  const int rc = eig_plan_create_impl(p, env, own_graph);
+  if (rc) {  // release what the earlier steps took (the error message of the first failure is kept)
+    eig_plan_destroy(p);
+    return rc;
+  }
   *out = p;
   return MUSED_OK;
 }
 
+// Copes with every partial state eig_plan_create_impl can leave behind.
 void eig_plan_destroy(EigPlan* p) {
   if (!p) return;
   CaptureLock resource_guard(capture_mutex());
-  if (p->have_graph) {
-    (void)hipGraphExecDestroy(p->exec);
-    (void)hipGraphDestroy(p->graph);
-    if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
+  if (p->capturing) {  // creation failed inside the capture: end it and drop whatever it recorded
+    hipGraph_t g = nullptr;
+    (void)hipStreamEndCapture(p->cap_stream, &g);
+    if (g) (void)hipGraphDestroy(g);
   }
-  for (int i = 0; i < 2; ++i) {
-    if (p->G[i]) (void)hipFree(p->G[i]);
-    if (p->V[i]) (void)hipFree(p->V[i]);
-  }
-  if (p->Gc) (void)hipFree(p->Gc);
-  if (p->lam) (void)hipFree(p->lam);
-  if (p->trace) (void)hipFree(p->trace);
-  if (p->q) (void)hipFree(p->q);
-  if (p->qctl) (void)hipFree(p->qctl);
-  if (p->qdone) (void)hipFree(p->qdone);
-  if (p->qclean) (void)hipFree(p->qclean);
-  if (p->trd_ws) (void)hipFree(p->trd_ws);
-  if (p->trd_done) (void)hipFree(p->trd_done);
-  if (p->trdx_act) (void)hipFree(p->trdx_act);
-  if (p->trdx_jrep) (void)hipFree(p->trdx_jrep);
-  if (p->trdx_nrej) (void)hipFree(p->trdx_nrej);
+  if (p->exec) (void)hipGraphExecDestroy(p->exec);
+  if (p->graph) (void)hipGraphDestroy(p->graph);
+  if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
+  void* bufs[] = {p->G,      p->Gc,       p->lam,      p->trace,     p->q,        p->qctl, p->qdone,
+                  p->qclean, p->trd_ws,   p->trd_done, p->trdx_act,  p->trdx_jrep, p->trdx_nrej};
+  for (void* b : bufs)
+    if (b) (void)hipFree(b);
   if (p->trdx_nrej_host) (void)hipHostFree(p->trdx_nrej_host);
   if (p->trdx_ev) (void)hipEventDestroy(p->trdx_ev);
-  if (p->ev0) {
-    for (size_t i = 0; i < p->ev0->size(); ++i) {
-      (void)hipEventDestroy((*p->ev0)[i]);
-      (void)hipEventDestroy((*p->ev1)[i]);
-      if (p->evm) (void)hipEventDestroy((*p->evm)[i]);
-    }
-    delete p->ev0;
-    delete p->ev1;
-    delete p->evm;
-  }
+  for (auto* v : {&p->ev0, &p->ev1, &p->evm})
+    for (hipEvent_t e : *v) (void)hipEventDestroy(e);
   delete p;
 }
 
-
-// Live timing of the Jacobi sweeps: between enable and read every replay of the sweep graph is bracketed
-// by HIP events on the launch stream.  Read (blocking) returns the summed duration, the number of
-// osj_round_kernel launches it covers and the bytes one launch moves (every matrix element read once
-// and written once).
+// Live timing: between enable and read every solve is bracketed by HIP events on the launch stream -- the direct solver
+// alone on plans that run one (eig_plan_profile_read_direct), else the Jacobi (eig_plan_profile_read).
 int eig_plan_profile(EigPlan* p, bool on) {
-  if (!p || p->method != 1) return MUSED_OK;
-  if (on && !p->ev0) {
-    p->ev0 = new std::vector<hipEvent_t>(2048);
-    p->ev1 = new std::vector<hipEvent_t>(2048);
-    if (p->trd) p->evm = new std::vector<hipEvent_t>(2048);
-    for (size_t i = 0; i < p->ev0->size(); ++i) {
-      MUSED_CHECK_HIP(hipEventCreate(&(*p->ev0)[i]));
-      MUSED_CHECK_HIP(hipEventCreate(&(*p->ev1)[i]));
-      if (p->evm) MUSED_CHECK_HIP(hipEventCreate(&(*p->evm)[i]));
+  if (!p) return MUSED_OK;
+  if (on && p->ev0.empty()) {
+    for (auto* v : {&p->ev1, &p->evm, &p->ev0}) {  // ev0 last: once it holds events, every vector is complete
+      if (v == &p->evm && p->c.direct == EigDirect::None) continue;
+      while (v->size() < 2048) {
+        hipEvent_t e;
+        MUSED_CHECK_HIP(hipEventCreate(&e));
+        v->push_back(e);
+      }
     }
   }
   p->prof = on;
@@ -1320,19 +1320,19 @@ int eig_plan_profile(EigPlan* p, bool on) {
   return MUSED_OK;
 }
 
+// Read (blocking) returns the summed duration of the Jacobi, the number of launch rounds it covers and the bytes one
+// launch moves (every matrix element read once and written once).
 int eig_plan_profile_read(EigPlan* p, double* total_ms, long* launches, double* bytes_per_launch) {
   *total_ms = 0.0; *launches = 0; *bytes_per_launch = 0.0;
-  if (!p || p->method != 1 || !p->ev0) return MUSED_OK;
+  if (!p || p->ev0.empty()) return MUSED_OK;
   for (int i = 0; i < p->prof_n; ++i) {
-    MUSED_CHECK_HIP(hipEventSynchronize((*p->ev1)[i]));
+    MUSED_CHECK_HIP(hipEventSynchronize(p->ev1[i]));
     float ms = 0.f;
-    MUSED_CHECK_HIP(hipEventElapsedTime(&ms, (*p->ev0)[i], (*p->ev1)[i]));
+    MUSED_CHECK_HIP(hipEventElapsedTime(&ms, p->ev0[i], p->ev1[i]));
     *total_ms += ms;
   }
-  const int nb = p->ldn / OSJ_CB;
   // per sweep: (nb - 1) block-pair rounds, plus one launch for the pairs inside the blocks in the row-per-thread kernel
-  *launches = (long)p->prof_n * p->sweeps * p->rps;
-  (void)nb;
+  *launches = (long)p->prof_n * p->sweeps * p->c.rps;
   // a launch reads and writes every element of every matrix that is still iterating; with the adaptive sweep
   // count the launches of later sweeps find fewer (or no) such matrices: average over the launches timed
   double frac = 1.0;
@@ -1340,23 +1340,23 @@ int eig_plan_profile_read(EigPlan* p, double* total_ms, long* launches, double* 
     unsigned long long w = 0;
     CaptureLock guard(capture_mutex());  // (a blocking legacy-stream copy: not beside another thread's stream capture)
     MUSED_CHECK_HIP(hipMemcpy(&w, p->work, 8, hipMemcpyDeviceToHost));
-    frac = (double)w / ((double)p->prof_n * p->sweeps * p->rps * p->batch);
+    frac = (double)w / ((double)p->prof_n * p->sweeps * p->c.rps * p->batch);
   }
-  *bytes_per_launch = 16.0 * (double)p->batch * p->ldn * p->ldn * frac;
+  *bytes_per_launch = 16.0 * (double)p->batch * p->c.ldn * p->c.ldn * frac;
   return MUSED_OK;
 }
 
 int eig_plan_profile_read_direct(EigPlan* p, double* total_ms, long* launches, double* matrices_solved, double* tridiag_ms) {
   *total_ms = 0.0; *launches = 0; *matrices_solved = 0.0;
   if (tridiag_ms) *tridiag_ms = 0.0;
-  if (!p || !p->trd || !p->ev0) return MUSED_OK;
+  if (!p || p->c.direct == EigDirect::None || p->ev0.empty()) return MUSED_OK;
   for (int i = 0; i < p->prof_n; ++i) {
-    MUSED_CHECK_HIP(hipEventSynchronize((*p->ev1)[i]));
+    MUSED_CHECK_HIP(hipEventSynchronize(p->ev1[i]));
     float ms = 0.f;
-    MUSED_CHECK_HIP(hipEventElapsedTime(&ms, (*p->ev0)[i], (*p->ev1)[i]));
+    MUSED_CHECK_HIP(hipEventElapsedTime(&ms, p->ev0[i], p->ev1[i]));
     *total_ms += ms;
-    if (tridiag_ms && p->evm) {
-      MUSED_CHECK_HIP(hipEventElapsedTime(&ms, (*p->ev0)[i], (*p->evm)[i]));
+    if (tridiag_ms) {
+      MUSED_CHECK_HIP(hipEventElapsedTime(&ms, p->ev0[i], p->evm[i]));
       *tridiag_ms += ms;
     }
   }
@@ -1370,157 +1370,106 @@ int eig_plan_profile_read_direct(EigPlan* p, double* total_ms, long* launches, d
   return MUSED_OK;
 }
 
-// Column-form access for callers that can use the raw result of the one-sided solver: after
-// eig_plan_run_inplace(p, nullptr, nullptr, ...) column j of matrix b, cols[(b * ld + j) * ld + 0..n), is
-// lam_j u_j and lam[b * ld + j] its norm (the eigenvalue).  Returns false for the two-sided fallback.
-bool eig_plan_columns(EigPlan* p, const double** cols, const double** lam, int* ld) {
-  const char* rw = getenv("MUSED_EIG_RAW");
-  if (p->method != 1 || (rw && rw[0] == '0')) return false;
-  *cols = p->Gc;
-  *lam = p->lam;
-  *ld = p->ldn;
-  return true;
+// The result in the one-sided solver's own form, valid after eig_plan_run_inplace(p, nullptr, nullptr, ...): column j of
+// matrix b, cols[(b * ld + j) * ld + 0..n), is lam_j u_j and lam[b * ld + j] its norm (the eigenvalue).
+EigColumns eig_plan_columns(EigPlan* p) { return {p->Gc, p->lam, p->c.ldn}; }
+
+bool eig_plan_direct_solver(EigPlan* p) { return p && p->c.direct != EigDirect::None; }
+
+// Where the caller writes the matrices (batch x n x n): the solver's working copy when the order needs no padding,
+// else the staging buffer the pack pass reads.
+double* eig_plan_input(EigPlan* p) { return p->G ? p->G : p->Gc; }
+
+// Direct phase: the leading pairs of every matrix that passes the solver's certificate; trd_done marks them.
+static int eig_run_direct(EigPlan* p, hipStream_t st, bool rec) {
+  unsigned long long* work = rec ? p->work : nullptr;
+  hipEvent_t after_a = rec ? p->evm[p->prof_n] : nullptr;
+  int rc;
+  if (p->c.direct == EigDirect::Trd) {
+    rc = trd_solve(p->Gc, p->n, p->c.ldn, p->c.need, p->c.cert_all, p->batch, p->rep, p->trd_done, p->trd_ws, st, nullptr, work,
+                   after_a, p->lam);
+  } else {
+    MUSED_CHECK_HIP(hipMemsetAsync(p->trdx_nrej, 0, sizeof(int), st));
+    rc = trdx_solve(p->Gc, p->c.ldn, p->c.need, p->c.cert_all, p->batch, p->rep, p->trd_done, p->trdx_act, p->trdx_jrep,
+                    p->trdx_nrej, p->trd_ws, st, work, after_a, nullptr, p->lam);
+  }
+  if (rc) return rc;
+  if (rec) {  // the events of a direct-solver plan bracket the direct solver alone (the Jacobi behind it only sees rejects)
+    MUSED_CHECK_HIP(hipEventRecord(p->ev1[p->prof_n], st));
+    ++p->prof_n;
+  }
+  return MUSED_OK;
 }
 
-bool eig_plan_direct_solver(EigPlan* p) { return p && p->trd != 0; }
-
-// Input buffer for a caller that writes the matrices itself; when the order needs no padding this is the
-// solver's working copy (no pack pass).
-double* eig_plan_input(EigPlan* p) {
-  const char* dd = getenv("MUSED_EIG_DIRECT");
-  if (p->method == 1 && p->n == p->ldn && !(dd && dd[0] == '0')) {
-    p->direct = true;
-    return p->Gc;
-  }
-  return p->G[0];
+// Does the Jacobi have anything to do?  Only the blocked direct solver can say no.
+static int eig_jacobi_needed(EigPlan* p, hipStream_t st, bool* needed) {
+  *needed = true;
+  if (p->c.direct != EigDirect::Trdx) return MUSED_OK;
+  // The blocked direct solver's fallback is the sweep graph: sweeps x rounds launches over the whole batch, each of which
+  // only finds out on the device that it has nothing to do (12 % of config 3's kernel time when it was launched
+  // unconditionally).  A rejection is rare, a solve of these orders takes milliseconds: the host waits for the count
+  // (an event on this stream: safe beside other threads' captures) and launches the graph only when it is not zero.
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(st, &cs);
+  if (cs != hipStreamCaptureStatusNone) return MUSED_OK;
+  MUSED_CHECK_HIP(hipMemcpyAsync(p->trdx_nrej_host, p->trdx_nrej, sizeof(int), hipMemcpyDeviceToHost, st));
+  MUSED_CHECK_HIP(hipEventRecord(p->trdx_ev, st));
+  MUSED_CHECK_HIP(hipEventSynchronize(p->trdx_ev));
+  *needed = *p->trdx_nrej_host != 0;
+  return MUSED_OK;
 }
 
 int eig_plan_run_inplace(EigPlan* p, double* evals, double* V, hipStream_t st, bool allow_graph) {
-  if (p->method == 1) {
-    const long per = (long)p->ldn * p->ldn;
-    if (!p->direct)
-      hipLaunchKernelGGL(osj_pack_kernel, dim3(cdiv(per, 256), p->batch), dim3(256), 0, st, p->G[0], p->n, p->ldn, p->Gc);
-    if (p->notconv && !(p->trd == 1))  // (behind the register-resident direct solver the queue's set-up kernel does it, for the
-      hipLaunchKernelGGL(osj_begin_kernel, dim3(p->batch), dim3(64), 0, st, p->Gc, p->ldn, p->sweeps * p->rps, p->trace,   // rejected matrices only)
-                         p->notconv);
-    const bool rec = p->prof && p->ev0 && p->prof_n < (int)p->ev0->size();
-    if (rec) MUSED_CHECK_HIP(hipEventRecord((*p->ev0)[p->prof_n], st));
-    if (p->trd) {
-      if (p->trd == 2) MUSED_CHECK_HIP(hipMemsetAsync(p->trdx_nrej, 0, sizeof(int), st));
-      const int rc = p->trd == 2
-                         ? trdx_solve(p->Gc, p->ldn, p->trd_need, p->trd_cert_all != 0, p->batch, p->rep, p->trd_done, p->trdx_act,
-                                      p->trdx_jrep, p->trdx_nrej, p->trd_ws, st, rec ? p->work : nullptr,
-                                      (rec && p->evm) ? (*p->evm)[p->prof_n] : nullptr, nullptr, p->lam)
-                         : trd_solve(p->Gc, p->n, p->ldn, p->trd_need, p->trd_cert_all != 0, p->batch, p->rep, p->trd_done,
-                                     p->trd_ws, st, nullptr, rec ? p->work : nullptr,
-                                     (rec && p->evm) ? (*p->evm)[p->prof_n] : nullptr, p->lam);
-      if (rc) return rc;
-      if (rec) {  // the events of a direct-solver plan bracket the direct solver alone (the Jacobi behind it only sees rejects)
-        MUSED_CHECK_HIP(hipEventRecord((*p->ev1)[p->prof_n], st));
-        ++p->prof_n;
-      }
-    }
-    bool run_jacobi = true;
-    if (p->trd == 2) {
-      // The blocked direct solver's fallback is the sweep graph: sweeps x rounds launches over the whole batch, each of which
-      // only finds out on the device that it has nothing to do (12 % of config 3's kernel time when it was launched
-      // unconditionally).  A rejection is rare, a solve of these orders takes milliseconds: the host waits for the count
-      // (an event on this stream: safe beside other threads' captures) and launches the graph only when it is not zero.
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      (void)hipStreamIsCapturing(st, &cs);
-      if (cs == hipStreamCaptureStatusNone) {
-        MUSED_CHECK_HIP(hipMemcpyAsync(p->trdx_nrej_host, p->trdx_nrej, sizeof(int), hipMemcpyDeviceToHost, st));
-        MUSED_CHECK_HIP(hipEventRecord(p->trdx_ev, st));
-        MUSED_CHECK_HIP(hipEventSynchronize(p->trdx_ev));
-        run_jacobi = *p->trdx_nrej_host != 0;
-      }
-    }
-    if (!run_jacobi) {
-    } else if (p->have_graph && allow_graph) {
-      MUSED_CHECK_HIP(hipGraphLaunch(p->exec, st));
-    } else {
-      const int rc = osj_enqueue_sweeps(p, st);
-      if (rc) return rc;
-    }
-    if (rec && !p->trd) {
-      MUSED_CHECK_HIP(hipEventRecord((*p->ev1)[p->prof_n], st));
-      ++p->prof_n;
-      if (p->notconv)
-        hipLaunchKernelGGL(osj_count_kernel, dim3(1), dim3(256), 0, st, p->notconv, p->batch, p->sweeps * p->rps, p->rps,
-                           p->work, p->rep);
-    }
-    hipLaunchKernelGGL(osj_norms_kernel, dim3(cdiv(p->ldn, 4), p->batch), dim3(256), 0, st, p->Gc, p->ldn, p->lam,
-                       p->trd ? p->trd_done : (const int*)nullptr);
-    if (evals)
-      hipLaunchKernelGGL(osj_extract_kernel, dim3(cdiv((long)p->n * p->n, 256), p->batch), dim3(256), 0, st, p->Gc, p->lam,
-                         p->n, p->ldn, evals, V);
-    MUSED_LAUNCH_CHECK();
-    return MUSED_OK;
+  const EigChoice& c = p->c;
+  const bool direct = c.direct != EigDirect::None;
+  int rc;
+  if (p->G) {
+    const long per = (long)c.ldn * c.ldn;
+    hipLaunchKernelGGL(osj_pack_kernel, dim3(cdiv(per, 256), p->batch), dim3(256), 0, st, p->G, p->n, c.ldn, p->Gc);
   }
-  set_error("eig_plan_run_inplace: unsupported solver");
-  return MUSED_ERR_STATE;
+  // (behind the register-resident direct solver the queue's set-up kernel does it, for the rejected matrices only)
+  if (p->notconv && c.direct != EigDirect::Trd)
+    hipLaunchKernelGGL(osj_begin_kernel, dim3(p->batch), dim3(64), 0, st, p->Gc, c.ldn, p->sweeps * c.rps, p->trace, p->notconv);
+  const bool rec = p->prof && p->prof_n < (int)p->ev0.size();
+  if (rec) MUSED_CHECK_HIP(hipEventRecord(p->ev0[p->prof_n], st));
+  if (direct && (rc = eig_run_direct(p, st, rec))) return rc;
+  bool jacobi = true;
+  if ((rc = eig_jacobi_needed(p, st, &jacobi))) return rc;
+  if (jacobi) {
+    if (p->exec && allow_graph)
+      MUSED_CHECK_HIP(hipGraphLaunch(p->exec, st));
+    else if ((rc = osj_enqueue_sweeps(p, st)))
+      return rc;
+  }
+  if (rec && !direct) {
+    MUSED_CHECK_HIP(hipEventRecord(p->ev1[p->prof_n], st));
+    ++p->prof_n;
+    if (p->notconv)
+      hipLaunchKernelGGL(osj_count_kernel, dim3(1), dim3(256), 0, st, p->notconv, p->batch, p->sweeps * c.rps, c.rps, p->work,
+                         p->rep);
+  }
+  // (matrices the direct solver solved carry their eigenvalues already)
+  hipLaunchKernelGGL(osj_norms_kernel, dim3(cdiv(c.ldn, 4), p->batch), dim3(256), 0, st, p->Gc, c.ldn, p->lam,
+                     (const int*)p->trd_done);
+  if (evals)
+    hipLaunchKernelGGL(osj_extract_kernel, dim3(cdiv((long)p->n * p->n, 256), p->batch), dim3(256), 0, st, p->Gc, p->lam, p->n,
+                       c.ldn, evals, V);
+  MUSED_LAUNCH_CHECK();
+  return MUSED_OK;
 }
 
 int eig_plan_run(EigPlan* p, const double* G, double* evals, double* V, hipStream_t st) {
   const size_t bytes = sizeof(double) * (size_t)p->batch * p->n * p->n;
-  MUSED_CHECK_HIP(hipMemcpyAsync(p->G[0], G, bytes, hipMemcpyDeviceToDevice, st));
-  p->direct = false;
+  MUSED_CHECK_HIP(hipMemcpyAsync(eig_plan_input(p), G, bytes, hipMemcpyDeviceToDevice, st));
   return eig_plan_run_inplace(p, evals, V, st, true);
 }
 
-}  // namespace mused
-
-using namespace mused;
-
-extern "C" {
-
-// Diagnostic: average kernel time (us, HIP events) of `reps` cross-round launches of the one-sided Jacobi
-// kernel on `batch` matrices of order 256, for timing ablation `variant` (0 = the real kernel).
-int mused_debug_osj_time(const double* init, int batch, int variant, int reps, double* out_us, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int ldn = 256, nb = ldn / OSJ_CB;
-  double* G = nullptr;
-  MUSED_CHECK_HIP(hipMalloc(&G, sizeof(double) * (size_t)batch * ldn * ldn));
-  MUSED_CHECK_HIP(hipMemcpy(G, init, sizeof(double) * (size_t)batch * ldn * ldn, hipMemcpyDeviceToDevice));
-  hipEvent_t e0, e1;
+// mused_debug_eig_time with the plan and the events owned by the caller
+static int eig_time(EigPlan* p, hipEvent_t& e0, hipEvent_t& e1, const double* G, int reps, double* evals, double* V,
+                    double* out_ms, int* out_err, hipStream_t st) {
   MUSED_CHECK_HIP(hipEventCreate(&e0));
   MUSED_CHECK_HIP(hipEventCreate(&e1));
-  auto launch = [&](int round) {
-    dim3 grid(nb / 2, batch), blk(256);
-    switch (variant) {
-      case 5: hipLaunchKernelGGL((osj_round_kernel<OSJ_CB, 256, 1, 5>), grid, blk, 0, st, G, 256, ldn, nb, round, (int*)nullptr, 0, 1, (const double*)nullptr, 1, (const int*)nullptr); break;
-      case 7: hipLaunchKernelGGL((osj_round_kernel<OSJ_CB, 256, 1, 7>), grid, blk, 0, st, G, 256, ldn, nb, round, (int*)nullptr, 0, 1, (const double*)nullptr, 1, (const int*)nullptr); break;
-      case 2: hipLaunchKernelGGL((osj_round_kernel<OSJ_CB, 256, 1, 2>), grid, blk, 0, st, G, 256, ldn, nb, round, (int*)nullptr, 0, 1, (const double*)nullptr, 1, (const int*)nullptr); break;
-      case 3: hipLaunchKernelGGL((osj_round_kernel<OSJ_CB, 256, 1, 3>), grid, blk, 0, st, G, 256, ldn, nb, round, (int*)nullptr, 0, 1, (const double*)nullptr, 1, (const int*)nullptr); break;
-      case 4: hipLaunchKernelGGL((osj_round_kernel<OSJ_CB, 256, 1, 4>), grid, blk, 0, st, G, 256, ldn, nb, round, (int*)nullptr, 0, 1, (const double*)nullptr, 1, (const int*)nullptr); break;
-      default: hipLaunchKernelGGL((osj_round_kernel<OSJ_CB, 256, 1, 0>), grid, blk, 0, st, G, 256, ldn, nb, round, (int*)nullptr, 0, 1, (const double*)nullptr, 1, (const int*)nullptr);
-    }
-  };
-  MUSED_CHECK_HIP(hipEventRecord(e0, st));
-  for (int i = 0; i < reps; ++i) launch(i % (nb - 1));
-  MUSED_CHECK_HIP(hipEventRecord(e1, st));
-  MUSED_CHECK_HIP(hipEventSynchronize(e1));
-  float ms = 0.f;
-  MUSED_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
-  *out_us = 1e3 * ms / reps;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipFree(G);
-  return MUSED_OK;
-}
-
-// Diagnostic (not part of the declared ABI): average time (ms, HIP events) of `reps` solves of `batch` matrices of order n
-// with one plan (created under the current environment: MUSED_EIG_QUEUE etc.); evals / V of the last solve are returned.
-int mused_debug_eig_time(const double* G, int n, int batch, int sweeps, int reps, double* evals, double* V, double* out_ms,
-                         int* out_err, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  EigPlan* p = nullptr;
-  int rc = eig_plan_create(n, batch, sweeps, true, &p);
-  if (rc) return rc;
-  hipEvent_t e0, e1;
-  MUSED_CHECK_HIP(hipEventCreate(&e0));
-  MUSED_CHECK_HIP(hipEventCreate(&e1));
-  rc = eig_plan_run(p, G, evals, V, st);  // warm-up (graph upload)
+  int rc = eig_plan_run(p, G, evals, V, st);  // warm-up (graph upload)
   MUSED_CHECK_HIP(hipStreamSynchronize(st));
   MUSED_CHECK_HIP(hipEventRecord(e0, st));
   for (int i = 0; i < reps && !rc; ++i) rc = eig_plan_run(p, G, evals, V, st);
@@ -1531,14 +1480,44 @@ int mused_debug_eig_time(const double* G, int n, int batch, int sweeps, int reps
   *out_ms = ms / (reps > 0 ? reps : 1);
   if (out_err) {
     *out_err = 0;
-    if (p->use_queue) {
+    if (p->c.jacobi == EigJacobi::Queue) {
       OsjqCtl c;
       MUSED_CHECK_HIP(hipMemcpy(&c, p->qctl, sizeof(c), hipMemcpyDeviceToHost));
       *out_err = c.error ? -1 : (int)c.tail;  // units queued in the last solve (or -1 on a timeout)
     }
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  return rc;
+}
+
+}  // namespace mused
+
+using namespace mused;
+
+extern "C" {
+
+// Diagnostic (not part of the declared ABI; touches no device): what eig_plan_create would choose for this plan under the
+// current environment.  out[8] = {direct (0 none, 1 trd, 2 trdx), jacobi (0 queue, 1 wave-private sweep graph, 2 row-per-thread
+// sweep graph), padded order, launch rounds per sweep, need, cert_all, sort, adaptive}.
+int mused_debug_eig_choice(int n, int batch, int sweeps, int flags, int need, int* out) {
+  MUSED_REQUIRE(out && n >= 2 && n % 2 == 0 && n <= 1024 && batch >= 1 && sweeps >= 1,
+                "mused_debug_eig_choice: the order must be even and <= 1024 (n=%d)", n);
+  const EigChoice c = eig_choose(n, batch, sweeps, flags, need, eig_read_env());
+  const int v[8] = {(int)c.direct, (int)c.jacobi, c.ldn, c.rps, c.need, c.cert_all, c.sort, c.adaptive};
+  memcpy(out, v, sizeof(v));
+  return MUSED_OK;
+}
+
+// Diagnostic (not part of the declared ABI): average time (ms, HIP events) of `reps` solves of `batch` matrices of order n
+// with one plan (created under the current environment: MUSED_EIG_QUEUE etc.); evals / V of the last solve are returned.
+int mused_debug_eig_time(const double* G, int n, int batch, int sweeps, int reps, double* evals, double* V, double* out_ms,
+                         int* out_err, void* stream) {
+  EigPlan* p = nullptr;
+  int rc = eig_plan_create(n, batch, sweeps, true, &p);
+  if (rc) return rc;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  rc = eig_time(p, e0, e1, G, reps, evals, V, out_ms, out_err, (hipStream_t)stream);
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
   eig_plan_destroy(p);
   return rc;
 }

@@ -62,37 +62,47 @@ int adj_csr_from_mask(const unsigned long long* mask, int n, int words, int* deg
 int zero_ints(int* p, long n, hipStream_t st);
 int adj_transpose(const unsigned long long* mask, int n, int words, unsigned long long* out, hipStream_t st);
 
-// Batched symmetric eigensolver (cyclic Jacobi, one launch per rotation set).
+// eig.hip: batched symmetric eigensolver for even orders up to 1024, fp64.  A plan fixes (order, batch, sweep cap) and, once,
+// at creation, which kernels solve it: a one-sided block Jacobi (one persistent work-queue launch, or a hipGraph of
+// launch-per-round sweeps), optionally behind a direct solver for the leading eigenpairs (trd.hip / trdx.hip) whose rejects
+// the Jacobi takes.  The result lives in the plan as columns lam_j u_j (eig_plan_columns); eigenvectors are extracted on request.
 struct EigPlan;
-// own_graph: capture the sweep launches into a private hipGraph (set false when the caller
-// captures a larger pipeline that contains this solve).
 constexpr int EIG_PLAN_FIXED_SWEEPS = 1;  // always `sweeps` sweeps (no convergence flags)
 constexpr int EIG_PLAN_NO_SORT = 2;       // no column sorting: column j of the result descends from column j of the input
-constexpr int EIG_PLAN_TOP_HALF = 4;      // the caller reads only the n / 2 largest eigenpairs (FD rotation): orders the direct
-                                          // solver covers (trd.hip) go to it, the Jacobi takes what its certificate rejects
+constexpr int EIG_PLAN_TOP_HALF = 4;      // the caller reads only the n / 2 largest eigenpairs (FD rotation): orders a direct
+                                          // solver covers go to it, the Jacobi takes what its certificate rejects
 constexpr int EIG_PLAN_TOP_NEED = 8;      // the caller reads the `need` largest eigenpairs, ALL of which must be certified (eigenstep)
 constexpr int EIG_PLAN_TOP_FD = 16;       // as TOP_HALF with an explicit `need` (sketch query: the l largest of 3 l or 4 l)
-int eig_plan_create(int n, int batch, int sweeps, bool own_graph, EigPlan** out, const int* rep = nullptr, int flags = 0,
-                    int* err_out = nullptr, int need = 0);
+// own_graph: capture the Jacobi's launches into a private hipGraph (false when the caller captures a larger pipeline that
+//   contains this solve).  MUSED_EIG_TRD, MUSED_EIG_QUEUE, MUSED_EIG_QUEUE_TIMEOUT_TICKS and MUSED_NO_GRAPH are read here, once
+//   per call, and by no solve.  On failure nothing is left allocated and *out is not written.
 // rep (device, batch ints, optional, read at every solve): matrix b is solved only when rep[b] == b
 // err_out (device int, optional): OR-ed with 1 by a solve of the persistent work-queue solver that gave up waiting
-// (timeout: the matrices are left partially rotated and the results of that solve are invalid)
+//   (timeout: the matrices are left partially rotated and the results of that solve are invalid)
+int eig_plan_create(int n, int batch, int sweeps, bool own_graph, EigPlan** out, const int* rep = nullptr, int flags = 0,
+                    int* err_out = nullptr, int need = 0);
 void eig_plan_destroy(EigPlan* p);
-// In: G (batch x n x n, symmetric) is copied into the plan's workspace.  Out: eigenvalues
-// (unsorted, batch x n) and eigenvectors V (batch x n x n, column j <-> eigenvalue j).
+// (batch x n x n) device buffer the caller fills with the symmetric matrices before eig_plan_run_inplace
+double* eig_plan_input(EigPlan* p);
+// Solves what eig_plan_input holds.  evals (batch x n, unsorted) and V (batch x n x n, column j <-> eigenvalue j) are
+// extracted when evals is not null; allow_graph: replay the plan's private graph, if it has one.
+int eig_plan_run_inplace(EigPlan* p, double* evals, double* V, hipStream_t stream, bool allow_graph);
+// The same on a copy of G (batch x n x n, symmetric)
 int eig_plan_run(EigPlan* p, const double* G, double* evals, double* V, hipStream_t stream);
+// The result of the last solve as the solver leaves it: cols[(b * ld + j) * ld + a] = lam_j u_j[a], lam[b * ld + j] = eigenvalue j
+struct EigColumns {
+  const double *cols, *lam;
+  int ld;
+};
+EigColumns eig_plan_columns(EigPlan* p);
+bool eig_plan_direct_solver(EigPlan* p);  // the plan runs a direct solver (trd.hip / trdx.hip) with the Jacobi as its fallback
+// Live timing (HIP events around every solve between profile(on) and a blocking read).  Plans without a direct solver:
+// summed ms of the Jacobi, its launch rounds and the bytes one of them moves.  Plans with one: summed ms of the direct
+// solver alone, its launches, the matrices it solved over all of them and the ms of its first kernel.
 int eig_plan_profile(EigPlan* p, bool on);
 int eig_plan_profile_read(EigPlan* p, double* total_ms, long* launches, double* bytes_per_launch);
-// plans that run the direct solver: summed ms of its launches (HIP events around the kernel alone), number of launches,
-// matrices it solved over all of them
 int eig_plan_profile_read_direct(EigPlan* p, double* total_ms, long* launches, double* matrices_solved,
                                  double* tridiag_ms = nullptr);
-bool eig_plan_direct_solver(EigPlan* p);  // the plan runs the direct solver (trd.hip) with the Jacobi as its fallback
-double* eig_plan_input(EigPlan* p);  // (batch x n x n) device buffer the caller may fill directly
-// Raw result of the one-sided solver (false: not available): cols[(b * ld + j) * ld + a] = lam_j u_j[a],
-// lam[b * ld + j] = eigenvalue j; valid after eig_plan_run_inplace(p, nullptr, nullptr, ...).
-bool eig_plan_columns(EigPlan* p, const double** cols, const double** lam, int* ld);
-int eig_plan_run_inplace(EigPlan* p, double* evals, double* V, hipStream_t stream, bool allow_graph);
 
 // trd.hip: direct solver for orders <= 256, the `need` <= 128 largest eigenpairs (tridiagonalisation + multisection +
 // twisted factorisation + back-transformation); matrices column-major with leading dimension ldn (n <= ldn <= 256)

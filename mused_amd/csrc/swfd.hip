@@ -41,7 +41,7 @@ struct Swfd {
   long long* dropped;  // S         largest timestamp of a snapshot lost to the ring capacity
   double* theta;       // S
   // rotation workspace
-  double *T, *Wc, *evals, *U;
+  double *T, *Wc;
   int gram_split;   // > 1: the buffers' Gram matrices by a batched split-K product (long rows: the K loop of a tile is the latency
   double* gpart;    //      of the rotation and the tiles of a launch do not fill the GPU) -- S x gram_split x n2 x n2 partial sums
   int* plan;      // S x ell x 2  {kind (0 none, 1 keep, 2 dump), position}
@@ -51,7 +51,7 @@ struct Swfd {
   int* status_host;  // pinned copy target of mused_swfd_status (asynchronous copy on the caller's stream)
   EigPlan* eig;
   // query workspace
-  double *stack, *evals_q, *Uq, *Wq, *Bout, *sig_out, *qinfo;
+  double *stack, *Wq, *Bout, *sig_out, *qinfo;
   int* qsel;  // {level, nsnap, nk, slots[cap]}
   EigPlan* eigq;
   EigPlan* eigq3;  // order n3 = 3l (even): enough whenever nothing is pending (snapshots <= 2l, kept rows <= l - 1)
@@ -159,10 +159,10 @@ __global__ void swfd_rep_kernel(const int* __restrict__ meta, int L, int nchains
 }
 
 // One workgroup per sketch: expiry, eigenvalue ordering, shrink, dump/keep plan, Wc.
-// (evals, U): eigenvalues and eigenvectors, row pitch ldu; cols != 0: U holds the solver's raw columns
-// lam_j u_j (column j contiguous) instead of the eigenvector matrix.
+// (evals, U): the solver's result as it leaves it (eig_plan_columns): eigenvalues and the columns lam_j u_j (column j
+// contiguous), pitch ldu.
 __global__ __launch_bounds__(1024) void swfd_decide_kernel(const double* __restrict__ evals,
-                                                          const double* __restrict__ U, int ldu, int cols, int n2,
+                                                          const double* __restrict__ U, int ldu, int n2,
                                                           int ell, int cap,
                                                           int N, const long long* __restrict__ now_p,
                                                           const double* __restrict__ theta, int* __restrict__ meta,
@@ -222,8 +222,7 @@ __global__ __launch_bounds__(1024) void swfd_decide_kernel(const double* __restr
     double s2 = l - delta;
     s2 = s2 > 0.0 ? s2 : 0.0;
     if (s2 > tol) {
-      sc = sqrt(s2 / l);
-      if (cols) sc /= l;  // the raw column is lam u
+      sc = sqrt(s2 / l) / l;  // (the column is lam u)
       kind = (s2 >= th) ? 2 : 1;
       near = (kind == 2 && s2 < 2.0 * th) ? 1 : 0;  // dumped here but kept one level up: this sketch parts with the next level
     }
@@ -286,7 +285,7 @@ __global__ __launch_bounds__(1024) void swfd_decide_kernel(const double* __restr
   for (int e = t; e < ell * n2; e += 1024) {
     const int i = e / n2, a = e - i * n2;
     const double sc = scale[i];
-    W[e] = (sc != 0.0) ? sc * (cols ? Us[(long)order[i] * ldu + a] : Us[(long)a * ldu + order[i]]) : 0.0;
+    W[e] = (sc != 0.0) ? sc * Us[(long)order[i] * ldu + a] : 0.0;
   }
 }
 
@@ -332,13 +331,10 @@ static int swfd_rotate_all(Swfd* h, hipStream_t st) {
   } else if ((rc = gemm_f64(true, true, h->buf, d, (long)n2 * d, h->buf, d, (long)n2 * d, eig_plan_input(h->eig), n2,
                             (long)n2 * n2, n2, n2, d, S, 1.0, st, h->rep)))
     return rc;
-  const double *ecols = nullptr, *elam = nullptr;
-  int eld = 0;
-  const bool raw = eig_plan_columns(h->eig, &ecols, &elam, &eld);
-  if ((rc = eig_plan_run_inplace(h->eig, raw ? nullptr : h->evals, raw ? nullptr : h->U, st, true))) return rc;
-  hipLaunchKernelGGL(swfd_decide_kernel, dim3(S), dim3(1024), 0, st, raw ? elam : h->evals, raw ? ecols : h->U,
-                     raw ? eld : n2, raw ? 1 : 0, n2, ell, h->cap, h->N,
-                     h->now_dev, h->theta, h->meta, h->qt, h->dropped, h->plan, h->keep_src, h->Wc, h->rep);
+  if ((rc = eig_plan_run_inplace(h->eig, nullptr, nullptr, st, true))) return rc;
+  const EigColumns e = eig_plan_columns(h->eig);
+  hipLaunchKernelGGL(swfd_decide_kernel, dim3(S), dim3(1024), 0, st, e.lam, e.cols, e.ld, n2, ell, h->cap, h->N, h->now_dev,
+                     h->theta, h->meta, h->qt, h->dropped, h->plan, h->keep_src, h->Wc, h->rep);
   if ((rc = gemm_f64(true, false, h->Wc, n2, (long)ell * n2, h->buf, d, (long)n2 * d, h->T, d, (long)ell * d, ell, d,
                      n2, S, 1.0, st, h->rep)))
     return rc;
@@ -413,9 +409,8 @@ static int swfd_prerotate(Swfd* h, const T* X, long ldx, long lane_stride, const
                      eig_plan_input(h->eigp));
   // matrices of the plan beyond Z keep whatever they held (their results are not read)
   if ((rc = eig_plan_run_inplace(h->eigp, nullptr, nullptr, st, true))) return rc;
-  const double *cols = nullptr, *lam = nullptr;
-  int ld = 0;
-  if (!eig_plan_columns(h->eigp, &cols, &lam, &ld)) return MUSED_ERR_STATE;
+  const double* cols = eig_plan_columns(h->eigp).cols;
+  const int ld = eig_plan_columns(h->eigp).ld;
   // P' = V^T P, V = rows l .. 2l-1 of the first l columns of the solver's working copy: A[j][i] = cols[j * ld + l + i]
   if ((rc = gemm_f64(true, false, cols + ell, ld, (long)ld * ld, h->pre_in, d, (long)ell * d, h->pre_out, d, (long)ell * d,
                      ell, d, ell, Z, 1.0, st)))
@@ -523,8 +518,7 @@ __global__ void swfd_stack_kernel(const int* __restrict__ qsel_all, const double
 }
 
 __global__ __launch_bounds__(1024) void swfd_decide_query_kernel(const double* __restrict__ evals_all,
-                                                                const double* __restrict__ U_all, int ldu, int cols,
-                                                                int n4, int ell,
+                                                                const double* __restrict__ U_all, int ldu, int n4, int ell,
                                                                 int cap, const int* __restrict__ qsel_all,
                                                                 double* __restrict__ Wq_all,
                                                                 double* __restrict__ qinfo_all) {
@@ -556,7 +550,7 @@ __global__ __launch_bounds__(1024) void swfd_decide_query_kernel(const double* _
     const double l = lam[order[t]];
     double s2 = l - delta;
     s2 = s2 > 0.0 ? s2 : 0.0;
-    scale[t] = (s2 > tol) ? (cols ? sqrt(s2 / l) / l : sqrt(s2 / l)) : 0.0;
+    scale[t] = (s2 > tol) ? sqrt(s2 / l) / l : 0.0;  // (the column is lam u)
   }
   if (t == 0) {
     qinfo[0] = (double)qsel[0];
@@ -566,7 +560,7 @@ __global__ __launch_bounds__(1024) void swfd_decide_query_kernel(const double* _
   for (int e = t; e < ell * n4; e += 1024) {
     const int i = e / n4, a = e - i * n4;
     const double sc = scale[i];
-    Wq[e] = (sc != 0.0) ? sc * (cols ? U[(long)order[i] * ldu + a] : U[(long)a * ldu + order[i]]) : 0.0;
+    Wq[e] = (sc != 0.0) ? sc * U[(long)order[i] * ldu + a] : 0.0;
   }
 }
 
@@ -620,13 +614,10 @@ static int swfd_query(Swfd* h, double* outB, double* outSigma, double* outInfo, 
   if ((rc = gemm_f64(true, true, h->stack, d, (long)n4 * d, h->stack, d, (long)n4 * d, eig_plan_input(eq), n4,
                      (long)n4 * n4, n4, n4, d, B, 1.0, st)))
     return rc;
-  const double *ecols = nullptr, *elam = nullptr;
-  int eld = 0;
-  const bool raw = eig_plan_columns(eq, &ecols, &elam, &eld);
-  if ((rc = eig_plan_run_inplace(eq, raw ? nullptr : h->evals_q, raw ? nullptr : h->Uq, st, true))) return rc;
-  hipLaunchKernelGGL(swfd_decide_query_kernel, dim3(B), dim3(1024), 0, st, raw ? elam : h->evals_q, raw ? ecols : h->Uq,
-                     raw ? eld : n4, raw ? 1 : 0, n4, ell, h->cap, h->qsel,
-                     h->Wq, h->qinfo);
+  if ((rc = eig_plan_run_inplace(eq, nullptr, nullptr, st, true))) return rc;
+  const EigColumns e = eig_plan_columns(eq);
+  hipLaunchKernelGGL(swfd_decide_query_kernel, dim3(B), dim3(1024), 0, st, e.lam, e.cols, e.ld, n4, ell, h->cap, h->qsel, h->Wq,
+                     h->qinfo);
   if ((rc = gemm_f64(true, false, h->Wq, n4, (long)ell * n4, h->stack, d, (long)n4 * d, h->Bout, d, (long)ell * d, ell,
                      d, n4, B, 1.0, st)))
     return rc;
@@ -713,7 +704,7 @@ static int swfd_create_impl(Swfd* h, long N, double R, int d, int ell, int sweep
   ZALLOC(h->status, 4);
   MUSED_CHECK_HIP(hipHostMalloc((void**)&h->status_host, sizeof(int), hipHostMallocDefault));
   ALLOC(h->theta, 8 * S);
-  ALLOC(h->T, 8 * S * l * dd); ALLOC(h->Wc, 8 * S * l * n2); ALLOC(h->evals, 8 * S * n2); ALLOC(h->U, 8 * S * n2 * n2);
+  ALLOC(h->T, 8 * S * l * dd); ALLOC(h->Wc, 8 * S * l * n2);
   ALLOC(h->plan, 4 * S * l * 2); ALLOC(h->keep_src, 4 * S * l); ALLOC(h->now_dev, 8);
   {
     // rows of 8,192 entries and more (the SWFDMC wiring: d = window size): eight K-slices per tile (measured at d = 10,000, 12 lanes:
@@ -725,7 +716,7 @@ static int swfd_create_impl(Swfd* h, long N, double R, int d, int ell, int sweep
     if (h->gram_split > 1) ALLOC(h->gpart, 8 * S * (size_t)h->gram_split * n2 * n2);
   }
   const size_t Bn = lanes;
-  ALLOC(h->stack, 8 * Bn * n4 * dd); ALLOC(h->evals_q, 8 * Bn * n4); ALLOC(h->Uq, 8 * Bn * n4 * n4);
+  ALLOC(h->stack, 8 * Bn * n4 * dd);
   ALLOC(h->Wq, 8 * Bn * l * n4); ALLOC(h->Bout, 8 * Bn * l * dd); ALLOC(h->sig_out, 8 * Bn * l);
   ALLOC(h->qinfo, 8 * 2 * Bn); ALLOC(h->qsel, 4 * Bn * (4 + cap));
 #undef ZALLOC
@@ -747,11 +738,9 @@ static int swfd_create_impl(Swfd* h, long N, double R, int d, int ell, int sweep
   {
     // input-block pre-rotation (swfd_prerotate): batches of `pre_chunk` blocks x lanes, workspace <= ~256 MB per array
     const char* pr = getenv("MUSED_SWFD_PREROT");
-    const double *c0 = nullptr, *l0 = nullptr;
-    int ld0 = 0;
     // (the pre-rotation only saves Jacobi sweeps: with the direct solver it is off unless MUSED_SWFD_PREROT=1 asks for it)
     const bool want_pre = pr ? (pr[0] != '0') : !eig_plan_direct_solver(h->eig);
-    if (want_pre && eig_plan_columns(h->eig, &c0, &l0, &ld0)) {
+    if (want_pre) {
       const size_t per_block = (size_t)lanes * ell * dd * 8;
       size_t c = ((size_t)256 << 20) / per_block;
       c = c < 1 ? 1 : (c > (size_t)SWFD_PRE_MAX ? (size_t)SWFD_PRE_MAX : c);
@@ -777,8 +766,8 @@ int mused_swfd_destroy(void* handle) {
   eig_plan_destroy(h->eigq);
   if (h->eigq3) eig_plan_destroy(h->eigq3);
   if (h->eigp) eig_plan_destroy(h->eigp);
-  void* bufs[] = {h->buf, h->queue, h->qt, h->meta, h->dropped, h->theta, h->T, h->Wc, h->evals, h->U, h->plan,
-                  h->keep_src, h->now_dev, h->stack, h->evals_q, h->Uq, h->Wq, h->Bout, h->sig_out, h->qinfo, h->qsel,
+  void* bufs[] = {h->buf, h->queue, h->qt, h->meta, h->dropped, h->theta, h->T, h->Wc, h->plan,
+                  h->keep_src, h->now_dev, h->stack, h->Wq, h->Bout, h->sig_out, h->qinfo, h->qsel,
                   h->rep, h->pre_in, h->pre_out, h->pre_gram, h->status, h->gpart};
   for (void* b : bufs) (void)hipFree(b);
   if (h->status_host) (void)hipHostFree(h->status_host);
