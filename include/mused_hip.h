@@ -214,7 +214,7 @@ int mused_gemm_f64_batched_splitk(int a_kc, int b_kc, const double* A, long lda,
                                   int nsplit, const int* rep, void* stream);
 
 /* ---- a10 / f2: the Lloyd iterations of perform_clustering (matrix_operations.py:149-153, sklearn KMeans) ------------
- * The k-means++ seeding stays on the host (scikit-learn's own routine on the same RandomState stream); E / M steps and
+ * The seeds come from mused_kmeans_seed below (or from scikit-learn's own routine on the host); E / M steps and
  * the stopping rule of sklearn's _kmeans_single_lloyd run here in fp64 with fixed-order sums.  X: n x d fp64 embedding
  * (pitch ld), mean: its d column means, centers: k x d seeds of the CENTRED rows (in/out), tol = mean(var(X, 0)) * 1e-4.
  * labels_out: n int32 (device); info_out (HOST, 4 ints) = {iterations, 1 strict / 2 tol / 0 max_iter, empty-cluster flag
@@ -222,6 +222,22 @@ int mused_gemm_f64_batched_splitk(int a_kc, int b_kc, const double* A, long lda,
 long mused_kmeans_ws_bytes(int n, int d, int k);
 int mused_kmeans_lloyd(const double* X, long ld, int n, int d, int k, const double* mean, double* centers, double tol,
                        int max_iter, int* labels_out, int* info_out, void* ws, long ws_bytes, void* stream);
+
+/* ---- what KMeans.fit does before the Lloyd iterations (csrc/kmeanspp.hip).  Both enqueue-only, fp64, fixed-order sums.
+ * mused_kmeans_moments: mean_out (d, device) = X.mean(axis=0) bit for bit (rows added in row order, / n); tol_out (1,
+ *   device) = mean(var(X, 0)) * 1e-4 with NumPy's steps for the variances (squares rounded, added in row order, / n).
+ * mused_kmeans_seed: sklearn `_kmeans_plusplus` on the rows X - mean with the generator's draws made up front on the host:
+ *   first = the first centre's row, U = (k - 1) x trials uniforms (DEVICE), trials = 2 + int(log(k)) <= 8.  centers_out:
+ *   k x d centred rows (the layout mused_kmeans_lloyd takes), indices_out: k int32 row indices, info_dev (2 int32, DEVICE) =
+ *   {ambiguity flag, centres chosen}.  The sums are not taken in scikit-learn's order; the flag is raised when a search or
+ *   the choice among the candidates was decided within 2 E, E = 4 (d + 8) 2^-52 (sum |x_i|^2 + n max |x_i|^2): seed that
+ *   window with scikit-learn then.  k <= 1024, d <= 512, k <= n.  ws: mused_kmeans_seed_ws_bytes(n, d, k) bytes; its third
+ *   block of n doubles (after the n x d centred rows and the n row norms, each block rounded up to 256 bytes) holds
+ *   closest_dist_sq when the call has run. */
+int mused_kmeans_moments(const double* X, long ld, int n, int d, double* mean_out, double* tol_out, void* stream);
+long mused_kmeans_seed_ws_bytes(int n, int d, int k);
+int mused_kmeans_seed(const double* X, long ld, int n, int d, int k, const double* mean, int first, const double* U, int trials,
+                      double* centers_out, int* indices_out, int* info_dev, void* ws, long ws_bytes, void* stream);
 
 /* ---- sSVDMC_mini: MiniBatchKMeans(n_clusters_total, random_state=seed, batch_size=W).partial_fit(X).predict(X) --------
  * (main.py:82-86; sklearn 1.7 cluster/_kmeans.py).  The arithmetic only: the RandomState stays on the host (k-means++ on the

@@ -1,7 +1,8 @@
 // the assign / update iterations of perform_clustering (matrix_operations.py:149-153 =
 // sklearn KMeans(n_clusters, random_state=seed): k-means++ seeding, n_init = 1, Lloyd, max_iter = 300, tol = 1e-4) on
-// the device.  The SEEDING stays on the host -- sklearn's own kmeans_plusplus driven by the same RandomState, on the
-// centred embedding -- because it is what couples the result to NumPy's MT19937 stream; what runs here is
+// the device.  The seeds are an input: mused_kmeans_seed (csrc/kmeanspp.hip) computes them on the device from the draws
+// the host takes from RandomState(seed) up front, or -- MUSED_KMEANS_SEED=host, and any window whose seeding the device
+// flags as decided within rounding -- sklearn's own kmeans_plusplus computes them on the host; what runs here is
 // sklearn:cluster/_kmeans.py `_kmeans_single_lloyd` (:586-720) / `_k_means_lloyd.pyx` `lloyd_iter_chunked_dense`:
 //
 //   repeat (<= max_iter):
@@ -246,9 +247,10 @@ long mused_kmeans_ws_bytes(int n, int d, int k) {
 }
 
 // Replaces the Lloyd iterations of KMeans(n_clusters = k, random_state = seed).fit_predict(X)
-// (matrix_operations.py:149-153) for the embedding X (n x d fp64, pitch ld, DEVICE), given -- all computed on the host
-// exactly as scikit-learn does -- the column means `mean` (d), the k-means++ centres of the CENTRED rows `centers`
-// (k x d, in: seeds, out: final centres of the centred data) and tol = mean(var(X, axis = 0)) * 1e-4.
+// (matrix_operations.py:149-153) for the embedding X (n x d fp64, pitch ld, DEVICE), given -- from mused_kmeans_moments
+// and mused_kmeans_seed, or computed on the host by NumPy and scikit-learn -- the column means `mean` (d), the k-means++
+// centres of the CENTRED rows `centers` (k x d, in: seeds, out: final centres of the centred data) and
+// tol = mean(var(X, axis = 0)) * 1e-4 (by value: a caller that computed it on the device reads it first).
 // labels_out: n int32 (DEVICE).  info_out (4 ints, HOST): {iterations, 1 strict / 2 tol / 0 max_iter, empty-cluster
 // flag, 0}.  BLOCKING (reads its stopping flag every few iterations).  k * d <= 8192.
 int mused_kmeans_lloyd(const double* X, long ld, int n, int d, int k, const double* mean, double* centers, double tol,

@@ -9,9 +9,10 @@ Same eight names `main.py:5` imports, same argument meaning, return types and er
 The numerical hot path (similarity -> kNN adjacency, fusion, randomized-SVD eigenstep) runs in
 libmused_hip on the GPU through `mused_amd.engine.WindowEngine`; there is no CPU fallback -- without
 the built extension or without a HIP device these functions raise.  The consumers that turn the
-embedding into event indices (k-means, Hungarian matching) stay on the
-host and call scikit-learn / SciPy exactly where the reference does, so label parity reduces to
-embedding parity.
+embedding into event indices (k-means, Hungarian matching) call
+scikit-learn / SciPy on the host exactly where the reference does, so label parity reduces to
+embedding parity; `perform_clustering_on_device` gives the same k-means labels from the device
+(k-means++ seeding from the host's random draws, Lloyd iterations).
 
 Two call styles:
   * NumPy in / NumPy out  -- drop-in for the reference (dense n x n matrices cross PCIe);
@@ -28,6 +29,8 @@ select on the device (csrc/meta.hip): "location" (haversine kNN, :22-31), "time"
 ball-tree traversal) the smaller row index wins here.
 """
 from __future__ import annotations
+
+import threading
 
 import numpy as np
 
@@ -279,52 +282,141 @@ def perform_clustering(matrix, n_clusters, seed):
 
 
 _KM_WS = {}
+# windows that perform_clustering_on_device did not finish on the device although it was asked to: seeded by scikit-learn
+# on the host (the seed kernel's ambiguity flag) or clustered by scikit-learn's KMeans (a cluster ran empty, k * d > 8192,
+# k > n)
+km_fallbacks = 0
+_km_fallback_lock = threading.Lock()
 
 
-def perform_clustering_on_device(emb_dev, n_clusters, seed, emb_host=None, stream=None):
-    """The same labels as `perform_clustering` (matrix_operations.py:149-153) with the Lloyd iterations on the device
-    (SURVEY 8 f2).  The k-means++ seeding is scikit-learn's own routine on the host, fed the same
-    `RandomState(seed)` stream and the centred embedding exactly as `KMeans.fit` does (sklearn:cluster/_kmeans.py
-    `fit`: tolerance from the raw rows, X -= X.mean(0), row norms, `_init_centroids` -> `_kmeans_plusplus`); assignment,
-    centre update and the stopping rule of `_kmeans_single_lloyd` run in libmused_hip (csrc/kmeans.hip).
-    emb_dev: (n, d) fp64 CUDA tensor; emb_host: its host copy if the caller already has one.  Returns int32 labels
-    (NumPy).  Falls back to scikit-learn when a cluster runs empty (sklearn relocates it) or k * d > 8192."""
+def _km_count_fallback():
+    global km_fallbacks
+    with _km_fallback_lock:   # the label workers of a pipeline call in parallel
+        km_fallbacks += 1
+
+
+def kmeanspp_draws(n, k, seed):
+    """Everything `sklearn.cluster.kmeans_plusplus` takes from its generator for n rows and k centres, drawn before a
+    row has been seen: (first, U) with `first` the first centre's row and U the (k - 1, L) uniforms of the further
+    centres, L = 2 + int(log(k)) local trials.  scikit-learn's own expressions in its own order (sklearn 1.7
+    cluster/_kmeans.py `_kmeans_plusplus`), so a RandomState(seed) ends in the same state either way
+    (`seed` may be such a generator: it is advanced)."""
+    rs = seed if isinstance(seed, np.random.RandomState) else np.random.RandomState(seed)
+    first = int(rs.choice(n, p=np.ones(n) / n))   # sample_weight / sample_weight.sum() with unit weights
+    L = 2 + int(np.log(k))
+    U = np.empty((k - 1, L), dtype=np.float64)
+    for c in range(k - 1):
+        U[c] = rs.uniform(size=L)
+    return first, U
+
+
+def _km_host_copy(emb_dev, emb_host):
+    """The host copy of the embedding, made (or taken from the caller) only where a fallback needs it."""
+    return np.ascontiguousarray(emb_host if emb_host is not None else emb_dev.cpu().numpy(), dtype=np.float64)
+
+
+def _km_workspace(key, nbytes, device):
+    import torch
+
+    ws = _KM_WS.get(key)
+    if ws is None:
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+        if len(_KM_WS) > 16:
+            _KM_WS.clear()
+        _KM_WS[key] = ws
+    return ws
+
+
+def _km_lloyd(Xd, n, d, k, mean_d, cen_d, tol, st):
+    """mused_kmeans_lloyd on stream st -> (int32 labels on the host, empty-cluster flag)."""
     import ctypes as C
 
+    import torch
+
+    from . import _lib
+
+    ws = _km_workspace((Xd.device, n, d, k, st.cuda_stream), _lib.lib().mused_kmeans_ws_bytes(n, d, k), Xd.device)
+    labels = torch.empty(n, dtype=torch.int32, device=Xd.device)
+    info = (C.c_int * 4)()
+    _lib.call("mused_kmeans_lloyd", _eng.ptr(Xd), Xd.stride(0), n, d, k, _eng.ptr(mean_d), _eng.ptr(cen_d),
+              tol, 300, _eng.ptr(labels), info, _eng.ptr(ws), ws.numel(), C.c_void_p(st.cuda_stream))
+    return labels.cpu().numpy(), info[2]
+
+
+def _km_host_seeded(Xd, X, k, seed, st):
+    """Seeding by scikit-learn's own kmeans_plusplus on the host copy X, Lloyd iterations on the device."""
     import torch
     from sklearn.cluster import kmeans_plusplus
     from sklearn.utils.extmath import row_norms
 
-    from . import _lib
-
-    n, d = emb_dev.shape
-    X = np.ascontiguousarray(emb_host if emb_host is not None else emb_dev.cpu().numpy(), dtype=np.float64)
-    if n_clusters * d > 8192 or n_clusters > n:
-        return perform_clustering(X, n_clusters, seed)
+    n, d = X.shape
     tol = float(np.mean(np.var(X, axis=0)) * 1e-4)   # KMeans._check_params_vs_input -> _tolerance, before centring
     mean = X.mean(axis=0)
     Xc = X - mean
-    centers, _ = kmeans_plusplus(Xc, n_clusters, x_squared_norms=row_norms(Xc, squared=True),
+    centers, _ = kmeans_plusplus(Xc, k, x_squared_norms=row_norms(Xc, squared=True),
                                  random_state=np.random.RandomState(seed))
-    st = stream if stream is not None else torch.cuda.current_stream()
     with torch.cuda.stream(st):
-        key = (emb_dev.device, n, d, n_clusters, st.cuda_stream)
-        ws = _KM_WS.get(key)
-        if ws is None:
-            ws = torch.empty(int(_lib.lib().mused_kmeans_ws_bytes(n, d, n_clusters)), dtype=torch.uint8, device=emb_dev.device)
-            if len(_KM_WS) > 16:
-                _KM_WS.clear()
-            _KM_WS[key] = ws
-        mean_d = torch.from_numpy(mean).to(emb_dev.device)
-        cen_d = torch.from_numpy(np.ascontiguousarray(centers)).to(emb_dev.device)
-        labels = torch.empty(n, dtype=torch.int32, device=emb_dev.device)
-        info = (C.c_int * 4)()
-        Xd = emb_dev if emb_dev.stride(1) == 1 else emb_dev.contiguous()
-        _lib.call("mused_kmeans_lloyd", _eng.ptr(Xd), Xd.stride(0), n, d, n_clusters, _eng.ptr(mean_d), _eng.ptr(cen_d),
-                  tol, 300, _eng.ptr(labels), info, _eng.ptr(ws), ws.numel(), C.c_void_p(st.cuda_stream))
-        out = labels.cpu().numpy()
-    if info[2]:
-        return perform_clustering(X, n_clusters, seed)
+        mean_d = torch.from_numpy(mean).to(Xd.device)
+        cen_d = torch.from_numpy(np.ascontiguousarray(centers)).to(Xd.device)
+        out, empty = _km_lloyd(Xd, n, d, k, mean_d, cen_d, tol, st)
+    if empty:
+        return perform_clustering(X, k, seed)
+    return out
+
+
+def perform_clustering_on_device(emb_dev, n_clusters, seed, emb_host=None, stream=None):
+    """The same labels as `perform_clustering` (matrix_operations.py:149-153) with what `KMeans.fit` computes on the
+    device (sklearn:cluster/_kmeans.py `fit`: tolerance from the raw rows, X -= X.mean(0), row norms,
+    `_init_centroids` -> `_kmeans_plusplus`, `_kmeans_single_lloyd`).  The host draws what k-means++ takes from
+    `RandomState(seed)` (`kmeanspp_draws`: the draws do not depend on the rows); mused_kmeans_moments, mused_kmeans_seed
+    (csrc/kmeanspp.hip) and mused_kmeans_lloyd (csrc/kmeans.hip) run on the stream, and the host reads the tolerance with
+    the seed kernel's flag (16 bytes) and the labels.  No host copy of the embedding is made on that path.
+    emb_dev: (n, d) fp64 CUDA tensor; emb_host: its host copy if the caller already has one (read only on a fallback).
+    Returns int32 labels (NumPy).
+    Fallbacks: the seed kernel's ambiguity flag (a decision of k-means++ within rounding) -> that window with
+    scikit-learn's seeding on the host and the device Lloyd iterations; MUSED_KMEANS_SEED=host -> every window that way
+    (d > 512 too); a cluster that runs empty (sklearn relocates it), k * d > 8192 or k > n -> scikit-learn's KMeans.
+    Every fallback that was not asked for is counted in `km_fallbacks`."""
+    import ctypes as C
+    import os
+
+    import torch
+
+    from . import _lib
+
+    n, d = emb_dev.shape
+    k = int(n_clusters)
+    if k * d > 8192 or k > n:
+        _km_count_fallback()
+        return perform_clustering(_km_host_copy(emb_dev, emb_host), k, seed)
+    st = stream if stream is not None else torch.cuda.current_stream()
+    Xd = emb_dev if emb_dev.stride(1) == 1 else emb_dev.contiguous()
+    if os.environ.get("MUSED_KMEANS_SEED", "device") == "host" or d > 512:
+        return _km_host_seeded(Xd, _km_host_copy(emb_dev, emb_host), k, seed, st)
+    first, U = kmeanspp_draws(n, k, seed)
+    dev = emb_dev.device
+    with torch.cuda.stream(st):
+        ws = _km_workspace((dev, n, d, k, st.cuda_stream, "seed"), _lib.lib().mused_kmeans_seed_ws_bytes(n, d, k), dev)
+        mean_d = torch.empty(d, dtype=torch.float64, device=dev)
+        cen_d = torch.empty((k, d), dtype=torch.float64, device=dev)
+        idx_d = torch.empty(k, dtype=torch.int32, device=dev)
+        head = torch.empty(2, dtype=torch.float64, device=dev)   # {tol, the two int32 of the seed kernel's info}
+        U_d = torch.from_numpy(U).to(dev) if k > 1 else None
+        sp = C.c_void_p(st.cuda_stream)
+        _lib.call("mused_kmeans_moments", _eng.ptr(Xd), Xd.stride(0), n, d, _eng.ptr(mean_d), _eng.ptr(head), sp)
+        _lib.call("mused_kmeans_seed", _eng.ptr(Xd), Xd.stride(0), n, d, k, _eng.ptr(mean_d), first,
+                  _eng.ptr(U_d) if k > 1 else None, U.shape[1], _eng.ptr(cen_d), _eng.ptr(idx_d),
+                  C.c_void_p(head.data_ptr() + 8), _eng.ptr(ws), ws.numel(), sp)
+        head_h = head.cpu().numpy()   # mused_kmeans_lloyd takes the tolerance by value
+        tol, ambiguous = float(head_h[0]), int(head_h[1:].view(np.int32)[0])
+        if not ambiguous:
+            out, empty = _km_lloyd(Xd, n, d, k, mean_d, cen_d, tol, st)
+    if ambiguous:
+        _km_count_fallback()
+        return _km_host_seeded(Xd, _km_host_copy(emb_dev, emb_host), k, seed, st)
+    if empty:
+        _km_count_fallback()
+        return perform_clustering(_km_host_copy(emb_dev, emb_host), k, seed)
     return out
 
 

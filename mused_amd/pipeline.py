@@ -123,9 +123,11 @@ class StreamPipeline:
             self._blas_limit = threadpool_limits(limits=1, user_api="blas") if nk > 1 and async_labels else None
         except Exception:  # threadpoolctl missing: keep the library default
             self._omp_limit = None
-        # k-means of the embedding: Lloyd iterations on the device (host k-means++ seeding) unless
-        # MUSED_KMEANS=host; every label worker drives its own high-priority stream
+        # k-means of the embedding: k-means++ seeding and Lloyd iterations on the device unless
+        # MUSED_KMEANS=host; MUSED_KMEANS_SEED=host keeps scikit-learn's seeding on the host.  Every label worker drives
+        # its own high-priority stream.  (Windows that fell back: matrix_operations.km_fallbacks.)
         self._km_device = os.environ.get("MUSED_KMEANS", "device") != "host"
+        self._km_seed_device = self._km_device and os.environ.get("MUSED_KMEANS_SEED", "device") != "host"
         self._km_local = threading.local()
         self.km_device_windows = 0
         self._pending = deque()
@@ -246,7 +248,8 @@ class StreamPipeline:
         slot_keys, job_eng = (job[9], job[10]) if len(job) > 10 else ([], self.eng)
         torch.cuda.set_device(self._device)
         ev.synchronize()
-        reduced_host, sigma_host = red_pin.numpy().copy(), sig_pin.numpy().copy()
+        on_dev = self._rows_stay_on_device(reduced_dev)
+        reduced_host, sigma_host = None if on_dev else red_pin.numpy().copy(), sig_pin.numpy().copy()
         flags_host = flag_pin.numpy().copy() if flag_pin is not None else None
         with self._pin_lock:
             self._pins.append((red_pin, sig_pin))
@@ -279,6 +282,12 @@ class StreamPipeline:
             clusters = mo.perform_clustering(reduced_host, n_clusters, self.seed)
         self.host_ms["kmeans"].append(1e3 * (time.perf_counter() - t0))
         return clusters, sigma_host
+
+    def _rows_stay_on_device(self, reduced):
+        """A k-means window with device seeding: nothing on the host reads the embedding (the labels, sigma and the flag
+        words are all the trace and the matching take), so it is not copied to the pinned buffer; a window that falls back
+        fetches it itself (matrix_operations._km_host_copy)."""
+        return self._km_seed_device and not self._mini and reduced is not None and reduced.dtype == torch.float64
 
     def _minibatch(self, reduced_dev, reduced_host):
         """main.py:82-86: clusterer.partial_fit(reduced).predict(reduced) on the stream's one MiniBatchKMeans.  Called in
@@ -379,7 +388,8 @@ class StreamPipeline:
             if self._side is not None:
                 torch.cuda.current_stream().wait_stream(self._side)  # window latency includes the sketch
             red_pin, sig_pin = self._get_pins(reduced, sigma)
-            red_pin.copy_(reduced, non_blocking=True)
+            if not self._rows_stay_on_device(reduced):
+                red_pin.copy_(reduced, non_blocking=True)
             sig_pin.copy_(sigma, non_blocking=True)
             flag_pin = None
             if flags is not None:
@@ -469,7 +479,8 @@ class StreamPipeline:
         t_start = time.perf_counter()
         n_clusters = len(np.unique(true_labels_window))
         red_pin, sig_pin = self._get_pins(reduced, sigma)
-        red_pin.copy_(reduced, non_blocking=True)
+        if not self._rows_stay_on_device(reduced):
+            red_pin.copy_(reduced, non_blocking=True)
         sig_pin.copy_(sigma, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
