@@ -261,6 +261,24 @@ int mused_mbkm_reassign(const double* X, long ld, int n, int d, int k, const int
 int mused_kmeans_assign(const double* X, long ld, int n, int d, int k, const double* centers, int* labels, void* ws,
                         long ws_bytes, void* stream);
 
+/* ---- sSVDMC_pot: the label chain match_clusters(prev, new, "pot", min_overlap) (matrix_operations.py:155-210) ---------
+ * with ot.sinkhorn(a, b, M, reg=0.1) written out (Sinkhorn-Knopp, 1000 iterations at most, stopThr 1e-9; the specification
+ * is mused_amd/sinkhorn.py -- POT itself is not available: specified, unpinned).  csrc/match.hip, ONE launch of one
+ * workgroup for the whole chain, enqueue-only.
+ * raw: K_windows x W int32 labels (DEVICE); matched_out: K_windows x W int32; for t = 0 .. K_windows - 1
+ *   matched_t = match(matched_{t-1}, raw_t), window 0 against prev0 (W int32, DEVICE) or copied through when prev0 is NULL.
+ * info_out (DEVICE, 8 int32 per window) = {P, N, iterations run, feasible, flag word, the smallest relative distance of a
+ *   plan entry from the selection threshold (float32 bits), 1 when matched_t was written, 0}.
+ * Flag word: 1 a plan entry within delta of 0.5 max(plan), 2 an error check within delta' of stopThr (the sums are not
+ *   taken in NumPy's order: a decision within rounding is not made here), 4 a label outside [0, 1024), 8 P or N beyond 256.
+ *   The chain ENDS at the first flagged window: that window and the ones behind it are not written (info word 6 = 0);
+ *   match it on the host and call again from the next window with its labels as prev0.
+ * plan_out (DEVICE, may be NULL; diagnostic): K_windows x 65536 doubles, window t's P x N plan at t * 65536, pitch N.
+ * ws: mused_match_pot_ws_bytes() bytes. */
+long mused_match_pot_ws_bytes(void);
+int mused_match_pot_chain(const int* raw, int K_windows, int W, const int* prev0, int min_overlap, int* matched_out,
+                          int* info_out, double* plan_out, void* ws, long ws_bytes, void* stream);
+
 /* ---- a5-a7: SeqBasedSWFD (swfd submodule; call sites main.py:62,65-67,70) ---------------------- */
 
 /* SeqBasedSWFD(N=, R=, d=, sketch_dim=) */

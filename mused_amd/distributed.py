@@ -90,12 +90,13 @@ def gather_raw_labels(raw_local: np.ndarray, counts, device=None) -> np.ndarray:
     return np.concatenate([p[: counts[r]].cpu().numpy() for r, p in enumerate(parts)], axis=0)
 
 
-def replay_label_chain(raw_windows: np.ndarray, match_fn) -> np.ndarray:
-    """main.py:105-119 over gathered raw labels: matched_t = match(matched_{t-1}, raw_t)."""
+def replay_label_chain(raw_windows: np.ndarray, match_fn, method="hungarian") -> np.ndarray:
+    """main.py:105-119 over gathered raw labels: matched_t = match(matched_{t-1}, raw_t); `method` is match_clusters'
+    ("pot" for approach sSVDMC_pot)."""
     prev = None
     out = []
     for raw in raw_windows:
-        matched = match_fn(prev, raw, method="hungarian", min_overlap=3)
+        matched = match_fn(prev, raw, method=method, min_overlap=3)
         if matched is None or len(matched) == 0:
             matched = np.full(len(raw), 0)
         prev = matched

@@ -454,17 +454,149 @@ def match_clusters(prev_clusters, new_clusters, method="hungarian", min_overlap=
         relabel = {un[c]: up[r] for r, c in zip(rows, cols)}
         return np.array([relabel.get(c, c) for c in new_arr])
     if method == "pot":
-        try:
-            import ot
-        except ImportError as e:  # the reference imports POT at module level (matrix_operations.py:12)
-            raise ImportError("match_clusters(method='pot') needs the POT package") from e
-        cost = np.abs(np.where(np.isinf(cost), 1e9, cost))
-        cost = cost / cost.max()
-        plan = ot.sinkhorn(np.full(len(up), 1.0 / len(up)), np.full(len(un), 1.0 / len(un)), cost, reg=0.1)
-        rows, cols = np.where(plan > plan.max() * 0.5)
-        relabel = {un[c]: up[r] for r, c in zip(rows, cols)}
+        # matrix_operations.py:187-210 with ot.sinkhorn written out (mused_amd/sinkhorn.py: specified, unpinned)
+        from . import sinkhorn as _sk
+
+        plan, _ = _sk.pot_plan(cost)
+        relabel = {un[c]: up[r] for c, r in _sk.select(plan).items()}
         return np.array([relabel.get(c, c) for c in new_arr])
     raise ValueError("Invalid method. Choose 'hungarian' or 'pot'.")
+
+
+# windows that match_clusters_on_device / match_chain_on_device finished with the host specification although the device was
+# asked: a flag of the kernel (a decision within rounding, a label outside [0, 1024), more than 256 distinct labels)
+match_fallbacks = 0
+_MATCH_WS = {}
+MATCH_FLAG_SELECT, MATCH_FLAG_STOP, MATCH_FLAG_RANGE, MATCH_FLAG_SIZE = 1, 2, 4, 8
+_MATCH_LABELS = 1024   # label values the kernel's histogram covers (csrc/match.hip)
+
+
+def _match_count_fallback():
+    global match_fallbacks
+    with _km_fallback_lock:
+        match_fallbacks += 1
+
+
+def _labels_to_device(x, device):
+    """int32 CUDA labels of a NumPy array or an int32 / int64 CUDA tensor; values outside [0, 1024) become 1024, which the
+    kernel flags (the host copy keeps the true values)."""
+    import torch
+
+    if isinstance(x, torch.Tensor):
+        return x.to(device).clamp(-1, _MATCH_LABELS).to(torch.int32).contiguous()
+    a = np.asarray(x)
+    a = np.where((a < 0) | (a >= _MATCH_LABELS), _MATCH_LABELS, a).astype(np.int32)
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
+def _match_stream(stream):
+    """The stream the matching runs on: the caller's, behind whatever the current stream holds (tensor arguments)."""
+    import torch
+
+    cur = torch.cuda.current_stream()
+    if stream is None:
+        return cur
+    stream.wait_stream(cur)
+    return stream
+
+
+def _labels_to_host(x):
+    return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+
+
+def match_chain_launch(raw_dev, prev_dev, min_overlap, stream=None, want_plan=False):
+    """One mused_match_pot_chain launch over raw_dev (K x W int32 CUDA) against prev_dev (W int32 CUDA or None) ->
+    (matched K x W int32 CUDA, info K x 8 int32 NumPy, plans K x 65536 fp64 CUDA or None).  Synchronises the stream."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+
+    K, W = raw_dev.shape
+    dev = raw_dev.device
+    st = stream if stream is not None else torch.cuda.current_stream()
+    with torch.cuda.stream(st):
+        ws = _MATCH_WS.get((dev, st.cuda_stream))
+        if ws is None:
+            if len(_MATCH_WS) > 16:
+                _MATCH_WS.clear()
+            ws = _MATCH_WS[(dev, st.cuda_stream)] = torch.empty(int(_lib.lib().mused_match_pot_ws_bytes()), dtype=torch.uint8,
+                                                                device=dev)
+        matched = torch.empty((K, W), dtype=torch.int32, device=dev)
+        info = torch.empty((K, 8), dtype=torch.int32, device=dev)
+        plans = torch.zeros((K, 65536), dtype=torch.float64, device=dev) if want_plan else None
+        _lib.call("mused_match_pot_chain", _eng.ptr(raw_dev), K, W, _eng.ptr(prev_dev) if prev_dev is not None else None,
+                  int(min_overlap), _eng.ptr(matched), _eng.ptr(info), _eng.ptr(plans) if want_plan else None, _eng.ptr(ws),
+                  ws.numel(), C.c_void_p(st.cuda_stream))
+        info_h = info.cpu().numpy()
+    return matched, info_h, plans
+
+
+def match_chain_on_device(raw_windows, prev0=None, min_overlap=3, stream=None):
+    """`distributed.replay_label_chain(raw_windows, match_clusters, method="pot")` with the whole chain in one launch of
+    csrc/match.hip: matched_t = match_clusters(matched_{t-1}, raw_t, "pot", min_overlap), window 0 against prev0 (None: it
+    passes through).  raw_windows: (K, W) NumPy array or int32 / int64 CUDA tensor.  Returns the K * W matched labels
+    (NumPy int64).  A window the kernel flags (module docstring of csrc/match.hip) is matched by the host specification and
+    counted in `match_fallbacks`; the chain is launched again behind it."""
+    import torch
+
+    dev = raw_windows.device if isinstance(raw_windows, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+    stream = _match_stream(stream)
+    with torch.cuda.stream(stream):
+        return _match_chain(raw_windows, prev0, min_overlap, stream, dev)
+
+
+def _match_chain(raw_windows, prev0, min_overlap, stream, dev):
+    raw_dev = _labels_to_device(raw_windows, dev)
+    if raw_dev.dim() != 2:
+        raise ValueError("raw_windows must be (K, W)")
+    K, W = raw_dev.shape
+    out = np.empty((K, W), dtype=np.int64)
+    if K == 0 or W == 0:
+        return out.ravel()
+    raw_host = None
+    prev_host = None if prev0 is None or len(prev0) == 0 else prev0
+    prev_dev = None if prev_host is None else _labels_to_device(prev_host, dev)
+    t0 = 0
+    while t0 < K:
+        matched, info, _ = match_chain_launch(raw_dev[t0:], prev_dev, min_overlap, stream)
+        done = int(np.argmin(info[:, 6])) if not info[:, 6].all() else K - t0
+        if done:
+            out[t0:t0 + done] = matched[:done].cpu().numpy()
+            prev_host = out[t0 + done - 1]
+        t0 += done
+        if t0 < K:   # the flagged window: host specification, then on from the next one
+            if raw_host is None:
+                raw_host = _labels_to_host(raw_windows)
+            _match_count_fallback()
+            out[t0] = match_clusters(None if prev_host is None else _labels_to_host(prev_host), raw_host[t0], "pot", min_overlap)
+            prev_host = out[t0]
+            prev_dev = _labels_to_device(prev_host, dev)
+            t0 += 1
+    return out.ravel()
+
+
+def match_clusters_on_device(prev_clusters, new_clusters, min_overlap=3, stream=None):
+    """`match_clusters(prev_clusters, new_clusters, "pot", min_overlap)` on the device (csrc/match.hip; NumPy arrays or
+    int32 / int64 CUDA tensors).  Returns what match_clusters returns: `new_clusters` itself without a previous window or
+    when the overlap costs are infeasible, the relabelled array otherwise.  A window the kernel flags is matched by the
+    host specification and counted in `match_fallbacks`."""
+    import torch
+
+    if prev_clusters is None or len(prev_clusters) == 0:
+        return new_clusters
+    dev = new_clusters.device if isinstance(new_clusters, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+    stream = _match_stream(stream)
+    with torch.cuda.stream(stream):
+        matched, info, _ = match_chain_launch(_labels_to_device(new_clusters, dev).reshape(1, -1),
+                                              _labels_to_device(prev_clusters, dev), min_overlap, stream)
+    if not info[0, 6]:
+        _match_count_fallback()
+        return match_clusters(_labels_to_host(prev_clusters), _labels_to_host(new_clusters), "pot", min_overlap)
+    if not info[0, 3]:
+        return new_clusters
+    return matched[0].cpu().numpy().astype(np.int64)
 
 
 def perform_dbscan_clustering(data, eps=0.5, min_samples=5):

@@ -3,12 +3,13 @@ built on the device engine.
 
 Per full window (trigger rule of main.py:32):
     per-modality kNN adjacency (device bitmask)  ->  OR-fusion  ->
-        approach "sSVDMC"/"sSVDMC_hung"/"sSVDMC_mini": randomized-SVD embedding (main.py:79)
+        approach "sSVDMC"/"sSVDMC_hung"/"sSVDMC_pot"/"sSVDMC_mini": randomized-SVD embedding (main.py:79)
         approach "SWFDMC"             : SeqBasedSWFD over the rows of the fused matrix, R from the
                                         first window only, sketch transposed to (W, l)  (main.py:58-76)
     -> k-means with n_clusters = #distinct true labels in the window (main.py:41,97); "sSVDMC_mini": one MiniBatchKMeans
        (n_clusters_total) for the whole stream, partial_fit + predict per window IN WINDOW ORDER (main.py:82-86)
-    -> Hungarian matching against the previous window, min_overlap = 3 (main.py:110)
+    -> Hungarian matching against the previous window, min_overlap = 3 (main.py:110); "sSVDMC_pot": matching by the
+       Sinkhorn transport plan (main.py:111) in csrc/match.hip
     -> labels appended (main.py:118-119).
 
 Device work of window t+1 is enqueued while the host runs k-means / matching of window t
@@ -36,7 +37,7 @@ class StreamPipeline:
     def __init__(self, window_size, reduced_dim, k_basis, seed, approach="sSVDMC", modality_types=None,
                  step_window_ratio=1, engine=None, async_labels=True, feature_sketch=False, stream=None,
                  assume_finite=False, window_slots=1, n_clusters_total=None):
-        if approach not in ("sSVDMC", "sSVDMC_hung", "sSVDMC_mini", "SWFDMC"):
+        if approach not in ("sSVDMC", "sSVDMC_hung", "sSVDMC_pot", "sSVDMC_mini", "SWFDMC"):
             raise ValueError(f"approach {approach!r} is not on the device hot path")
         if approach == "sSVDMC_mini" and n_clusters_total is None:
             raise ValueError("approach 'sSVDMC_mini' needs n_clusters_total (MiniBatchKMeans(n_clusters=n_clusters_total), "
@@ -45,6 +46,10 @@ class StreamPipeline:
         # thread that clusters).  Its state is a chain over windows, so its clustering runs on the chain worker, in window
         # order, not in the parallel k-means pool; the device work of later windows (slots included) still overlaps it.
         self._mini = approach == "sSVDMC_mini"
+        # "sSVDMC_pot": embedding and k-means as "sSVDMC"; the label chain matches by the Sinkhorn plan (main.py:111) on the
+        # device (csrc/match.hip), or with the host specification (mused_amd/sinkhorn.py) under MUSED_MATCH=host
+        self._pot = approach == "sSVDMC_pot"
+        self._match_device = os.environ.get("MUSED_MATCH", "device") != "host"
         self.n_clusters_total = None if n_clusters_total is None else int(n_clusters_total)
         self.clusterer = None
         self.W, self.ell, self.k, self.seed = int(window_size), int(reduced_dim), int(k_basis), int(seed)
@@ -349,11 +354,19 @@ class StreamPipeline:
             return reduced, sigma, flags_host
 
     def _chain(self, fut, job):
-        """Sequential over windows: Hungarian matching against the previous window (main.py:105-119)."""
+        """Sequential over windows: matching against the previous window (main.py:105-119), Hungarian or, for
+        "sSVDMC_pot", by the Sinkhorn plan."""
         clusters, sigma_host = fut.result() if hasattr(fut, "result") else fut
         trigger, t_start = job[4], job[5]
         t0 = time.perf_counter()
-        matched = mo.match_clusters(self.prev, clusters, method="hungarian", min_overlap=3)
+        if self._pot and self._match_device:
+            torch.cuda.set_device(self._device)
+            st = getattr(self._km_local, "stream", None)
+            if st is None:
+                st = self._km_local.stream = torch.cuda.Stream(priority=-1)
+            matched = mo.match_clusters_on_device(self.prev, clusters, min_overlap=3, stream=st)
+        else:
+            matched = mo.match_clusters(self.prev, clusters, method="pot" if self._pot else "hungarian", min_overlap=3)
         if matched is None or len(matched) == 0:  # main.py:114-116
             matched = np.full(self.W, 0)
         self.host_ms["match"].append(1e3 * (time.perf_counter() - t0))
