@@ -279,6 +279,23 @@ long mused_match_pot_ws_bytes(void);
 int mused_match_pot_chain(const int* raw, int K_windows, int W, const int* prev0, int min_overlap, int* matched_out,
                           int* info_out, double* plan_out, void* ws, long ws_bytes, void* stream);
 
+/* ---- sSVDMC, sSVDMC_hung, SWFDMC, sSVDMC_mini: the label chain match_clusters(prev, new, "hungarian", min_overlap) -----
+ * (matrix_operations.py:155-185) with scipy.optimize.linear_sum_assignment written out (shortest augmenting paths, SciPy's
+ * scan order and tie rule, integer arithmetic: the specification is mused_amd/hungarian.py, pinned to SciPy by the tests).
+ * csrc/match_hung.hip, ONE launch of one workgroup for the whole chain, enqueue-only.
+ * raw, prev0, matched_out: as for mused_match_pot_chain.
+ * info_out (DEVICE, 8 int32 per window) = {P, N, Dijkstra steps of the solver, feasible (every row and column of the cost
+ *   matrix keeps a finite entry; when 0 the window passes through unmatched), flag word, 0, 1 when matched_t was written, 0}.
+ * Flag word: 4 a label outside [0, 1024), 8 P or N beyond 256, 16 the feasibility test passed but no complete assignment
+ *   exists (SciPy raises ValueError there).  The chain ENDS at the first flagged window: that window and the ones behind
+ *   it are not written (info word 6 = 0); match it on the host and call again from the next window with its labels as prev0.
+ * assign_out (DEVICE, may be NULL; diagnostic): K_windows x 256 int32, the column assigned to each row of window t's P x N
+ *   cost matrix at t * 256, or -1.
+ * ws: mused_match_hung_ws_bytes() bytes. */
+long mused_match_hung_ws_bytes(void);
+int mused_match_hung_chain(const int* raw, int K_windows, int W, const int* prev0, int min_overlap, int* matched_out,
+                           int* info_out, int* assign_out, void* ws, long ws_bytes, void* stream);
+
 /* ---- a5-a7: SeqBasedSWFD (swfd submodule; call sites main.py:62,65-67,70) ---------------------- */
 
 /* SeqBasedSWFD(N=, R=, d=, sketch_dim=) */

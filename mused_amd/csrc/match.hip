@@ -33,17 +33,13 @@
 //   MT_FLAG_RANGE   a label outside [0, 1024);  MT_FLAG_SIZE  P or N beyond 256
 // The caller finishes a flagged window with the host specification and relaunches behind it.
 #include "internal.h"
+#include "match_labels.h"
 #include "wave_ops.h"
 
 namespace mused {
 
-constexpr int MT_THREADS = 1024;
-constexpr int MT_WAVES = 16;
-constexpr int MT_LABELS = 1024;   // label values the histogram covers (the project's MAX_CLUSTERS)
-constexpr int MT_MAXC = 256;      // largest P, N
 constexpr int MT_RREG = 10;       // rows per wave the largest size class keeps in its private array (of 16)
-constexpr int MT_INFO = 8;        // ints of info_out per window
-constexpr int MT_FLAG_SELECT = 1, MT_FLAG_STOP = 2, MT_FLAG_RANGE = 4, MT_FLAG_SIZE = 8;
+constexpr int MT_FLAG_SELECT = 1, MT_FLAG_STOP = 2;
 constexpr int MT_ITERMAX = 1000;
 constexpr double MT_STOPTHR = 1e-9;
 constexpr double MT_REG = 0.1;
@@ -57,11 +53,9 @@ constexpr long MT_WS_KX_BYTES = 8l * (16 - MT_RREG) * 4 * MT_THREADS;
 struct MatchLds {
   double part[2][MT_WAVES][MT_MAXC];  // column-sum partials, double-buffered over the iterations
   double red[2][MT_WAVES];
-  int rank_p[MT_LABELS], rank_n[MT_LABELS];  // presence flag, then rank among the present values or -1
-  int val_p[MT_MAXC];                        // sorted distinct values of prev
+  MatchTables tb;   // steps 1, 2 and 5 (match_labels.h)
   int row_ok[MT_MAXC], col_ok[MT_MAXC], map_row[MT_MAXC];
-  int wcnt[2][MT_WAVES];
-  int bad, any_inf, max_ov, infeasible;
+  int any_inf, max_ov, infeasible;
 };
 
 __device__ __forceinline__ double wave_allmax(double v) {
@@ -278,8 +272,7 @@ __global__ __launch_bounds__(MT_THREADS) void match_pot_chain_kernel(const int* 
                                                                      double* __restrict__ kx) {
   extern __shared__ __attribute__((aligned(16))) unsigned char mt_lds[];
   MatchLds& s = *reinterpret_cast<MatchLds*>(mt_lds);
-  const int t = threadIdx.x, l = t & 63, w = t >> 6;
-  const unsigned long long below = (1ull << l) - 1ull;
+  const int t = threadIdx.x;
   int tw = 0;
   for (; tw < K_windows; ++tw) {
     const int* nw = raw + (long)tw * W;
@@ -287,70 +280,23 @@ __global__ __launch_bounds__(MT_THREADS) void match_pot_chain_kernel(const int* 
     int* out = matched + (long)tw * W;
     int* inf = info + tw * MT_INFO;
     if (pv == nullptr) {   // no previous window: match_clusters returns the new labels as they are
-      if (t == 0) s.bad = 0;
-      __syncthreads();
-      for (int i = t; i < W; i += MT_THREADS) {
-        const int q = nw[i];
-        if ((unsigned)q >= (unsigned)MT_LABELS) s.bad = 1;   // the caller's device copy does not hold the true value
-        out[i] = q;
-      }
-      __threadfence();
-      __syncthreads();
-      const int bad = s.bad;
-      __syncthreads();   // the next window clears the mark
+      const int bad = mt_pass_through(s.tb, nw, out, W);
       if (t < MT_INFO) inf[t] = t == 6 ? !bad : (t == 4 && bad ? MT_FLAG_RANGE : 0);
       if (bad) break;
       continue;
     }
-    s.rank_p[t] = 0;
-    s.rank_n[t] = 0;
     if (t < MT_MAXC) {
       s.row_ok[t] = 0;
       s.col_ok[t] = 0;
       s.map_row[t] = -1;
     }
-    if (t == 0) s.bad = s.any_inf = s.max_ov = s.infeasible = 0;
-    __syncthreads();
-    for (int i = t; i < W; i += MT_THREADS) {
-      const int p = pv[i], q = nw[i];
-      if ((unsigned)p >= (unsigned)MT_LABELS || (unsigned)q >= (unsigned)MT_LABELS) s.bad = 1;
-      else {
-        s.rank_p[p] = 1;
-        s.rank_n[q] = 1;
-      }
-    }
-    __syncthreads();
-    const bool fp = s.rank_p[t] != 0, fn = s.rank_n[t] != 0;
-    const unsigned long long bp = __ballot(fp), bn = __ballot(fn);
-    if (l == 0) {
-      s.wcnt[0][w] = __popcll(bp);
-      s.wcnt[1][w] = __popcll(bn);
-    }
-    __syncthreads();
-    int P = 0, N = 0, offp = 0, offn = 0;
-    for (int h = 0; h < MT_WAVES; ++h) {
-      if (h == w) {
-        offp = P;
-        offn = N;
-      }
-      P += s.wcnt[0][h];
-      N += s.wcnt[1][h];
-    }
-    const int rp = offp + __popcll(bp & below), rn = offn + __popcll(bn & below);
-    s.rank_p[t] = fp ? rp : -1;
-    s.rank_n[t] = fn ? rn : -1;
-    if (fp && rp < MT_MAXC) s.val_p[rp] = t;
-    int flags = s.bad ? MT_FLAG_RANGE : 0;
-    if (P > MT_MAXC || N > MT_MAXC) flags |= MT_FLAG_SIZE;
+    if (t == 0) s.any_inf = s.max_ov = s.infeasible = 0;
+    int P, N;
+    int flags = mt_label_tables(s.tb, pv, nw, W, &P, &N);
     int iters = 0, feasible = 0;
     float margin = 0.f;
     if (!flags) {
-      for (int e = t; e < P * N; e += MT_THREADS) ov[e] = 0;
-      __threadfence();
-      __syncthreads();
-      for (int i = t; i < W; i += MT_THREADS) atomicAdd(&ov[s.rank_p[pv[i]] * N + s.rank_n[nw[i]]], 1);
-      __threadfence();
-      __syncthreads();
+      mt_overlap_counts(s.tb, pv, nw, W, P, N, ov);
       double* po = plan_out ? plan_out + (long)tw * MT_MAXC * MT_MAXC : nullptr;
       if (P <= 2 * MT_WAVES && N <= 64) flags = match_solve<2, 1, 2>(s, P, N, min_overlap, ov, kx, po, &iters, &feasible, &margin);
       else if (P <= 10 * MT_WAVES && N <= 192) flags = match_solve<10, 3, 10>(s, P, N, min_overlap, ov, kx, po, &iters, &feasible, &margin);
@@ -368,13 +314,7 @@ __global__ __launch_bounds__(MT_THREADS) void match_pot_chain_kernel(const int* 
     }
     if (flags) break;   // uniform: the chain ends at the first flagged window
     __syncthreads();    // map_row is complete
-    for (int i = t; i < W; i += MT_THREADS) {
-      const int q = nw[i];
-      const int m = feasible ? s.map_row[s.rank_n[q]] : -1;
-      out[i] = m >= 0 ? s.val_p[m] : q;
-    }
-    __threadfence();
-    __syncthreads();   // the next window reads `out` and reuses the LDS tables
+    mt_relabel(s.tb, nw, out, W, feasible ? s.map_row : nullptr);
   }
   // windows behind a flagged one were not run
   for (int e = t + (tw + 1) * MT_INFO; e < K_windows * MT_INFO; e += MT_THREADS) info[e] = 0;

@@ -464,10 +464,15 @@ def match_clusters(prev_clusters, new_clusters, method="hungarian", min_overlap=
 
 
 # windows that match_clusters_on_device / match_chain_on_device finished with the host specification although the device was
-# asked: a flag of the kernel (a decision within rounding, a label outside [0, 1024), more than 256 distinct labels)
+# asked: a flag of the kernel (a decision within rounding, a label outside [0, 1024), more than 256 distinct labels; for
+# "hungarian" also a cost matrix without a complete assignment, where the host call raises SciPy's ValueError)
 match_fallbacks = 0
 _MATCH_WS = {}
 MATCH_FLAG_SELECT, MATCH_FLAG_STOP, MATCH_FLAG_RANGE, MATCH_FLAG_SIZE = 1, 2, 4, 8
+MATCH_FLAG_ASSIGN = 16
+# method -> (chain entry, workspace size entry, diagnostic output per window: elements, dtype name)
+_MATCH_ENTRIES = {"pot": ("mused_match_pot_chain", "mused_match_pot_ws_bytes", 65536, "float64"),
+                  "hungarian": ("mused_match_hung_chain", "mused_match_hung_ws_bytes", 256, "int32")}
 _MATCH_LABELS = 1024   # label values the kernel's histogram covers (csrc/match.hip)
 
 
@@ -504,50 +509,62 @@ def _labels_to_host(x):
     return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
 
 
-def match_chain_launch(raw_dev, prev_dev, min_overlap, stream=None, want_plan=False):
-    """One mused_match_pot_chain launch over raw_dev (K x W int32 CUDA) against prev_dev (W int32 CUDA or None) ->
-    (matched K x W int32 CUDA, info K x 8 int32 NumPy, plans K x 65536 fp64 CUDA or None).  Synchronises the stream."""
+def _match_entry(method):
+    try:
+        return _MATCH_ENTRIES[method]
+    except (KeyError, TypeError):
+        raise ValueError("Invalid method. Choose 'hungarian' or 'pot'.") from None
+
+
+def match_chain_launch(raw_dev, prev_dev, min_overlap, stream=None, want_plan=False, method="pot"):
+    """One mused_match_pot_chain (method "pot") or mused_match_hung_chain ("hungarian") launch over raw_dev (K x W int32
+    CUDA) against prev_dev (W int32 CUDA or None) -> (matched K x W int32 CUDA, info K x 8 int32 NumPy, and with want_plan
+    the diagnostic output, else None: plans K x 65536 fp64 CUDA for "pot", assign K x 256 int32 CUDA -- the column of each
+    row of the P x N cost matrix or -1 -- for "hungarian").  Synchronises the stream."""
     import ctypes as C
 
     import torch
 
     from . import _lib
 
+    entry, ws_entry, diag_len, diag_dtype = _match_entry(method)
     K, W = raw_dev.shape
     dev = raw_dev.device
     st = stream if stream is not None else torch.cuda.current_stream()
     with torch.cuda.stream(st):
-        ws = _MATCH_WS.get((dev, st.cuda_stream))
+        ws = _MATCH_WS.get((dev, st.cuda_stream, method))
         if ws is None:
             if len(_MATCH_WS) > 16:
                 _MATCH_WS.clear()
-            ws = _MATCH_WS[(dev, st.cuda_stream)] = torch.empty(int(_lib.lib().mused_match_pot_ws_bytes()), dtype=torch.uint8,
-                                                                device=dev)
+            ws = _MATCH_WS[(dev, st.cuda_stream, method)] = torch.empty(int(getattr(_lib.lib(), ws_entry)()), dtype=torch.uint8,
+                                                                        device=dev)
         matched = torch.empty((K, W), dtype=torch.int32, device=dev)
         info = torch.empty((K, 8), dtype=torch.int32, device=dev)
-        plans = torch.zeros((K, 65536), dtype=torch.float64, device=dev) if want_plan else None
-        _lib.call("mused_match_pot_chain", _eng.ptr(raw_dev), K, W, _eng.ptr(prev_dev) if prev_dev is not None else None,
+        plans = torch.zeros((K, diag_len), dtype=getattr(torch, diag_dtype), device=dev) if want_plan else None
+        _lib.call(entry, _eng.ptr(raw_dev), K, W, _eng.ptr(prev_dev) if prev_dev is not None else None,
                   int(min_overlap), _eng.ptr(matched), _eng.ptr(info), _eng.ptr(plans) if want_plan else None, _eng.ptr(ws),
                   ws.numel(), C.c_void_p(st.cuda_stream))
         info_h = info.cpu().numpy()
     return matched, info_h, plans
 
 
-def match_chain_on_device(raw_windows, prev0=None, min_overlap=3, stream=None):
-    """`distributed.replay_label_chain(raw_windows, match_clusters, method="pot")` with the whole chain in one launch of
-    csrc/match.hip: matched_t = match_clusters(matched_{t-1}, raw_t, "pot", min_overlap), window 0 against prev0 (None: it
-    passes through).  raw_windows: (K, W) NumPy array or int32 / int64 CUDA tensor.  Returns the K * W matched labels
-    (NumPy int64).  A window the kernel flags (module docstring of csrc/match.hip) is matched by the host specification and
-    counted in `match_fallbacks`; the chain is launched again behind it."""
+def match_chain_on_device(raw_windows, prev0=None, min_overlap=3, stream=None, method="pot"):
+    """`distributed.replay_label_chain(raw_windows, match_clusters, method=method)` with the whole chain in one launch of
+    csrc/match.hip ("pot") or csrc/match_hung.hip ("hungarian"): matched_t = match_clusters(matched_{t-1}, raw_t, method,
+    min_overlap), window 0 against prev0 (None: it passes through).  raw_windows: (K, W) NumPy array or int32 / int64 CUDA
+    tensor.  Returns the K * W matched labels (NumPy int64).  A window the kernel flags (head of the kernel's source file) is
+    matched by the host `match_clusters` and counted in `match_fallbacks`; the chain is launched again behind it.  Where
+    SciPy finds no complete assignment (flag 16) that host call raises its ValueError, as the host chain does."""
     import torch
 
+    _match_entry(method)
     dev = raw_windows.device if isinstance(raw_windows, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
     stream = _match_stream(stream)
     with torch.cuda.stream(stream):
-        return _match_chain(raw_windows, prev0, min_overlap, stream, dev)
+        return _match_chain(raw_windows, prev0, min_overlap, stream, dev, method)
 
 
-def _match_chain(raw_windows, prev0, min_overlap, stream, dev):
+def _match_chain(raw_windows, prev0, min_overlap, stream, dev, method):
     raw_dev = _labels_to_device(raw_windows, dev)
     if raw_dev.dim() != 2:
         raise ValueError("raw_windows must be (K, W)")
@@ -560,7 +577,7 @@ def _match_chain(raw_windows, prev0, min_overlap, stream, dev):
     prev_dev = None if prev_host is None else _labels_to_device(prev_host, dev)
     t0 = 0
     while t0 < K:
-        matched, info, _ = match_chain_launch(raw_dev[t0:], prev_dev, min_overlap, stream)
+        matched, info, _ = match_chain_launch(raw_dev[t0:], prev_dev, min_overlap, stream, method=method)
         done = int(np.argmin(info[:, 6])) if not info[:, 6].all() else K - t0
         if done:
             out[t0:t0 + done] = matched[:done].cpu().numpy()
@@ -570,30 +587,32 @@ def _match_chain(raw_windows, prev0, min_overlap, stream, dev):
             if raw_host is None:
                 raw_host = _labels_to_host(raw_windows)
             _match_count_fallback()
-            out[t0] = match_clusters(None if prev_host is None else _labels_to_host(prev_host), raw_host[t0], "pot", min_overlap)
+            out[t0] = match_clusters(None if prev_host is None else _labels_to_host(prev_host), raw_host[t0], method, min_overlap)
             prev_host = out[t0]
             prev_dev = _labels_to_device(prev_host, dev)
             t0 += 1
     return out.ravel()
 
 
-def match_clusters_on_device(prev_clusters, new_clusters, min_overlap=3, stream=None):
-    """`match_clusters(prev_clusters, new_clusters, "pot", min_overlap)` on the device (csrc/match.hip; NumPy arrays or
-    int32 / int64 CUDA tensors).  Returns what match_clusters returns: `new_clusters` itself without a previous window or
-    when the overlap costs are infeasible, the relabelled array otherwise.  A window the kernel flags is matched by the
-    host specification and counted in `match_fallbacks`."""
+def match_clusters_on_device(prev_clusters, new_clusters, min_overlap=3, stream=None, method="pot"):
+    """`match_clusters(prev_clusters, new_clusters, method, min_overlap)` on the device (csrc/match.hip for "pot",
+    csrc/match_hung.hip for "hungarian"; NumPy arrays or int32 / int64 CUDA tensors).  Returns what match_clusters returns:
+    `new_clusters` itself without a previous window or when the overlap costs are infeasible, the relabelled array
+    otherwise.  A window the kernel flags is matched by the host `match_clusters` (which raises SciPy's ValueError where no
+    complete assignment exists) and counted in `match_fallbacks`."""
     import torch
 
+    _match_entry(method)
     if prev_clusters is None or len(prev_clusters) == 0:
         return new_clusters
     dev = new_clusters.device if isinstance(new_clusters, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
     stream = _match_stream(stream)
     with torch.cuda.stream(stream):
         matched, info, _ = match_chain_launch(_labels_to_device(new_clusters, dev).reshape(1, -1),
-                                              _labels_to_device(prev_clusters, dev), min_overlap, stream)
+                                              _labels_to_device(prev_clusters, dev), min_overlap, stream, method=method)
     if not info[0, 6]:
         _match_count_fallback()
-        return match_clusters(_labels_to_host(prev_clusters), _labels_to_host(new_clusters), "pot", min_overlap)
+        return match_clusters(_labels_to_host(prev_clusters), _labels_to_host(new_clusters), method, min_overlap)
     if not info[0, 3]:
         return new_clusters
     return matched[0].cpu().numpy().astype(np.int64)

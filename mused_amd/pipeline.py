@@ -46,8 +46,9 @@ class StreamPipeline:
         # thread that clusters).  Its state is a chain over windows, so its clustering runs on the chain worker, in window
         # order, not in the parallel k-means pool; the device work of later windows (slots included) still overlaps it.
         self._mini = approach == "sSVDMC_mini"
-        # "sSVDMC_pot": embedding and k-means as "sSVDMC"; the label chain matches by the Sinkhorn plan (main.py:111) on the
-        # device (csrc/match.hip), or with the host specification (mused_amd/sinkhorn.py) under MUSED_MATCH=host
+        # "sSVDMC_pot": embedding and k-means as "sSVDMC"; the label chain matches by the Sinkhorn plan (main.py:111), every
+        # other approach by SciPy's assignment (main.py:110).  Both chains run on the device (csrc/match.hip,
+        # csrc/match_hung.hip), or on the host (mused_amd/sinkhorn.py, SciPy) under MUSED_MATCH=host
         self._pot = approach == "sSVDMC_pot"
         self._match_device = os.environ.get("MUSED_MATCH", "device") != "host"
         self.n_clusters_total = None if n_clusters_total is None else int(n_clusters_total)
@@ -359,14 +360,15 @@ class StreamPipeline:
         clusters, sigma_host = fut.result() if hasattr(fut, "result") else fut
         trigger, t_start = job[4], job[5]
         t0 = time.perf_counter()
-        if self._pot and self._match_device:
+        method = "pot" if self._pot else "hungarian"
+        if self._match_device:
             torch.cuda.set_device(self._device)
             st = getattr(self._km_local, "stream", None)
             if st is None:
                 st = self._km_local.stream = torch.cuda.Stream(priority=-1)
-            matched = mo.match_clusters_on_device(self.prev, clusters, min_overlap=3, stream=st)
+            matched = mo.match_clusters_on_device(self.prev, clusters, min_overlap=3, stream=st, method=method)
         else:
-            matched = mo.match_clusters(self.prev, clusters, method="pot" if self._pot else "hungarian", min_overlap=3)
+            matched = mo.match_clusters(self.prev, clusters, method=method, min_overlap=3)
         if matched is None or len(matched) == 0:  # main.py:114-116
             matched = np.full(self.W, 0)
         self.host_ms["match"].append(1e3 * (time.perf_counter() - t0))
@@ -763,7 +765,10 @@ class SwfdmcLanes:
         self.sk.check()
         raw = {tr["trigger"]: tr["raw"] for tr in self.pipe.trace}
         self.sigma = {tr["trigger"]: tr["sigma"] for tr in self.pipe.trace}
-        return mdist.replay_label_chain(np.array([raw[t] for t in range(K)], dtype=np.int64), mo.match_clusters)
+        raw = np.array([raw[t] for t in range(K)], dtype=np.int64)
+        if self.pipe._match_device:   # the whole chain in one launch (csrc/match_hung.hip); MUSED_MATCH=host: SciPy per window
+            return mo.match_chain_on_device(raw, method="hungarian")
+        return mdist.replay_label_chain(raw, mo.match_clusters)
 
     def close(self):
         self.pipe.close()

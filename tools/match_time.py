@@ -1,19 +1,37 @@
-"""Per-window cost of the "sSVDMC_pot" label matching: `match_clusters_on_device` / `match_chain_on_device` (csrc/match.hip)
-against the host specification `match_clusters(..., "pot")` (mused_amd/sinkhorn.py, the stand-in for the reference's POT
-call) on label pairs (W, kp, kn, noise) and on a 20-window chain at W = 10000, k = 8.  Wall time of a call from NumPy labels
-to NumPy labels for both (the median of 12 calls), plus the kernel's time between events around the C call; labels compared.
-JSON on stdout."""
-import json, os, sys, time
+"""Per-window cost of the label matching on the device, `match_clusters_on_device` / `match_chain_on_device`, against the
+host `match_clusters`: --method pot (csrc/match.hip against mused_amd/sinkhorn.py, the stand-in for the reference's POT
+call) on label pairs (W, kp, kn, noise), --method hungarian (csrc/match_hung.hip against SciPy) on the same shapes and
+(2000, 4, 4) with labels that drift between groups of 8, so that the solver walks augmenting paths; both on a 20-window
+chain at W = 10000, k = 8.  Wall time of a call from NumPy labels to NumPy labels for both (the median of 12 calls), plus
+the kernel's time between events around the C call (for hungarian also with a min_overlap no count reaches: everything
+but the solver); labels compared.  JSON on stdout."""
+import argparse, json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mused_amd import matrix_operations as mo
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--method", choices=("pot", "hungarian"), default="pot")
+METHOD = ap.parse_args().method
+HUNG = METHOD == "hungarian"
 CALLS, WARM = 12, 2
 # the last pair is the largest size class of the kernel (part of K in the workspace)
 PAIRS = ((10000, 150, 150, .5), (2000, 50, 50, .1), (2000, 8, 8, .02), (2000, 2, 2, .2), (20000, 256, 256, .5))
 
 
+def drift_case(seed, W, kp, kn):
+    """tests/test_match_hung_host.py's generator: a new label stays in its previous label's group of 8 or moves to the next
+    group for 15 % of the rows.  As there, groups of 4 at 4 x 4 (with groups of 8 on 4 labels nothing would drift)."""
+    g = 4 if (kp, kn) == (4, 4) else 8
+    rng = np.random.default_rng(seed)
+    prev = rng.integers(0, kp, W)
+    base = (prev // g) * g + np.where(rng.random(W) < 0.15, g, 0)
+    return prev, (base + rng.integers(0, g, W)) % kn
+
+
 def case(seed, W, kp, kn, noise):
+    if HUNG:
+        return drift_case(seed, W, kp, kn)
     rng = np.random.default_rng(seed)
     prev = rng.integers(0, kp, W)
     perm = rng.permutation(max(kp, kn))
@@ -41,7 +59,7 @@ def median_ms(fn):
     return float(np.median(ms)), res
 
 
-def launch_ms(raw, prev):
+def launch_ms(raw, prev, min_overlap=3):
     """The kernel alone: events around the C call, every buffer allocated before, info read after the second event."""
     import ctypes as C
     from mused_amd import _lib, engine as eng
@@ -50,13 +68,14 @@ def launch_ms(raw, prev):
     K, W = rd.shape
     matched = torch.empty((K, W), dtype=torch.int32, device="cuda")
     info = torch.empty((K, 8), dtype=torch.int32, device="cuda")
-    ws = torch.empty(int(_lib.lib().mused_match_pot_ws_bytes()), dtype=torch.uint8, device="cuda")
+    entry, ws_entry = mo._MATCH_ENTRIES[METHOD][:2]
+    ws = torch.empty(int(getattr(_lib.lib(), ws_entry)()), dtype=torch.uint8, device="cuda")
     st = torch.cuda.current_stream()
     ms = []
     for i in range(WARM + CALLS):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        _lib.call("mused_match_pot_chain", eng.ptr(rd), K, W, eng.ptr(pd) if pd is not None else None, 3, eng.ptr(matched),
+        _lib.call(entry, eng.ptr(rd), K, W, eng.ptr(pd) if pd is not None else None, min_overlap, eng.ptr(matched),
                   eng.ptr(info), None, eng.ptr(ws), ws.numel(), C.c_void_p(st.cuda_stream))
         e1.record()
         e1.synchronize()
@@ -68,25 +87,29 @@ def launch_ms(raw, prev):
 def host_chain(raw):
     prev, out = None, []
     for r in raw:
-        prev = mo.match_clusters(prev, r, "pot", 3)
+        prev = mo.match_clusters(prev, r, METHOD, 3)
         out.extend(prev)
     return np.array(out)
 
 
-out = {"calls_timed": CALLS, "pairs": [], "chain": None}
-for W, kp, kn, noise in PAIRS:
+out = {"method": METHOD, "calls_timed": CALLS, "pairs": [], "chain": None}
+for W, kp, kn, noise in PAIRS + (((2000, 4, 4, 0),) if HUNG else ()):
     prev, new = case(0, W, kp, kn, noise)
     before = mo.match_fallbacks
-    dev_ms, lab_dev = median_ms(lambda: mo.match_clusters_on_device(prev, new, 3))
+    dev_ms, lab_dev = median_ms(lambda: mo.match_clusters_on_device(prev, new, 3, method=METHOD))
     fb = mo.match_fallbacks - before
-    host_ms, lab_host = median_ms(lambda: mo.match_clusters(prev, new, "pot", 3))
+    host_ms, lab_host = median_ms(lambda: mo.match_clusters(prev, new, METHOD, 3))
     ev_ms, info = launch_ms(new.reshape(1, -1), prev)
-    out["pairs"].append(dict(W=W, kp=kp, kn=kn, noise=noise, P=int(info[0, 0]), N=int(info[0, 1]), iterations=int(info[0, 2]),
-                             device_wall_ms_median=dev_ms, kernel_ms_median=ev_ms, host_wall_ms_median=host_ms,
-                             fallbacks=fb, same_labels=bool(np.array_equal(lab_dev, lab_host))))
+    row = dict(W=W, kp=kp, kn=kn, noise=noise, P=int(info[0, 0]), N=int(info[0, 1]), iterations=int(info[0, 2]),
+               feasible=int(info[0, 3]), device_wall_ms_median=dev_ms, kernel_ms_median=ev_ms, host_wall_ms_median=host_ms,
+               fallbacks=fb, same_labels=bool(np.array_equal(lab_dev, lab_host)))
+    if HUNG:   # `iterations` are the solver's Dijkstra steps; their cost from the same launch without a solve
+        row["kernel_ms_without_solve"] = launch_ms(new.reshape(1, -1), prev, min_overlap=W + 1)[0]
+        row["us_per_step"] = 1e3 * (ev_ms - row["kernel_ms_without_solve"]) / max(row["iterations"], 1)
+    out["pairs"].append(row)
 raw = chain()
 before = mo.match_fallbacks
-dev_ms, lab_dev = median_ms(lambda: mo.match_chain_on_device(raw))
+dev_ms, lab_dev = median_ms(lambda: mo.match_chain_on_device(raw, method=METHOD))
 fb = mo.match_fallbacks - before
 host_ms, lab_host = median_ms(lambda: host_chain(raw))
 ev_ms, info = launch_ms(raw, None)
