@@ -296,6 +296,21 @@ long mused_match_hung_ws_bytes(void);
 int mused_match_hung_chain(const int* raw, int K_windows, int W, const int* prev0, int min_overlap, int* matched_out,
                            int* info_out, int* assign_out, void* ws, long ws_bytes, void* stream);
 
+/* ---- DBSCAN_batch: perform_dbscan_clustering (matrix_operations.py:235-238, sklearn DBSCAN(eps, min_samples,
+ * metric="euclidean").fit_predict) on fp64 rows, csrc/dbscan.hip.  scikit-learn's index-order search in closed form
+ * (specification: mused_amd/dbscan.py): core rows have >= min_samples rows within eps (themselves included), clusters are the
+ * connected components of the core rows numbered by ascending smallest core index, another row takes the smallest label
+ * among its core neighbours or -1.  Three passes over the fp64 MFMA distance tiles (count, union-find, border rows) and
+ * O(n) workspace: no n x n array, neighbour list or bitmask.  Enqueue-only.
+ * X: n x d fp64 (pitch ld), n <= 2^19 (the tile grid of one launch).  labels_out: n int32 (DEVICE).  info_out (DEVICE, 4 int32) = {flags, clusters, core
+ *   rows, 0}.  Flags: 1 some pair i != j has | d2 - eps^2 | <= 2 (d + 8) 2^-52 (|x_i|^2 + |x_j|^2) + 4 ulp(eps^2), the bound
+ *   within which two ways of evaluating d2 can disagree; 2 a row is not finite.  With either flag the labels are NOT
+ *   scikit-learn's: call it on the host (it raises on non-finite input).
+ * ws: mused_dbscan_ws_bytes(n) bytes (24 n + 4 ceil(n / 128) and alignment; -1 for n outside [1, 2^19]). */
+long mused_dbscan_ws_bytes(long n);
+int mused_dbscan(const double* X, long n, int d, long ld, double eps, int min_samples, int* labels_out, int* info_out,
+                 void* ws, long ws_bytes, void* stream);
+
 /* ---- a5-a7: SeqBasedSWFD (swfd submodule; call sites main.py:62,65-67,70) ---------------------- */
 
 /* SeqBasedSWFD(N=, R=, d=, sketch_dim=) */

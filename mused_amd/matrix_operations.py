@@ -625,6 +625,80 @@ def perform_dbscan_clustering(data, eps=0.5, min_samples=5):
     return DBSCAN(eps=eps, min_samples=min_samples, metric="euclidean").fit_predict(data)
 
 
+# calls that perform_dbscan_clustering_on_device finished with scikit-learn on the host although the device was asked: the
+# kernel's ambiguity flag (a pair within rounding of eps) or its non-finite flag (scikit-learn raises there)
+dbscan_fallbacks = 0
+DBSCAN_MAX_ROWS = 1 << 19   # csrc/dbscan.hip: what the tile grid of one launch holds
+
+
+def _dbscan_count_fallback():
+    global dbscan_fallbacks
+    with _km_fallback_lock:
+        dbscan_fallbacks += 1
+
+
+def dbscan_launch(X_dev, eps, min_samples, stream=None):
+    """One mused_dbscan call on an (n, d) fp64 CUDA tensor (unit stride along the columns) -> (labels n int32 CUDA, info
+    4 int32 NumPy = {flags, clusters, core rows, 0}; flags: mused_amd.dbscan.FLAG_*).  Synchronises the stream."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+
+    n, d = X_dev.shape
+    st = stream if stream is not None else torch.cuda.current_stream()
+    with torch.cuda.stream(st):
+        ws = torch.empty(int(_lib.lib().mused_dbscan_ws_bytes(n)), dtype=torch.uint8, device=X_dev.device)
+        labels = torch.empty(n, dtype=torch.int32, device=X_dev.device)
+        info = torch.empty(4, dtype=torch.int32, device=X_dev.device)
+        _lib.call("mused_dbscan", _eng.ptr(X_dev), n, d, X_dev.stride(0), float(eps), int(min_samples), _eng.ptr(labels),
+                  _eng.ptr(info), _eng.ptr(ws), ws.numel(), C.c_void_p(st.cuda_stream))
+        info_h = info.cpu().numpy()
+    return labels, info_h
+
+
+def perform_dbscan_clustering_on_device(emb, eps=0.5, min_samples=5, stream=None):
+    """`perform_dbscan_clustering(emb, eps, min_samples)` with the pair work on the device (csrc/dbscan.hip; the rule and
+    its rounding margin: mused_amd/dbscan.py): scikit-learn's labels as int64 NumPy, O(n) device memory beside the rows.
+    emb: (n, d) fp64 CUDA tensor or ndarray.  Where the kernel raises its ambiguity flag (some pair lies within rounding
+    of eps) or its non-finite flag, the host `perform_dbscan_clustering` runs on a host copy -- it raises what
+    scikit-learn raises -- and the call is counted in `dbscan_fallbacks`.  What the kernel does not take goes to the host
+    call uncounted: MUSED_DBSCAN=host (the former path as a whole), rows that are not fp64 (scikit-learn's arithmetic
+    follows the dtype), arguments scikit-learn rejects, more than 2^19 rows.
+    stream: the kernels run on it behind whatever the current stream holds; the call returns after they have finished (it
+    reads the flags), so `emb` need only stay alive until then."""
+    import numbers
+    import os
+
+    import torch
+
+    on_dev = isinstance(emb, torch.Tensor)
+
+    def host():
+        return perform_dbscan_clustering(emb.cpu().numpy() if on_dev else emb, eps=eps, min_samples=min_samples)
+
+    if os.environ.get("MUSED_DBSCAN", "device") == "host":
+        return host()
+    X = emb if on_dev else np.asarray(emb)
+    ok = (isinstance(eps, numbers.Real) and not isinstance(eps, bool) and 0.0 < float(eps) < 1e150
+          and isinstance(min_samples, numbers.Integral) and not isinstance(min_samples, bool) and 1 <= min_samples < 2 ** 31
+          and X.ndim == 2 and 1 <= X.shape[0] <= DBSCAN_MAX_ROWS and 1 <= X.shape[1] < 2 ** 20
+          and X.dtype in (torch.float64, np.float64))
+    if not ok:
+        return host()
+    st = _match_stream(stream)
+    with torch.cuda.stream(st):
+        Xd = X if on_dev else torch.from_numpy(np.ascontiguousarray(X)).cuda()
+        if Xd.stride(1) != 1 or Xd.stride(0) < Xd.shape[1]:
+            Xd = Xd.contiguous()
+        labels, info = dbscan_launch(Xd, eps, min_samples, st)
+        if info[0]:
+            _dbscan_count_fallback()
+            return host()
+        return labels.cpu().numpy().astype(np.int64)
+
+
 def perform_hdbscan_clustering(data, min_cluster_size=5, min_samples=2):
     """matrix_operations.py:240-243 (needs the optional `hdbscan` package, as the reference does)."""
     import hdbscan

@@ -669,7 +669,8 @@ def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_
                        window_size, timings=None):
     """Same positional parameters as main.py:132: the whole subset as one window -- kNN adjacency per modality, fusion,
     randomized-SVD embedding on the device (`batch_embedding`), then "SVDMC_batch": k-means with n_clusters on the device
-    (perform_clustering_on_device: scikit-learn's labels); "DBSCAN_batch" / "HDBSCAN_batch": the host wrappers on the
+    (perform_clustering_on_device: scikit-learn's labels); "DBSCAN_batch": DBSCAN on the device embedding
+    (perform_dbscan_clustering_on_device: scikit-learn's labels, csrc/dbscan.hip); "HDBSCAN_batch": the host wrapper on the
     embedding, as the reference does.  Returns `results` with the labels ("all_clusters") and the wall time
     ("processing_time"), like process_streaming_data.  `timings`: see batch_embedding (plus "clustering" and "edges")."""
     if approach not in BATCH_APPROACHES:
@@ -683,7 +684,7 @@ def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_
         clusters = mo.perform_hdbscan_clustering(emb.cpu().numpy(), min_cluster_size=min_cluster_size,
                                                  min_samples=min_samples)
     elif approach == "DBSCAN_batch":
-        clusters = mo.perform_dbscan_clustering(emb.cpu().numpy(), eps=eps, min_samples=min_samples)
+        clusters = mo.perform_dbscan_clustering_on_device(emb, eps=eps, min_samples=min_samples)
     else:
         clusters = mo.perform_clustering_on_device(emb, n_clusters, seed)
     if timings is not None:
