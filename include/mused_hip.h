@@ -203,7 +203,10 @@ int mused_gemm_f64_batched(int a_kc, int b_kc, const double* A, long lda, long s
  * mused_gemm_f64_splitk: partial (nsplit x M x N, pitch N) = the products over k in [s kchunk, (s + 1) kchunk), then C (M x N,
  *   pitch N, alpha = 1) = their sum in split order.  kchunk > 0 a multiple of 16, nsplit >= 1, kchunk * nsplit >= K.
  * mused_gemm_f64_batched_splitk: the same per batch entry (partial: batch x nsplit x M x N, C: batch x M x N), entries with
- *   rep[z] != z skipped in both steps (rep may be NULL). */
+ *   rep[z] != z skipped in both steps (rep may be NULL).
+ * mused_kmeans_assign_rows: the rows per LDS sub-tile of the E/M-step kernel mused_kmeans_lloyd launches for (d, k): 64,
+ *   32 or 16 (the largest whose LDS need fits), 0 = the row-per-thread kernel (what MUSED_KMEANS_ASSIGN=p forces); -1
+ *   where mused_kmeans_lloyd rejects (d, k). */
 int mused_gemm_f64_batched_rep(int a_kc, int b_kc, const double* A, long lda, long strideA, const double* B, long ldb,
                                long strideB, double* C, long ldc, long strideC, int M, int N, int K, int batch,
                                double alpha, const int* rep, void* stream);
@@ -212,6 +215,7 @@ int mused_gemm_f64_splitk(int a_kc, int b_kc, const double* A, long lda, const d
 int mused_gemm_f64_batched_splitk(int a_kc, int b_kc, const double* A, long lda, long strideA, const double* B, long ldb,
                                   long strideB, double* partial, double* C, int M, int N, int K, int batch, int kchunk,
                                   int nsplit, const int* rep, void* stream);
+int mused_kmeans_assign_rows(int d, int k);
 
 /* ---- a10 / f2: the Lloyd iterations of perform_clustering (matrix_operations.py:149-153, sklearn KMeans) ------------
  * The seeds come from mused_kmeans_seed below (or from scikit-learn's own routine on the host); E / M steps and

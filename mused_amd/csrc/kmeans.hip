@@ -233,6 +233,25 @@ __global__ __launch_bounds__(1024) void km_update_kernel(const double* __restric
   }
 }
 
+// LDS bytes of km_assign_tiled_kernel<tr>: centres [k][d + 1], sums [k][d], rows [tr][d + 1], labels
+static size_t km_tiled_lds(int tr, int d, int k) {
+  return 8 * ((size_t)k * (d + 1) + (size_t)k * d + (size_t)tr * (d + 1)) + 4 * KM_CHUNK + 16;
+}
+constexpr size_t KM_LDS_MAX = 156 * 1024;
+
+// The E/M-step kernel of a call: the staged variant with the largest sub-tile (64 / 32 / 16 rows) whose LDS need fits;
+// 0 = the row-per-thread kernel (also with MUSED_KMEANS_ASSIGN=p, read once).
+static int km_assign_rows(int d, int k) {
+  static const bool plain_only = [] {
+    const char* e = getenv("MUSED_KMEANS_ASSIGN");
+    return e && e[0] == 'p';
+  }();
+  if (plain_only) return 0;
+  for (int tr = 64; tr >= 16; tr >>= 1)
+    if (km_tiled_lds(tr, d, k) <= KM_LDS_MAX) return tr;
+  return 0;
+}
+
 }  // namespace mused
 
 using namespace mused;
@@ -244,6 +263,12 @@ long mused_kmeans_ws_bytes(int n, int d, int k) {
   if (n <= 0 || d <= 0 || k <= 0) return -1;
   const long nchunk = (n + KM_CHUNK - 1) / KM_CHUNK;
   return 8l * n * d + 8l * nchunk * k * d + 4l * nchunk * k + 8l * k + 8l * n + 4096;
+}
+
+// diagnostic: the sub-tile rows mused_kmeans_lloyd launches its E/M step with for (d, k): 64 / 32 / 16, 0 = row per thread
+int mused_kmeans_assign_rows(int d, int k) {
+  if (d <= 0 || k <= 0 || (long)k * d > 8192 || k > 1024) return -1;
+  return km_assign_rows(d, k);
 }
 
 // Replaces the Lloyd iterations of KMeans(n_clusters = k, random_state = seed).fit_predict(X)
@@ -270,27 +295,19 @@ int mused_kmeans_lloyd(const double* X, long ld, int n, int d, int k, const doub
   int* lab2 = (int*)w; w += 4l * n;
   w = (char*)(((uintptr_t)w + 15) & ~(uintptr_t)15);
   KmInfo* info = (KmInfo*)w;
-  const size_t lds_plain = 8 * 2 * (size_t)k * d + 4 * (KM_CHUNK + (size_t)k) + 16;
-  // staged variant: the largest sub-tile (64 / 32 / 16 rows) whose LDS need fits; 0 = the row-per-thread kernel
-  auto tiled_lds = [&](int tr) -> size_t { return 8 * ((size_t)k * (d + 1) + (size_t)k * d + (size_t)tr * (d + 1)) + 4 * KM_CHUNK + 16; };
-  constexpr size_t LDS_MAX = 156 * 1024;
-  static const bool plain_only = [] {
-    const char* e = getenv("MUSED_KMEANS_ASSIGN");
-    return e && e[0] == 'p';
-  }();
-  const int tr = plain_only ? 0 : (tiled_lds(64) <= LDS_MAX ? 64 : (tiled_lds(32) <= LDS_MAX ? 32 : (tiled_lds(16) <= LDS_MAX ? 16 : 0)));
-  const size_t lds = tr ? tiled_lds(tr) : lds_plain;
+  const int tr = km_assign_rows(d, k);
+  const size_t lds = tr ? km_tiled_lds(tr, d, k) : 8 * 2 * (size_t)k * d + 4 * (KM_CHUNK + (size_t)k) + 16;
   static std::once_flag once;
   static hipError_t aerr = hipSuccess;
   std::call_once(once, [] {
     aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                8 * 2 * 8192 + 4 * (KM_CHUNK + 1024) + 16);
     if (aerr == hipSuccess)
-      aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_tiled_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
+      aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_tiled_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KM_LDS_MAX);
     if (aerr == hipSuccess)
-      aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_tiled_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
+      aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_tiled_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KM_LDS_MAX);
     if (aerr == hipSuccess)
-      aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_tiled_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
+      aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_tiled_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KM_LDS_MAX);
   });
   MUSED_CHECK_HIP(aerr);
   auto assign = [&](int* cur_, const int* old_, int want) {
