@@ -315,6 +315,22 @@ long mused_dbscan_ws_bytes(long n);
 int mused_dbscan(const double* X, long n, int d, long ld, double eps, int min_samples, int* labels_out, int* info_out,
                  void* ws, long ws_bytes, void* stream);
 
+/* ---- scoring a run: compute_all_metrics (metrics_evaluation.py:47-92: scikit-learn's NMI, NMI over the rows whose true
+ * label is > 0, weighted F1 / precision / recall, accuracy, MAE), csrc/score.hip.  All seven are functions of the
+ * true-class x predicted-cluster contingency table (specification: mused_amd/scores.py).  One launch, one workgroup per
+ * segment, enqueue-only.
+ * truth, pred (DEVICE int32): n_seg consecutive segments of seg_len labels, each scored on its own.
+ * out (DEVICE, n_seg x 8 fp64) = {f1, nmi, nmi_e, precision, recall, accuracy, mae, sum |truth - pred|}; accuracy and mae
+ *   are one division of exact integers (scikit-learn's bits), the other five carry the rounding of `log` and of the sums.
+ * info (DEVICE, n_seg x 8 int32) = {T distinct true values, P distinct predicted values, size of their union, rows with
+ *   truth > 0, rows with truth == pred, flags, 0, 0}.  Flags: 4 a label outside [-1, 65534]; 8 T > 4096, P > 4096 or
+ *   T * P > cells_cap.  A flagged segment has out = 0: score it on the host.
+ * ws: mused_score_ws_bytes(n_seg, cells_cap) bytes (4 n_seg cells_cap); tables above 24,576 cells live there and are cleared
+ *   by the kernel, smaller ones stay in LDS.  cells_cap <= 4096^2. */
+long mused_score_ws_bytes(long n_seg, long cells_cap);
+int mused_score_labels(const int* truth, const int* pred, long n_seg, long seg_len, long cells_cap, double* out, int* info,
+                       void* ws, long ws_bytes, void* stream);
+
 /* ---- a5-a7: SeqBasedSWFD (swfd submodule; call sites main.py:62,65-67,70) ---------------------- */
 
 /* SeqBasedSWFD(N=, R=, d=, sketch_dim=) */

@@ -602,19 +602,51 @@ class StreamPipeline:
 
 def process_streaming_data(results, data_modalities, modality_types, window_size, reduced_dim, k_basis, n_clusters_total,
                            seed, approach, complete_true_labels, step_window_ratio, noise_rate, label_mode, sorting,
-                           eps, min_samples):
-    """Same positional parameters as main.py:13.  The reference hands its outputs to
-    metrics_evaluation (out of scope here); this returns `results` with the label arrays and the
-    wall time instead."""
+                           eps, min_samples, score=False):
+    """Same positional parameters as main.py:13.  Returns `results` with the label arrays ("all_clusters") and the wall
+    time ("processing_time").  `score=True`: `results` (get_initial_results()'s lists when none is given) also receives
+    what the reference's compute_all_metrics appends (main.py:128: the concatenated window labels against the
+    concatenated true labels of main.py:39-40, which repeat rows when step_window_ratio > 1; "processing_time" is then
+    the reference's list), and "window_scores", the (K, 7) scores of the K windows from one launch
+    (metrics_evaluation.score_windows)."""
     t0 = time.time_ns()
     # modality types go through unchanged: "" / anything the reference does not special-case = Euclidean kNN
     # (matrix_operations.py:112), "text" and "cosine" = the cosine kernel, the other SED2012 metadata types raise
     with StreamPipeline(window_size, reduced_dim, k_basis, seed, approach, list(modality_types), step_window_ratio,
                         window_slots=int(os.environ.get("MUSED_WINDOW_SLOTS", "1")), n_clusters_total=n_clusters_total) as pipe:
         clusters = pipe.run(data_modalities, np.asarray(complete_true_labels))
+    t1 = time.time_ns()
+    if score:
+        return _scored(results, clusters, _window_true_labels(complete_true_labels, len(data_modalities[0]), window_size,
+                                                              step_window_ratio),
+                       (len(data_modalities[0]), noise_rate, label_mode, sorting, reduced_dim, k_basis, window_size), t1, t0,
+                       window_size)
     results = dict(results or {})
     results["all_clusters"] = clusters
-    results["processing_time"] = (time.time_ns() - t0) / 1e9
+    results["processing_time"] = (t1 - t0) / 1e9
+    return results
+
+
+def _window_true_labels(complete_true_labels, n, window_size, step_window_ratio):
+    """all_true_labels of main.py:39-40: the true labels of every processed window, concatenated."""
+    labels = np.asarray(complete_true_labels)
+    parts = [labels[i + 1 - window_size : i + 1] for i in range(n)
+             if i + 1 >= window_size and (i + 1) * step_window_ratio % window_size == 0]   # main.py:32
+    return np.concatenate(parts) if parts else labels[:0]
+
+
+def _scored(results, clusters, true_labels, variables, t1, t0, window_size=None):
+    """`results` after the reference's compute_all_metrics call (main.py:128, :165), plus "all_clusters" and, for a
+    stream, the per-window scores."""
+    from . import metrics_evaluation as me
+
+    results = dict(results) if results else me.get_initial_results()[0]
+    clusters = np.asarray(clusters)
+    me.compute_all_metrics(results, *variables, clusters, true_labels, t1, t0)
+    results["all_clusters"] = clusters
+    if window_size is not None:
+        results["window_scores"] = (me.score_windows(true_labels.reshape(-1, window_size), clusters.reshape(-1, window_size))
+                                    if len(clusters) else np.empty((0, 7)))
     return results
 
 
@@ -666,13 +698,14 @@ def batch_embedding(data_modalities, modality_types, reduced_dim, k_basis, seed,
 
 def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_basis, n_clusters, seed, approach,
                        complete_true_labels, noise_rate, label_mode, sorting, eps, min_samples, min_cluster_size,
-                       window_size, timings=None):
+                       window_size, timings=None, score=False):
     """Same positional parameters as main.py:132: the whole subset as one window -- kNN adjacency per modality, fusion,
     randomized-SVD embedding on the device (`batch_embedding`), then "SVDMC_batch": k-means with n_clusters on the device
     (perform_clustering_on_device: scikit-learn's labels); "DBSCAN_batch": DBSCAN on the device embedding
     (perform_dbscan_clustering_on_device: scikit-learn's labels, csrc/dbscan.hip); "HDBSCAN_batch": the host wrapper on the
     embedding, as the reference does.  Returns `results` with the labels ("all_clusters") and the wall time
-    ("processing_time"), like process_streaming_data.  `timings`: see batch_embedding (plus "clustering" and "edges")."""
+    ("processing_time"), like process_streaming_data.  `timings`: see batch_embedding (plus "clustering" and "edges").
+    `score=True`: `results` also receives what the reference's compute_all_metrics appends (main.py:165)."""
     if approach not in BATCH_APPROACHES:
         raise ValueError(f"approach {approach!r} is not a batch approach {BATCH_APPROACHES}")
     if approach == "HDBSCAN_batch":
@@ -690,9 +723,13 @@ def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_
     if timings is not None:
         timings["clustering"] = time.perf_counter() - t1
         timings["edges"] = nnz
+    t_end = time.time_ns()
+    if score:
+        return _scored(results, clusters, np.array(complete_true_labels),
+                       (len(data_modalities[0]), noise_rate, label_mode, sorting, reduced_dim, k_basis, window_size), t_end, t0)
     results = dict(results or {})
     results["all_clusters"] = np.asarray(clusters)
-    results["processing_time"] = (time.time_ns() - t0) / 1e9
+    results["processing_time"] = (t_end - t0) / 1e9
     return results
 
 
