@@ -380,7 +380,8 @@ __global__ __launch_bounds__(64) void trd_t_kernel(const int* __restrict__ rep, 
 // a tile is at the same time the B operand of the K-slice of rows 16 T + 4 r .. 4 r + 3, so S needs no data movement, and
 // the same holds for S in C = T S and for C in Z -= V C.  The A operands (V^T, T, V) come from LDS, one 8-byte read per
 // lane and MFMA, from two copies of the reflector block laid out for conflict-free reads ([row][reflector] for V^T,
-// [reflector][row], pitch 272, for V).  No cross-wave reduction, two barriers per block of 16 reflectors (staging).
+// [reflector][row], pitch 272, for V).  No cross-wave reduction; the copies are double-buffered: one barrier per block of 16
+// reflectors.  The certificate's cosines are formed from the same tiles before the first block.
 constexpr int DM_VA = 0;                 // [256][16]   V as [row][reflector]
 constexpr int DM_VB = 4096;              // [16][272]   V as [reflector][row]
 constexpr int DM_TM = DM_VB + 16 * 272;  // [16][16]    T
@@ -418,27 +419,7 @@ __global__ __launch_bounds__(TNT, 1) void trd_d_kernel(double* __restrict__ Gc, 
     for (int o = 32; o > 0; o >>= 1) rmax = fmax(rmax, __shfl_xor(rmax, o));
     if (t == 0) sm[L_MISC + 10] = rmax;
   }
-  __syncthreads();
-  // certificate: cosines between neighbours in the spectrum, clusters wider than the neighbourhood
-  {
-    const int c = t >> 2, dl = (t & 3) + 1, c2 = c + dl;
-    if (c2 < TM && significant(c) && significant(c2)) {
-      double dotv = 0.0;
-#pragma unroll 8
-      for (int i = off; i < TN; ++i) dotv = fma(Zg[(long)i * TM + c], Zg[(long)i * TM + c2], dotv);
-      if (!(fabs(dotv) * sm[L_ZS + c] * sm[L_ZS + c2] <= TRD_COS_MAX)) atomicOr(badflag, 2);
-    }
-    if ((t & 3) == 0 && c + 5 < TM && significant(c) && significant(c + 5)) {
-      const double width = fmax(1e-7 * lam0, TRD_GAP_PER_RES * sm[L_MISC + 10] * wsm[W_MI]);
-      if ((sm[L_LAM + c] - sm[L_LAM + c + 5]) <= width) atomicOr(badflag, 4);
-    }
-  }
-  __syncthreads();
-  if (*badflag) {  // leave G as it is: the Jacobi solver takes this matrix
-    if (t == 0) done[bm] = 0;
-    return;
-  }
-  // Z tiles of this wave: column 16 w + li, rows 16 T + kq + 4 r
+  // Z tiles of this wave, normalised: column 16 w + li, rows 16 T + kq + 4 r
   const int col = 16 * w + li;
   const bool wact = 16 * w < sh.nvec;  // (nvec is a multiple of 32: a wave's 16 columns are all formed or none is)
   v4f64 Zt[16];
@@ -449,9 +430,6 @@ __global__ __launch_bounds__(TNT, 1) void trd_d_kernel(double* __restrict__ Gc, 
 #pragma unroll
       for (int r = 0; r < 4; ++r) Zt[T][r] = wact ? Zg[(long)(16 * T + kq + 4 * r) * TM + col] * zs : 0.0;
   }
-  double* vA = S + DM_VA;
-  double* vB = S + DM_VB;
-  double* tm = S + DM_TM;
   // staging of a block: 16 reflectors x 256 rows = 8 values per thread (coalesced along the row), T: 256 values
   const int kb_lo = off >> 4;  // blocks below hold identity reflectors only (embedded order)
   auto fetch = [&](int kb, double (&nx)[8], double& tx) {
@@ -462,22 +440,76 @@ __global__ __launch_bounds__(TNT, 1) void trd_d_kernel(double* __restrict__ Gc, 
     }
     tx = (kb >= kb_lo && t < 256) ? wsm[W_TM + kb * 256 + t] : 0.0;
   };
-  auto store = [&](const double (&nx)[8], double tx) {
+  auto store = [&](double* __restrict__ buf, const double (&nx)[8], double tx) {
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
       const int idx = t + TNT * m, rr = idx >> 8, row = idx & 255;
-      vA[row * 16 + rr] = nx[m];
-      vB[rr * 272 + row] = nx[m];
+      buf[DM_VA + row * 16 + rr] = nx[m];
+      buf[DM_VB + rr * 272 + row] = nx[m];
     }
-    if (t < 256) tm[t] = tx;
+    if (t < 256) buf[DM_TM + t] = tx;
   };
   double nx[8], tx;
   const int kb_top = (TN - 3) >> 4;
-  fetch(kb_top, nx, tx);
-  store(nx, tx);
+  fetch(kb_top, nx, tx);  // (in flight during the certificate)
+  // certificate: cosines between neighbours in the spectrum from the tiles, clusters wider than the neighbourhood.  The
+  // neighbours c + 1 .. c + 4 of a column sit in the next lanes of its 16-lane row; the first four columns of every wave go
+  // through the (still unused) staging memory for the last four columns of the wave before it.
+  {
+    double* bnd = S;  // [wave][4][256]
+    if (li < 4) {
+#pragma unroll
+      for (int T = 0; T < 16; ++T)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bnd[w * 1024 + li * 256 + 16 * T + kq + 4 * r] = Zt[T][r];
+    }
+    __syncthreads();
+    const double* xb = bnd + (w < 7 ? w + 1 : w) * 1024 + (li & 3) * 256;  // (wave 7 has no successor: its pairs are skipped)
+    double dot[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int T = 0; T < 16; ++T) {
+      if (16 * T + 15 >= off) {  // uniform: rows above an embedded order do not count
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * T + kq + 4 * r;
+          const double z = row >= off ? Zt[T][r] : 0.0;
+          const double x = row >= off ? xb[row] : 0.0;  // lanes li < 4: column li of the next wave
+#pragma unroll
+          for (int dl = 1; dl <= 4; ++dl) {
+            const double y = li < dl ? x : z;  // lane m of the row: column m of this wave, or of the next one for m < dl
+            dot[dl - 1] = fma(z, __shfl(y, (l & 48) | ((li + dl) & 15)), dot[dl - 1]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int dl = 1; dl <= 4; ++dl) {
+      double dv = dot[dl - 1];
+      dv += __shfl_xor(dv, 16);
+      dv += __shfl_xor(dv, 32);
+      const int c2 = col + dl;
+      if (kq == 0 && c2 < TM && significant(col) && significant(c2) && !(fabs(dv) <= TRD_COS_MAX)) atomicOr(badflag, 2);
+    }
+    const int c = t >> 2;
+    if ((t & 3) == 0 && c + 5 < TM && significant(c) && significant(c + 5)) {
+      const double width = fmax(1e-7 * lam0, TRD_GAP_PER_RES * sm[L_MISC + 10] * wsm[W_MI]);
+      if ((sm[L_LAM + c] - sm[L_LAM + c + 5]) <= width) atomicOr(badflag, 4);
+    }
+  }
   __syncthreads();
+  if (*badflag) {  // leave G as it is: the Jacobi solver takes this matrix
+    if (t == 0) done[bm] = 0;
+    return;
+  }
+  // two staging buffers, used alternately: block kb - 1 is stored while other waves still multiply by block kb
+  store(S, nx, tx);
+  __syncthreads();
+  int cur = 0;
   for (int kb = kb_top; kb >= kb_lo; --kb) {
     fetch(kb - 1, nx, tx);
+    const double* vA = S + cur * DM_TOTAL + DM_VA;
+    const double* vB = S + cur * DM_TOTAL + DM_VB;
+    const double* tm = S + cur * DM_TOTAL + DM_TM;
     const int Tlo = wact ? (16 * kb + 1) >> 4 : 16;  // row tiles below hold no entry of these reflectors
     // S = V^T Z_w : M = reflector, K = row, N = column
     v4f64 Sa = {0.0, 0.0, 0.0, 0.0}, Sb = {0.0, 0.0, 0.0, 0.0};
@@ -507,27 +539,49 @@ __global__ __launch_bounds__(TNT, 1) void trd_d_kernel(double* __restrict__ Gc, 
           Zt[T] = __builtin_amdgcn_mfma_f64_16x16x4f64(vB[(4 * s4 + kq) * 272 + 16 * T + li], Cw[s4], Zt[T], 0, 0, 0);
       }
     }
-    __syncthreads();  // every wave is done with this block's LDS copies
-    store(nx, tx);
+    store(S + (cur ^ 1) * DM_TOTAL, nx, tx);  // (the idle buffer: every wave left it before the last barrier)
     __syncthreads();
+    cur ^= 1;
   }
   {
     // column c of the result: rows [0, n) = lam_c v_c (the embedded rows [off, 256) moved up), everything else of the
-    // ldn x ldn matrix zeros
+    // ldn x ldn matrix zeros.  Each wave transposes its 16 columns through the staging memory, 128 rows at a time, so that a
+    // store instruction writes 64 consecutive rows of one column.
     const int ncol = n < sh.nvec ? n : sh.nvec;
     const bool cval = col < ncol;
     const double lc = cval ? sm[L_LAM + col] : 0.0;
     const double f = lc > 0.0 ? lc : 0.0;
+    double* tr = S + w * (16 * 132 + 64);  // [16 columns][132]
 #pragma unroll
-    for (int T = 0; T < 16; ++T)
+    for (int h = 0; h < 2; ++h) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = 16 * T + kq + 4 * r - off;
-        if (i >= 0) {
-          if (col < ldn) G[(long)col * ldn + i] = cval ? f * Zt[T][r] : 0.0;
-          if (col + TM < ldn) G[(long)(col + TM) * ldn + i] = 0.0;
+      for (int T = 0; T < 8; ++T)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tr[li * 132 + 16 * T + kq + 4 * r] = cval ? f * Zt[8 * h + T][r] : 0.0;
+      __syncthreads();
+      for (int c = 0; c < 16; ++c) {
+        const int cc = 16 * w + c;
+        if (cc < ldn) {
+#pragma unroll
+          for (int g = 0; g < 2; ++g) {
+            const int i = 128 * h + 64 * g + l - off;
+            if (i >= 0) G[(long)cc * ldn + i] = tr[c * 132 + 64 * g + l];
+          }
         }
       }
+      __syncthreads();
+    }
+    // the zero columns behind the TM formed ones: one contiguous run
+    if (ldn > TM) {
+      double* Z0 = G + (long)TM * ldn;
+      const int nz = (ldn - TM) * ldn;
+      if ((ldn & 1) == 0 && (reinterpret_cast<unsigned long long>(Z0) & 15ull) == 0ull) {
+        double2* Z2 = reinterpret_cast<double2*>(Z0);
+        for (int idx = t; idx < nz / 2; idx += TNT) Z2[idx] = make_double2(0.0, 0.0);
+      } else {
+        for (int idx = t; idx < nz; idx += TNT) Z0[idx] = 0.0;
+      }
+    }
     // the column norms the caller reads next are the eigenvalues themselves (|lam_c v_c| = lam_c): written here, the norms
     // pass over the matrix is skipped for solved matrices
     // (an eigenvalue whose square underflows is written as zero, as the norm of its column would come out: the spectrum of
@@ -536,8 +590,8 @@ __global__ __launch_bounds__(TNT, 1) void trd_d_kernel(double* __restrict__ Gc, 
       const double lv = t < ncol ? sm[L_LAM + t] : 0.0;
       lam_out[(long)bm * ldn + t] = (lv > 0.0 && lv * lv > 0.0) ? lv : 0.0;
     }
-    const int npad = ldn - n;  // padding rows of the Jacobi's layout
-    for (int idx = t; idx < npad * ldn; idx += TNT) {
+    const int npad = ldn - n;  // padding rows of the Jacobi's layout (columns below TM: the others are zeroed whole above)
+    for (int idx = t; idx < npad * (ldn < TM ? ldn : TM); idx += TNT) {
       const int c = idx / npad;
       G[(long)c * ldn + n + (idx - c * npad)] = 0.0;
     }
@@ -555,7 +609,7 @@ namespace mused {
 size_t trd_workspace_doubles(int batch) { return (size_t)batch * (size_t)W_PER; }
 
 constexpr int L_A_TOTAL = L_S + 2314;            // kernel A: persistent part + its scratch
-constexpr int L_DM_TOTAL = L_S + DM_TOTAL;       // kernel D
+constexpr int L_DM_TOTAL = L_S + 2 * DM_TOTAL;     // kernel D
 constexpr int C_LDS = trd_c_lds_doubles<L256, 32>();        // kernel C: T, exchange, the pivot sequences of 32 vectors
 
 int trd_prepare() {
