@@ -126,6 +126,35 @@ int mused_sparse_cosine_knn(const int* rowptr, const int* terms, const double* v
 int mused_lists_to_mask(const int* idx, int n_rows, int k, const int* row_map, int n, unsigned long long* out_mask,
                         int mask_words, void* stream);
 
+/* ---- a2, "text": the TF-IDF of one window of a corpus that was tokenised once (matrix_operations.py:101-103:
+ * TfidfVectorizer().fit_transform on the window's valid rows), csrc/tfidf.hip; specification: mused_amd/tfidf.py,
+ * scikit-learn's indptr / indices / data bit for bit.  Enqueue-only; all arrays DEVICE, all integers int32.
+ * Corpus (mused_amd/text.py; n_rows rows, n_terms global terms = ranks in the sorted vocabulary): rowptr[n_rows + 1],
+ *   term[], cnt[] = CSR over all rows (invalid rows empty); pos[] = ordinal of the term's first occurrence in its
+ *   document; vrank[n_rows + 1] = prefix count of valid rows, vrow[] = valid rank -> row; gpostptr[n_terms + 1],
+ *   gpostrow[] (ascending rows), gpostent[] (the CSR entry of a posting) = term-major postings.
+ *   max_row_terms: the longest row of the corpus, <= 1024 (one row is ranked in LDS).
+ * Window: rows [s, e), n_docs = vrank[e] - vrank[s] >= 1 documents, nnz_w = rowptr[e] - rowptr[s] >= 1 entries (the
+ *   caller has the host arrays and sizes the outputs from them); idf[j] = log((n_docs + 1) / (j + 1)) + 1 for
+ *   j = 0 .. n_docs, computed on the host (the device never calls log).
+ * Outputs: the window CSR in scikit-learn's STORED order (a row's entries ascend by the vocabulary's first-appearance
+ *   numbering, not by column) -- out_rowptr[n_docs + 1], out_term[nnz_w] (global ids), out_col[nnz_w] (window column =
+ *   rank among the present terms), out_val[nnz_w] (fit_transform's data), out_val2[nnz_w] (after normalize once more:
+ *   what cosine_similarity multiplies) -- and the posting lists mused_sparse_cosine_knn reads with n_terms global terms:
+ *   out_postptr[n_terms + 1] (absent terms: empty lists), out_postrow[nnz_w] (documents ascending), out_postval[nnz_w]
+ *   (out_val2 of the entry).  info (4 int32) = {V_w present terms, flags, entries, 0}; flag 1: the window on the device
+ *   is not the one the caller sized for (documents, entries or a row beyond max_row_terms) -- outputs invalid.
+ * ws: mused_tfidf_ws_bytes(n_terms) bytes, 8-byte aligned (-1 for n_terms outside [1, 2^31)).
+ * mused_tfidf_dense: the n_docs x n_cols fp64 matrix T.todense() (pitch ld, zero-filled here) from the window CSR. */
+long mused_tfidf_ws_bytes(long n_terms);
+int mused_tfidf_window(const int* rowptr, const int* term, const int* cnt, const int* pos, const int* vrank, const int* vrow,
+                       const int* gpostptr, const int* gpostrow, const int* gpostent, int n_rows, int n_terms,
+                       int max_row_terms, int s, int e, int n_docs, int nnz_w, const double* idf, int* out_rowptr,
+                       int* out_term, int* out_col, double* out_val, double* out_val2, int* out_postptr, int* out_postrow,
+                       double* out_postval, int* info, void* ws, long ws_bytes, void* stream);
+int mused_tfidf_dense(const int* w_rowptr, const int* w_col, const double* w_val, int n_docs, int n_cols, double* out,
+                      long ld, void* stream);
+
 /* ---- a3 / a4: adjacency bitmasks -------------------------------------------------------------
  * An adjacency is n rows x words uint64 (words >= ceil(n/64)); bit j of row i <=> A[i][j] = 1. */
 

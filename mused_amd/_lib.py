@@ -44,6 +44,9 @@ _PROTOS = {
     "mused_jaccard_knn_chunked": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "mused_sparse_cosine_knn": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "mused_lists_to_mask": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "mused_tfidf_ws_bytes": (_l, [_l]),
+    "mused_tfidf_window": (_i, [_vp] * 9 + [_i] * 7 + [_vp] * 11 + [_l, _vp]),
+    "mused_tfidf_dense": (_i, [_vp, _vp, _vp, _i, _i, _vp, _l, _vp]),
     "mused_adj_fuse": (_i, [C.POINTER(_vp), _i, _i, _i, _vp, _vp]),
     "mused_adj_degrees": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mused_adj_csr_fill": (_i, [_vp, _i, _i, _vp, _vp, _vp]),

@@ -132,6 +132,26 @@ class Adjacency:
         return Adjacency(mask, n, fused=(t.dtype == torch.int64))
 
 
+class DeviceTfidf:
+    """The TF-IDF of one text window on the device (`WindowEngine.tfidf_window`): n documents, nnz entries, n_terms
+    global terms.  Window CSR in scikit-learn's stored order -- rowptr[n + 1], term[nnz] (global ids), col[nnz] (window
+    column ids), val[nnz] (fit_transform's data), val2[nnz] (normalised once more) -- the posting lists of the global
+    terms postptr[n_terms + 1], postrow[nnz], postval[nnz], and info = int32 {V_w, flags, entries, 0}."""
+
+    __slots__ = ("n", "nnz", "n_terms", "rowptr", "term", "col", "val", "val2", "postptr", "postrow", "postval", "info")
+
+    def __init__(self, *fields):
+        for name, v in zip(self.__slots__, fields):
+            setattr(self, name, v)
+
+    def read_info(self):
+        """V_w -- one small blocking read; raises on the flag word (the outputs are invalid then)."""
+        info = self.info.cpu().numpy()
+        if info[1]:
+            raise MusedError(f"mused_tfidf_window: the window on the device is not the one the host sized for (flags {info[1]})")
+        return int(info[0])
+
+
 class WindowEngine:
     """Workspaces + ops for windows of at most n_max rows (see module docstring)."""
 
@@ -157,6 +177,7 @@ class WindowEngine:
         self.slot_keys = []
         self._hop = {}          # hopping windows: key -> workspace + stream position of the window it holds (knn_adjacency_hop)
         self.hop_windows = self.hop_reused = self.hop_recomputes = 0
+        self._tfidf_cache = {}  # idf tables per document count, workspaces per vocabulary size (tfidf_window)
         self._rsvd = None
         self._rsvd_fb = None       # fallback handle (mode 2), created on first use
         self._rsvd_fb_key = None
@@ -429,6 +450,55 @@ class WindowEngine:
         call("mused_sparse_cosine_knn", *[ptr(t) for t in dev], n, int(n_terms), kk, int(chunk), ptr(idx), None, 0,
              stream_ptr())
         self._keep = dev
+        return idx
+
+    # ---- a2, "text": per-window TF-IDF from a corpus tokenised once (csrc/tfidf.hip; the rule: mused_amd/tfidf.py) ----
+    def tfidf_window(self, corpus, s: int, e: int) -> "DeviceTfidf":
+        """TfidfVectorizer().fit_transform of the valid rows of [s, e) of `corpus` (mused_amd.text.TextCorpus) and what
+        cosine_similarity makes of it, as device arrays (`DeviceTfidf`); the window must hold a document and a token (the
+        caller has the host arrays: `matrix_operations._text_adjacency`).  Enqueue-only apart from the corpus' one upload
+        and the idf table of a document count not seen before; read `.info` for V_w and the flag word."""
+        from . import tfidf as _tfidf
+
+        n = int(corpus.vrank[e] - corpus.vrank[s])
+        nnz = int(corpus.rowptr[e]) - int(corpus.rowptr[s])
+        if n < 1 or nnz < 1:
+            raise ValueError(f"tfidf_window: rows [{s}, {e}) hold {n} documents and {nnz} entries")
+        c = corpus.device_arrays(self.device)
+        cache = self._tfidf_cache
+        idf = cache.get(("idf", n))
+        if idf is None:
+            if len(cache) > 16:
+                cache.clear()
+            idf = cache[("idf", n)] = torch.from_numpy(_tfidf.idf_table(n)).to(self.device)
+        ws = cache.get(("ws", corpus.V))
+        if ws is None:
+            ws = cache[("ws", corpus.V)] = torch.empty(int(_lib.lib().mused_tfidf_ws_bytes(corpus.V)), dtype=torch.uint8,
+                                                         device=self.device)
+        i32 = lambda m: torch.empty(m, dtype=torch.int32, device=self.device)
+        f64 = lambda m: torch.empty(m, dtype=torch.float64, device=self.device)
+        w = DeviceTfidf(n, nnz, corpus.V, i32(n + 1), i32(nnz), i32(nnz), f64(nnz), f64(nnz), i32(corpus.V + 1), i32(nnz),
+                        f64(nnz), i32(4))
+        call("mused_tfidf_window", *[ptr(c[f]) for f in ("rowptr", "term", "cnt", "pos", "vrank", "vrow", "gpostptr",
+                                                          "gpostrow", "gpostent")],
+             corpus.N, corpus.V, corpus.max_row_terms, int(s), int(e), n, nnz, ptr(idf), ptr(w.rowptr), ptr(w.term),
+             ptr(w.col), ptr(w.val), ptr(w.val2), ptr(w.postptr), ptr(w.postrow), ptr(w.postval), ptr(w.info), ptr(ws),
+             ws.numel(), stream_ptr())
+        return w
+
+    def tfidf_dense(self, w: "DeviceTfidf", n_cols: int) -> torch.Tensor:
+        """T.todense() of a `tfidf_window` result with V_w = n_cols columns: (n, n_cols) fp64 on the device."""
+        out = torch.empty((w.n, n_cols), dtype=torch.float64, device=self.device)
+        call("mused_tfidf_dense", ptr(w.rowptr), ptr(w.col), ptr(w.val), w.n, int(n_cols), ptr(out), int(n_cols), stream_ptr())
+        return out
+
+    def tfidf_cosine_lists(self, w: "DeviceTfidf", kk: int, chunk: int = 0) -> torch.Tensor:
+        """`sparse_cosine_lists` on a `tfidf_window` result: the twice-normalised rows in their stored order and the
+        posting lists over the corpus' global terms (absent terms have empty lists), all of it already on the device."""
+        idx = self._lists_out(w.n, kk)
+        call("mused_sparse_cosine_knn", ptr(w.rowptr), ptr(w.term), ptr(w.val2), ptr(w.postptr), ptr(w.postrow), ptr(w.postval),
+             w.n, w.n_terms, kk, int(chunk), ptr(idx), None, 0, stream_ptr())
+        self._keep = w
         return idx
 
     def knn_lists(self, rows, k: int, metric: str = "l2") -> torch.Tensor:

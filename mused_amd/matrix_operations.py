@@ -20,9 +20,10 @@ Two call styles:
                              (`adjacency_on_device`, `fuse_matrices` on Adjacency objects,
                              `svd_reduce_on_device`) and nothing W x W ever visits the host.
 
-modality_type "text" (matrix_operations.py:91-110) vectorises the ('title', 'description') strings on the
-host with the same scikit-learn TfidfVectorizer call as the reference and runs the cosine / top-(k+1)
-kernel on the device; already vectorised rows can use modality_type="cosine".
+modality_type "text" (matrix_operations.py:91-110) tokenises the ('title', 'description') strings once with
+scikit-learn's analyser (mused_amd/text.py), computes the TF-IDF of a window on the device from the corpus' integer
+arrays (csrc/tfidf.hip: TfidfVectorizer().fit_transform's values bit for bit) and runs the cosine / top-(k+1) kernel
+there; MUSED_TEXT=host keeps the TfidfVectorizer call per window.  Already vectorised rows can use modality_type="cosine".
 The metadata modality types of the SED2012 stream keep their string handling on the host and score /
 select on the device (csrc/meta.hip): "location" (haversine kNN, :22-31), "time" (:33-54), "username" (:56-71),
 "tags" (Jaccard, :73-89).  Where the reference's own choice between EQUAL scores is undefined (unstable argsort,
@@ -129,12 +130,67 @@ def _scatter_valid(sub: _eng.Adjacency, valid_idx, n: int) -> _eng.Adjacency:
     return _eng.Adjacency.from_dense(dense)
 
 
+def text_on_device() -> bool:
+    """MUSED_TEXT (read at every call): "device" (default) = the per-window TF-IDF runs on the device from a corpus
+    tokenised once (csrc/tfidf.hip); "host" = scikit-learn's TfidfVectorizer per window, the former path as a whole."""
+    import os
+
+    return os.environ.get("MUSED_TEXT", "device") != "host"
+
+
 def _text_adjacency(data, k_basis, engine=None, sparse=None) -> _eng.Adjacency:
-    """matrix_operations.py:91-110: rows with a non-empty title or description are valid; TF-IDF of
-    "title description" on the host (same TfidfVectorizer call), then cosine similarity and the k_basis + 1 most
-    similar rows per row on the device: dense rows through `MUSED_METRIC_COSINE`, or (`sparse`, or a dense TF-IDF beyond
-    TEXT_DENSE_BYTES) the rows scikit-learn's normalize returns, as they are stored, through mused_sparse_cosine_knn --
-    the similarities of cosine_similarity on sparse input bit for bit."""
+    """matrix_operations.py:91-110: rows with a non-empty title or description are valid; TF-IDF of "title description",
+    then cosine similarity and the k_basis + 1 most similar rows per row on the device: dense rows through
+    `MUSED_METRIC_COSINE`, or (`sparse`, or a dense TF-IDF beyond TEXT_DENSE_BYTES) the rows scikit-learn's normalize
+    returns, as they are stored, through mused_sparse_cosine_knn -- the similarities of cosine_similarity on sparse input
+    bit for bit.
+    data: a window of a tokenised corpus (mused_amd.text.TextWindow / TextCorpus) or the (n, 2) strings, which are
+    tokenised as a corpus of their own.  The TF-IDF itself runs on the device (`_text_adjacency_device`) unless
+    MUSED_TEXT=host or the corpus is host-only (`_text_adjacency_host`: the same TfidfVectorizer call as the reference)."""
+    from . import text as _text
+
+    if isinstance(data, _text.TextCorpus):
+        data = data.window()
+    if not text_on_device():
+        return _text_adjacency_host(data.records if isinstance(data, _text.TextWindow) else data, k_basis, engine, sparse)
+    win = data if isinstance(data, _text.TextWindow) else _text.tokenise(data).window()
+    if win.corpus.host_only:
+        return _text_adjacency_host(win.records, k_basis, engine, sparse)
+    return _text_adjacency_device(win, k_basis, engine, sparse)
+
+
+def _text_adjacency_device(win, k_basis, engine=None, sparse=None) -> _eng.Adjacency:
+    """Rows [win.lo, win.hi) of a tokenised corpus: the window's TF-IDF from the corpus' integer arrays in one
+    mused_tfidf_window call (document frequencies, column ids, stored order, both normalisations, posting lists), then
+    the kernels the host path feeds -- with the n x V_w matrix scattered on the device, or with the sparse rows and the
+    posting lists over the corpus' global terms as they are.  One 16-byte read (V_w and the flag word) per window."""
+    import torch
+
+    from . import tfidf as _tfidf
+
+    c, s, e = win.corpus, win.lo, win.hi
+    n = e - s
+    eng = engine or _eng.default_engine(max(n, 1))
+    n_docs = int(c.vrank[e] - c.vrank[s])
+    if n_docs == 0:
+        return _eng.Adjacency(torch.zeros((n, _eng.words_for(n)), dtype=torch.int64, device=eng.device), n)
+    if c.rowptr[e] == c.rowptr[s]:
+        raise ValueError(_tfidf.EMPTY_VOCABULARY)   # what TfidfVectorizer raises for documents without a token
+    w = eng.tfidf_window(c, s, e)
+    n_cols = w.read_info()
+    if sparse is None:
+        sparse = n_docs * n_cols * 8 > TEXT_DENSE_BYTES
+    valid_idx = None
+    if n_docs != n:
+        valid_idx = torch.from_numpy(c.vrow[c.vrank[s]:c.vrank[e]].astype(np.int64) - s).to(eng.device)
+    if sparse:
+        return eng.lists_to_adjacency(eng.tfidf_cosine_lists(w, min(int(k_basis) + 1, n_docs)), n, valid_idx)
+    return _dense_knn(eng, eng.tfidf_dense(w, n_cols), k_basis, "cosine", n, valid_idx)
+
+
+def _text_adjacency_host(data, k_basis, engine=None, sparse=None) -> _eng.Adjacency:
+    """The TF-IDF on the host, per window, with the same TfidfVectorizer call as the reference; the result is uploaded
+    (dense, or the sparse rows with posting lists built on the host) for the same device kernels."""
     import torch
     from sklearn.feature_extraction.text import TfidfVectorizer
 

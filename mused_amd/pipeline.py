@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import matrix_operations as mo
+from . import text as _text
 from ._lib import MusedError
 from .engine import WindowEngine
 from .swfd import SeqBasedSWFD
@@ -525,12 +526,21 @@ class StreamPipeline:
         """Stream whole modalities (host or device arrays) through the window loop; returns the
         concatenated event labels (`all_clusters`, main.py:125)."""
         dev = []
-        for m in data_modalities:
+        types = self.types or [""] * len(data_modalities)
+        for m, t in zip(data_modalities, types):
             if isinstance(m, torch.Tensor):
                 dev.append(m.cuda())
                 continue
+            if isinstance(m, _text.TextCorpus):
+                dev.append(m)
+                continue
+            if t == "text" and mo.text_on_device():
+                # tokenised once for the whole stream; every window is a view of the corpus and its TF-IDF runs on the
+                # device (MUSED_TEXT=host: the strings stay as they are and every window is vectorised on the host)
+                dev.append(_text.tokenise(m))
+                continue
             a = np.asarray(m)
-            # numeric modalities live on the device; string records ("text") stay on the host for the TF-IDF step
+            # numeric modalities live on the device; other string records stay on the host
             dev.append(torch.from_numpy(np.ascontiguousarray(a)).cuda() if a.dtype.kind in "fiub" else a)
         torch.cuda.current_stream().synchronize()  # rows resident before the first window (see _adjacency)
         n = dev[0].shape[0]
@@ -677,6 +687,9 @@ def batch_embedding(data_modalities, modality_types, reduced_dim, k_basis, seed,
         for i, (m, ty) in enumerate(zip(data_modalities, modality_types)):
             if len(m) != n:
                 raise ValueError(f"modality {i} has {len(m)} rows, modality 0 has {n}")
+            if ty == "text" and mo.text_on_device() and not isinstance(m, (_text.TextCorpus, _text.TextWindow)):
+                m = _text.tokenise(m)   # the whole subset is one window of this corpus
+                t = tick(f"tokenise[{i}]", t)
             adj = mo.adjacency_on_device(m, ty, k_basis, engine=eng)
             t = tick(f"knn[{i}:{ty or 'l2'}]", t)
             fused = adj if fused is None else eng.fuse_into(fused, adj)
