@@ -100,6 +100,28 @@ int mused_record_knn(const double* rec, int n, int kind, int k, int* out_idx, un
 int mused_jaccard_knn(const int* rowptr, const int* tags, const int* postptr, const int* postrow, int n, int n_tags, int k,
                       int* out_idx, unsigned long long* out_mask, int mask_words, void* stream);
 
+/* ---- a1, metadata types of a stream that was encoded ONCE (mused_amd/meta.py; csrc/meta_window.hip): the adjacency of
+ * window rows [s, e) from arrays that cover all n_rows rows of the stream.  Enqueue-only; all arrays DEVICE, all integers
+ * int32; nothing is read on the host and nothing is gathered, zero-filled or scattered around the call.
+ * Stream: vrank[n_rows + 1] = prefix count of valid rows (row r is valid iff vrank[r + 1] != vrank[r]).
+ *   mused_meta_window_records: rec = n_rows x 2 fp64 records, kind MUSED_REC_LOCATION / MUSED_REC_TIME.
+ *   mused_meta_window_tags: rowptr[n_rows + 1], tag[] = tag sets as CSR over ALL rows with stream-global ids < n_tags
+ *     (ascending inside a row, invalid rows empty); gpostptr[n_tags + 1], gpostrow[] = the rows that hold a tag,
+ *     ascending: the part of a list inside [s, e) is one contiguous range, found by a binary search per list.
+ * Output: the whole (e - s) x mask_words bitmask in WINDOW coordinates (mask_words >= ceil((e - s) / 64); words past the
+ *   last column are written as zero).  An invalid row gets an empty row and is selected by no row; a valid row selects
+ *   its min(k, n_valid) closest valid rows, n_valid = vrank[e] - vrank[s] read on the device, own bit cleared.  Scores,
+ *   selection and tie rule (the smaller row) are those of mused_record_knn / mused_jaccard_knn on the gathered valid
+ *   rows: invalid rows keep their position, so the order among the valid ones is the same.
+ * e - s <= 16384 (records) / 15000 (tags); e == s is a successful no-op.  Error, nothing launched: s < 0, s > e,
+ *   e > n_rows, kind other than 0 / 1, k < 1, mask_words too small, a window beyond the cap.
+ * "username" needs no entry: mused_group_mask(uid + s, e - s, ...) on the stream's id array (< 0: no name). */
+int mused_meta_window_records(const double* rec, const int* vrank, int n_rows, int kind, int s, int e, int k,
+                              unsigned long long* out_mask, int mask_words, void* stream);
+int mused_meta_window_tags(const int* rowptr, const int* tag, const int* gpostptr, const int* gpostrow, const int* vrank,
+                           int n_rows, int n_tags, int s, int e, int k, unsigned long long* out_mask, int mask_words,
+                           void* stream);
+
 /* Batch scale (process_batch_data, main.py:132-167: the whole subset as one window, 150,000 rows by default): the same
  * selections for ANY n, with no n x n matrix and no global scratch.  One workgroup per row walks the columns in chunks of
  * at most `chunk` (0: the largest that fits, <= 16384) and keeps the row's k smallest (score, column) pairs in LDS;

@@ -43,6 +43,8 @@ _PROTOS = {
     "mused_record_knn_chunked": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "mused_jaccard_knn_chunked": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "mused_sparse_cosine_knn": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "mused_meta_window_records": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "mused_meta_window_tags": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "mused_lists_to_mask": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp]),
     "mused_tfidf_ws_bytes": (_l, [_l]),
     "mused_tfidf_window": (_i, [_vp] * 9 + [_i] * 7 + [_vp] * 11 + [_l, _vp]),

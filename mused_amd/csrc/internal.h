@@ -12,6 +12,11 @@ int select_from_records(const double* rec, int n, int kind, int k, int* out_idx,
 int select_from_tag_sets(const int* rowptr, const int* tags, const int* postptr, const int* postrow, int n, int k,
                          int* out_idx, unsigned long long* out_mask, int mask_words, hipStream_t stream);
 int select_max_fused_rows(bool tag_sets);
+// the same selections for rows [s, e) of arrays that cover a whole stream, bitmask in window coordinates (meta_window.hip)
+int select_window_records(const double* rec, const int* vrank, int s, int e, int kind, int k, unsigned long long* out_mask,
+                          int mask_words, hipStream_t stream);
+int select_window_tag_sets(const int* rowptr, const int* tags, const int* postptr, const int* postrow, const int* vrank, int s,
+                           int e, int k, unsigned long long* out_mask, int mask_words, hipStream_t stream);
 
 // One process-wide lock around every stream capture of this library AND around the calls that create or release HIP
 // resources next to one (handle / plan creation and destruction: hipMalloc, hipFree, hipGraph(Exec)Destroy,

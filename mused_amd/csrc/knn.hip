@@ -148,13 +148,22 @@ __device__ __forceinline__ int block_excl_scan(int v, int* ws /*[SEL_WAVES]*/, i
 // Where a row of scores comes from.  SRC_MATRIX: row `row` of S (the classic path).  The others compute the row on the
 // fly (rows of at most SEL_MAX_LDS_KEYS scores, kept as keys in LDS) -- the metadata modality types of meta.hip without
 // an n x n score matrix: SRC_HAVERSINE / SRC_TIME from n x 2 records, SRC_JACCARD from tag sets (CSR + posting lists).
-enum { SRC_MATRIX = 0, SRC_HAVERSINE = 1, SRC_TIME = 2, SRC_JACCARD = 3 };
+// SRC_*_WIN: the same scores for rows [win_s, win_e) of arrays that cover a whole STREAM (csrc/meta_window.hip): n is the
+// window length and every row, column and mask bit is a window coordinate; a row is valid iff vrank steps at it.  Invalid
+// rows keep their position with the largest key, so they are never among the min(k, valid rows) smallest, and write an
+// empty mask row.
+enum { SRC_MATRIX = 0, SRC_HAVERSINE = 1, SRC_TIME = 2, SRC_JACCARD = 3, SRC_HAVERSINE_WIN = 4, SRC_TIME_WIN = 5,
+       SRC_JACCARD_WIN = 6 };
+constexpr bool src_windowed(int src) { return src >= SRC_HAVERSINE_WIN; }
+constexpr bool src_tag_sets(int src) { return src == SRC_JACCARD || src == SRC_JACCARD_WIN; }
 struct SelSource {
   const double* rec;     // SRC_HAVERSINE / SRC_TIME: n x 2 records
   const int* rowptr;     // SRC_JACCARD: tag sets as CSR ...
   const int* tags;
   const int* postptr;    // ... and the posting lists of the tags
   const int* postrow;
+  const int* vrank;      // SRC_*_WIN: prefix count of valid rows over the stream ...
+  int win_s, win_e;      // ... and the window's rows
 };
 
 template <int SRC>
@@ -180,9 +189,23 @@ __global__ __launch_bounds__(SEL_THREADS) void select_k_kernel(const double* __r
   [[maybe_unused]] unsigned short* inter = reinterpret_cast<unsigned short*>(sel_smem + n);  // SRC_JACCARD: behind the keys
   [[maybe_unused]] double r0 = 0.0, r1 = 0.0;
   [[maybe_unused]] int li = 0;
+  [[maybe_unused]] int ws0 = 0;  // SRC_*_WIN: stream row of window row 0
+  if constexpr (src_windowed(SRC)) {
+    ws0 = src.win_s;
+    if (src.vrank[ws0 + row + 1] == src.vrank[ws0 + row]) {  // an invalid row: no neighbours (the whole workgroup leaves)
+      for (int w = tid; w < mask_words; w += SEL_THREADS) out_mask[(long)row * mask_words + w] = 0ull;
+      return;
+    }
+    const int n_valid = src.vrank[src.win_e] - src.vrank[ws0];
+    k = k < n_valid ? k : n_valid;
+  }
   if constexpr (SRC == SRC_HAVERSINE || SRC == SRC_TIME) {
     r0 = src.rec[2 * (long)row];
     r1 = src.rec[2 * (long)row + 1];
+  }
+  if constexpr (SRC == SRC_HAVERSINE_WIN || SRC == SRC_TIME_WIN) {
+    r0 = src.rec[2 * (long)(ws0 + row)];
+    r1 = src.rec[2 * (long)(ws0 + row) + 1];
   }
   if constexpr (SRC == SRC_JACCARD) {
     // intersection sizes of this row's tag set with every row's: walk the posting lists of its tags (rows inside a
@@ -198,6 +221,36 @@ __global__ __launch_bounds__(SEL_THREADS) void select_k_kernel(const double* __r
       __syncthreads();
     }
   }
+  if constexpr (SRC == SRC_JACCARD_WIN) {
+    // the same counters, indexed by window row, from the part of every posting list that lies in [win_s, win_e): rows
+    // ascend inside a list, so that part starts at the lower bound of win_s (one lane searches, the others read it from
+    // LDS; two slots, so one barrier per list separates both the slots' reuse and the lists' additions) and ends at the
+    // first row >= win_e
+    __shared__ int s_lb[2];
+    const int we = src.win_e;
+    for (int j = tid; j < n; j += SEL_THREADS) inter[j] = 0;
+    const int t0 = src.rowptr[ws0 + row], t1 = src.rowptr[ws0 + row + 1];
+    li = t1 - t0;
+    for (int t = t0; t < t1; ++t) {
+      const int tag = src.tags[t];
+      const int p1 = src.postptr[tag + 1];
+      if (tid == 0) {
+        int lo = src.postptr[tag], hi = p1;
+        while (lo < hi) {
+          const int mid = lo + ((hi - lo) >> 1);
+          if (src.postrow[mid] < ws0) lo = mid + 1; else hi = mid;
+        }
+        s_lb[(t - t0) & 1] = lo;
+      }
+      __syncthreads();
+      for (int q = s_lb[(t - t0) & 1] + tid; q < p1; q += SEL_THREADS) {
+        const int r = src.postrow[q];
+        if (r >= we) break;
+        inter[r - ws0] += 1;
+      }
+    }
+    __syncthreads();
+  }
   auto score_at = [&](int i) -> double {
     if constexpr (SRC == SRC_MATRIX) return srow[i];
     if constexpr (SRC == SRC_HAVERSINE) return haversine_km(r0, r1, src.rec[2 * (long)i], src.rec[2 * (long)i + 1]);
@@ -209,13 +262,29 @@ __global__ __launch_bounds__(SEL_THREADS) void select_k_kernel(const double* __r
       const int in = inter[i];
       return 0.0 - (double)in / (double)(li + lj - in);
     }
+    if constexpr (SRC == SRC_HAVERSINE_WIN)
+      return haversine_km(r0, r1, src.rec[2 * (long)(ws0 + i)], src.rec[2 * (long)(ws0 + i) + 1]);
+    if constexpr (SRC == SRC_TIME_WIN) return time_l1(r0, r1, src.rec[2 * (long)(ws0 + i)], src.rec[2 * (long)(ws0 + i) + 1]);
+    if constexpr (SRC == SRC_JACCARD_WIN) {
+      if (i == row) return 1.0;
+      const int lj = src.rowptr[ws0 + i + 1] - src.rowptr[ws0 + i];
+      if (li == 0 || lj == 0) return 0.0;
+      const int in = inter[i];
+      return 0.0 - (double)in / (double)(li + lj - in);
+    }
     return 0.0;
+  };
+  auto fresh_key = [&](int i) -> unsigned long long {
+    if constexpr (src_windowed(SRC)) {
+      if (src.vrank[ws0 + i + 1] == src.vrank[ws0 + i]) return ~0ull;  // above every score's key
+    }
+    return f64_key(score_at(i));
   };
 
   // pass 0: keys, min, max
   unsigned long long kmin = ~0ull, kmax = 0ull;
   for (int i = tid; i < n; i += SEL_THREADS) {
-    const unsigned long long key = f64_key(score_at(i));
+    const unsigned long long key = fresh_key(i);
     if (cached) keys[i] = key;
     kmin = key < kmin ? key : kmin;
     kmax = key > kmax ? key : kmax;
@@ -382,13 +451,13 @@ template <int SRC>
 static int select_launch_src(const double* S, long ld, int n, int k, int* out_idx, unsigned long long* out_mask,
                              int mask_words, const SelSource& src, hipStream_t stream) {
   // keys of the row (cached case) + the 16-bit intersection counters of SRC_JACCARD behind them
-  const size_t lds = ((SRC != SRC_MATRIX || n <= SEL_MAX_LDS_KEYS) ? (size_t)n * 8 : 0) + (SRC == SRC_JACCARD ? (size_t)n * 2 + 8 : 0);
+  const size_t lds = ((SRC != SRC_MATRIX || n <= SEL_MAX_LDS_KEYS) ? (size_t)n * 8 : 0) + (src_tag_sets(SRC) ? (size_t)n * 2 + 8 : 0);
   static std::once_flag once;
   static hipError_t attr_rc = hipSuccess;
   std::call_once(once, [] {
     attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(select_k_kernel<SRC>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  SRC == SRC_JACCARD ? SEL_MAX_JACCARD_ROWS * 10 + 64 : SEL_MAX_LDS_KEYS * 8);
+                                  src_tag_sets(SRC) ? SEL_MAX_JACCARD_ROWS * 10 + 64 : SEL_MAX_LDS_KEYS * 8);
   });
   MUSED_CHECK_HIP(attr_rc);
   hipLaunchKernelGGL(select_k_kernel<SRC>, dim3(n), dim3(SEL_THREADS), lds, stream, S, ld, n, k, out_idx, out_mask,
@@ -415,6 +484,22 @@ int select_from_tag_sets(const int* rowptr, const int* tags, const int* postptr,
   SelSource src{};
   src.rowptr = rowptr; src.tags = tags; src.postptr = postptr; src.postrow = postrow;
   return select_launch_src<SRC_JACCARD>(nullptr, 0, n, k, out_idx, out_mask, mask_words, src, stream);
+}
+// the same for rows [s, e) of stream-wide arrays, in window coordinates (csrc/meta_window.hip); k is capped by the window's
+// valid rows on the device
+int select_window_records(const double* rec, const int* vrank, int s, int e, int kind, int k, unsigned long long* out_mask,
+                          int mask_words, hipStream_t stream) {
+  SelSource src{};
+  src.rec = rec; src.vrank = vrank; src.win_s = s; src.win_e = e;
+  if (kind == 0) return select_launch_src<SRC_HAVERSINE_WIN>(nullptr, 0, e - s, k, nullptr, out_mask, mask_words, src, stream);
+  return select_launch_src<SRC_TIME_WIN>(nullptr, 0, e - s, k, nullptr, out_mask, mask_words, src, stream);
+}
+int select_window_tag_sets(const int* rowptr, const int* tags, const int* postptr, const int* postrow, const int* vrank, int s,
+                           int e, int k, unsigned long long* out_mask, int mask_words, hipStream_t stream) {
+  SelSource src{};
+  src.rowptr = rowptr; src.tags = tags; src.postptr = postptr; src.postrow = postrow;
+  src.vrank = vrank; src.win_s = s; src.win_e = e;
+  return select_launch_src<SRC_JACCARD_WIN>(nullptr, 0, e - s, k, nullptr, out_mask, mask_words, src, stream);
 }
 int select_max_fused_rows(bool tag_sets) { return tag_sets ? SEL_MAX_JACCARD_ROWS : SEL_MAX_LDS_KEYS; }
 

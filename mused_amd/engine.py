@@ -594,6 +594,32 @@ class WindowEngine:
         call("mused_group_mask", ptr(ids_d), n, ptr(mask), w, stream_ptr())
         return Adjacency(mask, n)
 
+    def meta_window_adjacency(self, window, kk: int) -> Adjacency:
+        """Adjacency of a window of an encoded metadata stream (mused_amd.meta.MetaWindow) from the corpus' resident
+        arrays: one enqueue-only launch writes the window-coordinate bitmask (csrc/meta_window.hip; "username":
+        mused_group_mask on the window's slice of the id array) -- nothing is read, gathered or uploaded per window.
+        kk: the rows a valid row selects, itself included where the type counts it (capped by the window's valid rows on
+        the device; unused for "username").  The window must hold a row."""
+        c, s, e = window.corpus, window.lo, window.hi
+        n = e - s
+        if n < 1:
+            raise ValueError(f"meta_window_adjacency: rows [{s}, {e}) hold no row")
+        if c.kind != "username" and n > self.n_max:
+            raise ValueError(f"window of {n} rows exceeds the engine capacity {self.n_max}")
+        d = c.device_arrays(self.device)
+        w = words_for(n)
+        mask = torch.empty((n, w), dtype=torch.int64, device=self.device)
+        if c.kind == "username":
+            call("mused_group_mask", C.c_void_p(d["uid"].data_ptr() + 4 * s), n, ptr(mask), w, stream_ptr())
+        elif c.kind == "tags":
+            call("mused_meta_window_tags", ptr(d["rowptr"]), ptr(d["tag"]), ptr(d["gpostptr"]), ptr(d["gpostrow"]),
+                 ptr(d["vrank"]), c.N, c.V, int(s), int(e), int(kk), ptr(mask), w, stream_ptr())
+        else:
+            call("mused_meta_window_records", ptr(d["rec"]), ptr(d["vrank"]), c.N, {"location": 0, "time": 1}[c.kind], int(s),
+                 int(e), int(kk), ptr(mask), w, stream_ptr())
+        self._keep = d  # the corpus' arrays stay alive until the stream has consumed them
+        return Adjacency(mask, n)
+
     # ---- a3 / a4 ------------------------------------------------------------------------
     def fuse(self, adjs) -> Adjacency:
         n, w = adjs[0].n, adjs[0].words

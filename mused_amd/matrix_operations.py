@@ -24,8 +24,9 @@ modality_type "text" (matrix_operations.py:91-110) tokenises the ('title', 'desc
 scikit-learn's analyser (mused_amd/text.py), computes the TF-IDF of a window on the device from the corpus' integer
 arrays (csrc/tfidf.hip: TfidfVectorizer().fit_transform's values bit for bit) and runs the cosine / top-(k+1) kernel
 there; MUSED_TEXT=host keeps the TfidfVectorizer call per window.  Already vectorised rows can use modality_type="cosine".
-The metadata modality types of the SED2012 stream keep their string handling on the host and score /
-select on the device (csrc/meta.hip): "location" (haversine kNN, :22-31), "time" (:33-54), "username" (:56-71),
+The metadata modality types of the SED2012 stream keep their string handling on the host -- per window for
+raw rows, once per stream for a corpus of mused_amd/meta.py, whose windows are one launch each (csrc/meta_window.hip) --
+and score / select on the device (csrc/meta.hip): "location" (haversine kNN, :22-31), "time" (:33-54), "username" (:56-71),
 "tags" (Jaccard, :73-89).  Where the reference's own choice between EQUAL scores is undefined (unstable argsort,
 ball-tree traversal) the smaller row index wins here.
 """
@@ -218,11 +219,50 @@ def _text_adjacency_host(data, k_basis, engine=None, sparse=None) -> _eng.Adjace
     return _dense_knn(eng, _eng.to_device_rows(V), k_basis, "cosine", n, valid_idx)
 
 
-def _metadata_adjacency(data, modality_type, k_basis, engine=None) -> _eng.Adjacency:
-    """matrix_operations.py:22-89.  Row validity, k and the string handling follow the reference branch by branch on
-    the host; scores and the selection run on the device."""
+def meta_on_device() -> bool:
+    """MUSED_META (read at every call): "device" (default) = a window of a stream that was encoded once
+    (mused_amd.meta.encode) is one launch on the corpus' resident arrays (csrc/meta_window.hip); "host" = the per-window
+    host handling of `_metadata_adjacency` on the window's records, the former path as a whole."""
+    import os
+
+    return os.environ.get("MUSED_META", "device") != "host"
+
+
+def _metadata_window_adjacency(win, modality_type, k_basis, eng) -> _eng.Adjacency:
+    """Rows [win.lo, win.hi) of an encoded stream (mused_amd.meta.MetaWindow): the early returns of `_metadata_adjacency`
+    decided from the host copy of vrank, then one enqueue-only call.  k per type as there: k + 1 ("location": a row is
+    its own nearest neighbour), 3 k + 1 ("time"), k ("tags"); the device caps it by the window's valid rows."""
     import torch
 
+    c, s, e = win.corpus, win.lo, win.hi
+    n, k = e - s, int(k_basis)
+    kk = {"location": k + 1, "time": 3 * k + 1, "username": 1, "tags": k}[modality_type]
+    if n == 0 or c.vrank[e] == c.vrank[s] or (modality_type in ("time", "tags") and kk <= 0):
+        return _eng.Adjacency(torch.zeros((n, _eng.words_for(n)), dtype=torch.int64, device=eng.device), n)
+    return eng.meta_window_adjacency(win, kk)
+
+
+def _metadata_adjacency(data, modality_type, k_basis, engine=None) -> _eng.Adjacency:
+    """matrix_operations.py:22-89.  Row validity, k and the string handling follow the reference branch by branch on
+    the host; scores and the selection run on the device.
+    data: the rows of one window, or a window of a stream that was encoded once (mused_amd.meta.MetaWindow / MetaCorpus):
+    that one runs from the corpus' device arrays (`_metadata_window_adjacency`) unless MUSED_META=host, the corpus is
+    host-only, the engine is in classic kNN mode or the window is beyond _FUSED_META_ROWS -- then its records take the
+    path below."""
+    import torch
+
+    from . import meta as _meta
+
+    if isinstance(data, _meta.MetaCorpus):
+        data = data.window()
+    if isinstance(data, _meta.MetaWindow):
+        if data.corpus.kind != modality_type:
+            raise ValueError(f"a {data.corpus.kind!r} corpus was given as modality_type={modality_type!r}")
+        engine = engine or _eng.default_engine(max(len(data), 1))
+        if (meta_on_device() and not data.corpus.host_only and engine.knn_mode != "classic"
+                and len(data) <= _eng._FUSED_META_ROWS):
+            return _metadata_window_adjacency(data, modality_type, k_basis, engine)
+        data = data.records
     if isinstance(data, torch.Tensor):
         data = data.cpu().numpy()
     data = np.asarray(data)

@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import matrix_operations as mo
+from . import meta as _meta
 from . import text as _text
 from ._lib import MusedError
 from .engine import WindowEngine
@@ -528,11 +529,20 @@ class StreamPipeline:
         dev = []
         types = self.types or [""] * len(data_modalities)
         for m, t in zip(data_modalities, types):
+            if isinstance(m, (_text.TextCorpus, _meta.MetaCorpus)):
+                dev.append(m)
+                continue
+            if t in mo._METADATA_TYPES and mo.meta_on_device():
+                # encoded once for the whole stream (validity, user ids, tag sets and their posting lists); every window
+                # is a view of the corpus and one launch on its resident arrays (MUSED_META=host: the rows stay as they
+                # are and every window is handled on the host)
+                c = _meta.encode(m, t)
+                if not c.host_only:
+                    c.device_arrays(self.eng.device)
+                dev.append(c)
+                continue
             if isinstance(m, torch.Tensor):
                 dev.append(m.cuda())
-                continue
-            if isinstance(m, _text.TextCorpus):
-                dev.append(m)
                 continue
             if t == "text" and mo.text_on_device():
                 # tokenised once for the whole stream; every window is a view of the corpus and its TF-IDF runs on the

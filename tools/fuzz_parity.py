@@ -205,6 +205,35 @@ def meta_case(rng, i):
     return f"meta n={n:3d} k={k:2d} " + " ".join(out)
 
 
+def metawin_case(rng, i):
+    """Random windows of a random metadata stream that was encoded once (mused_amd/meta.py, csrc/meta_window.hip) against
+    the host path on the window's raw rows: bit for bit, whatever the share of invalid rows."""
+    from mused_amd import meta, synth
+
+    n = int(rng.integers(2, 900))
+    k = int(rng.integers(0, 40))
+    cols, _ = synth.metadata_stream(n, int(rng.integers(0, 1 << 30)), events=int(rng.integers(1, 8)),
+                                    users=int(rng.integers(3, 60)), vocab=int(rng.integers(8, 80)),
+                                    missing=float(rng.choice([0.0, 0.05, 0.5, 0.9])), integer_time=bool(rng.random() < 0.5))
+    cols["tags"][rng.random(n) < rng.choice([0.0, 0.3]), 0] = ""   # rows the "tags" branch rejects
+    if rng.random() < 0.3:  # duplicate geotags / stamps
+        src, dst = rng.integers(0, n, n // 2), rng.integers(0, n, n // 2)
+        cols["location"][dst] = cols["location"][src]
+        cols["time"][dst] = cols["time"][src]
+    windows = 0
+    for t in ("location", "time", "username", "tags"):
+        corpus = meta.encode(cols[t], t)
+        for _ in range(4):
+            s = int(rng.integers(0, n))
+            e = int(rng.integers(s + 1, n + 1))
+            got = mo.adjacency_on_device(corpus.window(s, e), t, k).to_numpy()
+            ref = mo.adjacency_on_device(cols[t][s:e], t, k).to_numpy()
+            assert np.array_equal(got, ref), f"metawin case {i} type={t} n={n} k={k} window=[{s}, {e}): " \
+                                             f"{int((got != ref).sum())} entries differ"
+            windows += 1
+    return f"metawin n={n:3d} k={k:2d} windows={windows}"
+
+
 def kmeans_ill_posed(emb, nc, seed, labels):
     """Adjudication of a label difference from the REFERENCE side: is the oracle's own k-means answer stable under a
     perturbation of its input at the level of one unit in the last place?  If scikit-learn's labels on `emb` change when
@@ -370,7 +399,8 @@ def pipeline_case(rng, i):
     return f"{head} {what} from window {first} on: {why}"
 
 
-CASES = {"swfd": swfd_case, "knn": knn_case, "rsvd": rsvd_case, "pipe": pipeline_case, "lanes": lanes_case, "meta": meta_case}
+CASES = {"swfd": swfd_case, "knn": knn_case, "rsvd": rsvd_case, "pipe": pipeline_case, "lanes": lanes_case, "meta": meta_case,
+         "metawin": metawin_case}
 
 
 def main():
@@ -378,7 +408,7 @@ def main():
     ap.add_argument("--cases", type=int, default=60)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--only", type=int, default=-1, help="run this case index only")
-    ap.add_argument("--kinds", default="swfd,knn", help="comma-separated subset of swfd,knn,rsvd,pipe,lanes,meta (round robin)")
+    ap.add_argument("--kinds", default="swfd,knn", help="comma-separated subset of swfd,knn,rsvd,pipe,lanes,meta,metawin (round robin)")
     a = ap.parse_args()
     t0 = time.time()
     np.set_printoptions(linewidth=200, precision=10)
