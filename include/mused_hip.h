@@ -233,6 +233,15 @@ int mused_rsvd_set_mode(void* handle, int mode);
 int mused_rsvd_status(void* handle, int* flags_out, int* stats_out, void* stream);
 
 /* building blocks of the eigenstep, exported for unit tests */
+/* One Cholesky-QR pass of the eigenstep on the handle's scratch: Y, Q_out n x r (pitch r), r <= n, r <= 286, handle not in
+ * mode 2.  G_out / L_out: Gram (rb x rb) and packed lower factor (rb (rb + 1) / 2) of the last block factorised -- rb = r
+ * for r <= 143, else the second block, rb = r - r / 2.  weak_out: one int, the weak-pivot word.  All device pointers. */
+int mused_rsvd_cholqr(void* handle, const double* Y, int n, int r, double* Q_out, double* G_out, double* L_out,
+                      int* weak_out, void* stream);
+/* The eigenstep's selection tail on eigenpairs of the caller: evals (en), U (en x en, columns), en = (r_max + 1) & ~1;
+ * Bt n x r (pitch r).  V_out (n x n_comp) = Bt U[:, order] S^-1 after svd_flip, sigma_out (n_comp) descending. */
+int mused_rsvd_select(void* handle, const double* evals, const double* U, const double* Bt, int n, int r, int n_comp,
+                      double* V_out, double* sigma_out, void* stream);
 int mused_spmm_binary(const int* rowptr, const int* colidx, int n, const double* Q, long ldq, int r, double* Y,
                       long ldy, void* stream);
 /* ws_int: n + ceil(n/16) ints, ws_f64: 4 * (r + n) doubles */

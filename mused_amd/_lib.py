@@ -63,6 +63,8 @@ _PROTOS = {
     "mused_rsvd_reduce": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mused_rsvd_flags": (_vp, [_vp]),
     "mused_rsvd_status": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "mused_rsvd_cholqr": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mused_rsvd_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "mused_spmm_binary": (_i, [_vp, _vp, _i, _vp, _l, _i, _vp, _l, _vp]),
     "mused_lu_permute_l": (_i, [_vp, _i, _i, _l, _vp, _vp, _vp]),
     "mused_qr_economic": (_i, [_vp, _i, _i, _l, _vp, _l, _vp, _vp]),

@@ -337,6 +337,66 @@ __global__ void col_scale_kernel(double* __restrict__ V, long total, int ncol, c
   if (gid < total) V[gid] *= signs[gid % ncol];
 }
 
+// trsm_rows_kernel asks for more dynamic LDS than a kernel gets by default: set once per process, before its first launch
+static int trsm_rows_prepare() {
+  static std::once_flag once;
+  static hipError_t attr_rc = hipSuccess;
+  std::call_once(once, [] {
+    const int tri = (int)(sizeof(double) * CHOLQR_MAX_R * (CHOLQR_MAX_R + 1) / 2);
+    attr_rc = hipFuncSetAttribute((const void*)trsm_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  tri + (int)(sizeof(double) * 64 * (CHOLQR_MAX_R | 1)));
+  });
+  MUSED_CHECK_HIP(attr_rc);
+  return MUSED_OK;
+}
+
+// dst = an orthonormal-ish basis of span(Y) by Cholesky-QR; weak (optional device int): raised on a weak pivot.
+//   r <= CHOLQR_MAX_R:  G = Y^T Y in U;  L = chol(G + delta I) packed in Cm;  dst = Y L^-T
+//   larger r (BASELINE config 3: r = 266; two packed triangles of that order do not fit the LDS): the columns in two
+//   halves, block Gram-Schmidt -- Q1 = cholqr(Y1);  Y2' = Y2 - Q1 (Q1^T Y2);  Q2 = cholqr(Y2') -- from the same kernels
+//   plus two GEMMs.  One projection leaves Q1^T Q2 ~ cond(Y) eps: fine for the normaliser of a power iteration; the final
+//   basis runs the whole routine twice, which restores orthogonality to rounding as Cholesky-QR2 does.
+static int rsvd_normalise(Rsvd* h, const double* Y, double* dst, int n, int r, int* weak, hipStream_t st) {
+  const long ld = r;
+  const int nsp = cdiv(n, CHOLQR_KCHUNK);
+  auto cholqr_block = [&](const double* Yb, int rb, double* dstb) -> int {
+    int e;
+    const size_t lds_l = sizeof(double) * (size_t)rb * (rb + 1) / 2;
+    const size_t lds_t = lds_l + sizeof(double) * 64 * (size_t)(rb | 1);
+    if ((e = gemm_f64_splitk(false, false, Yb, ld, Yb, ld, h->gpart, rb, rb, n, CHOLQR_KCHUNK, nsp, st))) return e;
+    hipLaunchKernelGGL(gram_reduce_kernel, dim3(cdiv((long)rb * rb, 256)), dim3(256), 0, st, h->gpart, nsp, rb, h->U);
+    hipLaunchKernelGGL(chol_kernel, dim3(1), dim3(256), 0, st, h->U, rb, h->Cm, weak);
+    hipLaunchKernelGGL(trsm_rows_kernel, dim3(cdiv(n, 64)), dim3(256), lds_t, st, Yb, ld, n, rb, h->Cm, dstb, ld);
+    return MUSED_OK;
+  };
+  if (r <= CHOLQR_MAX_R) return cholqr_block(Y, r, dst);
+  const int r1 = r / 2, r2 = r - r1;
+  int e;
+  if ((e = cholqr_block(Y, r1, dst))) return e;                                   // Q1 -> dst[:, :r1]
+  // r1 x r2, behind the packed L of either block (<= CHOLQR_MAX_R (CHOLQR_MAX_R + 1) / 2 = 10,296 doubles)
+  MUSED_REQUIRE(CHOLQR_P_OFF + (long)r1 * r2 <= h->cm_len, "rsvd: projection scratch of the two-block Cholesky-QR does not fit (r = %d)", r);
+  double* P = h->Cm + CHOLQR_P_OFF;
+  if ((e = gemm_f64_splitk(false, false, dst, ld, Y + r1, ld, h->gpart, r1, r2, n, CHOLQR_KCHUNK, nsp, st))) return e;
+  if ((e = gemm_splitk_reduce(h->gpart, nsp, (long)r1 * r2, P, st))) return e;   // P = Q1^T Y2
+  if ((e = gemm_f64(true, false, dst, ld, 0, P, r2, 0, h->Vsel, r2, 0, n, r2, r1, 1, 1.0, st))) return e;  // Q1 P
+  hipLaunchKernelGGL(panel_sub_kernel, dim3(cdiv((long)n * r2, 256)), dim3(256), 0, st, Y + r1, ld, h->Vsel, (long)r2, n, r2,
+                     dst + r1, ld);                                               // Y2' -> dst[:, r1:]
+  return cholqr_block(dst + r1, r2, dst + r1);                                    // Q2 (in place: a workgroup owns its rows)
+}
+
+// The selection tail: eigenpairs (evals, U: order h->eig_n) of the Gram of Bt (n x rc, pitch ld) -> h->sigma (n_comp, descending)
+// and h->Vsel (n x n_comp) = Bt U[:, order] S^-1 with the signs of svd_flip.
+static int rsvd_select(Rsvd* h, const double* evals, const double* U, const double* Bt, long ld, int n, int rc, int n_comp,
+                       hipStream_t st) {
+  int e;
+  hipLaunchKernelGGL(rsvd_decide_kernel, dim3(1), dim3(1024), 0, st, evals, U, h->eig_n, rc, n_comp, h->Cm, h->sigma);
+  if ((e = gemm_f64(true, false, Bt, ld, 0, h->Cm, n_comp, 0, h->Vsel, n_comp, 0, n, n_comp, rc, 1, 1.0, st))) return e;
+  hipLaunchKernelGGL(col_sign_kernel, dim3(n_comp), dim3(256), 0, st, h->Vsel, n, n_comp, n_comp, h->signs);
+  hipLaunchKernelGGL(col_scale_kernel, dim3(cdiv((long)n * n_comp, 256)), dim3(256), 0, st, h->Vsel, (long)n * n_comp,
+                     n_comp, h->signs);
+  return MUSED_OK;
+}
+
 static int rsvd_enqueue(Rsvd* h, int n, int r, int n_comp, int n_iter, hipStream_t st, bool capturing) {
   const int words = (n + 63) / 64;
   const long ld = r;
@@ -366,38 +426,6 @@ static int rsvd_enqueue(Rsvd* h, int n, int r, int n_comp, int n_iter, hipStream
     return e && (e[0] == 'l' || e[0] == 'L');
   }();
   const bool cholqr = !want_lu && h->mode != 2 && r <= 2 * CHOLQR_MAX_R && r <= n;
-  // dst = an orthonormal-ish basis of span(Y) by Cholesky-QR; weak (optional device int): raised on a weak pivot.
-  //   r <= CHOLQR_MAX_R:  G = Y^T Y in U;  L = chol(G + delta I) packed in Cm;  dst = Y L^-T
-  //   larger r (BASELINE config 3: r = 266; two packed triangles of that order do not fit the LDS): the columns in two
-  //   halves, block Gram-Schmidt -- Q1 = cholqr(Y1);  Y2' = Y2 - Q1 (Q1^T Y2);  Q2 = cholqr(Y2') -- from the same kernels
-  //   plus two GEMMs.  One projection leaves Q1^T Q2 ~ cond(Y) eps: fine for the normaliser of a power iteration; the final
-  //   basis runs the whole routine twice, which restores orthogonality to rounding as Cholesky-QR2 does.
-  auto normalise = [&](const double* Y, double* dst, int* weak) -> int {
-    const int nsp = cdiv(n, CHOLQR_KCHUNK);
-    auto cholqr_block = [&](const double* Yb, int rb, double* dstb) -> int {
-      int e;
-      const size_t lds_l = sizeof(double) * (size_t)rb * (rb + 1) / 2;
-      const size_t lds_t = lds_l + sizeof(double) * 64 * (size_t)(rb | 1);
-      if ((e = gemm_f64_splitk(false, false, Yb, ld, Yb, ld, h->gpart, rb, rb, n, CHOLQR_KCHUNK, nsp, st))) return e;
-      hipLaunchKernelGGL(gram_reduce_kernel, dim3(cdiv((long)rb * rb, 256)), dim3(256), 0, st, h->gpart, nsp, rb, h->U);
-      hipLaunchKernelGGL(chol_kernel, dim3(1), dim3(256), 0, st, h->U, rb, h->Cm, weak);
-      hipLaunchKernelGGL(trsm_rows_kernel, dim3(cdiv(n, 64)), dim3(256), lds_t, st, Yb, ld, n, rb, h->Cm, dstb, ld);
-      return MUSED_OK;
-    };
-    if (r <= CHOLQR_MAX_R) return cholqr_block(Y, r, dst);
-    const int r1 = r / 2, r2 = r - r1;
-    int e;
-    if ((e = cholqr_block(Y, r1, dst))) return e;                                   // Q1 -> dst[:, :r1]
-    // r1 x r2, behind the packed L of either block (<= CHOLQR_MAX_R (CHOLQR_MAX_R + 1) / 2 = 10,296 doubles)
-    MUSED_REQUIRE(CHOLQR_P_OFF + (long)r1 * r2 <= h->cm_len, "rsvd: projection scratch of the two-block Cholesky-QR does not fit (r = %d)", r);
-    double* P = h->Cm + CHOLQR_P_OFF;
-    if ((e = gemm_f64_splitk(false, false, dst, ld, Y + r1, ld, h->gpart, r1, r2, n, CHOLQR_KCHUNK, nsp, st))) return e;
-    if ((e = gemm_splitk_reduce(h->gpart, nsp, (long)r1 * r2, P, st))) return e;   // P = Q1^T Y2
-    if ((e = gemm_f64(true, false, dst, ld, 0, P, r2, 0, h->Vsel, r2, 0, n, r2, r1, 1, 1.0, st))) return e;  // Q1 P
-    hipLaunchKernelGGL(panel_sub_kernel, dim3(cdiv((long)n * r2, 256)), dim3(256), 0, st, Y + r1, ld, h->Vsel, (long)r2, n, r2,
-                       dst + r1, ld);                                               // Y2' -> dst[:, r1:]
-    return cholqr_block(dst + r1, r2, dst + r1);                                    // Q2 (in place: a workgroup owns its rows)
-  };
   if (cholqr) {
     // ONE normalisation per power iteration, of A^T (A Q): the two products in a row square the spread of the basis
     // ((sigma_1 / sigma_r)^2 ~ 1e3 .. 1e4 for these adjacency matrices), far inside what a Cholesky of the Gram takes
@@ -407,7 +435,7 @@ static int rsvd_enqueue(Rsvd* h, int n, int r, int n_comp, int n_iter, hipStream
       RC(spmm_binary(h->rowptr, h->colidx, n, Qcur, ld, rc, X, ld, st));
       double* Z = (X == h->Qa) ? h->Qb : h->Qa;  // (the buffer of the old basis, unless that is Q0)
       RC(spmm_binary(h->rowptrT, h->colidxT, n, X, ld, rc, Z, ld, st));
-      RC(normalise(Z, X, nullptr));
+      RC(rsvd_normalise(h, Z, X, n, r, nullptr, st));
       Qcur = X;
     }
   } else {
@@ -430,7 +458,7 @@ static int rsvd_enqueue(Rsvd* h, int n, int r, int n_comp, int n_iter, hipStream
     const double* src = Yf;
     double* dsts[2] = {Yt, h->Qf};
     for (int pass = 0; pass < 2; ++pass) {
-      RC(normalise(src, dsts[pass], h->flags + 2));
+      RC(rsvd_normalise(h, src, dsts[pass], n, r, h->flags + 2, st));
       src = dsts[pass];
     }
     if (h->mode == 0) RC(qr_economic(Yf, n, rc, ld, h->Qf, ld, h->tau, h->wpart, st, h->flags + 2));
@@ -451,11 +479,7 @@ static int rsvd_enqueue(Rsvd* h, int n, int r, int n_comp, int n_iter, hipStream
   hipLaunchKernelGGL(gram_reduce_pad_kernel, dim3(cdiv((long)en * en, 256)), dim3(256), 0, st, h->gpart, nsplit, rc,
                      eig_plan_input(ep), en);
   RC(eig_plan_run_inplace(ep, h->evals, h->U, st, false));
-  hipLaunchKernelGGL(rsvd_decide_kernel, dim3(1), dim3(1024), 0, st, h->evals, h->U, en, rc, n_comp, h->Cm, h->sigma);
-  RC(gemm_f64(true, false, h->Bt, ld, 0, h->Cm, n_comp, 0, h->Vsel, n_comp, 0, n, n_comp, rc, 1, 1.0, st));
-  hipLaunchKernelGGL(col_sign_kernel, dim3(n_comp), dim3(256), 0, st, h->Vsel, n, n_comp, n_comp, h->signs);
-  hipLaunchKernelGGL(col_scale_kernel, dim3(cdiv((long)n * n_comp, 256)), dim3(256), 0, st, h->Vsel, (long)n * n_comp,
-                     n_comp, h->signs);
+  RC(rsvd_select(h, h->evals, h->U, h->Bt, ld, n, rc, n_comp, st));
   RC(spmm_binary(h->rowptr, h->colidx, n, h->Vsel, n_comp, n_comp, h->embed, n_comp, st));
   MUSED_LAUNCH_CHECK();
 #undef RC
@@ -544,16 +568,7 @@ static int rsvd_create_impl(Rsvd* h, int n_max, int r_max, long nnz_cap, int swe
     }
   }
   if ((rc = gemm_f64_prepare_all())) return rc;
-  {
-    static std::once_flag once;
-    static hipError_t attr_rc = hipSuccess;
-    std::call_once(once, [] {
-      const int tri = (int)(sizeof(double) * CHOLQR_MAX_R * (CHOLQR_MAX_R + 1) / 2);
-      attr_rc = hipFuncSetAttribute((const void*)trsm_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      tri + (int)(sizeof(double) * 64 * (CHOLQR_MAX_R | 1)));
-    });
-    MUSED_CHECK_HIP(attr_rc);
-  }
+  if ((rc = trsm_rows_prepare())) return rc;
   const char* ng = getenv("MUSED_NO_GRAPH");
   h->use_graph = !(ng && ng[0] == '1');
   return MUSED_OK;
@@ -632,6 +647,53 @@ int mused_rsvd_reduce(void* handle, int n, int n_comp, int r, int n_iter, double
   if (out_components)
     MUSED_CHECK_HIP(hipMemcpyAsync(out_components, h->Vsel, sizeof(double) * (size_t)n * n_comp,
                                    hipMemcpyDeviceToDevice, st));
+  return MUSED_OK;
+}
+
+// ---- test-facing entries: one Cholesky-QR pass and the selection tail on their own, on the handle's scratch, launched
+// ---- directly on the stream (nothing is captured).  Every pointer is a device pointer.
+
+// One rsvd_normalise(Y -> Q_out), n x r panels of pitch r, as a power iteration or a final pass runs it.  G_out / L_out: the
+// Gram (rb x rb) and the packed factor (rb (rb + 1) / 2) of the LAST block it factorised: rb = r for r <= 143, else the second
+// block, rb = r - r / 2, whose Gram is that of Y2 - Q1 (Q1^T Y2).  weak_out (one int): the weak-pivot word of this pass.
+int mused_rsvd_cholqr(void* handle, const double* Y, int n, int r, double* Q_out, double* G_out, double* L_out, int* weak_out,
+                      void* stream) {
+  Rsvd* h = (Rsvd*)handle;
+  MUSED_REQUIRE(h && Y && Q_out && G_out && L_out && weak_out, "mused_rsvd_cholqr: null pointer");
+  MUSED_REQUIRE(h->mode != 2, "mused_rsvd_cholqr: the handle is in mode 2 (LU / Householder chain), which never runs the Cholesky-QR");
+  MUSED_REQUIRE(n >= 1 && n <= h->n_max, "mused_rsvd_cholqr: n = %d outside 1 .. n_max = %d", n, h->n_max);
+  MUSED_REQUIRE(r >= 1 && r <= h->r_max, "mused_rsvd_cholqr: r = %d outside 1 .. r_max = %d", r, h->r_max);
+  MUSED_REQUIRE(r <= 2 * CHOLQR_MAX_R, "mused_rsvd_cholqr: r = %d above %d, the largest panel the Cholesky-QR takes", r, 2 * CHOLQR_MAX_R);
+  MUSED_REQUIRE(r <= n, "mused_rsvd_cholqr: r = %d columns in n = %d rows (the eigenstep takes the LU chain then)", r, n);
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if ((rc = trsm_rows_prepare())) return rc;
+  int* weak = h->flags + 2;
+  if ((rc = zero_ints(weak, 1, st))) return rc;
+  if ((rc = rsvd_normalise(h, Y, Q_out, n, r, weak, st))) return rc;
+  MUSED_LAUNCH_CHECK();
+  const size_t rb = r <= CHOLQR_MAX_R ? r : r - r / 2;
+  MUSED_CHECK_HIP(hipMemcpyAsync(G_out, h->U, sizeof(double) * rb * rb, hipMemcpyDeviceToDevice, st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(L_out, h->Cm, sizeof(double) * rb * (rb + 1) / 2, hipMemcpyDeviceToDevice, st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(weak_out, weak, sizeof(int), hipMemcpyDeviceToDevice, st));
+  return MUSED_OK;
+}
+
+// rsvd_select on eigenpairs the caller supplies: evals (en) and U (en x en, column j <-> evals[j]) with en = the handle's
+// eigensolver order, (r_max + 1) & ~1, of which rows and entries r .. en - 1 are the zero padding of the Gram; Bt: n x r,
+// pitch r.  V_out: n x n_comp, sigma_out: n_comp.
+int mused_rsvd_select(void* handle, const double* evals, const double* U, const double* Bt, int n, int r, int n_comp,
+                      double* V_out, double* sigma_out, void* stream) {
+  Rsvd* h = (Rsvd*)handle;
+  MUSED_REQUIRE(h && evals && U && Bt && V_out && sigma_out, "mused_rsvd_select: null pointer");
+  MUSED_REQUIRE(n >= 1 && n <= h->n_max && r >= 1 && r <= h->r_max && n_comp >= 1 && n_comp <= r,
+                "mused_rsvd_select: bad sizes n=%d r=%d n_comp=%d (n_max %d, r_max %d)", n, r, n_comp, h->n_max, h->r_max);
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if ((rc = rsvd_select(h, evals, U, Bt, r, n, r, n_comp, st))) return rc;
+  MUSED_LAUNCH_CHECK();
+  MUSED_CHECK_HIP(hipMemcpyAsync(V_out, h->Vsel, sizeof(double) * (size_t)n * n_comp, hipMemcpyDeviceToDevice, st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(sigma_out, h->sigma, sizeof(double) * (size_t)n_comp, hipMemcpyDeviceToDevice, st));
   return MUSED_OK;
 }
 

@@ -243,6 +243,56 @@ def test_spmm_binary(L):
     np.testing.assert_allclose(Y.cpu().numpy(), A.astype(np.float64) @ Q, atol=1e-12)
 
 
+SPMM_N = 203            # n % 4 = 3: the last workgroup holds three rows
+SPMM_DEGREES = (0, 1, 2, 3, 50, 51)
+
+
+@pytest.fixture(scope="module")
+def spmm_lists():
+    """Neighbour lists of SPMM_N rows with degrees 0, 1, 2, 3, 50, 51 in turn (the kernel takes two neighbours per step and
+    one more behind them), ascending, every eighth row with a neighbour listed twice."""
+    rng = np.random.default_rng(11)
+    lists = []
+    for i in range(SPMM_N):
+        nb = np.sort(rng.choice(SPMM_N, SPMM_DEGREES[i % len(SPMM_DEGREES)], replace=False))
+        if i % 8 == 3 and len(nb) >= 2:
+            nb[len(nb) // 2] = nb[len(nb) // 2 - 1]
+        lists.append(nb.astype(np.int32))
+    assert {len(nb) for nb in lists} == set(SPMM_DEGREES) and len(lists[-1]) > 0
+    assert any(len(nb) > len(set(nb)) for nb in lists)
+    return lists
+
+
+@pytest.mark.parametrize("r", [1, 63, 64, 65, 128, 191, 192, 193, 266, 385])
+def test_spmm_binary_shapes_and_pitches(L, spmm_lists, r):
+    """Every lane mask of the 192-column trip (one, two and three 64-lane groups, a second and a third trip), pitches that
+    are not r with NaN behind the rows: bit for bit the sequential fp64 sum in list order that spmm.hip promises, and within
+    deg eps sum |Q| of the exact sum."""
+    n, ldq, ldy = SPMM_N, r + 3, r + 5
+    rng = np.random.default_rng(r)
+    Q = rng.standard_normal((n, r)) * np.exp(rng.uniform(-8.0, 8.0, (n, 1)))     # rows of very different size: order matters
+    Qp = np.full((n, ldq), np.nan)
+    Qp[:, :r] = Q
+    rowptr = np.concatenate([[0], np.cumsum([len(nb) for nb in spmm_lists])]).astype(np.int32)
+    col = np.concatenate(spmm_lists).astype(np.int32)
+    want = np.zeros((n, r))
+    exact = np.zeros((n, r), dtype=np.longdouble)
+    scale = np.zeros((n, r))
+    for i, nb in enumerate(spmm_lists):
+        for j in nb:
+            want[i] = want[i] + Q[j]
+        exact[i] = Q[nb].astype(np.longdouble).sum(axis=0)
+        scale[i] = len(nb) * np.abs(Q[nb]).sum(axis=0)
+    Y = torch.full((n + 1, ldy), np.nan, dtype=torch.float64, device="cuda")
+    d_rowptr, d_col, d_Q = dev(rowptr), dev(col), dev(Qp)
+    L.call("mused_spmm_binary", P(d_rowptr), P(d_col), n, P(d_Q), ldq, r, P(Y), ldy, S())
+    sync()
+    got = Y.cpu().numpy()
+    assert np.isnan(got[:n, r:]).all() and np.isnan(got[n]).all(), "written outside the n x r panel"
+    assert np.array_equal(got[:n, :r].view(np.int64), want.view(np.int64))
+    assert np.all(np.abs(got[:n, :r] - exact) <= 2.0 ** -52 * scale)
+
+
 # ---------------------------------------------------------------- panels ---------------
 @pytest.mark.parametrize("n,r", [(500, 26), (2000, 74), (8, 12), (40, 40), (1030, 138)])
 def test_lu_permute_l(L, n, r):
