@@ -177,6 +177,39 @@ int mused_tfidf_window(const int* rowptr, const int* term, const int* cnt, const
 int mused_tfidf_dense(const int* w_rowptr, const int* w_col, const double* w_val, int n_docs, int n_cols, double* out,
                       long ld, void* stream);
 
+/* ---- a2, "text": the one tokenised pass itself (mused_amd/text.py: tokenise_on_device), csrc/tokenise.hip;
+ * specification: mused_amd/tokens.py -- scikit-learn's default analyser on ASCII text as a rule on bytes (lower-case
+ * 'A'..'Z'; every maximal run of [0-9A-Za-z_] of length >= 2 is a token; vocabulary in byte order).  All integers int32.
+ * Input: buf (DEVICE, n_bytes in [1, 2^31), 16-byte aligned) = the strings of the n_docs valid rows, each followed by one
+ *   separator byte that is no word byte; docptr_host (HOST, n_docs + 1 ints, read and checked at the call: from 0 to
+ *   n_bytes, strictly ascending -- a document holds at least its separator -- and copied to the workspace on the stream).
+ * Two calls, because the host sorts the V distinct tokens between them; both enqueue-only.  The workspace carries the
+ * token spans (text order, from a prefix scan), the hash table and the lower-cased bytes from the first to the second.
+ * mused_tokenise_scan: info (DEVICE, 4 ints) <- {T tokens, V distinct tokens, flags, tokens of the longest document};
+ *   voc_start / voc_len (DEVICE, voc_cap ints each; n_bytes / 3 + 1 always suffices) <- byte span of one occurrence of
+ *   every distinct token, in the order of the PROVISIONAL ids 0 .. V - 1 (table order: arbitrary, may differ from call
+ *   to call).  table_slots: slots of the open-addressing table, 0 = the default 2 * (n_bytes / 3 + 1), at least twice
+ *   T; any count in [1, 2^31) is accepted, and flag 2 is raised (nothing inserted, V = 0) when T exceeds it.
+ *   max_doc_tokens in [1, 8192]: flag 1 when a document holds more tokens (the second call sorts a document in LDS).
+ *   HOST READS after it: the 16 bytes of info, then voc_start[0 .. V) and voc_len[0 .. V).
+ * mused_tokenise_build (same n_bytes, n_docs, table_slots, ws): n_tokens = T >= 1, n_terms = V in [1, 2^24),
+ *   doc_tokens = info[3] in [1, 8192]; rank (DEVICE, V): provisional id -> rank in the sorted vocabulary; vrow (DEVICE,
+ *   n_docs): document -> row.  Outputs (DEVICE): doc_rowptr[n_docs + 1] = CSR pointers over the DOCUMENTS (the host
+ *   spreads them over all rows), term / cnt / pos [capacity T, nnz = doc_rowptr[n_docs] used] as TextCorpus documents
+ *   them, gpostptr[V + 1], gpostrow / gpostent [capacity T] = the term-major postings (stable LSD radix sort of the
+ *   entries by term).  info[2] |= 4: the workspace is not what the first call left (outputs invalid).
+ *   HOST READS after it: doc_rowptr and info.
+ * Nothing depends on scheduling: two runs give identical bytes in every output but voc_start / voc_len / rank.
+ * ws: mused_tokenise_ws_bytes(n_bytes, n_docs, table_slots) bytes, 16-byte aligned (-1 for sizes out of range).
+ * Bad arguments: MUSED_ERR_ARG, nothing enqueued, outputs untouched. */
+long mused_tokenise_ws_bytes(long n_bytes, long n_docs, long table_slots);
+int mused_tokenise_scan(const unsigned char* buf, long n_bytes, const int* docptr_host, long n_docs, long table_slots,
+                        int max_doc_tokens, int* voc_start, int* voc_len, long voc_cap, int* info, void* ws, long ws_bytes,
+                        void* stream);
+int mused_tokenise_build(long n_bytes, long n_docs, long table_slots, int n_tokens, int n_terms, int doc_tokens,
+                         const int* rank, const int* vrow, int* doc_rowptr, int* term, int* cnt, int* pos, int* gpostptr,
+                         int* gpostrow, int* gpostent, int* info, void* ws, long ws_bytes, void* stream);
+
 /* ---- a3 / a4: adjacency bitmasks -------------------------------------------------------------
  * An adjacency is n rows x words uint64 (words >= ceil(n/64)); bit j of row i <=> A[i][j] = 1. */
 

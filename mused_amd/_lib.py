@@ -49,6 +49,9 @@ _PROTOS = {
     "mused_tfidf_ws_bytes": (_l, [_l]),
     "mused_tfidf_window": (_i, [_vp] * 9 + [_i] * 7 + [_vp] * 11 + [_l, _vp]),
     "mused_tfidf_dense": (_i, [_vp, _vp, _vp, _i, _i, _vp, _l, _vp]),
+    "mused_tokenise_ws_bytes": (_l, [_l, _l, _l]),
+    "mused_tokenise_scan": (_i, [_vp, _l, _vp, _l, _l, _i, _vp, _vp, _l, _vp, _vp, _l, _vp]),
+    "mused_tokenise_build": (_i, [_l, _l, _l, _i, _i, _i] + [_vp] * 10 + [_vp, _l, _vp]),
     "mused_adj_fuse": (_i, [C.POINTER(_vp), _i, _i, _i, _vp, _vp]),
     "mused_adj_degrees": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mused_adj_csr_fill": (_i, [_vp, _i, _i, _vp, _vp, _vp]),

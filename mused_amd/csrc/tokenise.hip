@@ -1,0 +1,580 @@
+// The one tokenised pass of the "text" modality (mused_amd/text.py: TextCorpus) from the bytes of the corpus: scikit-learn's
+// default analyser on ASCII text is a rule on bytes -- lower-case 'A'..'Z', every maximal run of [0-9A-Za-z_] of length >= 2
+// is a token -- and Python's str order on such tokens is byte order.  The rule, statement by statement: mused_amd/tokens.py.
+//
+// The corpus is one buffer: the strings of the D valid rows, each followed by one separator byte that is no word byte;
+// document d is buf[docptr[d], docptr[d + 1]), so no run crosses a document.  Two calls, because the alphabetical order
+// of the V distinct tokens is made on the host between them (sorted() over V strings, the order of `_sort_features`):
+//
+//   mused_tokenise_scan
+//     scan     (count, block scan, write) classify and lower-case 16 bytes per thread, mark the start of every run of
+//              length >= 2, count per block of 4096 bytes, exclusive scan of the block counts, then write tok_start / tok_len
+//              in TEXT ORDER (the order comes from the scan, not from atomics; a run may cross a block's byte range: the
+//              thread that owns its start walks to its end).  The document of a token is never stored: tok_start
+//              ascends, so the tokens of document d are the slice between two binary searches of docptr[d], docptr[d + 1].
+//     docs     one thread per document: its token count -> the longest document (info[3]) and the flag for one beyond the cap
+//     insert   one thread per token into an open-addressing table of token indices keyed by the token's bytes: atomicCAS
+//              on the slot, linear probing; identity is decided by comparing ALL bytes of the two tokens.  A slot is read only
+//              through the return value of the atomic (a plain load of a slot is not seen across XCDs within a launch).
+//              Once filled a slot keeps a token of the same bytes; WHICH equal token represents the group, and which
+//              slot a group ends up in, is arbitrary and nothing downstream depends on it.
+//     compact  (count, block scan, write) occupied slots -> provisional ids 0 .. V - 1 (slot order), voc_start / voc_len,
+//              and the slot now holds the id
+//   host: reads info, then the V spans; sorts; uploads rank[V] (provisional id -> rank in the sorted vocabulary)
+//   mused_tokenise_build
+//     rows     one workgroup per document, twice (count, then write, with the exclusive scan of the counts = rowptr in
+//              between): (term << 32 | position) of its tokens to LDS, bitonic sort; equal terms collapse to one entry: cnt =
+//              run length, first position = the run's smallest; pos = rank of the first position among the entries
+//              (a second sort, of first position << 16 | entry)
+//     postings stable LSD radix sort of the entries by term, 8 bits a pass (histogram per tile of 1024, one exclusive scan
+//              of the digit-major table, scatter in tile order -- one wave per tile, ranks inside a chunk of 64 from
+//              ballots): entries are row-major, so rows ascend inside a term.  gpostptr[t] = first sorted entry >= t.
+// No float anywhere and no result that depends on arrival order: two calls on the same input give identical bytes.
+#include "common.h"
+#include "internal.h"
+
+namespace mused {
+
+constexpr int TK_MAX_DOC_TOKENS = 8192;  // keys (8 B), second keys (4 B), run heads (4 B) of one document in LDS: 128 KiB + 80 B
+constexpr int TK_SCAN_THREADS = 256;
+constexpr int TK_SCAN_TILE = TK_SCAN_THREADS * 16;  // bytes per workgroup of the scan
+constexpr int TK_BLOCKSCAN_THREADS = 1024;
+constexpr int TK_RADIX_TILE = 1024;  // entries per wave of the radix passes
+constexpr int TK_FLAG_DOC = 1;       // a document holds more tokens than the caller's cap
+constexpr int TK_FLAG_TABLE = 2;     // more tokens than table slots: nothing was inserted
+constexpr int TK_FLAG_STATE = 4;     // the workspace is not what mused_tokenise_scan left (ids or slices out of range)
+constexpr unsigned char TK_BLANK = ' ';
+
+__device__ __forceinline__ bool tk_is_word(unsigned c) {
+  return (c - '0' < 10u) | ((c | 32u) - 'a' < 26u) | (c == '_');
+}
+__device__ __forceinline__ unsigned char tk_lower(unsigned c) { return (unsigned char)(c - 'A' < 26u ? c + 32u : c); }
+
+// exclusive prefix sum over the workgroup (any multiple of 64 threads up to 1024); ws: 16 ints of LDS
+__device__ __forceinline__ int tk_excl_scan(int v, int* ws, int& total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  int x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(x, o);
+    if (lane >= o) x += y;
+  }
+  if (lane == 63) ws[w] = x;
+  __syncthreads();
+  int base = 0, tot = 0;
+  for (int i = 0; i < nw; ++i) {
+    const int c = ws[i];
+    base += (i < w) ? c : 0;
+    tot += c;
+  }
+  total = tot;
+  __syncthreads();
+  return base + x - v;
+}
+
+// first position p in [0, n) with a[p] >= v (n if none)
+__device__ __forceinline__ int tk_lower_bound(const int* __restrict__ a, int n, int v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (a[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// WRITE = false: lower-cased bytes -> low, token starts per block -> blk[block]
+// WRITE = true:  blk holds the exclusive scan of those counts; tok_start / tok_len in text order (reads `low`)
+template <bool WRITE>
+__global__ __launch_bounds__(TK_SCAN_THREADS) void tk_scan_kernel(const unsigned char* __restrict__ src, long n,
+                                                                 unsigned char* __restrict__ low, int* __restrict__ blk,
+                                                                 int* __restrict__ tok_start, int* __restrict__ tok_len,
+                                                                 int tok_cap) {
+  __shared__ int ws[16];
+  const long base = (long)blockIdx.x * TK_SCAN_TILE + threadIdx.x * 16;
+  unsigned char b[18];  // the byte before, 16 bytes, the byte behind
+  if (base + 16 <= n) {
+    const uint4 v = *reinterpret_cast<const uint4*>(src + base);
+    const unsigned q[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 16; ++j) b[j + 1] = (unsigned char)(q[j >> 2] >> (8 * (j & 3)));
+  } else {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) b[j + 1] = base + j < n ? src[base + j] : TK_BLANK;
+  }
+  b[0] = (base > 0 && base - 1 < n) ? src[base - 1] : TK_BLANK;
+  b[17] = base + 16 < n ? src[base + 16] : TK_BLANK;
+  unsigned wbits = 0;
+#pragma unroll
+  for (int j = 0; j < 18; ++j) wbits |= tk_is_word(b[j]) ? (1u << j) : 0u;
+  // bit j of starts: byte base + j is a word byte behind a non-word byte and in front of a word byte
+  const unsigned starts = ((wbits >> 1) & ~wbits & (wbits >> 2)) & 0xffffu;
+  const int mine = __popc(starts);
+  if (!WRITE) {
+    if (base + 16 <= n) {
+      unsigned q[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int j = 0; j < 16; ++j) q[j >> 2] |= (unsigned)tk_lower(b[j + 1]) << (8 * (j & 3));
+      *reinterpret_cast<uint4*>(low + base) = make_uint4(q[0], q[1], q[2], q[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        if (base + j < n) low[base + j] = tk_lower(b[j + 1]);
+    }
+  }
+  int total;
+  const int before = tk_excl_scan(mine, ws, total);
+  if (!WRITE) {
+    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    return;
+  }
+  int o = blk[blockIdx.x] + before;
+  unsigned s = starts;
+  while (s) {
+    const int j = __ffs(s) - 1;
+    s &= s - 1;
+    long e = base + j + 2;  // the run holds bytes base + j and base + j + 1
+    while (e < n && tk_is_word(low[e])) ++e;
+    if (o < tok_cap) {
+      tok_start[o] = (int)(base + j);
+      tok_len[o] = (int)(e - (base + j));
+    }
+    ++o;
+  }
+}
+
+// one workgroup: a[0 .. m) <- its exclusive prefix sums, *total <- the sum
+__global__ __launch_bounds__(TK_BLOCKSCAN_THREADS) void tk_blockscan_kernel(int* __restrict__ a, int m, int* __restrict__ total) {
+  __shared__ int ws[16];
+  int carry = 0;
+  for (int base = 0; base < m; base += TK_BLOCKSCAN_THREADS) {
+    const int i = base + threadIdx.x;
+    const int v = i < m ? a[i] : 0;
+    int tot;
+    const int x = carry + tk_excl_scan(v, ws, tot);
+    if (i < m) a[i] = x;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) *total = carry;
+}
+
+__global__ __launch_bounds__(256) void tk_docs_kernel(const int* __restrict__ docptr, int n_docs, const int* __restrict__ tok_start,
+                                                     int max_doc_tokens, int* __restrict__ info) {
+  const int d = blockIdx.x * 256 + threadIdx.x;
+  const int T = info[0];
+  int nt = 0;
+  if (d < n_docs) nt = tk_lower_bound(tok_start, T, docptr[d + 1]) - tk_lower_bound(tok_start, T, docptr[d]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) nt = max(nt, __shfl_xor(nt, o));
+  if ((threadIdx.x & 63) == 0) {
+    atomicMax(&info[3], nt);
+    if (nt > max_doc_tokens) atomicOr(&info[2], TK_FLAG_DOC);
+  }
+}
+
+__device__ __forceinline__ bool tk_same_bytes(const unsigned char* __restrict__ low, int s0, int s1, int len) {
+  for (int i = 0; i < len; ++i)
+    if (low[s0 + i] != low[s1 + i]) return false;
+  return true;
+}
+
+__global__ __launch_bounds__(256) void tk_insert_kernel(const unsigned char* __restrict__ low, const int* __restrict__ tok_start,
+                                                       const int* __restrict__ tok_len, int* __restrict__ table, int slots,
+                                                       int* __restrict__ tok_slot, int* __restrict__ info) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const int T = info[0];
+  if (T > slots) {  // a table that cannot hold every token distinct: the probe loop would not end
+    if (t == 0) atomicOr(&info[2], TK_FLAG_TABLE);
+    return;
+  }
+  if (t >= T) return;
+  const int s = tok_start[t], len = tok_len[t];
+  unsigned h = 2166136261u;  // FNV-1a, then a finaliser: the hash only places the token, the bytes identify it
+  for (int i = 0; i < len; ++i) h = (h ^ low[s + i]) * 16777619u;
+  h ^= h >> 16;
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  int slot = (int)(h % (unsigned)slots);
+  for (int probe = 0; probe < slots; ++probe) {
+    const int old = atomicCAS(&table[slot], -1, t);
+    if (old == -1 || (tok_len[old] == len && tk_same_bytes(low, tok_start[old], s, len))) {
+      tok_slot[t] = slot;
+      return;
+    }
+    slot = slot + 1 == slots ? 0 : slot + 1;
+  }
+}
+
+// WRITE = false: occupied slots per block -> blk[block];  WRITE = true: blk scanned; slot -> provisional id, spans written
+template <bool WRITE>
+__global__ __launch_bounds__(256) void tk_compact_kernel(int* __restrict__ table, int slots, int* __restrict__ blk,
+                                                        const int* __restrict__ tok_start, const int* __restrict__ tok_len,
+                                                        int* __restrict__ voc_start, int* __restrict__ voc_len, int voc_cap) {
+  __shared__ int ws[16];
+  const long slot = (long)blockIdx.x * 256 + threadIdx.x;
+  const int t = slot < slots ? table[slot] : -1;
+  int total;
+  const int before = tk_excl_scan(t >= 0 ? 1 : 0, ws, total);
+  if (!WRITE) {
+    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    return;
+  }
+  if (t >= 0) {
+    const int id = blk[blockIdx.x] + before;
+    if (id < voc_cap) {
+      voc_start[id] = tok_start[t];
+      voc_len[id] = tok_len[t];
+    }
+    table[slot] = id;
+  }
+}
+
+template <class K>
+__device__ __forceinline__ void tk_bitonic(K* a, int n) {
+  __syncthreads();
+  for (int k = 2; k <= n; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int p = threadIdx.x; p < (n >> 1); p += blockDim.x) {
+        const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
+        const K x = a[i], y = a[i | j];
+        if ((x > y) == ((i & k) == 0)) {
+          a[i] = y;
+          a[i | j] = x;
+        }
+      }
+      __syncthreads();
+    }
+}
+
+struct TkRows {
+  const int *docptr, *tok_start, *tok_slot, *table, *rank, *vrow;
+  int n_docs, T, V, slots, n;  // n: power of two >= the longest document's token count
+};
+
+// WRITE = false: rowcnt[d] <- distinct terms of document d.  WRITE = true: rowptr scanned; term / cnt / pos / ent_row written
+template <bool WRITE>
+__global__ __launch_bounds__(256) void tk_rows_kernel(TkRows a, int* __restrict__ rowcnt, const int* __restrict__ rowptr,
+                                                     int* __restrict__ term, int* __restrict__ cnt, int* __restrict__ pos,
+                                                     int* __restrict__ ent_row, int* __restrict__ info) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long tk_smem[];
+  const int n = a.n, d = blockIdx.x, tid = threadIdx.x, bd = blockDim.x;
+  unsigned long long* keys = tk_smem;                      // [n]
+  unsigned* k2 = reinterpret_cast<unsigned*>(keys + n);    // [n]
+  int* ws = reinterpret_cast<int*>(k2 + n);                // [16]
+  int* hidx = ws + 16;                                     // [n + 1]
+  const int t0 = tk_lower_bound(a.tok_start, a.T, a.docptr[d]);
+  const int nt = tk_lower_bound(a.tok_start, a.T, a.docptr[d + 1]) - t0;
+  if (nt < 0 || nt > n) {  // uniform over the workgroup
+    if (tid == 0) {
+      atomicOr(&info[2], TK_FLAG_STATE);
+      if (!WRITE) rowcnt[d] = 0;
+    }
+    return;
+  }
+  bool bad = false;
+  for (int i = tid; i < n; i += bd) {
+    unsigned long long k = ~0ull;
+    if (i < nt) {
+      const int slot = a.tok_slot[t0 + i];
+      int id = (unsigned)slot < (unsigned)a.slots ? a.table[slot] : -1;
+      int r = (unsigned)id < (unsigned)a.V ? a.rank[id] : -1;
+      if ((unsigned)r >= (unsigned)a.V) {
+        bad = true;
+        r = 0;
+      }
+      k = ((unsigned long long)(unsigned)r << 32) | (unsigned)i;
+    }
+    keys[i] = k;
+  }
+  if (bad) atomicOr(&info[2], TK_FLAG_STATE);
+  tk_bitonic(keys, n);
+  int L = 0;
+  for (int base = 0; base < n; base += bd) {
+    const int i = base + tid;
+    const bool head = i < nt && (i == 0 || (unsigned)(keys[i] >> 32) != (unsigned)(keys[i - 1] >> 32));
+    int tot;
+    const int e = L + tk_excl_scan(head ? 1 : 0, ws, tot);
+    if (head) hidx[e] = i;
+    L += tot;
+  }
+  if (!WRITE) {
+    if (tid == 0) rowcnt[d] = L;
+    return;
+  }
+  if (tid == 0) hidx[L] = nt;
+  __syncthreads();
+  const int o0 = rowptr[d];
+  const int row = a.vrow[d];
+  for (int e = tid; e < n; e += bd) {
+    unsigned q = ~0u;
+    if (e < L) {
+      const int i = hidx[e];
+      const unsigned long long k = keys[i];
+      term[o0 + e] = (int)(k >> 32);
+      cnt[o0 + e] = hidx[e + 1] - i;
+      ent_row[o0 + e] = row;
+      q = ((unsigned)k << 16) | (unsigned)e;  // first position and entry, both < 2^13
+    }
+    k2[e] = q;
+  }
+  tk_bitonic(k2, n);
+  for (int r = tid; r < L; r += bd) pos[o0 + (k2[r] & 0xffffu)] = r;
+}
+
+__device__ __forceinline__ int tk_digit(int key, int shift) { return (key >> shift) & 255; }
+
+// hist[digit * nb + tile] <- entries of the tile with that digit
+__global__ __launch_bounds__(64) void tk_radix_hist_kernel(const int* __restrict__ key, const int* __restrict__ nnz_p, int shift,
+                                                          int* __restrict__ hist, int nb) {
+  __shared__ int c[256];
+  const int lane = threadIdx.x, nnz = *nnz_p;
+  for (int j = lane; j < 256; j += 64) c[j] = 0;
+  __syncthreads();
+  const long t0 = (long)blockIdx.x * TK_RADIX_TILE;
+  for (int q = 0; q < TK_RADIX_TILE; q += 64) {
+    const long i = t0 + q + lane;
+    if (i < nnz) atomicAdd(&c[tk_digit(key[i], shift)], 1);
+  }
+  __syncthreads();
+  for (int j = lane; j < 256; j += 64) hist[(long)j * nb + blockIdx.x] = c[j];
+}
+
+// hist scanned (digit-major): entry i of tile b goes to hist[digit][b] + its rank among the tile's earlier entries of the digit
+__global__ __launch_bounds__(64) void tk_radix_scatter_kernel(const int* __restrict__ key, const int* __restrict__ val,
+                                                             const int* __restrict__ nnz_p, int shift,
+                                                             const int* __restrict__ hist, int nb, int* __restrict__ key_out,
+                                                             int* __restrict__ val_out, const int* __restrict__ ent_row,
+                                                             int* __restrict__ row_out) {
+  __shared__ int run[256];
+  const int lane = threadIdx.x, nnz = *nnz_p;
+  for (int j = lane; j < 256; j += 64) run[j] = hist[(long)j * nb + blockIdx.x];
+  __syncthreads();
+  const long t0 = (long)blockIdx.x * TK_RADIX_TILE;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (int q = 0; q < TK_RADIX_TILE; q += 64) {
+    const long i = t0 + q + lane;
+    const bool live = i < nnz;
+    const int k = live ? key[i] : 0;
+    const int dg = tk_digit(k, shift);
+    unsigned long long peers = __ballot(live);
+#pragma unroll
+    for (int bit = 0; bit < 8; ++bit) {
+      const bool on = (dg >> bit) & 1;
+      const unsigned long long m = __ballot(live && on);
+      peers &= on ? m : ~m;
+    }
+    const int ahead = __popcll(peers & below);
+    const int p = live ? run[dg] + ahead : 0;
+    __syncthreads();
+    if (live && ahead == 0) run[dg] += __popcll(peers);  // one lane per digit present in the chunk
+    __syncthreads();
+    if (live && (unsigned)p < (unsigned)nnz) {
+      const int v = val ? val[i] : (int)i;
+      key_out[p] = k;
+      val_out[p] = v;
+      if (row_out) row_out[p] = ent_row[v];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void tk_postptr_kernel(const int* __restrict__ sorted_key, const int* __restrict__ nnz_p, int V,
+                                                        int* __restrict__ gpostptr) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t <= V) gpostptr[t] = tk_lower_bound(sorted_key, *nnz_p, t);
+}
+
+static long tk_align(long b) { return (b + 15) / 16 * 16; }
+
+struct TkLayout {
+  long tok_cap, nb_scan, nb_tab, nb_radix;
+  long low, docptr, blk, tok_start, tok_len, tok_slot, table, blk2, ent_row, ka, va, kb, vb, hist, scratch, bytes;
+};
+
+static long tk_default_slots(long n_bytes) { return 2 * (n_bytes / 3 + 1); }
+
+static TkLayout tk_layout(long n_bytes, long n_docs, long slots) {
+  TkLayout l;
+  l.tok_cap = n_bytes / 3 + 1;  // a token is two word bytes or more and a non-word byte (or the end of the buffer) behind them
+  l.nb_scan = (n_bytes + TK_SCAN_TILE - 1) / TK_SCAN_TILE;
+  l.nb_tab = (slots + 255) / 256;
+  l.nb_radix = (l.tok_cap + TK_RADIX_TILE - 1) / TK_RADIX_TILE;
+  long o = 0;
+  auto take = [&](long bytes) {
+    const long at = o;
+    o += tk_align(bytes);
+    return at;
+  };
+  l.low = take(n_bytes);
+  l.docptr = take(4 * (n_docs + 1));
+  l.blk = take(4 * l.nb_scan);
+  l.tok_start = take(4 * l.tok_cap);
+  l.tok_len = take(4 * l.tok_cap);
+  l.tok_slot = take(4 * l.tok_cap);
+  l.table = take(4 * slots);
+  l.blk2 = take(4 * l.nb_tab);
+  l.ent_row = take(4 * l.tok_cap);
+  l.ka = take(4 * l.tok_cap);
+  l.va = take(4 * l.tok_cap);
+  l.kb = take(4 * l.tok_cap);
+  l.vb = take(4 * l.tok_cap);
+  l.hist = take(4 * 256 * l.nb_radix);
+  l.scratch = take(16);
+  l.bytes = o;
+  return l;
+}
+
+static bool tk_sizes_ok(long n_bytes, long n_docs, long slots) {
+  return n_bytes >= 1 && n_bytes < (1l << 31) && n_docs >= 1 && n_docs <= n_bytes && slots >= 1 && slots < (1l << 31);
+}
+
+static size_t tk_rows_lds(int n) { return (size_t)tk_align(8l * n + 4l * n + 4 * 16 + 4l * (n + 1)); }
+
+}  // namespace mused
+
+using namespace mused;
+
+extern "C" {
+
+long mused_tokenise_ws_bytes(long n_bytes, long n_docs, long table_slots) {
+  const long slots = table_slots == 0 && n_bytes >= 1 ? tk_default_slots(n_bytes) : table_slots;
+  return tk_sizes_ok(n_bytes, n_docs, slots) ? tk_layout(n_bytes, n_docs, slots).bytes : -1;
+}
+
+int mused_tokenise_scan(const unsigned char* buf, long n_bytes, const int* docptr_host, long n_docs, long table_slots,
+                        int max_doc_tokens, int* voc_start, int* voc_len, long voc_cap, int* info, void* ws, long ws_bytes,
+                        void* stream) {
+  const long slots = table_slots == 0 && n_bytes >= 1 ? tk_default_slots(n_bytes) : table_slots;
+  MUSED_REQUIRE(tk_sizes_ok(n_bytes, n_docs, slots),
+                "mused_tokenise_scan: bad sizes (bytes=%ld in [1, 2^31), docs=%ld in [1, bytes], table slots=%ld in [1, 2^31))",
+                n_bytes, n_docs, table_slots);
+  MUSED_REQUIRE(buf && docptr_host && voc_start && voc_len && info, "mused_tokenise_scan: an array is missing");
+  MUSED_REQUIRE(((uintptr_t)buf & 15) == 0, "mused_tokenise_scan: the buffer must start on a 16-byte boundary");
+  MUSED_REQUIRE(docptr_host[0] == 0 && docptr_host[n_docs] == n_bytes,
+                "mused_tokenise_scan: docptr runs from %d to %d, not from 0 to the %ld bytes of the buffer", docptr_host[0],
+                docptr_host[n_docs], n_bytes);
+  for (long d = 0; d < n_docs; ++d)
+    MUSED_REQUIRE(docptr_host[d + 1] > docptr_host[d], "mused_tokenise_scan: document %ld is empty or docptr descends (a document "
+                  "holds at least its separator)", d);
+  MUSED_REQUIRE(max_doc_tokens >= 1 && max_doc_tokens <= TK_MAX_DOC_TOKENS,
+                "mused_tokenise_scan: max_doc_tokens=%d outside [1, %d] (one document is sorted in LDS)", max_doc_tokens,
+                TK_MAX_DOC_TOKENS);
+  const TkLayout l = tk_layout(n_bytes, n_docs, slots);
+  MUSED_REQUIRE(voc_cap >= 1, "mused_tokenise_scan: voc_cap=%ld", voc_cap);
+  MUSED_REQUIRE(ws && ws_bytes >= l.bytes && ((uintptr_t)ws & 15) == 0,
+                "mused_tokenise_scan: workspace of %ld bytes, need %ld (16-byte aligned)", ws_bytes, l.bytes);
+  hipStream_t st = (hipStream_t)stream;
+  char* w = reinterpret_cast<char*>(ws);
+  unsigned char* low = reinterpret_cast<unsigned char*>(w + l.low);
+  int* docptr = reinterpret_cast<int*>(w + l.docptr);
+  int* blk = reinterpret_cast<int*>(w + l.blk);
+  int* tok_start = reinterpret_cast<int*>(w + l.tok_start);
+  int* tok_len = reinterpret_cast<int*>(w + l.tok_len);
+  int* tok_slot = reinterpret_cast<int*>(w + l.tok_slot);
+  int* table = reinterpret_cast<int*>(w + l.table);
+  int* blk2 = reinterpret_cast<int*>(w + l.blk2);
+  MUSED_CHECK_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int), st));
+  MUSED_CHECK_HIP(hipMemsetAsync(table, 0xff, (size_t)slots * sizeof(int), st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(docptr, docptr_host, (size_t)(n_docs + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+  const int cap = (int)l.tok_cap;
+  hipLaunchKernelGGL(tk_scan_kernel<false>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, buf, n_bytes, low, blk,
+                     tok_start, tok_len, cap);
+  MUSED_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tk_blockscan_kernel, dim3(1), dim3(TK_BLOCKSCAN_THREADS), 0, st, blk, (int)l.nb_scan, info + 0);
+  MUSED_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tk_scan_kernel<true>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, low, n_bytes, low, blk,
+                     tok_start, tok_len, cap);
+  MUSED_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tk_docs_kernel, dim3(cdiv(n_docs, 256)), dim3(256), 0, st, docptr, (int)n_docs, tok_start, max_doc_tokens,
+                     info);
+  MUSED_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tk_insert_kernel, dim3(cdiv(l.tok_cap, 256)), dim3(256), 0, st, low, tok_start, tok_len, table, (int)slots,
+                     tok_slot, info);
+  MUSED_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tk_compact_kernel<false>, dim3((unsigned)l.nb_tab), dim3(256), 0, st, table, (int)slots, blk2, tok_start,
+                     tok_len, voc_start, voc_len, (int)(voc_cap < (1l << 31) ? voc_cap : (1l << 31) - 1));
+  MUSED_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tk_blockscan_kernel, dim3(1), dim3(TK_BLOCKSCAN_THREADS), 0, st, blk2, (int)l.nb_tab, info + 1);
+  MUSED_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tk_compact_kernel<true>, dim3((unsigned)l.nb_tab), dim3(256), 0, st, table, (int)slots, blk2, tok_start,
+                     tok_len, voc_start, voc_len, (int)(voc_cap < (1l << 31) ? voc_cap : (1l << 31) - 1));
+  MUSED_LAUNCH_CHECK();
+  return MUSED_OK;
+}
+
+int mused_tokenise_build(long n_bytes, long n_docs, long table_slots, int n_tokens, int n_terms, int doc_tokens,
+                         const int* rank, const int* vrow, int* doc_rowptr, int* term, int* cnt, int* pos, int* gpostptr,
+                         int* gpostrow, int* gpostent, int* info, void* ws, long ws_bytes, void* stream) {
+  const long slots = table_slots == 0 && n_bytes >= 1 ? tk_default_slots(n_bytes) : table_slots;
+  MUSED_REQUIRE(tk_sizes_ok(n_bytes, n_docs, slots),
+                "mused_tokenise_build: bad sizes (bytes=%ld in [1, 2^31), docs=%ld in [1, bytes], table slots=%ld in [1, 2^31))",
+                n_bytes, n_docs, table_slots);
+  const TkLayout l = tk_layout(n_bytes, n_docs, slots);
+  MUSED_REQUIRE(n_tokens >= 1 && n_tokens <= l.tok_cap && n_tokens <= slots && n_terms >= 1 && n_terms <= n_tokens &&
+                    n_terms < (1 << 24),
+                "mused_tokenise_build: %d tokens (at most %ld and the table's %ld slots), %d terms (at most 2^24 - 1: three "
+                "radix passes)", n_tokens, l.tok_cap, slots, n_terms);
+  MUSED_REQUIRE(doc_tokens >= 1 && doc_tokens <= TK_MAX_DOC_TOKENS && doc_tokens <= n_tokens,
+                "mused_tokenise_build: the longest document has %d tokens, outside [1, %d]", doc_tokens, TK_MAX_DOC_TOKENS);
+  MUSED_REQUIRE(rank && vrow && doc_rowptr && term && cnt && pos && gpostptr && gpostrow && gpostent && info,
+                "mused_tokenise_build: an array is missing");
+  MUSED_REQUIRE(ws && ws_bytes >= l.bytes && ((uintptr_t)ws & 15) == 0,
+                "mused_tokenise_build: workspace of %ld bytes, need %ld (16-byte aligned)", ws_bytes, l.bytes);
+  hipStream_t st = (hipStream_t)stream;
+  char* w = reinterpret_cast<char*>(ws);
+  int n = 1;
+  while (n < doc_tokens) n <<= 1;
+  const size_t lds = tk_rows_lds(n);
+  static std::once_flag once;
+  static hipError_t aerr = hipSuccess;
+  std::call_once(once, [&] {
+    CaptureLock lock(capture_mutex());
+    const int most = (int)tk_rows_lds(TK_MAX_DOC_TOKENS);
+    aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(tk_rows_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
+    if (aerr == hipSuccess)
+      aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(tk_rows_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
+  });
+  MUSED_CHECK_HIP(aerr);
+  TkRows a{reinterpret_cast<int*>(w + l.docptr), reinterpret_cast<int*>(w + l.tok_start), reinterpret_cast<int*>(w + l.tok_slot),
+           reinterpret_cast<int*>(w + l.table), rank, vrow, (int)n_docs, n_tokens, n_terms, (int)slots, n};
+  int* ent_row = reinterpret_cast<int*>(w + l.ent_row);
+  int* hist = reinterpret_cast<int*>(w + l.hist);
+  int* scratch = reinterpret_cast<int*>(w + l.scratch);
+  const int threads = n / 2 < 64 ? 64 : (n / 2 > 256 ? 256 : n / 2);
+  hipLaunchKernelGGL(tk_rows_kernel<false>, dim3((unsigned)n_docs), dim3(threads), lds, st, a, doc_rowptr, doc_rowptr, term, cnt,
+                     pos, ent_row, info);
+  MUSED_LAUNCH_CHECK();
+  // doc_rowptr[n_docs] <- the sum: the scan's total lands where the exclusive scan of n_docs + 1 counts would put it
+  hipLaunchKernelGGL(tk_blockscan_kernel, dim3(1), dim3(TK_BLOCKSCAN_THREADS), 0, st, doc_rowptr, (int)n_docs, doc_rowptr + n_docs);
+  MUSED_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tk_rows_kernel<true>, dim3((unsigned)n_docs), dim3(threads), lds, st, a, doc_rowptr, doc_rowptr, term, cnt,
+                     pos, ent_row, info);
+  MUSED_LAUNCH_CHECK();
+  const int* nnz_p = doc_rowptr + n_docs;  // at most n_tokens: the grids below cover that many
+  const int nb = cdiv(n_tokens, TK_RADIX_TILE);
+  int bits = 0;
+  while (bits < 24 && (1 << bits) < n_terms) ++bits;
+  const int passes = bits <= 8 ? 1 : (bits <= 16 ? 2 : 3);
+  int* kbuf[2] = {reinterpret_cast<int*>(w + l.ka), reinterpret_cast<int*>(w + l.kb)};
+  int* vbuf[2] = {reinterpret_cast<int*>(w + l.va), reinterpret_cast<int*>(w + l.vb)};
+  const int* kin = term;
+  const int* vin = nullptr;
+  for (int p = 0; p < passes; ++p) {
+    const bool last = p == passes - 1;
+    int* kout = kbuf[p & 1];
+    int* vout = last ? gpostent : vbuf[p & 1];
+    hipLaunchKernelGGL(tk_radix_hist_kernel, dim3(nb), dim3(64), 0, st, kin, nnz_p, 8 * p, hist, nb);
+    MUSED_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tk_blockscan_kernel, dim3(1), dim3(TK_BLOCKSCAN_THREADS), 0, st, hist, 256 * nb, scratch);
+    MUSED_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tk_radix_scatter_kernel, dim3(nb), dim3(64), 0, st, kin, vin, nnz_p, 8 * p, hist, nb, kout, vout, ent_row,
+                       last ? gpostrow : (int*)nullptr);
+    MUSED_LAUNCH_CHECK();
+    kin = kout;
+    vin = vout;
+  }
+  hipLaunchKernelGGL(tk_postptr_kernel, dim3(cdiv((long)n_terms + 1, 256)), dim3(256), 0, st, kin, nnz_p, n_terms, gpostptr);
+  MUSED_LAUNCH_CHECK();
+  return MUSED_OK;
+}
+
+}  // extern "C"

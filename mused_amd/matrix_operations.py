@@ -147,14 +147,15 @@ def _text_adjacency(data, k_basis, engine=None, sparse=None) -> _eng.Adjacency:
     bit for bit.
     data: a window of a tokenised corpus (mused_amd.text.TextWindow / TextCorpus) or the (n, 2) strings, which are
     tokenised as a corpus of their own.  The TF-IDF itself runs on the device (`_text_adjacency_device`) unless
-    MUSED_TEXT=host or the corpus is host-only (`_text_adjacency_host`: the same TfidfVectorizer call as the reference)."""
+    MUSED_TEXT=host or the corpus is host-only (`_text_adjacency_host`: the same TfidfVectorizer call as the reference).
+    MUSED_TOKENISE=device|host names the tokeniser of raw strings (`text.tokenise_for_device`)."""
     from . import text as _text
 
     if isinstance(data, _text.TextCorpus):
         data = data.window()
     if not text_on_device():
         return _text_adjacency_host(data.records if isinstance(data, _text.TextWindow) else data, k_basis, engine, sparse)
-    win = data if isinstance(data, _text.TextWindow) else _text.tokenise(data).window()
+    win = data if isinstance(data, _text.TextWindow) else _text.tokenise_for_device(data).window()
     if win.corpus.host_only:
         return _text_adjacency_host(win.records, k_basis, engine, sparse)
     return _text_adjacency_device(win, k_basis, engine, sparse)

@@ -547,7 +547,8 @@ class StreamPipeline:
             if t == "text" and mo.text_on_device():
                 # tokenised once for the whole stream; every window is a view of the corpus and its TF-IDF runs on the
                 # device (MUSED_TEXT=host: the strings stay as they are and every window is vectorised on the host)
-                dev.append(_text.tokenise(m))
+                # (MUSED_TOKENISE=device|host: which tokeniser, `text.tokenise_for_device`)
+                dev.append(_text.tokenise_for_device(m, self.eng.device))
                 continue
             a = np.asarray(m)
             # numeric modalities live on the device; other string records stay on the host
@@ -698,7 +699,7 @@ def batch_embedding(data_modalities, modality_types, reduced_dim, k_basis, seed,
             if len(m) != n:
                 raise ValueError(f"modality {i} has {len(m)} rows, modality 0 has {n}")
             if ty == "text" and mo.text_on_device() and not isinstance(m, (_text.TextCorpus, _text.TextWindow)):
-                m = _text.tokenise(m)   # the whole subset is one window of this corpus
+                m = _text.tokenise_for_device(m, eng.device)   # the whole subset is one window of this corpus
                 t = tick(f"tokenise[{i}]", t)
             adj = mo.adjacency_on_device(m, ty, k_basis, engine=eng)
             t = tick(f"knn[{i}:{ty or 'l2'}]", t)

@@ -4,10 +4,18 @@ of a corpus tokenised once, csrc/tfidf.hip -- and under MUSED_TEXT=host, the per
 path as a whole: the yardstick).  Both in one process, alternating window by window; every call ends in a device
 synchronisation.  The one-off tokenisation of the corpus is reported separately ("tokenise_s").
 
+--tokenise: the two tokenisers (text.tokenise on the host, text.tokenise_on_device: host preparation, both calls of
+csrc/tokenise.hip, the host's sort of the vocabulary) on the same rows in one process, alternating, each call ended by a
+device synchronisation; median of --tok-repeat (>= 5) after one warm-up each.  Shapes: --tok-rows rows of text_stream
+and of sparse_text_stream, the --batch rows of text_stream, one window of --tok-window rows of each.  The corpora are
+compared field for field once per shape.  No window is timed in this mode (kernel times: run it under
+`rocprofv3 --kernel-trace --stats -- python tools/text_time.py --tokenise ...`).
+
 Stream shapes: 12 hopping windows (step W / 4) of synth.text_stream / synth.sparse_text_stream, median of the 12; the
 sparse stream also with text_sparse=True.  Batch shape: the whole text_stream subset as one window (best of --repeat).
 
     python tools/text_time.py [--shapes 2000,10000] [--k 50] [--batch 150000] [--repeat 2] [--out FILE]
+    python tools/text_time.py --tokenise [--tok-rows 37500] [--tok-window 2000] [--batch 150000] [--tok-repeat 7]
 """
 import argparse
 import json
@@ -37,6 +45,35 @@ def one(mode, x, k, eng, sparse):
     return timed(lambda: mo.adjacency_on_device(x, "text", k, engine=eng, text_sparse=sparse).mask)
 
 
+def tokenise_times(a, emit):
+    import numpy as np
+
+    from mused_amd import synth, text
+
+    shapes = [("text_stream", a.tok_rows), ("sparse_text_stream", a.tok_rows), ("text_stream", a.tok_window),
+              ("sparse_text_stream", a.tok_window)] + ([("text_stream", a.batch)] if a.batch > 0 else [])
+    for stream, n in shapes:
+        rec = getattr(synth, stream)(n, 0)[0]
+        fallbacks = text.tokenise_fallbacks
+        s = {"device": [], "host": []}
+        same = None
+        for r in range(a.tok_repeat + 1):   # round 0 warms both up (code objects, the allocator's blocks)
+            dev, td = timed(lambda: text.tokenise_on_device(rec))
+            host, th = timed(lambda: text.tokenise(rec))
+            if r == 0:
+                same = (dev.vocabulary == host.vocabulary and
+                        all(np.array_equal(getattr(dev, f), getattr(host, f)) for f in text._DEVICE_FIELDS))
+            else:
+                s["device"].append(td)
+                s["host"].append(th)
+            del dev, host
+        emit({"tokenise": stream, "rows": n, "bytes": int(text.corpus_buffer(*text._valid_rows(rec))[1][-1]),
+              "repeat": a.tok_repeat, "device_s_median": round(statistics.median(s["device"]), 4),
+              "host_s_median": round(statistics.median(s["host"]), 4),
+              "device_s": [round(x, 4) for x in s["device"]], "host_s": [round(x, 4) for x in s["host"]],
+              "fallbacks": text.tokenise_fallbacks - fallbacks, "corpora_equal": same})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="2000,10000")
@@ -45,6 +82,10 @@ def main():
     ap.add_argument("--batch", type=int, default=150000)
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--out", default="")
+    ap.add_argument("--tokenise", action="store_true")
+    ap.add_argument("--tok-rows", type=int, default=37500)
+    ap.add_argument("--tok-window", type=int, default=2000)
+    ap.add_argument("--tok-repeat", type=int, default=7)
     a = ap.parse_args()
 
     import torch
@@ -62,6 +103,10 @@ def main():
                 f.write("\n".join(json.dumps(r) for r in lines) + "\n")
 
     torch.cuda.init()
+    if a.tokenise:
+        if a.tok_repeat < 5:
+            ap.error("--tok-repeat: at least 5")
+        return tokenise_times(a, emit)
     for W in (int(x) for x in a.shapes.split(",") if x):
         step = W // 4
         N = W + step * (a.windows - 1)
