@@ -210,6 +210,33 @@ int mused_tokenise_build(long n_bytes, long n_docs, long table_slots, int n_toke
                          const int* rank, const int* vrow, int* doc_rowptr, int* term, int* cnt, int* pos, int* gpostptr,
                          int* gpostrow, int* gpostent, int* info, void* ws, long ws_bytes, void* stream);
 
+/* ---- a2, "text": the tokenised pass for text that is not pure ASCII (mused_amd/text.py: tokenise_codepoints_on_device),
+ * csrc/tokenise.hip; specification: mused_amd/tokens.py, "code points" -- the same analyser as a rule on CODE POINTS: a
+ * token is a maximal run of word code points of length >= 2 in code points, a run also ends behind a code point whose
+ * lower case expands (U+0130), a token is the sequence of its lowered code points; vocabulary in code-point order.
+ * The three entries mirror the byte entries above argument for argument; what differs:
+ * Input: buf (DEVICE, n_cp uint32 code points, n_cp in [1, 2^30), 16-byte aligned), laid out as the byte buffer is, one
+ *   element a code point, every U+03A3 already replaced by the host with its lower case in context (the final-sigma
+ *   rule is not restated on the device); docptr_host in ELEMENTS.
+ *   cls (DEVICE, n_cls uint32 in [128, 0x110000], read-only during the call, uploaded before it): the class table, entry
+ *   c = lowered code point of c in bits 0..20 | bit 21 "word code point" | bit 22 "the run ends behind it".  The caller
+ *   builds it from its own Unicode data (tokens.class_table()), so no Unicode version is compiled into the library.
+ *   Code points below 128 take the rule of the byte entries, which entries 0..127 of a correct table equal; a code
+ *   point >= n_cls is no word code point.
+ * mused_tokenise_cp_scan: info, voc_start / voc_len (ELEMENT spans; capacity n_cp / 2 + 1 always suffices: two tokens
+ *   may touch, "aİbİ" holds "ai" and "bi"), table_slots (0 = the default 2 * (n_cp / 2 + 1)), max_doc_tokens, flags
+ *   and HOST READS as mused_tokenise_scan.  The host gathers the V spans from its own buffer through the same table.
+ * mused_tokenise_cp_build: as mused_tokenise_build, n_cp in place of n_bytes, on the workspace the cp_scan call left.
+ * ws: mused_tokenise_cp_ws_bytes(n_cp, n_docs, table_slots) bytes, 16-byte aligned (-1 for sizes out of range).
+ * Bad arguments: MUSED_ERR_ARG, nothing enqueued, outputs untouched. */
+long mused_tokenise_cp_ws_bytes(long n_cp, long n_docs, long table_slots);
+int mused_tokenise_cp_scan(const unsigned* buf, long n_cp, const unsigned* cls, long n_cls, const int* docptr_host, long n_docs,
+                           long table_slots, int max_doc_tokens, int* voc_start, int* voc_len, long voc_cap, int* info, void* ws,
+                           long ws_bytes, void* stream);
+int mused_tokenise_cp_build(long n_cp, long n_docs, long table_slots, int n_tokens, int n_terms, int doc_tokens, const int* rank,
+                            const int* vrow, int* doc_rowptr, int* term, int* cnt, int* pos, int* gpostptr, int* gpostrow,
+                            int* gpostent, int* info, void* ws, long ws_bytes, void* stream);
+
 /* ---- a3 / a4: adjacency bitmasks -------------------------------------------------------------
  * An adjacency is n rows x words uint64 (words >= ceil(n/64)); bit j of row i <=> A[i][j] = 1. */
 

@@ -52,6 +52,9 @@ _PROTOS = {
     "mused_tokenise_ws_bytes": (_l, [_l, _l, _l]),
     "mused_tokenise_scan": (_i, [_vp, _l, _vp, _l, _l, _i, _vp, _vp, _l, _vp, _vp, _l, _vp]),
     "mused_tokenise_build": (_i, [_l, _l, _l, _i, _i, _i] + [_vp] * 10 + [_vp, _l, _vp]),
+    "mused_tokenise_cp_ws_bytes": (_l, [_l, _l, _l]),
+    "mused_tokenise_cp_scan": (_i, [_vp, _l, _vp, _l, _vp, _l, _l, _i, _vp, _vp, _l, _vp, _vp, _l, _vp]),
+    "mused_tokenise_cp_build": (_i, [_l, _l, _l, _i, _i, _i] + [_vp] * 10 + [_vp, _l, _vp]),
     "mused_adj_fuse": (_i, [C.POINTER(_vp), _i, _i, _i, _vp, _vp]),
     "mused_adj_degrees": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mused_adj_csr_fill": (_i, [_vp, _i, _i, _vp, _vp, _vp]),

@@ -30,6 +30,20 @@
 //              of the digit-major table, scatter in tile order -- one wave per tile, ranks inside a chunk of 64 from
 //              ballots): entries are row-major, so rows ascend inside a term.  gpostptr[t] = first sorted entry >= t.
 // No float anywhere and no result that depends on arrival order: two calls on the same input give identical bytes.
+//
+// Text that is not pure ASCII takes the same steps on CODE POINTS (mused_tokenise_cp_scan / _cp_build; the rule:
+// mused_amd/tokens.py, "code points").  The corpus is one uint32 per code point, and the caller hands in a class table
+// of one uint32 per code point -- lowered code point in the low 21 bits, TK_CP_WORD, TK_CP_END -- so no Unicode version
+// is compiled in.  Two kernels are siblings of the byte ones, everything from `docs` onward is shared:
+//     scan     8 code points per thread (two 16-byte loads), 2048 per workgroup; the count pass writes the table entry of
+//              every element to `low` (below 128 the ALU rule of the byte path, which the table's first 128 entries
+//              equal), so the write pass, the run walk and the insert kernel read flags and lowered code points from
+//              `low` and never the table.  A token starts at a word element whose predecessor is no word element or
+//              ends the run (U+0130: a word code point that lower-cases to 'i' and a combining dot, which is no word
+//              code point), that does not end the run itself and has a word element behind it; its owner walks on
+//              while the current element does not end the run and the next one is a word element.
+//     insert   hashes and compares the 21-bit lowered code points of the two tokens, flags masked off
+// Two tokens may touch ("aİbİ" holds "ai" and "bi"), so a buffer of n code points holds up to n / 2 tokens.
 #include "common.h"
 #include "internal.h"
 
@@ -198,6 +212,124 @@ __global__ __launch_bounds__(256) void tk_insert_kernel(const unsigned char* __r
   for (int probe = 0; probe < slots; ++probe) {
     const int old = atomicCAS(&table[slot], -1, t);
     if (old == -1 || (tok_len[old] == len && tk_same_bytes(low, tok_start[old], s, len))) {
+      tok_slot[t] = slot;
+      return;
+    }
+    slot = slot + 1 == slots ? 0 : slot + 1;
+  }
+}
+
+// ---- code points: one uint32 an element; an element of `low` is its class-table entry ----
+constexpr int TK_CP_PER_THREAD = 8;
+constexpr int TK_CP_TILE = TK_SCAN_THREADS * TK_CP_PER_THREAD;  // code points per workgroup of the scan
+constexpr unsigned TK_CP_MASK = 0x1fffffu;  // the lowered code point
+constexpr unsigned TK_CP_WORD = 1u << 21;
+constexpr unsigned TK_CP_END = 1u << 22;    // a word code point behind which the run ends
+constexpr long TK_CP_TABLE_MAX = 0x110000;
+
+__device__ __forceinline__ unsigned tk_cp_entry(unsigned c, const unsigned* __restrict__ cls, unsigned n_cls) {
+  if (c < 128u) return (unsigned)tk_lower(c) | (tk_is_word(c) ? TK_CP_WORD : 0u);
+  return c < n_cls ? cls[c] : (unsigned)TK_BLANK;  // beyond the table: no word code point
+}
+
+// WRITE = false: src = code points; table entries -> low, token starts per block -> blk[block]
+// WRITE = true:  src = low; blk holds the exclusive scan of those counts; tok_start / tok_len in text order
+template <bool WRITE>
+__global__ __launch_bounds__(TK_SCAN_THREADS) void tk_cp_scan_kernel(const unsigned* __restrict__ src, long n,
+                                                                    const unsigned* __restrict__ cls, unsigned n_cls,
+                                                                    unsigned* __restrict__ low, int* __restrict__ blk,
+                                                                    int* __restrict__ tok_start, int* __restrict__ tok_len,
+                                                                    int tok_cap) {
+  __shared__ int ws[16];
+  constexpr int P = TK_CP_PER_THREAD;
+  const long base = (long)blockIdx.x * TK_CP_TILE + threadIdx.x * P;
+  const unsigned blank = TK_BLANK;  // as a code point and as a table entry: no word element
+  unsigned e[P + 2];                // the element before, P elements, the element behind
+  if (base + P <= n) {
+#pragma unroll
+    for (int q = 0; q < P / 4; ++q) {
+      const uint4 v = *reinterpret_cast<const uint4*>(src + base + 4 * q);
+      e[4 * q + 1] = v.x;
+      e[4 * q + 2] = v.y;
+      e[4 * q + 3] = v.z;
+      e[4 * q + 4] = v.w;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < P; ++j) e[j + 1] = base + j < n ? src[base + j] : blank;
+  }
+  e[0] = (base > 0 && base - 1 < n) ? src[base - 1] : blank;
+  e[P + 1] = base + P < n ? src[base + P] : blank;
+  if (!WRITE) {
+#pragma unroll
+    for (int j = 0; j < P + 2; ++j) e[j] = tk_cp_entry(e[j], cls, n_cls);
+    if (base + P <= n) {
+#pragma unroll
+      for (int q = 0; q < P / 4; ++q)
+        *reinterpret_cast<uint4*>(low + base + 4 * q) = make_uint4(e[4 * q + 1], e[4 * q + 2], e[4 * q + 3], e[4 * q + 4]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < P; ++j)
+        if (base + j < n) low[base + j] = e[j + 1];
+    }
+  }
+  unsigned wbits = 0, cbits = 0;  // bit j: e[j] is a word element / is one and the run goes on behind it
+#pragma unroll
+  for (int j = 0; j < P + 2; ++j) {
+    wbits |= (e[j] & TK_CP_WORD) ? (1u << j) : 0u;
+    cbits |= (e[j] & (TK_CP_WORD | TK_CP_END)) == TK_CP_WORD ? (1u << j) : 0u;
+  }
+  // bit j of starts: element base + j goes on, the one before it does not, the one behind it is a word element
+  const unsigned starts = ((cbits >> 1) & ~cbits & (wbits >> 2)) & ((1u << P) - 1u);
+  const int mine = __popc(starts);
+  int total;
+  const int before = tk_excl_scan(mine, ws, total);
+  if (!WRITE) {
+    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    return;
+  }
+  int o = blk[blockIdx.x] + before;
+  unsigned s = starts;
+  while (s) {
+    const int j = __ffs(s) - 1;
+    s &= s - 1;
+    long last = base + j + 1;  // the run holds elements base + j and base + j + 1
+    while (!(src[last] & TK_CP_END) && last + 1 < n && (src[last + 1] & TK_CP_WORD)) ++last;
+    if (o < tok_cap) {
+      tok_start[o] = (int)(base + j);
+      tok_len[o] = (int)(last + 1 - (base + j));
+    }
+    ++o;
+  }
+}
+
+__device__ __forceinline__ bool tk_cp_same(const unsigned* __restrict__ low, int s0, int s1, int len) {
+  for (int i = 0; i < len; ++i)
+    if ((low[s0 + i] ^ low[s1 + i]) & TK_CP_MASK) return false;
+  return true;
+}
+
+// tk_insert_kernel on code points: identity is the sequence of ALL 21 bits of the lowered code points
+__global__ __launch_bounds__(256) void tk_cp_insert_kernel(const unsigned* __restrict__ low, const int* __restrict__ tok_start,
+                                                          const int* __restrict__ tok_len, int* __restrict__ table, int slots,
+                                                          int* __restrict__ tok_slot, int* __restrict__ info) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const int T = info[0];
+  if (T > slots) {  // a table that cannot hold every token distinct: the probe loop would not end
+    if (t == 0) atomicOr(&info[2], TK_FLAG_TABLE);
+    return;
+  }
+  if (t >= T) return;
+  const int s = tok_start[t], len = tok_len[t];
+  unsigned h = 2166136261u;  // FNV-1a over whole code points, then a finaliser
+  for (int i = 0; i < len; ++i) h = (h ^ (low[s + i] & TK_CP_MASK)) * 16777619u;
+  h ^= h >> 16;
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  int slot = (int)(h % (unsigned)slots);
+  for (int probe = 0; probe < slots; ++probe) {
+    const int old = atomicCAS(&table[slot], -1, t);
+    if (old == -1 || (tok_len[old] == len && tk_cp_same(low, tok_start[old], s, len))) {
       tok_slot[t] = slot;
       return;
     }
@@ -392,10 +524,11 @@ struct TkLayout {
 
 static long tk_default_slots(long n_bytes) { return 2 * (n_bytes / 3 + 1); }
 
-static TkLayout tk_layout(long n_bytes, long n_docs, long slots) {
+// n elements of `elem` bytes, at most tok_cap tokens, `tile` elements per workgroup of the scan
+static TkLayout tk_layout_of(long n, long n_docs, long slots, long elem, long tok_cap, long tile) {
   TkLayout l;
-  l.tok_cap = n_bytes / 3 + 1;  // a token is two word bytes or more and a non-word byte (or the end of the buffer) behind them
-  l.nb_scan = (n_bytes + TK_SCAN_TILE - 1) / TK_SCAN_TILE;
+  l.tok_cap = tok_cap;
+  l.nb_scan = (n + tile - 1) / tile;
   l.nb_tab = (slots + 255) / 256;
   l.nb_radix = (l.tok_cap + TK_RADIX_TILE - 1) / TK_RADIX_TILE;
   long o = 0;
@@ -404,7 +537,7 @@ static TkLayout tk_layout(long n_bytes, long n_docs, long slots) {
     o += tk_align(bytes);
     return at;
   };
-  l.low = take(n_bytes);
+  l.low = take(elem * n);
   l.docptr = take(4 * (n_docs + 1));
   l.blk = take(4 * l.nb_scan);
   l.tok_start = take(4 * l.tok_cap);
@@ -423,72 +556,45 @@ static TkLayout tk_layout(long n_bytes, long n_docs, long slots) {
   return l;
 }
 
+// a token is two word bytes or more and a non-word byte (or the end of the buffer) behind them
+static TkLayout tk_layout(long n_bytes, long n_docs, long slots) {
+  return tk_layout_of(n_bytes, n_docs, slots, 1, n_bytes / 3 + 1, TK_SCAN_TILE);
+}
+
+// code points: two tokens may touch, so a token is two elements or more and nothing else
+static long tk_cp_default_slots(long n_cp) { return 2 * (n_cp / 2 + 1); }
+static TkLayout tk_cp_layout(long n_cp, long n_docs, long slots) {
+  return tk_layout_of(n_cp, n_docs, slots, 4, n_cp / 2 + 1, TK_CP_TILE);
+}
+// below 2^30 code points every element offset, token count and block count is an int and the workspace stays below 2^36 bytes
+static bool tk_cp_sizes_ok(long n_cp, long n_docs, long slots) {
+  return n_cp >= 1 && n_cp < (1l << 30) && n_docs >= 1 && n_docs <= n_cp && slots >= 1 && slots < (1l << 31);
+}
+
 static bool tk_sizes_ok(long n_bytes, long n_docs, long slots) {
   return n_bytes >= 1 && n_bytes < (1l << 31) && n_docs >= 1 && n_docs <= n_bytes && slots >= 1 && slots < (1l << 31);
 }
 
 static size_t tk_rows_lds(int n) { return (size_t)tk_align(8l * n + 4l * n + 4 * 16 + 4l * (n + 1)); }
 
-}  // namespace mused
-
-using namespace mused;
-
-extern "C" {
-
-long mused_tokenise_ws_bytes(long n_bytes, long n_docs, long table_slots) {
-  const long slots = table_slots == 0 && n_bytes >= 1 ? tk_default_slots(n_bytes) : table_slots;
-  return tk_sizes_ok(n_bytes, n_docs, slots) ? tk_layout(n_bytes, n_docs, slots).bytes : -1;
-}
-
-int mused_tokenise_scan(const unsigned char* buf, long n_bytes, const int* docptr_host, long n_docs, long table_slots,
-                        int max_doc_tokens, int* voc_start, int* voc_len, long voc_cap, int* info, void* ws, long ws_bytes,
-                        void* stream) {
-  const long slots = table_slots == 0 && n_bytes >= 1 ? tk_default_slots(n_bytes) : table_slots;
-  MUSED_REQUIRE(tk_sizes_ok(n_bytes, n_docs, slots),
-                "mused_tokenise_scan: bad sizes (bytes=%ld in [1, 2^31), docs=%ld in [1, bytes], table slots=%ld in [1, 2^31))",
-                n_bytes, n_docs, table_slots);
-  MUSED_REQUIRE(buf && docptr_host && voc_start && voc_len && info, "mused_tokenise_scan: an array is missing");
-  MUSED_REQUIRE(((uintptr_t)buf & 15) == 0, "mused_tokenise_scan: the buffer must start on a 16-byte boundary");
-  MUSED_REQUIRE(docptr_host[0] == 0 && docptr_host[n_docs] == n_bytes,
-                "mused_tokenise_scan: docptr runs from %d to %d, not from 0 to the %ld bytes of the buffer", docptr_host[0],
-                docptr_host[n_docs], n_bytes);
-  for (long d = 0; d < n_docs; ++d)
-    MUSED_REQUIRE(docptr_host[d + 1] > docptr_host[d], "mused_tokenise_scan: document %ld is empty or docptr descends (a document "
-                  "holds at least its separator)", d);
-  MUSED_REQUIRE(max_doc_tokens >= 1 && max_doc_tokens <= TK_MAX_DOC_TOKENS,
-                "mused_tokenise_scan: max_doc_tokens=%d outside [1, %d] (one document is sorted in LDS)", max_doc_tokens,
-                TK_MAX_DOC_TOKENS);
-  const TkLayout l = tk_layout(n_bytes, n_docs, slots);
-  MUSED_REQUIRE(voc_cap >= 1, "mused_tokenise_scan: voc_cap=%ld", voc_cap);
-  MUSED_REQUIRE(ws && ws_bytes >= l.bytes && ((uintptr_t)ws & 15) == 0,
-                "mused_tokenise_scan: workspace of %ld bytes, need %ld (16-byte aligned)", ws_bytes, l.bytes);
-  hipStream_t st = (hipStream_t)stream;
-  char* w = reinterpret_cast<char*>(ws);
-  unsigned char* low = reinterpret_cast<unsigned char*>(w + l.low);
+// what follows the scan on either kind of element: docs, insert, compact (the vocabulary's spans and provisional ids)
+static int tk_vocab_launch(const TkLayout& l, char* w, bool cp, long n_docs, long slots, int max_doc_tokens, int* voc_start,
+                           int* voc_len, long voc_cap, int* info, hipStream_t st) {
   int* docptr = reinterpret_cast<int*>(w + l.docptr);
-  int* blk = reinterpret_cast<int*>(w + l.blk);
   int* tok_start = reinterpret_cast<int*>(w + l.tok_start);
   int* tok_len = reinterpret_cast<int*>(w + l.tok_len);
   int* tok_slot = reinterpret_cast<int*>(w + l.tok_slot);
   int* table = reinterpret_cast<int*>(w + l.table);
   int* blk2 = reinterpret_cast<int*>(w + l.blk2);
-  MUSED_CHECK_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int), st));
-  MUSED_CHECK_HIP(hipMemsetAsync(table, 0xff, (size_t)slots * sizeof(int), st));
-  MUSED_CHECK_HIP(hipMemcpyAsync(docptr, docptr_host, (size_t)(n_docs + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-  const int cap = (int)l.tok_cap;
-  hipLaunchKernelGGL(tk_scan_kernel<false>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, buf, n_bytes, low, blk,
-                     tok_start, tok_len, cap);
-  MUSED_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tk_blockscan_kernel, dim3(1), dim3(TK_BLOCKSCAN_THREADS), 0, st, blk, (int)l.nb_scan, info + 0);
-  MUSED_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tk_scan_kernel<true>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, low, n_bytes, low, blk,
-                     tok_start, tok_len, cap);
-  MUSED_LAUNCH_CHECK();
   hipLaunchKernelGGL(tk_docs_kernel, dim3(cdiv(n_docs, 256)), dim3(256), 0, st, docptr, (int)n_docs, tok_start, max_doc_tokens,
                      info);
   MUSED_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tk_insert_kernel, dim3(cdiv(l.tok_cap, 256)), dim3(256), 0, st, low, tok_start, tok_len, table, (int)slots,
-                     tok_slot, info);
+  if (cp)
+    hipLaunchKernelGGL(tk_cp_insert_kernel, dim3(cdiv(l.tok_cap, 256)), dim3(256), 0, st, reinterpret_cast<const unsigned*>(w + l.low),
+                       tok_start, tok_len, table, (int)slots, tok_slot, info);
+  else
+    hipLaunchKernelGGL(tk_insert_kernel, dim3(cdiv(l.tok_cap, 256)), dim3(256), 0, st,
+                       reinterpret_cast<const unsigned char*>(w + l.low), tok_start, tok_len, table, (int)slots, tok_slot, info);
   MUSED_LAUNCH_CHECK();
   hipLaunchKernelGGL(tk_compact_kernel<false>, dim3((unsigned)l.nb_tab), dim3(256), 0, st, table, (int)slots, blk2, tok_start,
                      tok_len, voc_start, voc_len, (int)(voc_cap < (1l << 31) ? voc_cap : (1l << 31) - 1));
@@ -501,24 +607,10 @@ int mused_tokenise_scan(const unsigned char* buf, long n_bytes, const int* docpt
   return MUSED_OK;
 }
 
-int mused_tokenise_build(long n_bytes, long n_docs, long table_slots, int n_tokens, int n_terms, int doc_tokens,
-                         const int* rank, const int* vrow, int* doc_rowptr, int* term, int* cnt, int* pos, int* gpostptr,
-                         int* gpostrow, int* gpostent, int* info, void* ws, long ws_bytes, void* stream) {
-  const long slots = table_slots == 0 && n_bytes >= 1 ? tk_default_slots(n_bytes) : table_slots;
-  MUSED_REQUIRE(tk_sizes_ok(n_bytes, n_docs, slots),
-                "mused_tokenise_build: bad sizes (bytes=%ld in [1, 2^31), docs=%ld in [1, bytes], table slots=%ld in [1, 2^31))",
-                n_bytes, n_docs, table_slots);
-  const TkLayout l = tk_layout(n_bytes, n_docs, slots);
-  MUSED_REQUIRE(n_tokens >= 1 && n_tokens <= l.tok_cap && n_tokens <= slots && n_terms >= 1 && n_terms <= n_tokens &&
-                    n_terms < (1 << 24),
-                "mused_tokenise_build: %d tokens (at most %ld and the table's %ld slots), %d terms (at most 2^24 - 1: three "
-                "radix passes)", n_tokens, l.tok_cap, slots, n_terms);
-  MUSED_REQUIRE(doc_tokens >= 1 && doc_tokens <= TK_MAX_DOC_TOKENS && doc_tokens <= n_tokens,
-                "mused_tokenise_build: the longest document has %d tokens, outside [1, %d]", doc_tokens, TK_MAX_DOC_TOKENS);
-  MUSED_REQUIRE(rank && vrow && doc_rowptr && term && cnt && pos && gpostptr && gpostrow && gpostent && info,
-                "mused_tokenise_build: an array is missing");
-  MUSED_REQUIRE(ws && ws_bytes >= l.bytes && ((uintptr_t)ws & 15) == 0,
-                "mused_tokenise_build: workspace of %ld bytes, need %ld (16-byte aligned)", ws_bytes, l.bytes);
+// rows and postings: nothing here reads text, so bytes and code points share it
+static int tk_build_launch(const TkLayout& l, long n_docs, long slots, int n_tokens, int n_terms, int doc_tokens, const int* rank,
+                           const int* vrow, int* doc_rowptr, int* term, int* cnt, int* pos, int* gpostptr, int* gpostrow,
+                           int* gpostent, int* info, void* ws, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   char* w = reinterpret_cast<char*>(ws);
   int n = 1;
@@ -575,6 +667,157 @@ int mused_tokenise_build(long n_bytes, long n_docs, long table_slots, int n_toke
   hipLaunchKernelGGL(tk_postptr_kernel, dim3(cdiv((long)n_terms + 1, 256)), dim3(256), 0, st, kin, nnz_p, n_terms, gpostptr);
   MUSED_LAUNCH_CHECK();
   return MUSED_OK;
+}
+
+}  // namespace mused
+
+using namespace mused;
+
+extern "C" {
+
+long mused_tokenise_ws_bytes(long n_bytes, long n_docs, long table_slots) {
+  const long slots = table_slots == 0 && n_bytes >= 1 ? tk_default_slots(n_bytes) : table_slots;
+  return tk_sizes_ok(n_bytes, n_docs, slots) ? tk_layout(n_bytes, n_docs, slots).bytes : -1;
+}
+
+int mused_tokenise_scan(const unsigned char* buf, long n_bytes, const int* docptr_host, long n_docs, long table_slots,
+                        int max_doc_tokens, int* voc_start, int* voc_len, long voc_cap, int* info, void* ws, long ws_bytes,
+                        void* stream) {
+  const long slots = table_slots == 0 && n_bytes >= 1 ? tk_default_slots(n_bytes) : table_slots;
+  MUSED_REQUIRE(tk_sizes_ok(n_bytes, n_docs, slots),
+                "mused_tokenise_scan: bad sizes (bytes=%ld in [1, 2^31), docs=%ld in [1, bytes], table slots=%ld in [1, 2^31))",
+                n_bytes, n_docs, table_slots);
+  MUSED_REQUIRE(buf && docptr_host && voc_start && voc_len && info, "mused_tokenise_scan: an array is missing");
+  MUSED_REQUIRE(((uintptr_t)buf & 15) == 0, "mused_tokenise_scan: the buffer must start on a 16-byte boundary");
+  MUSED_REQUIRE(docptr_host[0] == 0 && docptr_host[n_docs] == n_bytes,
+                "mused_tokenise_scan: docptr runs from %d to %d, not from 0 to the %ld bytes of the buffer", docptr_host[0],
+                docptr_host[n_docs], n_bytes);
+  for (long d = 0; d < n_docs; ++d)
+    MUSED_REQUIRE(docptr_host[d + 1] > docptr_host[d], "mused_tokenise_scan: document %ld is empty or docptr descends (a document "
+                  "holds at least its separator)", d);
+  MUSED_REQUIRE(max_doc_tokens >= 1 && max_doc_tokens <= TK_MAX_DOC_TOKENS,
+                "mused_tokenise_scan: max_doc_tokens=%d outside [1, %d] (one document is sorted in LDS)", max_doc_tokens,
+                TK_MAX_DOC_TOKENS);
+  const TkLayout l = tk_layout(n_bytes, n_docs, slots);
+  MUSED_REQUIRE(voc_cap >= 1, "mused_tokenise_scan: voc_cap=%ld", voc_cap);
+  MUSED_REQUIRE(ws && ws_bytes >= l.bytes && ((uintptr_t)ws & 15) == 0,
+                "mused_tokenise_scan: workspace of %ld bytes, need %ld (16-byte aligned)", ws_bytes, l.bytes);
+  hipStream_t st = (hipStream_t)stream;
+  char* w = reinterpret_cast<char*>(ws);
+  unsigned char* low = reinterpret_cast<unsigned char*>(w + l.low);
+  int* docptr = reinterpret_cast<int*>(w + l.docptr);
+  int* blk = reinterpret_cast<int*>(w + l.blk);
+  int* tok_start = reinterpret_cast<int*>(w + l.tok_start);
+  int* tok_len = reinterpret_cast<int*>(w + l.tok_len);
+  int* table = reinterpret_cast<int*>(w + l.table);
+  MUSED_CHECK_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int), st));
+  MUSED_CHECK_HIP(hipMemsetAsync(table, 0xff, (size_t)slots * sizeof(int), st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(docptr, docptr_host, (size_t)(n_docs + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+  const int cap = (int)l.tok_cap;
+  hipLaunchKernelGGL(tk_scan_kernel<false>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, buf, n_bytes, low, blk,
+                     tok_start, tok_len, cap);
+  MUSED_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tk_blockscan_kernel, dim3(1), dim3(TK_BLOCKSCAN_THREADS), 0, st, blk, (int)l.nb_scan, info + 0);
+  MUSED_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tk_scan_kernel<true>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, low, n_bytes, low, blk,
+                     tok_start, tok_len, cap);
+  MUSED_LAUNCH_CHECK();
+  return tk_vocab_launch(l, w, false, n_docs, slots, max_doc_tokens, voc_start, voc_len, voc_cap, info, st);
+}
+
+int mused_tokenise_build(long n_bytes, long n_docs, long table_slots, int n_tokens, int n_terms, int doc_tokens,
+                         const int* rank, const int* vrow, int* doc_rowptr, int* term, int* cnt, int* pos, int* gpostptr,
+                         int* gpostrow, int* gpostent, int* info, void* ws, long ws_bytes, void* stream) {
+  const long slots = table_slots == 0 && n_bytes >= 1 ? tk_default_slots(n_bytes) : table_slots;
+  MUSED_REQUIRE(tk_sizes_ok(n_bytes, n_docs, slots),
+                "mused_tokenise_build: bad sizes (bytes=%ld in [1, 2^31), docs=%ld in [1, bytes], table slots=%ld in [1, 2^31))",
+                n_bytes, n_docs, table_slots);
+  const TkLayout l = tk_layout(n_bytes, n_docs, slots);
+  MUSED_REQUIRE(n_tokens >= 1 && n_tokens <= l.tok_cap && n_tokens <= slots && n_terms >= 1 && n_terms <= n_tokens &&
+                    n_terms < (1 << 24),
+                "mused_tokenise_build: %d tokens (at most %ld and the table's %ld slots), %d terms (at most 2^24 - 1: three "
+                "radix passes)", n_tokens, l.tok_cap, slots, n_terms);
+  MUSED_REQUIRE(doc_tokens >= 1 && doc_tokens <= TK_MAX_DOC_TOKENS && doc_tokens <= n_tokens,
+                "mused_tokenise_build: the longest document has %d tokens, outside [1, %d]", doc_tokens, TK_MAX_DOC_TOKENS);
+  MUSED_REQUIRE(rank && vrow && doc_rowptr && term && cnt && pos && gpostptr && gpostrow && gpostent && info,
+                "mused_tokenise_build: an array is missing");
+  MUSED_REQUIRE(ws && ws_bytes >= l.bytes && ((uintptr_t)ws & 15) == 0,
+                "mused_tokenise_build: workspace of %ld bytes, need %ld (16-byte aligned)", ws_bytes, l.bytes);
+  return tk_build_launch(l, n_docs, slots, n_tokens, n_terms, doc_tokens, rank, vrow, doc_rowptr, term, cnt, pos, gpostptr, gpostrow,
+                         gpostent, info, ws, stream);
+}
+
+long mused_tokenise_cp_ws_bytes(long n_cp, long n_docs, long table_slots) {
+  const long slots = table_slots == 0 && n_cp >= 1 ? tk_cp_default_slots(n_cp) : table_slots;
+  return tk_cp_sizes_ok(n_cp, n_docs, slots) ? tk_cp_layout(n_cp, n_docs, slots).bytes : -1;
+}
+
+int mused_tokenise_cp_scan(const unsigned* buf, long n_cp, const unsigned* cls, long n_cls, const int* docptr_host, long n_docs,
+                           long table_slots, int max_doc_tokens, int* voc_start, int* voc_len, long voc_cap, int* info, void* ws,
+                           long ws_bytes, void* stream) {
+  const long slots = table_slots == 0 && n_cp >= 1 ? tk_cp_default_slots(n_cp) : table_slots;
+  MUSED_REQUIRE(tk_cp_sizes_ok(n_cp, n_docs, slots),
+                "mused_tokenise_cp_scan: bad sizes (code points=%ld in [1, 2^30), docs=%ld in [1, code points], table slots=%ld "
+                "in [1, 2^31))", n_cp, n_docs, table_slots);
+  MUSED_REQUIRE(buf && cls && docptr_host && voc_start && voc_len && info, "mused_tokenise_cp_scan: an array is missing");
+  MUSED_REQUIRE(n_cls >= 128 && n_cls <= TK_CP_TABLE_MAX,
+                "mused_tokenise_cp_scan: a class table of %ld entries, outside [128, %ld]", n_cls, TK_CP_TABLE_MAX);
+  MUSED_REQUIRE(((uintptr_t)buf & 15) == 0, "mused_tokenise_cp_scan: the buffer must start on a 16-byte boundary");
+  MUSED_REQUIRE(docptr_host[0] == 0 && docptr_host[n_docs] == n_cp,
+                "mused_tokenise_cp_scan: docptr runs from %d to %d, not from 0 to the %ld code points of the buffer",
+                docptr_host[0], docptr_host[n_docs], n_cp);
+  for (long d = 0; d < n_docs; ++d)
+    MUSED_REQUIRE(docptr_host[d + 1] > docptr_host[d], "mused_tokenise_cp_scan: document %ld is empty or docptr descends (a "
+                  "document holds at least its separator)", d);
+  MUSED_REQUIRE(max_doc_tokens >= 1 && max_doc_tokens <= TK_MAX_DOC_TOKENS,
+                "mused_tokenise_cp_scan: max_doc_tokens=%d outside [1, %d] (one document is sorted in LDS)", max_doc_tokens,
+                TK_MAX_DOC_TOKENS);
+  const TkLayout l = tk_cp_layout(n_cp, n_docs, slots);
+  MUSED_REQUIRE(voc_cap >= 1, "mused_tokenise_cp_scan: voc_cap=%ld", voc_cap);
+  MUSED_REQUIRE(ws && ws_bytes >= l.bytes && ((uintptr_t)ws & 15) == 0,
+                "mused_tokenise_cp_scan: workspace of %ld bytes, need %ld (16-byte aligned)", ws_bytes, l.bytes);
+  hipStream_t st = (hipStream_t)stream;
+  char* w = reinterpret_cast<char*>(ws);
+  unsigned* low = reinterpret_cast<unsigned*>(w + l.low);
+  int* docptr = reinterpret_cast<int*>(w + l.docptr);
+  int* blk = reinterpret_cast<int*>(w + l.blk);
+  int* tok_start = reinterpret_cast<int*>(w + l.tok_start);
+  int* tok_len = reinterpret_cast<int*>(w + l.tok_len);
+  MUSED_CHECK_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int), st));
+  MUSED_CHECK_HIP(hipMemsetAsync(w + l.table, 0xff, (size_t)slots * sizeof(int), st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(docptr, docptr_host, (size_t)(n_docs + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+  const int cap = (int)l.tok_cap;
+  hipLaunchKernelGGL(tk_cp_scan_kernel<false>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, buf, n_cp, cls,
+                     (unsigned)n_cls, low, blk, tok_start, tok_len, cap);
+  MUSED_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tk_blockscan_kernel, dim3(1), dim3(TK_BLOCKSCAN_THREADS), 0, st, blk, (int)l.nb_scan, info + 0);
+  MUSED_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tk_cp_scan_kernel<true>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, low, n_cp, cls,
+                     (unsigned)n_cls, low, blk, tok_start, tok_len, cap);
+  MUSED_LAUNCH_CHECK();
+  return tk_vocab_launch(l, w, true, n_docs, slots, max_doc_tokens, voc_start, voc_len, voc_cap, info, st);
+}
+
+int mused_tokenise_cp_build(long n_cp, long n_docs, long table_slots, int n_tokens, int n_terms, int doc_tokens, const int* rank,
+                            const int* vrow, int* doc_rowptr, int* term, int* cnt, int* pos, int* gpostptr, int* gpostrow,
+                            int* gpostent, int* info, void* ws, long ws_bytes, void* stream) {
+  const long slots = table_slots == 0 && n_cp >= 1 ? tk_cp_default_slots(n_cp) : table_slots;
+  MUSED_REQUIRE(tk_cp_sizes_ok(n_cp, n_docs, slots),
+                "mused_tokenise_cp_build: bad sizes (code points=%ld in [1, 2^30), docs=%ld in [1, code points], table slots=%ld "
+                "in [1, 2^31))", n_cp, n_docs, table_slots);
+  const TkLayout l = tk_cp_layout(n_cp, n_docs, slots);
+  MUSED_REQUIRE(n_tokens >= 1 && n_tokens <= l.tok_cap && n_tokens <= slots && n_terms >= 1 && n_terms <= n_tokens &&
+                    n_terms < (1 << 24),
+                "mused_tokenise_cp_build: %d tokens (at most %ld and the table's %ld slots), %d terms (at most 2^24 - 1: three "
+                "radix passes)", n_tokens, l.tok_cap, slots, n_terms);
+  MUSED_REQUIRE(doc_tokens >= 1 && doc_tokens <= TK_MAX_DOC_TOKENS && doc_tokens <= n_tokens,
+                "mused_tokenise_cp_build: the longest document has %d tokens, outside [1, %d]", doc_tokens, TK_MAX_DOC_TOKENS);
+  MUSED_REQUIRE(rank && vrow && doc_rowptr && term && cnt && pos && gpostptr && gpostrow && gpostent && info,
+                "mused_tokenise_cp_build: an array is missing");
+  MUSED_REQUIRE(ws && ws_bytes >= l.bytes && ((uintptr_t)ws & 15) == 0,
+                "mused_tokenise_cp_build: workspace of %ld bytes, need %ld (16-byte aligned)", ws_bytes, l.bytes);
+  return tk_build_launch(l, n_docs, slots, n_tokens, n_terms, doc_tokens, rank, vrow, doc_rowptr, term, cnt, pos, gpostptr, gpostrow,
+                         gpostent, info, ws, stream);
 }
 
 }  // extern "C"

@@ -111,6 +111,27 @@ def sparse_text_stream(n: int, seed: int = 0, vocab: int = 20000, zipf: float = 
     return data.astype(str), labels
 
 
+# what `swap_letters` draws from: both cases of several scripts, the two code points str.lower() treats specially
+# (U+0130, which expands, and U+03A3, whose lower case depends on its neighbours), CJK and a Deseret case pair
+_SWAP_POOL = "áÁéÉñÑöÖçÇßıİσςΣωΩжЖдДшШ文字語𐐨𐐀𐑌𐐤"
+
+
+def swap_letters(records, share: float, seed: int = 0):
+    """A copy of (n, 2) string records with the share `share` of their ASCII letters, chosen and replaced by draws of
+    a generator seeded with `seed`, swapped for letters that are not ASCII (one code point for one, so every length
+    stays).  What the Unicode tokeniser is measured and tested on."""
+    rng = np.random.default_rng([seed, 0x0130])
+    out = np.array(records, dtype=str)
+    if out.size == 0 or out.dtype.itemsize == 0:
+        return out
+    cp = out.view(np.uint32)
+    letter = ((cp | 32) >= ord("a")) & ((cp | 32) <= ord("z")) & (cp < 128)
+    hit = letter & (rng.random(cp.shape) < share)
+    pool = np.array([ord(c) for c in _SWAP_POOL], dtype=np.uint32)
+    cp[hit] = pool[rng.integers(0, len(pool), size=int(hit.sum()))]
+    return out
+
+
 def metadata_stream(n: int, seed: int = 0, events: int = 5, users: int = 24, vocab: int = 60, missing: float = 0.05,
                     integer_time: bool = False):
     """Synthetic SED2012-style metadata columns, in the layout data_loader.py:87-99 hands to the reference:

@@ -29,7 +29,7 @@ _MAX_DEVICE_TERMS = 2 ** 24      # the posting sort of csrc/tokenise.hip runs th
 _TK_FLAG_DOC, _TK_FLAG_TABLE, _TK_FLAG_STATE = 1, 2, 4
 
 # corpora `tokenise_on_device` handed to the host `tokenise`: not pure ASCII, 2^31 bytes or more, a document beyond
-# max_doc_tokens, 2^24 distinct terms or more
+# max_doc_tokens, 2^24 distinct terms or more; and those `tokenise_codepoints_on_device` handed over (its docstring)
 tokenise_fallbacks = 0
 
 _LAZY_FIELDS = ("term", "cnt", "pos", "gpostptr", "gpostrow", "gpostent")
@@ -262,6 +262,53 @@ def corpus_buffer(records, valid):
     return grid[keep], docptr
 
 
+# the most code points of a corpus `tokenise_codepoints_on_device` takes (csrc/tokenise.hip: tk_cp_sizes_ok): below it
+# every element offset and token count is an int32 and the workspace arithmetic stays far inside an int64
+_MAX_CODEPOINTS = 2 ** 30
+
+
+def corpus_codepoints(records, valid):
+    """`corpus_buffer` for any text: the strings of the valid rows as one buffer of code points, every string followed by
+    tokens.SEPARATOR, every U+03A3 replaced by what the row's str.lower() has in its place (tokens.resolve_sigma), and
+    docptr[D + 1] in ELEMENTS from the string lengths: (buf uint32, docptr int32).
+
+    None -- the corpus is the host's -- if the buffer would hold _MAX_CODEPOINTS = 2^30 elements or more (element offsets are
+    int32, and the workspace of 2^30 code points is some 24 GiB), if an element is no code point (above U+10FFFF: not from
+    a str) or is one of tokens.unsupported_codepoints().  The fixed-width string array is UCS-4 already, so this works on
+    it as a whole: no Python per row but for the rows that hold U+03A3."""
+    from . import tokens
+
+    vd = records[valid]
+    if vd.dtype.kind != "U":
+        vd = vd.astype(str)
+    D, k = len(vd), vd.dtype.itemsize // 4
+    cp = np.ascontiguousarray(vd).view(np.uint32).reshape(D, 2, k)
+    if vd.dtype.byteorder == ">" or int(cp.max()) >= tokens.N_CODEPOINTS:
+        return None
+    length = np.char.str_len(vd).astype(np.int32)
+    blank = length == 0
+    length = np.where(blank, 1, length)
+    doclen = length.sum(axis=1, dtype=np.int64) + 2
+    if int(doclen.sum()) >= _MAX_CODEPOINTS:
+        return None
+    grid = np.empty((D, 2 * k + 2), dtype=np.uint32)
+    grid[:, :k], grid[:, k + 1:2 * k + 1] = cp[:, 0], cp[:, 1]
+    grid[:, k], grid[:, 2 * k + 1] = ord(" "), tokens.SEPARATOR
+    grid[blank[:, 0], 0] = ord(" ")
+    grid[blank[:, 1], k + 1] = ord(" ")
+    keep = np.ones((D, 2 * k + 2), dtype=bool)
+    col = np.arange(k, dtype=np.int32)
+    keep[:, :k] = col < length[:, :1]
+    keep[:, k + 1:2 * k + 1] = col < length[:, 1:]
+    docptr = np.concatenate([[0], np.cumsum(doclen)]).astype(np.int32)
+    buf = grid[keep]
+    unsupported = tokens.unsupported_codepoints()
+    if len(unsupported) and np.isin(buf, unsupported).any():
+        return None
+    tokens.resolve_sigma(buf, docptr)
+    return buf, docptr
+
+
 def _fallback(records, max_row_terms):
     global tokenise_fallbacks
     tokenise_fallbacks += 1
@@ -344,17 +391,136 @@ def tokenise_on_device(records, device=None, max_row_terms=TFIDF_MAX_ROW_TERMS, 
     return TextCorpus._from_device(records, vocabulary, rowptr, valid, tensors, device, max_row_terms)
 
 
+_CLASS_TABLES = {}   # device -> tokens.class_table() as a tensor, uploaded once per device
+
+
+def _class_table_on(device):
+    import torch
+
+    from . import tokens
+
+    key = _device_key(device)
+    if key not in _CLASS_TABLES:
+        _CLASS_TABLES[key] = torch.from_numpy(tokens.class_table().view(np.int32)).to(device)
+    return _CLASS_TABLES[key]
+
+
+def tokenise_codepoints_on_device(records, device=None, max_row_terms=TFIDF_MAX_ROW_TERMS,
+                                  max_doc_tokens=TOKENISE_MAX_DOC_TOKENS, table_slots=0) -> TextCorpus:
+    """`tokenise_on_device` for text of any script: the same steps on code points (the mused_tokenise_cp_* entries of
+    csrc/tokenise.hip; the rule: mused_amd/tokens.py, "code points"), equal to `tokenise(records)` field for field, the six
+    large arrays left on the device.
+
+    The host joins the strings into one uint32 buffer (`corpus_codepoints`) and hands the device the class table of the
+    running interpreter (built once per process, uploaded once per device).  The V distinct tokens come back as spans;
+    the host gathers those spans from its own buffer through the same table, decodes them in one call, sorts the V
+    strings and uploads their ranks.  A corpus of 2^30 code points or more, with a document of more than
+    `max_doc_tokens` tokens, 2^24 distinct terms or more, or a code point the table cannot express is tokenised by
+    `tokenise` (counted in `tokenise_fallbacks`)."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib, tokens
+
+    records, valid = _valid_rows(records)
+    N, D = len(records), int(valid.sum())
+    if not 1 <= int(max_doc_tokens) <= TOKENISE_MAX_DOC_TOKENS:
+        raise ValueError(f"max_doc_tokens={max_doc_tokens} outside [1, {TOKENISE_MAX_DOC_TOKENS}]")
+    empty = np.zeros(0, dtype=np.int64)
+    if D == 0:   # no string at all
+        return TextCorpus(records, [], np.zeros(N + 1, dtype=np.int64), empty, empty, empty, valid, max_row_terms)
+    joined = corpus_codepoints(records, valid)
+    if joined is None:
+        return _fallback(records, max_row_terms)
+    buf, docptr = joined
+    B = len(buf)
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    L = _lib.lib()
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    i32 = lambda m: torch.empty(m, dtype=torch.int32, device=device)
+    ws_bytes = int(L.mused_tokenise_cp_ws_bytes(B, D, int(table_slots)))
+    if ws_bytes < 0:
+        raise ValueError(f"tokenise_codepoints_on_device: {B} code points, {D} documents, table_slots={table_slots}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+    tok_cap = B // 2 + 1
+    table = tokens.class_table()
+    table_d = _class_table_on(device)
+    buf_d = torch.from_numpy(buf.view(np.int32)).to(device)
+    voc_start, voc_len, info = i32(tok_cap), i32(tok_cap), i32(4)
+    _lib.call("mused_tokenise_cp_scan", ptr(buf_d), B, ptr(table_d), len(table), docptr.ctypes.data_as(C.c_void_p), D,
+              int(table_slots), int(max_doc_tokens), ptr(voc_start), ptr(voc_len), tok_cap, ptr(info), ptr(ws), ws_bytes, stream())
+    T, V, flags, doc_tokens = (int(x) for x in info.cpu().numpy())
+    if flags & _TK_FLAG_TABLE:
+        raise ValueError(f"tokenise_codepoints_on_device: {T} tokens do not fit a table of {table_slots} slots")
+    if flags & _TK_FLAG_DOC or V >= _MAX_DEVICE_TERMS:
+        return _fallback(records, max_row_terms)
+    if T == 0:   # documents without a token
+        return TextCorpus(records, [], np.zeros(N + 1, dtype=np.int64), empty, empty, empty, valid, max_row_terms)
+    # alphabetical ids: the V spans gathered from the host's buffer through the table, decoded at once, sorted as str
+    # (code-point order, as scikit-learn's _sort_features)
+    vs, vl = voc_start[:V].cpu().numpy().astype(np.int64), voc_len[:V].cpu().numpy().astype(np.int64)
+    off = np.concatenate([[0], np.cumsum(vl)])
+    packed = table[buf[np.repeat(vs - off[:-1], vl) + np.arange(off[-1])]] & tokens.CP_MASK
+    text_ = packed.astype("<u4").tobytes().decode("utf-32-le")
+    bounds = off.tolist()
+    found = [text_[a:b] for a, b in zip(bounds[:-1], bounds[1:])]
+    order = sorted(range(V), key=found.__getitem__)
+    rank = np.empty(V, dtype=np.int32)
+    rank[order] = np.arange(V, dtype=np.int32)
+    vocabulary = [found[i] for i in order]
+    rank_d = torch.from_numpy(rank).to(device)
+    vrow_d = torch.from_numpy(np.flatnonzero(valid).astype(np.int32)).to(device)
+    doc_rowptr, gpostptr = i32(D + 1), i32(V + 1)
+    big = {name: i32(T) for name in ("term", "cnt", "pos", "gpostrow", "gpostent")}
+    _lib.call("mused_tokenise_cp_build", B, D, int(table_slots), T, V, doc_tokens, ptr(rank_d), ptr(vrow_d), ptr(doc_rowptr),
+              ptr(big["term"]), ptr(big["cnt"]), ptr(big["pos"]), ptr(gpostptr), ptr(big["gpostrow"]), ptr(big["gpostent"]),
+              ptr(info), ptr(ws), ws_bytes, stream())
+    doc_rowptr_h = doc_rowptr.cpu().numpy()
+    flags = int(info.cpu().numpy()[2])
+    if flags:
+        raise _lib.MusedError(f"mused_tokenise_cp_build: the workspace is not what mused_tokenise_cp_scan left (flags {flags})")
+    nnz = int(doc_rowptr_h[D])
+    rowptr = doc_rowptr_h[np.concatenate([[0], np.cumsum(valid)])]   # invalid rows are empty
+    tensors = {name: t[:nnz] for name, t in big.items()}
+    tensors["gpostptr"] = gpostptr
+    return TextCorpus._from_device(records, vocabulary, rowptr, valid, tensors, device, max_row_terms)
+
+
+def _is_ascii(records) -> bool:
+    """No code point of the (N, 2) strings is above 127 (one pass over the UCS-4 array)."""
+    records = np.asarray(records)
+    if records.dtype.kind != "U":
+        records = records.astype(str)
+    if records.size == 0 or records.dtype.itemsize == 0:
+        return True
+    return int(np.ascontiguousarray(records).view(np.uint32).max()) <= 127 and records.dtype.byteorder != ">"
+
+
 def tokenise_for_device(records, device=None) -> TextCorpus:
-    """The corpus of `records` by the tokeniser MUSED_TOKENISE names (read at every call): "device" =
-    `tokenise_on_device`, "host" = `tokenise`; unset: the device from TOKENISE_DEVICE_MIN_ROWS rows on."""
+    """The corpus of `records` by the tokeniser MUSED_TOKENISE names (read at every call): "host" = `tokenise`;
+    "device" = `tokenise_on_device` for a pure-ASCII corpus and `tokenise_codepoints_on_device` for any other; unset:
+    the device from TOKENISE_DEVICE_MIN_ROWS rows of ASCII on, from TOKENISE_CODEPOINTS_MIN_ROWS rows of other text."""
     mode = os.environ.get("MUSED_TOKENISE", "")
     if mode not in ("", "device", "host"):
         raise ValueError(f"MUSED_TOKENISE={mode!r}: device or host")
-    if mode == "device" or (mode == "" and len(records) >= TOKENISE_DEVICE_MIN_ROWS):
-        return tokenise_on_device(records, device)
+    n = len(records)
+    if mode == "host" or (mode == "" and n < min(TOKENISE_DEVICE_MIN_ROWS, TOKENISE_CODEPOINTS_MIN_ROWS)):
+        return tokenise(records)
+    if _is_ascii(records):
+        if mode == "device" or n >= TOKENISE_DEVICE_MIN_ROWS:
+            return tokenise_on_device(records, device)
+    elif mode == "device" or n >= TOKENISE_CODEPOINTS_MIN_ROWS:
+        return tokenise_codepoints_on_device(records, device)
     return tokenise(records)
 
 
 # measured (DESIGN section 13a): the device tokeniser was the faster one from 500 rows on, by more than the spread between
 # repeated runs; at 100 rows the two are level (a call of either takes about 0.5 ms) and the host stays the default
 TOKENISE_DEVICE_MIN_ROWS = 500
+# the code-point path against `tokenise` on the same swapped-letter rows (DESIGN section 13a), a threshold of its own: 500
+# rows was the smallest measured count at which it was faster on both streams by more than the spread (2.6 against 5.9 ms,
+# 1.4 against 2.2 ms); at 100 rows it won on one stream and lost on the other
+TOKENISE_CODEPOINTS_MIN_ROWS = 500

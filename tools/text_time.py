@@ -9,13 +9,16 @@ csrc/tokenise.hip, the host's sort of the vocabulary) on the same rows in one pr
 device synchronisation; median of --tok-repeat (>= 5) after one warm-up each.  Shapes: --tok-rows rows of text_stream
 and of sparse_text_stream, the --batch rows of text_stream, one window of --tok-window rows of each.  The corpora are
 compared field for field once per shape.  No window is timed in this mode (kernel times: run it under
-`rocprofv3 --kernel-trace --stats -- python tools/text_time.py --tokenise ...`).
+`rocprofv3 --kernel-trace --stats -- python tools/text_time.py --tokenise ...`).  --non-ascii SHARE: the share SHARE
+of the streams' letters is swapped for letters that are not ASCII (synth.swap_letters, seeded: both cases of several
+scripts, U+0130 and U+03A3 among them) and the device side is text.tokenise_codepoints_on_device.
 
 Stream shapes: 12 hopping windows (step W / 4) of synth.text_stream / synth.sparse_text_stream, median of the 12; the
 sparse stream also with text_sparse=True.  Batch shape: the whole text_stream subset as one window (best of --repeat).
 
     python tools/text_time.py [--shapes 2000,10000] [--k 50] [--batch 150000] [--repeat 2] [--out FILE]
     python tools/text_time.py --tokenise [--tok-rows 37500] [--tok-window 2000] [--batch 150000] [--tok-repeat 7]
+                                         [--non-ascii 0.3]
 """
 import argparse
 import json
@@ -54,11 +57,15 @@ def tokenise_times(a, emit):
               ("sparse_text_stream", a.tok_window)] + ([("text_stream", a.batch)] if a.batch > 0 else [])
     for stream, n in shapes:
         rec = getattr(synth, stream)(n, 0)[0]
+        on_device = text.tokenise_on_device
+        if a.non_ascii > 0:
+            rec = synth.swap_letters(rec, a.non_ascii, 0)
+            on_device = text.tokenise_codepoints_on_device
         fallbacks = text.tokenise_fallbacks
         s = {"device": [], "host": []}
         same = None
         for r in range(a.tok_repeat + 1):   # round 0 warms both up (code objects, the allocator's blocks)
-            dev, td = timed(lambda: text.tokenise_on_device(rec))
+            dev, td = timed(lambda: on_device(rec))
             host, th = timed(lambda: text.tokenise(rec))
             if r == 0:
                 same = (dev.vocabulary == host.vocabulary and
@@ -67,7 +74,8 @@ def tokenise_times(a, emit):
                 s["device"].append(td)
                 s["host"].append(th)
             del dev, host
-        emit({"tokenise": stream, "rows": n, "bytes": int(text.corpus_buffer(*text._valid_rows(rec))[1][-1]),
+        joined = (text.corpus_codepoints if a.non_ascii > 0 else text.corpus_buffer)(*text._valid_rows(rec))
+        emit({"tokenise": stream, "rows": n, "non_ascii": a.non_ascii, "bytes": int(joined[1][-1]) * joined[0].itemsize,
               "repeat": a.tok_repeat, "device_s_median": round(statistics.median(s["device"]), 4),
               "host_s_median": round(statistics.median(s["host"]), 4),
               "device_s": [round(x, 4) for x in s["device"]], "host_s": [round(x, 4) for x in s["host"]],
@@ -86,6 +94,7 @@ def main():
     ap.add_argument("--tok-rows", type=int, default=37500)
     ap.add_argument("--tok-window", type=int, default=2000)
     ap.add_argument("--tok-repeat", type=int, default=7)
+    ap.add_argument("--non-ascii", type=float, default=0.0)
     a = ap.parse_args()
 
     import torch
