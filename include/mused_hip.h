@@ -435,6 +435,28 @@ long mused_dbscan_ws_bytes(long n);
 int mused_dbscan(const double* X, long n, int d, long ld, double eps, int min_samples, int* labels_out, int* info_out,
                  void* ws, long ws_bytes, void* stream);
 
+/* ---- HDBSCAN_batch: the exact Euclidean minimum spanning tree of n fp64 rows, csrc/emst.hip.  For
+ * sklearn.cluster.HDBSCAN(min_samples <= 2, metric="euclidean") the mutual-reachability distance is the distance itself, so
+ * this tree is the one its Prim loop builds; the sequential rest (Prim's edge order, single-linkage and condensed tree,
+ * labels) runs on the host (mused_amd/hdbscan.py, which is also the specification of the rounds).  Boruvka rounds over the
+ * fp64 MFMA distance tiles, d2 = max(0, |x_i|^2 + |x_j|^2 - 2 x_i.x_j) recomputed in every round, one evaluation serving
+ * both ends of a pair: every component picks its smallest outgoing edge under the total order (d2, min(i, j), max(i, j)),
+ * the picks are united by a lock-free union-find.  O(n) workspace: no n x n array, neighbour list or bitmask.  ceil(log2 n)
+ * rounds are enqueued; the kernels of the rounds behind the last needed one return at once (a device word).  Enqueue-only.
+ * X: n x d fp64 (pitch ld), n <= 2^19 (the tile grid of one launch).
+ * edge_a, edge_b (DEVICE, n - 1 int32 each), edge_d2 (DEVICE, n - 1 fp64: the kernel's own d2): the tree's edges in
+ *   ARBITRARY order and orientation (the edge SET does not depend on scheduling); may be NULL for n == 1.
+ * info_out (DEVICE, 4 int32) = {flags, edges written, rounds run, 0}.  Flags: 1 in some round some outgoing edge of a
+ *   component lies within tau(pick) + tau(edge) of its pick, tau(i, j) = 2 (d + 8) 2^-52 (|x_i|^2 + |x_j|^2) + 4 ulp(d2(i, j))
+ *   being the bound within which two ways of evaluating d2 can disagree (the second tau is bounded from one end of the
+ *   edge: csrc/emst.hip), so another evaluation might pick another tree; 2 a row or a squared distance is not finite;
+ *   4 internal error (the two passes of a round disagreed about a distance).  With any flag the edges are NOT to be used:
+ *   run the host estimator.
+ * ws: mused_emst_ws_bytes(n) bytes (56 n + 4 ceil(n / 128) and alignment; -1 for n outside [1, 2^19]). */
+long mused_emst_ws_bytes(long n);
+int mused_emst(const double* X, long n, int d, long ld, int* edge_a, int* edge_b, double* edge_d2, int* info_out, void* ws,
+               long ws_bytes, void* stream);
+
 /* ---- scoring a run: compute_all_metrics (metrics_evaluation.py:47-92: scikit-learn's NMI, NMI over the rows whose true
  * label is > 0, weighted F1 / precision / recall, accuracy, MAE), csrc/score.hip.  All seven are functions of the
  * true-class x predicted-cluster contingency table (specification: mused_amd/scores.py).  One launch, one workgroup per

@@ -8,5 +8,6 @@ from mused_amd.matrix_operations import (  # noqa: F401
     perform_dbscan_clustering,
     perform_dbscan_incr_clustering,
     perform_hdbscan_clustering,
+    perform_hdbscan_clustering_on_device,
     perform_svd_reduction,
 )

@@ -39,6 +39,7 @@
 // scikit-learn itself: exact labels or a flag, never labels that hang on the last bits.
 #include "gemm_f64.h"
 #include "internal.h"
+#include "union_find.h"
 
 extern "C" int mused_row_sq_norms(const void* X, int dtype, long n, int d, long ld, double* out, void* stream);
 
@@ -60,35 +61,6 @@ struct DbArgs {
   double eps2, ctau, etau;  // tau(i, j) = ctau * (nrm[i] + nrm[j]) + etau
   int min_samples;
 };
-
-__device__ __forceinline__ int db_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// root of x; halves the path on its way (a row that has a parent below itself is never a root again, and any ancestor is a
-// valid parent: the stores race with nothing that matters)
-__device__ __forceinline__ int db_find(int* parent, int x) {
-  int p = db_load(parent + x);
-  while (p != x) {
-    const int g = db_load(parent + p);
-    if (g != p) __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x = p;
-    p = g;
-  }
-  return x;
-}
-
-// joins the trees of a and b; returns the smaller of the two roots it ended with
-__device__ __forceinline__ int db_unite(int* parent, int a, int b) {
-  while (true) {
-    a = db_find(parent, a);
-    b = db_find(parent, b);
-    if (a == b) return a;
-    const int lo = a < b ? a : b, hi = a < b ? b : a;
-    const int old = atomicCAS(parent + hi, hi, lo);
-    if (old == hi) return lo;
-    a = old;  // hi was hooked elsewhere in the meantime: on from its new parent
-    b = lo;
-  }
-}
 
 // tile (I, (I + delta) mod tiles), delta in [0, tiles / 2]: every unordered pair of row tiles once; 64 consecutive workgroups
 // (one XCD's share) touch 8 A row-panels and 15 B row-panels.  Grid: ceil(tiles / 8) * 8 * (tiles / 2 + 1).

@@ -803,6 +803,115 @@ def perform_hdbscan_clustering(data, min_cluster_size=5, min_samples=2):
     return hdbscan.HDBSCAN(min_cluster_size=min_cluster_size, min_samples=min_samples, metric="euclidean").fit_predict(data)
 
 
+def perform_hdbscan_clustering_sklearn(data, min_cluster_size=5, min_samples=2):
+    """scikit-learn's own estimator on host rows (its labels as int64; rows that are not finite are labelled as it labels
+    them): what `perform_hdbscan_clustering_on_device` is pinned to, and its host path."""
+    from sklearn.cluster import HDBSCAN
+
+    labels = HDBSCAN(min_cluster_size=min_cluster_size, min_samples=min_samples, metric="euclidean").fit_predict(data)
+    return np.asarray(labels, dtype=np.int64)
+
+
+# calls that perform_hdbscan_clustering_on_device finished with scikit-learn on the host although the device was asked: the
+# kernel's ambiguity flag (some component's runner-up within rounding of its pick), its non-finite flag, or two tree edges
+# of exactly equal weight
+hdbscan_fallbacks = 0
+
+
+def _hdbscan_count_fallback():
+    global hdbscan_fallbacks
+    with _km_fallback_lock:
+        hdbscan_fallbacks += 1
+
+
+def emst_launch(X_dev, stream=None, events=None):
+    """One mused_emst call on an (n, d) fp64 CUDA tensor (unit stride along the columns) -> (edges (2, n - 1) int32 CUDA, d2
+    (n - 1) fp64 CUDA, info 4 int32 NumPy = {flags, edges written, rounds run, 0}; flags: mused_amd.hdbscan.FLAG_*).
+    Synchronises the stream (the one read of `info`).  events: a pair of torch.cuda.Event(enable_timing=True), recorded
+    on the stream right before and right after the C call."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+
+    n, d = X_dev.shape
+    st = stream if stream is not None else torch.cuda.current_stream()
+    with torch.cuda.stream(st):
+        ws = torch.empty(int(_lib.lib().mused_emst_ws_bytes(n)), dtype=torch.uint8, device=X_dev.device)
+        edges = torch.empty((2, max(n - 1, 1)), dtype=torch.int32, device=X_dev.device)
+        d2 = torch.empty(max(n - 1, 1), dtype=torch.float64, device=X_dev.device)
+        info = torch.empty(4, dtype=torch.int32, device=X_dev.device)
+        if events:
+            events[0].record(st)
+        _lib.call("mused_emst", _eng.ptr(X_dev), n, d, X_dev.stride(0), _eng.ptr(edges[0]), _eng.ptr(edges[1]), _eng.ptr(d2),
+                  _eng.ptr(info), _eng.ptr(ws), ws.numel(), C.c_void_p(st.cuda_stream))
+        if events:
+            events[1].record(st)
+        info_h = info.cpu().numpy()
+    return edges[:, :n - 1], d2[:n - 1], info_h
+
+
+def perform_hdbscan_clustering_on_device(emb, min_cluster_size=5, min_samples=2, stream=None, timings=None):
+    """sklearn.cluster.HDBSCAN(min_cluster_size, min_samples, metric="euclidean").fit_predict(emb) as int64 NumPy labels, with
+    the O(n^2 d) part on the device: for min_samples <= 2 the mutual-reachability distance is the distance, so the
+    estimator's tree is the Euclidean minimum spanning tree, which csrc/emst.hip computes in O(n) device memory beside the
+    rows (the split, the rounding argument and why min_samples >= 3 is not taken: mused_amd/hdbscan.py).  Device: `mused_emst`
+    on the caller's stream, one read of its `info`, the 2 (n - 1) edge indices.  Host: the weights with scikit-learn's bits,
+    Prim's edge order from row 0, then scikit-learn's own single-linkage, condensed-tree and labelling routines.
+    emb: (n, d) fp64 CUDA tensor or ndarray.  Where the kernel raises its ambiguity or non-finite flag, or two tree edges
+    weigh exactly the same, `perform_hdbscan_clustering_sklearn` runs on a host copy and the call is counted in
+    `hdbscan_fallbacks`.  What the device does not take goes there uncounted: min_samples >= 3 or None, rows that are not
+    fp64, fewer than 2 or more than 2^19 rows, arguments scikit-learn rejects (it raises its own errors), a scikit-learn
+    without the private routines.  This pins the labels to scikit-learn's HDBSCAN, NOT to the `hdbscan` package
+    `perform_hdbscan_clustering` calls.
+    stream: the kernels run on it behind whatever the current stream holds; the call returns after they have finished.
+    timings: a dict that receives, where the device ran, "emst_ms" (events around the C call), "rounds" and "host_ms"
+    (everything behind the read of the edges: host copy of the rows, weights, Prim's order, scikit-learn's routines)."""
+    import numbers
+    import time
+
+    import torch
+
+    from . import hdbscan as _hd
+
+    on_dev = isinstance(emb, torch.Tensor)
+
+    def host():
+        return perform_hdbscan_clustering_sklearn(emb.cpu().numpy() if on_dev else emb, min_cluster_size=min_cluster_size,
+                                                  min_samples=min_samples)
+
+    X = emb if on_dev else np.asarray(emb)
+    ok = (isinstance(min_cluster_size, numbers.Integral) and not isinstance(min_cluster_size, bool) and 2 <= min_cluster_size < 2 ** 31
+          and isinstance(min_samples, numbers.Integral) and not isinstance(min_samples, bool) and 1 <= min_samples <= 2
+          and X.ndim == 2 and 2 <= X.shape[0] <= _hd.MAX_ROWS and 1 <= X.shape[1] < 2 ** 20
+          and X.dtype in (torch.float64, np.float64) and _hd.sklearn_internals() is not None)
+    if not ok:
+        return host()
+    st = _match_stream(stream)
+    with torch.cuda.stream(st):
+        Xd = X if on_dev else torch.from_numpy(np.ascontiguousarray(X)).cuda()
+        if Xd.stride(1) != 1 or Xd.stride(0) < Xd.shape[1]:
+            Xd = Xd.contiguous()
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if timings is not None else None
+        edges, _, info = emst_launch(Xd, st, events=ev)
+        if timings is not None:
+            timings.update(emst_ms=ev[0].elapsed_time(ev[1]), rounds=int(info[2]))
+        if info[0] or info[1] != X.shape[0] - 1:
+            _hdbscan_count_fallback()
+            return host()
+        e = edges.cpu().numpy()
+    t0 = time.perf_counter()
+    Xh = emb.cpu().numpy() if on_dev else np.asarray(emb)
+    labels, _ = _hd.labels_from_edges(Xh, e[0], e[1], min_cluster_size)
+    if timings is not None:
+        timings["host_ms"] = 1e3 * (time.perf_counter() - t0)
+    if labels is None:
+        _hdbscan_count_fallback()
+        return host()
+    return labels
+
+
 def perform_dbscan_incr_clustering(data, previous_centroids, previous_labels, eps=0.5, min_samples=5):
     """matrix_operations.py:265-298: DBSCAN on the window, clusters renamed after the closest
     centroid of the previous window."""

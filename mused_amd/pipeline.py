@@ -726,18 +726,28 @@ def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_
     """Same positional parameters as main.py:132: the whole subset as one window -- kNN adjacency per modality, fusion,
     randomized-SVD embedding on the device (`batch_embedding`), then "SVDMC_batch": k-means with n_clusters on the device
     (perform_clustering_on_device: scikit-learn's labels); "DBSCAN_batch": DBSCAN on the device embedding
-    (perform_dbscan_clustering_on_device: scikit-learn's labels, csrc/dbscan.hip); "HDBSCAN_batch": the host wrapper on the
-    embedding, as the reference does.  Returns `results` with the labels ("all_clusters") and the wall time
+    (perform_dbscan_clustering_on_device: scikit-learn's labels, csrc/dbscan.hip); "HDBSCAN_batch": MUSED_HDBSCAN, read at every call --
+    unset or `package`: the host wrapper around the `hdbscan` package on the embedding, as the reference does; `device`:
+    perform_hdbscan_clustering_on_device on the device embedding (scikit-learn's HDBSCAN labels, csrc/emst.hip; pinned to
+    scikit-learn, NOT to the package, hence opt-in); `sklearn`: scikit-learn's estimator on a host copy.  Returns `results` with the labels ("all_clusters") and the wall time
     ("processing_time"), like process_streaming_data.  `timings`: see batch_embedding (plus "clustering" and "edges").
     `score=True`: `results` also receives what the reference's compute_all_metrics appends (main.py:165)."""
     if approach not in BATCH_APPROACHES:
         raise ValueError(f"approach {approach!r} is not a batch approach {BATCH_APPROACHES}")
-    if approach == "HDBSCAN_batch":
+    hd_mode = os.environ.get("MUSED_HDBSCAN", "package") if approach == "HDBSCAN_batch" else None
+    if hd_mode is not None and hd_mode not in ("package", "device", "sklearn"):
+        raise ValueError(f"MUSED_HDBSCAN={hd_mode!r}: expected package, device or sklearn")
+    if hd_mode == "package":
         import hdbscan  # noqa: F401  (the reference imports it at module level: without it nothing runs)
     t0 = time.time_ns()
     emb, _, nnz = batch_embedding(data_modalities, list(modality_types), reduced_dim, k_basis, seed, timings=timings)
     t1 = time.perf_counter()
-    if approach == "HDBSCAN_batch":
+    if hd_mode == "device":
+        clusters = mo.perform_hdbscan_clustering_on_device(emb, min_cluster_size=min_cluster_size, min_samples=min_samples)
+    elif hd_mode == "sklearn":
+        clusters = mo.perform_hdbscan_clustering_sklearn(emb.cpu().numpy(), min_cluster_size=min_cluster_size,
+                                                         min_samples=min_samples)
+    elif hd_mode == "package":
         clusters = mo.perform_hdbscan_clustering(emb.cpu().numpy(), min_cluster_size=min_cluster_size,
                                                  min_samples=min_samples)
     elif approach == "DBSCAN_batch":
