@@ -346,6 +346,17 @@ int mused_kmeans_assign_rows(int d, int k);
 long mused_kmeans_ws_bytes(int n, int d, int k);
 int mused_kmeans_lloyd(const double* X, long ld, int n, int d, int k, const double* mean, double* centers, double tol,
                        int max_iter, int* labels_out, int* info_out, void* ws, long ws_bytes, void* stream);
+/* mused_kmeans_lloyd_wide: the same arguments and contract for any k <= 1024, d <= 512, k <= n (the limits of
+ *   mused_kmeans_seed and mused_kmeans_assign): the centres stream through LDS in tiles, the M-step partials take a tile
+ *   of columns per workgroup and the centre sums are spread over workgroups, every sum in mused_kmeans_lloyd's order, so
+ *   labels, info and the BITS of the centres equal mused_kmeans_lloyd's wherever both accept the shape.  BLOCKING.
+ *   ws: mused_kmeans_wide_ws_bytes(n, d, k) bytes (-1 for a rejected shape).
+ * mused_kmeans_wide_tiles: out[0..2] = {rows per tile, centres per tile of the E step (LDS 8 (out[0] + out[1]) (d + 1)
+ *   bytes), columns per tile of the M-step partials (LDS 8 k out[2] + 1040 bytes)} for (d, k); needs no device. */
+long mused_kmeans_wide_ws_bytes(int n, int d, int k);
+int mused_kmeans_lloyd_wide(const double* X, long ld, int n, int d, int k, const double* mean, double* centers, double tol,
+                            int max_iter, int* labels_out, int* info_out, void* ws, long ws_bytes, void* stream);
+int mused_kmeans_wide_tiles(int d, int k, int* out);
 
 /* ---- what KMeans.fit does before the Lloyd iterations (csrc/kmeanspp.hip).  Both enqueue-only, fp64, fixed-order sums.
  * mused_kmeans_moments: mean_out (d, device) = X.mean(axis=0) bit for bit (rows added in row order, / n); tol_out (1,

@@ -83,6 +83,9 @@ _PROTOS = {
     "mused_kmeans_ws_bytes": (_l, [_i, _i, _i]),
     "mused_kmeans_lloyd": (_i, [_vp, _l, _i, _i, _i, _vp, _vp, _d, _i, _vp, C.POINTER(_i), _vp, _l, _vp]),
     "mused_kmeans_assign_rows": (_i, [_i, _i]),
+    "mused_kmeans_wide_ws_bytes": (_l, [_i, _i, _i]),
+    "mused_kmeans_lloyd_wide": (_i, [_vp, _l, _i, _i, _i, _vp, _vp, _d, _i, _vp, C.POINTER(_i), _vp, _l, _vp]),
+    "mused_kmeans_wide_tiles": (_i, [_i, _i, C.POINTER(_i)]),
     "mused_kmeans_moments": (_i, [_vp, _l, _i, _i, _vp, _vp, _vp]),
     "mused_kmeans_seed_ws_bytes": (_l, [_i, _i, _i]),
     "mused_kmeans_seed": (_i, [_vp, _l, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _l, _vp]),

@@ -17,6 +17,9 @@
 // golden window and on the 20-window benchmark stream).  An empty cluster (sklearn relocates its centre,
 // _k_means_common.pyx `_relocate_empty_clusters_dense`) is not handled here: it raises info[2] and the host falls back to
 // scikit-learn for that window.
+//
+// Two entries: mused_kmeans_lloyd keeps all k centres and the k x d sums of a chunk in LDS (k * d <= 8192);
+// mused_kmeans_lloyd_wide (second half of this file) works in tiles for any k <= 1024, d <= 512 and returns the same bits.
 #include <stdlib.h>
 
 #include <mutex>
@@ -252,11 +255,310 @@ static int km_assign_rows(int d, int k) {
   return 0;
 }
 
+// ---- any k x d (k <= 1024, d <= 512): mused_kmeans_lloyd_wide ---------------------------------------------------------
+// The kernels above keep all k centres and a k x d block of sums in LDS, hence k * d <= 8192.  Here the iteration is three
+// steps that each hold a tile: the E step streams the centres through LDS (mbkm_assign_kernel's scheme, csrc/minibatch.hip),
+// the M-step partials take a column tile of the sums per workgroup, and the centre sums are spread over workgroups.  Every
+// sum keeps the order of the kernels above -- a dot product runs over c = 0 .. d - 1, the rows of a 256-row chunk are added
+// in row order from 0.0, the chunks in chunk order, the shift as the per-thread sums e = t, t + 1024, ... and the same tree
+// -- so labels, info and the centres' bits equal mused_kmeans_lloyd's wherever both accept the shape.
+constexpr size_t KMW_ASSIGN_LDS_DOUBLES = 19456;  // 152 KiB: row tile + centre tile of the E step
+
+// E step.  A workgroup owns TR rows (LDS, pitch d + 1) and walks the centres in tiles of KT (LDS, pitch d + 1); PT = 256 / TR
+// adjacent lanes share a row and take centres part, part + PT, ... of every tile, two at a time (two independent chains: each
+// dot product is still sequential over c).  Candidates of one thread come in ascending j, so strict < keeps the first
+// minimum; the PT lanes then agree on the lexicographic (distance, j) minimum.
+__global__ __launch_bounds__(KM_CHUNK) void kmw_assign_kernel(const double* __restrict__ Xc, int n, int d, int k,
+                                                             const double* __restrict__ C, const double* __restrict__ csq,
+                                                             int* __restrict__ labels, const int* __restrict__ labels_old,
+                                                             KmInfo* __restrict__ info, int TR, int KT) {
+  extern __shared__ __attribute__((aligned(16))) double km_lds[];
+  if (info->done) return;  // converged in an earlier iteration of this batch of launches
+  const int dp = d + 1, PT = KM_CHUNK / TR;
+  double* xs = km_lds;                  // [TR][dp]
+  double* cs = km_lds + (long)TR * dp;  // [KT][dp]
+  const int t = threadIdx.x;
+  const long r0 = (long)blockIdx.x * TR;
+  const int nr = (int)min((long)TR, n - r0);
+  for (int e = t; e < nr * d; e += KM_CHUNK) {
+    const int r = e / d, c = e - r * d;
+    xs[(long)r * dp + c] = Xc[(r0 + r) * d + c];
+  }
+  const int row = t / PT, part = t % PT;
+  const double* x = xs + (long)row * dp;
+  double best = 1.7976931348623157e308;
+  int lab = 0x7fffffff;
+  for (int j0 = 0; j0 < k; j0 += KT) {
+    const int kt = min(KT, k - j0);
+    __syncthreads();  // the row tile is staged / the previous centre tile is consumed
+    for (int e = t; e < kt * d; e += KM_CHUNK) {
+      const int jj = e / d, c = e - jj * d;
+      cs[(long)jj * dp + c] = C[(long)(j0 + jj) * d + c];
+    }
+    __syncthreads();
+    if (row >= nr) continue;
+    int jj = part;
+    for (; jj + PT < kt; jj += 2 * PT) {
+      const double* ca = cs + (long)jj * dp;
+      const double* cb = cs + (long)(jj + PT) * dp;
+      double da = 0.0, db = 0.0;
+      for (int c = 0; c < d; ++c) {
+        da = fma(x[c], ca[c], da);
+        db = fma(x[c], cb[c], db);
+      }
+      const double dista = csq[j0 + jj] - 2.0 * da;
+      if (lab == 0x7fffffff || dista < best) {  // strict <: the first minimum wins, as in sklearn
+        best = dista;
+        lab = j0 + jj;
+      }
+      const double distb = csq[j0 + jj + PT] - 2.0 * db;
+      if (distb < best) {
+        best = distb;
+        lab = j0 + jj + PT;
+      }
+    }
+    if (jj < kt) {
+      const double* ca = cs + (long)jj * dp;
+      double da = 0.0;
+      for (int c = 0; c < d; ++c) da = fma(x[c], ca[c], da);
+      const double dista = csq[j0 + jj] - 2.0 * da;
+      if (lab == 0x7fffffff || dista < best) {
+        best = dista;
+        lab = j0 + jj;
+      }
+    }
+  }
+  for (int o = 1; o < PT; o <<= 1) {  // the PT threads of a row are adjacent lanes of one wave (PT <= 16)
+    const double ob = __shfl_xor(best, o);
+    const int ol = __shfl_xor(lab, o);
+    if (ol != 0x7fffffff && (lab == 0x7fffffff || ob < best || (ob == best && ol < lab))) {
+      best = ob;
+      lab = ol;
+    }
+  }
+  if (part == 0 && row < nr) {
+    labels[r0 + row] = lab;
+    if (labels_old && labels_old[r0 + row] != lab) info->changed = 1;  // benign race: everybody writes 1
+  }
+}
+
+// M-step partials of one 256-row chunk (blockIdx.x) and one tile of DT columns (blockIdx.y).  LDS: sums [k][DT], labels.
+// The 256 threads are 256 / DT groups of DT columns; group g owns the clusters j = g mod 256 / DT, and every thread walks the
+// chunk's rows in order, so the sum of a (cluster, column) is taken as km_assign_kernel takes it.
+__global__ __launch_bounds__(KM_CHUNK) void kmw_partial_kernel(const double* __restrict__ Xc, int n, int d, int k,
+                                                              const int* __restrict__ labels, double* __restrict__ psum,
+                                                              int* __restrict__ pcnt, const KmInfo* __restrict__ info, int DT) {
+  extern __shared__ __attribute__((aligned(16))) double km_lds[];
+  if (info->done) return;
+  double* sS = km_lds;                                      // [k][DT]
+  int* sL = reinterpret_cast<int*>(sS + (long)k * DT);      // [KM_CHUNK]
+  const int t = threadIdx.x, c0 = blockIdx.y * DT;
+  const long r0 = (long)blockIdx.x * KM_CHUNK;
+  const int rows = (int)min((long)KM_CHUNK, n - r0);
+  const int gmask = KM_CHUNK / DT - 1, c = t % DT, g = t / DT;  // DT is a power of two
+  for (int e = t; e < k * DT; e += KM_CHUNK) sS[e] = 0.0;
+  sL[t] = t < rows ? labels[r0 + t] : -1;
+  __syncthreads();
+  if (c0 + c < d) {
+    const double* x = Xc + r0 * d + c0 + c;
+    for (int r = 0; r < rows; ++r) {
+      const int j = sL[r];
+      if ((j & gmask) == g && (unsigned)j < (unsigned)k) sS[(long)j * DT + c] += x[(long)r * d];
+    }
+  }
+  if (blockIdx.y == 0) {
+    for (int j = t; j < k; j += KM_CHUNK) {
+      int cnt = 0;
+      for (int r = 0; r < rows; ++r) cnt += (sL[r] == j);
+      pcnt[(long)blockIdx.x * k + j] = cnt;
+    }
+  }
+  __syncthreads();
+  for (int e = t; e < k * DT; e += KM_CHUNK) {
+    const int j = e / DT, cc = e - j * DT;
+    if (c0 + cc < d) psum[((long)blockIdx.x * k + j) * d + c0 + cc] = sS[e];
+  }
+}
+
+// M step, first half: element e of the centres from the chunk partials (chunks in order) -- km_update_kernel's arithmetic
+// with one thread per element over as many workgroups as k * d asks for.  shift[e] = new - old for the second half.
+__global__ __launch_bounds__(256) void kmw_centres_kernel(const double* __restrict__ psum, const int* __restrict__ pcnt,
+                                                         int nchunk, int k, int d, double* __restrict__ C,
+                                                         double* __restrict__ shift, KmInfo* __restrict__ info) {
+  if (info->done) return;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= k * d) return;
+  const int j = e / d;
+  int cnt = 0;
+  for (int ch = 0; ch < nchunk; ++ch) cnt += pcnt[(long)ch * k + j];
+  if (cnt == 0) info->empty = 1;
+  double s = 0.0;
+  for (int ch = 0; ch < nchunk; ++ch) s += psum[(long)ch * k * d + e];
+  const double nw = cnt > 0 ? s * (1.0 / (double)cnt) : C[e];
+  shift[e] = nw - C[e];
+  C[e] = nw;
+}
+
+// M step, second half: the total squared shift in km_update_kernel's order, the centre norms and the stopping rule.
+__global__ __launch_bounds__(1024) void kmw_finish_kernel(const double* __restrict__ shift, int k, int d,
+                                                         const double* __restrict__ C, double* __restrict__ csq, double tol,
+                                                         int first_iter, KmInfo* __restrict__ info) {
+  __shared__ double red[1024];
+  if (info->done) return;
+  const int t = threadIdx.x;
+  double acc = 0.0;  // this thread's share of the squared shift, elements in a fixed order
+  for (int e = t; e < k * d; e += 1024) {
+    const double df = shift[e];
+    acc += df * df;
+  }
+  red[t] = acc;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if (t < o) red[t] += red[t + o];
+    __syncthreads();
+  }
+  for (int j = t; j < k; j += 1024) {
+    double s = 0.0;
+    for (int c = 0; c < d; ++c) s += C[(long)j * d + c] * C[(long)j * d + c];
+    csq[j] = s;
+  }
+  if (t == 0) {
+    info->iters += 1;
+    if (!first_iter && info->changed == 0) info->done = 1;       // labels repeated: strict convergence
+    else if (red[0] <= tol) info->done = 2;                       // centres stopped moving
+    info->changed = 0;
+  }
+}
+
+// Tiles of the wide kernels: TR rows (32, else 16) and KT centres (a multiple of PT = 256 / TR, or all k) of the E step
+// within its budget; DT columns (64 / 32 / 16) of the M-step partials: the widest whose k x DT sums stay within 64 KiB
+// (several workgroups per CU), 16 beyond that (128 KiB at k = 1024), and no wider than d needs.
+static size_t kmw_partial_lds(int dt, int k) { return 8 * (size_t)k * dt + 4 * KM_CHUNK + 16; }
+static bool kmw_tiles(int d, int k, int* TR, int* KT, int* DT) {
+  if (d <= 0 || k <= 0 || d > 512 || k > 1024) return false;
+  const int cap = (int)(KMW_ASSIGN_LDS_DOUBLES / (d + 1));
+  bool ok = false;
+  for (int tr : {32, 16}) {
+    const int pt = KM_CHUNK / tr;
+    int kt = cap - tr;
+    if (kt >= k) kt = k;
+    else kt = (kt / pt) * pt;
+    if (kt >= 1 && (kt >= pt || kt == k)) {
+      *TR = tr;
+      *KT = kt;
+      ok = true;
+      break;
+    }
+  }
+  if (!ok) return false;
+  int dt = 16;
+  for (int w : {64, 32})
+    if (8 * (size_t)k * w <= 64 * 1024) {
+      dt = w;
+      break;
+    }
+  while (dt > 16 && dt / 2 >= d) dt /= 2;
+  *DT = dt;
+  return kmw_partial_lds(dt, k) <= KM_LDS_MAX;
+}
+
 }  // namespace mused
 
 using namespace mused;
 
 extern "C" {
+
+// workspace bytes for mused_kmeans_lloyd_wide; -1 for a shape it rejects
+long mused_kmeans_wide_ws_bytes(int n, int d, int k) {
+  if (n <= 0 || d <= 0 || k <= 0 || k > 1024 || d > 512 || k > n) return -1;
+  const long nchunk = (n + KM_CHUNK - 1) / KM_CHUNK;
+  return 8l * n * d + 8l * nchunk * k * d + 8l * k * d + 4l * nchunk * k + 8l * k + 8l * n + 4096;
+}
+
+// diagnostic: out[0..2] = {rows per tile, centres per tile of the E step, columns per tile of the M-step partials} that
+// mused_kmeans_lloyd_wide launches for (d, k).  LDS: 8 (out[0] + out[1]) (d + 1) and 8 k out[2] + 1040 bytes.
+int mused_kmeans_wide_tiles(int d, int k, int* out) {
+  MUSED_REQUIRE(out, "mused_kmeans_wide_tiles: bad arguments");
+  MUSED_REQUIRE(kmw_tiles(d, k, out, out + 1, out + 2), "mused_kmeans_wide_tiles: k <= 1024 and d <= 512 (got k = %d, d = %d)", k, d);
+  return MUSED_OK;
+}
+
+// mused_kmeans_lloyd for any k x d within k <= 1024, d <= 512: the same arguments, contract and -- where both accept the
+// shape -- bits.  ws: mused_kmeans_wide_ws_bytes(n, d, k) bytes.  BLOCKING.
+int mused_kmeans_lloyd_wide(const double* X, long ld, int n, int d, int k, const double* mean, double* centers, double tol,
+                            int max_iter, int* labels_out, int* info_out, void* ws, long ws_bytes, void* stream) {
+  MUSED_REQUIRE(X && mean && centers && labels_out && info_out && ws && n > 0 && d > 0 && k > 0 && k <= n && ld >= d,
+                "mused_kmeans_lloyd_wide: bad arguments");
+  MUSED_REQUIRE(k <= 1024 && d <= 512, "mused_kmeans_lloyd_wide: k <= 1024 and d <= 512 (got k = %d, d = %d)", k, d);
+  MUSED_REQUIRE(ws_bytes >= mused_kmeans_wide_ws_bytes(n, d, k), "mused_kmeans_lloyd_wide: workspace too small");
+  int TR = 0, KT = 0, DT = 0;
+  MUSED_REQUIRE(kmw_tiles(d, k, &TR, &KT, &DT), "mused_kmeans_lloyd_wide: no tile fits d = %d, k = %d", d, k);
+  hipStream_t st = (hipStream_t)stream;
+  const int nchunk = cdiv(n, KM_CHUNK);
+  char* w = (char*)ws;
+  double* Xc = (double*)w; w += 8l * n * d;
+  double* psum = (double*)w; w += 8l * nchunk * k * d;
+  double* shift = (double*)w; w += 8l * k * d;
+  double* csq = (double*)w; w += 8l * k;
+  int* pcnt = (int*)w; w += 4l * nchunk * k;
+  w = (char*)(((uintptr_t)w + 15) & ~(uintptr_t)15);
+  int* lab2 = (int*)w; w += 4l * n;
+  w = (char*)(((uintptr_t)w + 15) & ~(uintptr_t)15);
+  KmInfo* info = (KmInfo*)w;
+  static std::once_flag once;
+  static hipError_t aerr = hipSuccess;
+  std::call_once(once, [] {
+    aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(kmw_assign_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(8 * KMW_ASSIGN_LDS_DOUBLES));
+    if (aerr == hipSuccess)
+      aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(kmw_partial_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KM_LDS_MAX);
+  });
+  MUSED_CHECK_HIP(aerr);
+  const size_t lds_e = 8 * (size_t)(TR + KT) * (d + 1), lds_m = kmw_partial_lds(DT, k);
+  auto assign = [&](int* cur_, const int* old_, int want) {
+    hipLaunchKernelGGL(kmw_assign_kernel, dim3(cdiv(n, TR)), dim3(KM_CHUNK), lds_e, st, Xc, n, d, k, centers, csq, cur_, old_,
+                       info, TR, KT);
+    if (want)
+      hipLaunchKernelGGL(kmw_partial_kernel, dim3(nchunk, cdiv(d, DT)), dim3(KM_CHUNK), lds_m, st, Xc, n, d, k, cur_, psum,
+                         pcnt, info, DT);
+  };
+  MUSED_CHECK_HIP(hipMemsetAsync(info, 0, sizeof(KmInfo), st));
+  hipLaunchKernelGGL(km_center_kernel, dim3(cdiv((long)n * d, 256)), dim3(256), 0, st, X, ld, mean, n, d, Xc);
+  hipLaunchKernelGGL(km_csq_kernel, dim3(cdiv(k, 64)), dim3(64), 0, st, centers, k, d, csq);
+  KmInfo h;
+  memset(&h, 0, sizeof(h));
+  int* cur = labels_out;
+  int* old = lab2;
+  int it = 0;
+  while (it < max_iter && !h.done) {
+    const int batch = (max_iter - it) < 4 ? (max_iter - it) : 4;  // iterations between two reads of the stopping flag
+    for (int b = 0; b < batch; ++b, ++it) {
+      assign(cur, it > 0 ? old : (const int*)nullptr, 1);
+      hipLaunchKernelGGL(kmw_centres_kernel, dim3(cdiv(k * d, 256)), dim3(256), 0, st, psum, pcnt, nchunk, k, d, centers,
+                         shift, info);
+      hipLaunchKernelGGL(kmw_finish_kernel, dim3(1), dim3(1024), 0, st, shift, k, d, centers, csq, tol, it == 0 ? 1 : 0,
+                         info);
+      int* tmp = cur; cur = old; old = tmp;  // `old` now holds the labels of the iteration just queued
+    }
+    MUSED_LAUNCH_CHECK();
+    MUSED_CHECK_HIP(hipMemcpyAsync(&h, info, sizeof(h), hipMemcpyDeviceToHost, st));
+    MUSED_CHECK_HIP(hipStreamSynchronize(st));
+    if (h.empty) break;
+  }
+  // as in mused_kmeans_lloyd: iteration i (0-based) wrote labels_out when i is even
+  int* last = ((h.iters - 1) % 2 == 0) ? labels_out : lab2;
+  if (h.done != 1 && !h.empty) {
+    // not strictly converged: labels must match the final centres (one more E step, no update)
+    MUSED_CHECK_HIP(hipMemsetAsync(&info->done, 0, sizeof(int), st));
+    assign(labels_out, (const int*)nullptr, 0);
+    MUSED_LAUNCH_CHECK();
+  } else if (last != labels_out) {
+    MUSED_CHECK_HIP(hipMemcpyAsync(labels_out, last, 4l * n, hipMemcpyDeviceToDevice, st));
+  }
+  MUSED_CHECK_HIP(hipStreamSynchronize(st));
+  info_out[0] = h.iters; info_out[1] = h.done; info_out[2] = h.empty; info_out[3] = 0;
+  return MUSED_OK;
+}
 
 // workspace bytes for mused_kmeans_lloyd
 long mused_kmeans_ws_bytes(int n, int d, int k) {

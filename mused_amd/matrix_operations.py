@@ -379,9 +379,10 @@ def perform_clustering(matrix, n_clusters, seed):
 
 
 _KM_WS = {}
+_KM_LDS_KD = 8192   # mused_kmeans_lloyd's limit on k * d; mused_kmeans_lloyd_wide takes over beyond it
 # windows that perform_clustering_on_device did not finish on the device although it was asked to: seeded by scikit-learn
-# on the host (the seed kernel's ambiguity flag) or clustered by scikit-learn's KMeans (a cluster ran empty, k * d > 8192,
-# k > n)
+# on the host (the seed kernel's ambiguity flag) or clustered by scikit-learn's KMeans (a cluster ran empty, k > n,
+# k * d > 8192 together with k > 1024, d > 512 or MUSED_KMEANS_WIDE=host)
 km_fallbacks = 0
 _km_fallback_lock = threading.Lock()
 
@@ -425,17 +426,21 @@ def _km_workspace(key, nbytes, device):
 
 
 def _km_lloyd(Xd, n, d, k, mean_d, cen_d, tol, st):
-    """mused_kmeans_lloyd on stream st -> (int32 labels on the host, empty-cluster flag)."""
+    """The Lloyd iterations on stream st -> (int32 labels on the host, empty-cluster flag): mused_kmeans_lloyd where
+    k * d <= 8192 (all centres and sums in LDS), mused_kmeans_lloyd_wide (tiles; the same bits) beyond that."""
     import ctypes as C
 
     import torch
 
     from . import _lib
 
-    ws = _km_workspace((Xd.device, n, d, k, st.cuda_stream), _lib.lib().mused_kmeans_ws_bytes(n, d, k), Xd.device)
+    wide = k * d > _KM_LDS_KD
+    entry = "mused_kmeans_lloyd_wide" if wide else "mused_kmeans_lloyd"
+    nbytes = (_lib.lib().mused_kmeans_wide_ws_bytes if wide else _lib.lib().mused_kmeans_ws_bytes)(n, d, k)
+    ws = _km_workspace((Xd.device, n, d, k, st.cuda_stream), nbytes, Xd.device)
     labels = torch.empty(n, dtype=torch.int32, device=Xd.device)
     info = (C.c_int * 4)()
-    _lib.call("mused_kmeans_lloyd", _eng.ptr(Xd), Xd.stride(0), n, d, k, _eng.ptr(mean_d), _eng.ptr(cen_d),
+    _lib.call(entry, _eng.ptr(Xd), Xd.stride(0), n, d, k, _eng.ptr(mean_d), _eng.ptr(cen_d),
               tol, 300, _eng.ptr(labels), info, _eng.ptr(ws), ws.numel(), C.c_void_p(st.cuda_stream))
     return labels.cpu().numpy(), info[2]
 
@@ -466,14 +471,17 @@ def perform_clustering_on_device(emb_dev, n_clusters, seed, emb_host=None, strea
     device (sklearn:cluster/_kmeans.py `fit`: tolerance from the raw rows, X -= X.mean(0), row norms,
     `_init_centroids` -> `_kmeans_plusplus`, `_kmeans_single_lloyd`).  The host draws what k-means++ takes from
     `RandomState(seed)` (`kmeanspp_draws`: the draws do not depend on the rows); mused_kmeans_moments, mused_kmeans_seed
-    (csrc/kmeanspp.hip) and mused_kmeans_lloyd (csrc/kmeans.hip) run on the stream, and the host reads the tolerance with
-    the seed kernel's flag (16 bytes) and the labels.  No host copy of the embedding is made on that path.
+    (csrc/kmeanspp.hip) and mused_kmeans_lloyd -- mused_kmeans_lloyd_wide where k * d > 8192 -- (csrc/kmeans.hip) run on
+    the stream, and the host reads the tolerance with the seed kernel's flag (16 bytes) and the labels.  No host copy of
+    the embedding is made on that path.
     emb_dev: (n, d) fp64 CUDA tensor; emb_host: its host copy if the caller already has one (read only on a fallback).
     Returns int32 labels (NumPy).
     Fallbacks: the seed kernel's ambiguity flag (a decision of k-means++ within rounding) -> that window with
     scikit-learn's seeding on the host and the device Lloyd iterations; MUSED_KMEANS_SEED=host -> every window that way
-    (d > 512 too); a cluster that runs empty (sklearn relocates it), k * d > 8192 or k > n -> scikit-learn's KMeans.
-    Every fallback that was not asked for is counted in `km_fallbacks`."""
+    (d > 512 too, where k * d <= 8192); a cluster that runs empty (sklearn relocates it), k > n, or
+    k * d > 8192 with k > 1024 or d > 512 -> scikit-learn's KMeans.  MUSED_KMEANS_WIDE=host (read per call) sends every window with
+    k * d > 8192 to scikit-learn's KMeans, as before mused_kmeans_lloyd_wide existed.
+    Every fallback is counted in `km_fallbacks`, except the host seeding that MUSED_KMEANS_SEED=host asks for."""
     import ctypes as C
     import os
 
@@ -483,7 +491,8 @@ def perform_clustering_on_device(emb_dev, n_clusters, seed, emb_host=None, strea
 
     n, d = emb_dev.shape
     k = int(n_clusters)
-    if k * d > 8192 or k > n:
+    wide_on_host = k > 1024 or d > 512 or os.environ.get("MUSED_KMEANS_WIDE", "device") == "host"
+    if k > n or (k * d > _KM_LDS_KD and wide_on_host):
         _km_count_fallback()
         return perform_clustering(_km_host_copy(emb_dev, emb_host), k, seed)
     st = stream if stream is not None else torch.cuda.current_stream()
