@@ -446,6 +446,30 @@ long mused_dbscan_ws_bytes(long n);
 int mused_dbscan(const double* X, long n, int d, long ld, double eps, int min_samples, int* labels_out, int* info_out,
                  void* ws, long ws_bytes, void* stream);
 
+/* ---- DBSCAN_incr: incremental DBSCAN under insertions (main.py:87-91: IncrementalDBSCAN(eps, min_pts), insert per window),
+ * csrc/dbscan_incr.hip.  After every insert the labels of ALL rows inserted so far equal sklearn DBSCAN(eps, min_samples,
+ * metric="euclidean").fit_predict(those rows), numbering included (specification: mused_amd/dbscan_incr.py; pinned to
+ * scikit-learn's refit, NOT to the `incdbscan` package).  An insert runs the fp64 MFMA distance tiles of (new rows) x (all
+ * rows) for the counts, (rows that turned core) x (all rows) for the union-find, and for min_samples >= 3 (core rows whose
+ * root moved) x (all rows) and (new rows) x (all rows) for the border rows; never all x all, no n x n array or neighbour list.
+ * NOT enqueue-only: the call reads the dirty counts between its phases and returns after the stream has finished.
+ * X: ALL n0 + w rows, fp64 (pitch ld), the w new rows in place behind the n0 old ones; n0 + w <= 2^19.
+ * nrm (fp64), count, parent, best (int32): the caller's state arrays, n0 + w entries at least, kept from insert to insert
+ *   (what they hold for the n0 old rows is read; n0 = 0 starts a stream: nothing is read).  Rows may move to larger arrays
+ *   between inserts as long as their contents move with them.
+ * chunk: rows per staging panel, a multiple of 128 in [128, 65536].
+ * labels_out: n0 + w int32 (DEVICE), -1 = noise.  info_out (HOST, 6 int32) = {flags, clusters, core rows, dirty rows,
+ *   rows that turned core, core rows whose root moved}; dirty rows is the sum of the last two.  Flags as mused_dbscan: 1
+ *   some pair of this insert lies within tau of eps^2, 2 a new row is not finite.  With either flag the call stops behind
+ *   the counting pass: labels_out is NOT written and the state is spent (refit on the host, start a new state).
+ * ws: mused_dbscan_incr_ws_bytes(capacity, d, chunk) bytes for any capacity >= n0 + w (16 capacity + 8 ceil(capacity / 128)
+ *   + 8 chunk (d rounded up to even) and alignment; -1 for capacity outside [1, 2^19] or a bad d or chunk).  Scratch only:
+ *   it carries nothing from insert to insert.  Outside these limits the call returns an error and writes nothing. */
+long mused_dbscan_incr_ws_bytes(long capacity, int d, long chunk);
+int mused_dbscan_incr_insert(const double* X, long ld, int d, double* nrm, int* count, int* parent, int* best, long n0, long w,
+                             double eps, int min_samples, long chunk, int* labels_out, int* info_out, void* ws, long ws_bytes,
+                             void* stream);
+
 /* ---- HDBSCAN_batch: the exact Euclidean minimum spanning tree of n fp64 rows, csrc/emst.hip.  For
  * sklearn.cluster.HDBSCAN(min_samples <= 2, metric="euclidean") the mutual-reachability distance is the distance itself, so
  * this tree is the one its Prim loop builds; the sequential rest (Prim's edge order, single-linkage and condensed tree,

@@ -39,6 +39,7 @@
 // scikit-learn itself: exact labels or a flag, never labels that hang on the last bits.
 #include "gemm_f64.h"
 #include "internal.h"
+#include "dbscan_common.h"
 #include "union_find.h"
 
 extern "C" int mused_row_sq_norms(const void* X, int dtype, long n, int d, long ld, double* out, void* stream);
@@ -46,10 +47,6 @@ extern "C" int mused_row_sq_norms(const void* X, int dtype, long n, int d, long 
 namespace mused {
 
 constexpr int DB_COUNT = 0, DB_UNION = 1, DB_BORDER = 2;
-constexpr int DB_NONE = 0x7fffffff;        // root of a row that no cluster has reached
-constexpr int DB_HAS_CORE = 1, DB_HAS_NONCORE = 2;
-constexpr long DB_MAX_ROWS = 1l << 19;     // 4096 row tiles: the tile grid, 4096 * 2049 workgroups of 256 threads, stays below the
-                                           // 2^32 threads one launch may hold (reached near 740,000 rows)
 
 struct DbArgs {
   const double* nrm;  // [n] squared norms
@@ -236,33 +233,6 @@ __global__ void dbscan_flatten_kernel(DbArgs a, int n) {
   a.root[i] = x;
 }
 
-// rank[i] = number of roots (core rows with root[i] == i) below i; one workgroup walks the rows in chunks of 1024 consecutive
-// ones (coalesced): wave ballots give the position inside a wave, the 16 wave totals and a running carry the rest
-constexpr int DB_RANK_THREADS = 1024;
-__global__ __launch_bounds__(DB_RANK_THREADS) void dbscan_rank_kernel(DbArgs a, int* __restrict__ rank, int n) {
-  __shared__ int wtot[DB_RANK_THREADS / 64];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  int carry = 0;
-  for (int base = 0; base < n; base += DB_RANK_THREADS) {
-    const int i = base + t;
-    const bool is_root = i < n && a.root[i] == i;
-    const unsigned long long bal = __ballot(is_root);
-    if (lane == 0) wtot[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < DB_RANK_THREADS / 64; ++w) {
-      const int c = wtot[w];
-      total += c;
-      before += w < wave ? c : 0;
-    }
-    if (i < n) rank[i] = carry + before + __popcll(bal & ((1ull << lane) - 1ull));
-    carry += total;
-    __syncthreads();  // wtot is rewritten by the next chunk
-  }
-  if (t == 0) a.info[1] = carry;
-}
-
 __global__ void dbscan_labels_kernel(DbArgs a, const int* __restrict__ rank, int* __restrict__ labels, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -357,7 +327,7 @@ int mused_dbscan(const double* X, long n, int d, long ld, double eps, int min_sa
   hipLaunchKernelGGL(dbscan_core_kernel, rows, blk, 0, st, a, (int)n, tiles);
   if ((rc = db_tile_launch<DB_UNION>(g, a, vec, tiles, st))) return rc;
   hipLaunchKernelGGL(dbscan_flatten_kernel, rows, blk, 0, st, a, (int)n);
-  hipLaunchKernelGGL(dbscan_rank_kernel, dim3(1), dim3(DB_RANK_THREADS), 0, st, a, w.rank, (int)n);
+  hipLaunchKernelGGL(dbscan_rank_kernel, dim3(1), dim3(DB_RANK_THREADS), 0, st, w.root, w.rank, w.info, (int)n);
   if ((rc = db_tile_launch<DB_BORDER>(g, a, vec, tiles, st))) return rc;
   hipLaunchKernelGGL(dbscan_labels_kernel, rows, blk, 0, st, a, w.rank, labels_out, (int)n);
   MUSED_LAUNCH_CHECK();

@@ -1,0 +1,412 @@
+// Incremental DBSCAN under insertions (the reference's DBSCAN_incr approach, main.py:87-91) on fp64 rows: after every insert
+// the labels of ALL rows inserted so far equal sklearn.cluster.DBSCAN(eps, min_samples).fit_predict(those rows), numbering
+// included -- the rule of mused_amd/dbscan_incr.py (pinned to scikit-learn's refit by the tests; NOT pinned to the `incdbscan`
+// package, which is not available).  An insert costs (rows it touches) x (all rows) distances, never all x all.
+//
+// State, owned by the caller, over the n rows so far: nrm[i], count[i] = |N(i)|, parent[] (union-find over the core rows,
+// parent[x] <= x: a component's root is its smallest core index), best[i] (a non-core row's smallest root among its core
+// neighbours as of the last insert, DB_NONE without one).  Inserting rows n0 .. n0 + w - 1:
+//
+//   norms, dbi_begin  nrm of the new rows; parent / count / best of the new slice; rootb[i] = find(i) for the rows that are
+//                     core BEFORE the insert, -1 for the others; a non-finite norm raises flag 2
+//   tile pass COUNT   new rows x all rows: count[new] += |N(new)| (both orientations of a new-new pair lie in the rectangle,
+//                     so the row side counts them, once each), count[old] += the new rows within eps (column side, old
+//                     columns only); a pair i != j with |d2 - eps^2| <= tau(i, j) raises flag 1 (tau: csrc/dbscan.hip)
+//   dbi_core          tile flags, the number of core rows, dirtyA = rows that are core now and were not (old rows among
+//                     them), compacted into a list                                        [the host reads flags, |dirtyA|]
+//   tile pass UNION   dirtyA x all rows: every core-core edge within eps^2 is united (db_unite, the larger root under the
+//                     smaller).  Two old clusters merge here through an old row that has only now turned core.
+//   dbi_resolve       core rows: root[i] = find(i); dirtyB = those whose root differs from rootb (every newly core row
+//                     included), compacted.  Non-core rows: best = find(best): roots only ever decrease, so a stale
+//                     minimum resolves to a root that is still <= the root of every neighbour that did not move
+//                                                                                                 [the host reads |dirtyB|]
+//   tile pass BCOL    dirtyB x all rows: best[b] = min(best[b], root[c]) for the non-core b within eps^2 of c (atomicMin)
+//   tile pass BROW    new rows x all rows: a new non-core row gets the smallest root among its core neighbours
+//                     (both border passes are skipped for min_samples <= 2: a non-core row then has no neighbour)
+//   dbscan_rank, dbi_labels   rank[r] = number of roots below r; core rows rank[root], the others rank[best] or -1
+//
+// The A side of a tile pass is a contiguous slice of the rows (COUNT, BROW) or a staging panel into which the dirty rows
+// are gathered, with their row ids beside it (UNION, BCOL); either is walked in chunks of `chunk` rows.  The B side is all
+// rows.  The tile is the fp64 MFMA tile of gemm_f64.h and the epilogues are those of csrc/dbscan.hip, one-sided.  The
+// distance of a pair has the same bits in every pass and in either orientation (the same products summed in the same
+// order), so the passes agree with one another.  No n x n array, no neighbour list, no pass over all x all.
+// Every write to global memory is a vector store or a device-scope vector atomic; kernel boundaries are the only
+// synchronisation between workgroups.
+#include "gemm_f64.h"
+#include "internal.h"
+#include "dbscan_common.h"
+#include "union_find.h"
+
+extern "C" int mused_row_sq_norms(const void* X, int dtype, long n, int d, long ld, double* out, void* stream);
+
+namespace mused {
+
+constexpr int DBI_COUNT = 0, DBI_UNION = 1, DBI_BCOL = 2, DBI_BROW = 3;
+constexpr long DBI_MAX_CHUNK = 1l << 16;  // 512 x 4096 tiles of 256 threads: far below the 2^32 threads of one launch
+
+struct DbiArgs {
+  const double* nrm;
+  int *count, *parent, *best;
+  const int* root;    // [n] BCOL / BROW: final root of a core row, DB_NONE for the others
+  const int* ids;     // row ids of the A rows (staging panel); nullptr: a_base + local row (slice)
+  const int* tflag;   // [tiles of all rows] DB_HAS_CORE | DB_HAS_NONCORE
+  const int* aflag;   // BROW: the same per 128-row tile of the new slice, from this chunk's first tile on
+  int* info;          // {flags, clusters, core rows, -, |dirtyA|, |dirtyB|, -, -}
+  double eps2, ctau, etau;
+  int min_samples, a_base, n0;
+};
+
+// A rows [I * 128, ...) of the chunk against rows [J * 128, ...) of all rows; consecutive workgroups (one XCD's share) walk
+// the A tiles of one B tile, so the chunk stays in L2 while the rows stream by once.  Grid: tiles_a * tiles_b.
+template <int PASS, bool VEC>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_incr_tile_kernel(GemmArgs g, DbiArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int tiles_a = (g.M + GEMM_BM - 1) / GEMM_BM;
+  const int e = xcd_remap(blockIdx.x, gridDim.x);
+  const int J = e / tiles_a, I = e - J * tiles_a;
+  if (PASS == DBI_UNION && !(a.tflag[J] & DB_HAS_CORE)) return;
+  if (PASS == DBI_BCOL && !(a.tflag[J] & DB_HAS_NONCORE)) return;
+  if (PASS == DBI_BROW && (!(a.tflag[J] & DB_HAS_CORE) || !(a.aflag[I] & DB_HAS_NONCORE))) return;
+  const int m0 = I * GEMM_BM, n0 = J * GEMM_BN;
+  v4f64 acc[4][4];
+  gemm_tile_mainloop<double, double, true, true, VEC>(g, reinterpret_cast<const double*>(g.A), reinterpret_cast<const double*>(g.B),
+                                                      m0, n0, 0, g.K, smem, acc);
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wr = wave >> 1, wc = wave & 1, kq = lane >> 4, li = lane & 15;
+  const int ma = g.M, n = g.N;
+
+  // Rows and columns beyond the end read the last entry and are masked (no branch around a load: csrc/dbscan.hip)
+  double ncol[4];
+  int ccol[4];  // COUNT: new rows seen in the column; UNION: cached root; BCOL: running min; BROW: the core column's root
+  bool cok[4], corec[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = n0 + wc * 64 + j * 16 + li;
+    const int cc = min(col, n - 1);
+    cok[j] = col < n;
+    ncol[j] = a.nrm[cc];
+    corec[j] = (PASS != DBI_COUNT) && cok[j] && a.count[cc] >= a.min_samples;
+    if (PASS == DBI_COUNT) ccol[j] = 0;
+    if (PASS == DBI_UNION) ccol[j] = corec[j] ? db_find(a.parent, col) : -1;
+    if (PASS == DBI_BCOL) ccol[j] = DB_NONE;
+    if (PASS == DBI_BROW) ccol[j] = corec[j] ? a.root[cc] : DB_NONE;
+  }
+  int rsum[16];  // COUNT / BROW: the row's count / minimum over this wave's 64 columns
+  int rids[16];
+  double slack = __longlong_as_double(0x7ff0000000000000ll);  // COUNT: smallest |d2 - eps^2| - tau of the patch
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int lrow = m0 + wr * 64 + i * 16 + kq + 4 * r;
+      const bool rok = lrow < ma;
+      const int lr = min(lrow, ma - 1);
+      const int rid = a.ids ? a.ids[lr] : a.a_base + lr;  // (a valid row also where rok is false)
+      rids[i * 4 + r] = rid;
+      const double nrow = a.nrm[rid];
+      // UNION, BCOL: every A row is core.  BROW: only the non-core rows of the slice take part
+      const bool rtake = rok && (PASS != DBI_BROW || a.count[rid] < a.min_samples);
+      const int rroot = (PASS == DBI_BCOL) ? a.root[rid] : DB_NONE;
+      int racc = (PASS == DBI_COUNT) ? 0 : (PASS == DBI_UNION ? -1 : DB_NONE);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int col = n0 + wc * 64 + j * 16 + li;
+        const bool ok = rtake && cok[j];
+        const double s = nrow + ncol[j];
+        const double dd = s - 2.0 * acc[i][j][r];
+        const bool same = (rid == col);
+        const bool in = ok && (same || dd <= a.eps2);
+        if (PASS == DBI_COUNT) {
+          slack = fmin(slack, (ok && !same) ? fabs(dd - a.eps2) - (a.ctau * s + a.etau) : slack);
+          racc += in ? 1 : 0;
+          ccol[j] += in ? 1 : 0;
+        }
+        if (PASS == DBI_UNION) {
+          if (in && !same && corec[j]) {
+            if (racc < 0) racc = db_find(a.parent, rid);
+            if (racc != ccol[j]) racc = ccol[j] = db_unite(a.parent, racc, ccol[j]);
+          }
+        }
+        if (PASS == DBI_BCOL) ccol[j] = (in && !corec[j]) ? min(ccol[j], rroot) : ccol[j];
+        if (PASS == DBI_BROW) racc = (in && corec[j]) ? min(racc, ccol[j]) : racc;
+      }
+      if (PASS == DBI_COUNT || PASS == DBI_BROW) {
+        // the 16 lanes that share kq hold the 64 columns of this row in this wave
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {
+          const int x = __shfl_xor(racc, o);
+          racc = (PASS == DBI_COUNT) ? racc + x : min(racc, x);
+        }
+        rsum[i * 4 + r] = racc;
+        // the row's results are complete HERE (csrc/dbscan.hip: otherwise the distances of the whole patch stay alive)
+        if (PASS == DBI_BROW) asm volatile("" : "+v"(rsum[i * 4 + r]));
+        if (PASS == DBI_COUNT) asm volatile("" : "+v"(slack), "+v"(ccol[0]), "+v"(ccol[1]), "+v"(ccol[2]), "+v"(ccol[3]), "+v"(rsum[i * 4 + r]));
+      }
+      if (PASS == DBI_BCOL) asm volatile("" : "+v"(ccol[0]), "+v"(ccol[1]), "+v"(ccol[2]), "+v"(ccol[3]));
+    }
+  }
+  if (PASS == DBI_COUNT || PASS == DBI_BROW) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int lrow = m0 + wr * 64 + (q >> 2) * 16 + kq + 4 * (q & 3);
+      if (li == 0 && lrow < ma) {
+        if (PASS == DBI_COUNT && rsum[q]) atomicAdd(a.count + rids[q], rsum[q]);
+        if (PASS == DBI_BROW && rsum[q] != DB_NONE) atomicMin(a.best + rids[q], rsum[q]);
+      }
+    }
+  }
+  if (PASS == DBI_COUNT || PASS == DBI_BCOL) {
+    // the 4 lanes that share li hold the 64 rows of this column in this wave
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      int v = ccol[j];
+#pragma unroll
+      for (int o = 16; o < 64; o <<= 1) {
+        const int x = __shfl_xor(v, o);
+        v = (PASS == DBI_COUNT) ? v + x : min(v, x);
+      }
+      const int col = n0 + wc * 64 + j * 16 + li;
+      if (kq == 0 && col < n) {
+        if (PASS == DBI_COUNT && v && col < a.n0) atomicAdd(a.count + col, v);  // (new columns: counted from their row side)
+        if (PASS == DBI_BCOL && v != DB_NONE) atomicMin(a.best + col, v);
+      }
+    }
+  }
+  if (PASS == DBI_COUNT) {
+    if (__ballot(slack <= 0.0) && lane == 0) atomicOr(a.info, 1);
+  }
+}
+
+// (behind the memset of info)
+__global__ void dbi_begin_kernel(DbiArgs a, int* __restrict__ rootb, int n0, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool bad = false;
+  if (i < n0) {
+    rootb[i] = a.count[i] >= a.min_samples ? db_find(a.parent, i) : -1;
+  } else if (i < n) {
+    a.parent[i] = i;
+    a.count[i] = 0;
+    a.best[i] = DB_NONE;
+    rootb[i] = -1;
+    bad = !(fabs(a.nrm[i]) <= 1.7976931348623157e308);  // NaN or inf (an overflowing norm of finite values included)
+  }
+  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(a.info, 2);
+}
+
+// appends i to list[] (counter: *cnt) for the lanes with `take`: one atomic per wave
+__device__ __forceinline__ void dbi_append(bool take, int i, int* list, int* cnt) {
+  const unsigned long long bal = __ballot(take);
+  if (!bal) return;
+  const int lane = threadIdx.x & 63;
+  int base = 0;
+  if (lane == 0) base = atomicAdd(cnt, __popcll(bal));
+  base = __shfl(base, 0);
+  if (take) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = i;
+}
+
+__global__ void dbi_core_kernel(DbiArgs a, const int* __restrict__ rootb, int* __restrict__ list, int* __restrict__ tflag,
+                                int* __restrict__ aflag, int n0, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int tiles = (n + GEMM_BM - 1) / GEMM_BM, tiles_new = (n - n0 + GEMM_BM - 1) / GEMM_BM;
+  if (i < tiles) {
+    int f = 0;
+    const int hi = min(n, (i + 1) * GEMM_BM);
+    for (int r = i * GEMM_BM; r < hi; ++r) f |= (a.count[r] >= a.min_samples) ? DB_HAS_CORE : DB_HAS_NONCORE;
+    tflag[i] = f;
+  }
+  if (i < tiles_new) {
+    int f = 0;
+    const int hi = min(n, n0 + (i + 1) * GEMM_BM);
+    for (int r = n0 + i * GEMM_BM; r < hi; ++r) f |= (a.count[r] >= a.min_samples) ? DB_HAS_CORE : DB_HAS_NONCORE;
+    aflag[i] = f;
+  }
+  const bool core = i < n && a.count[i] >= a.min_samples;
+  const int c = __popcll(__ballot(core));
+  if (c && (threadIdx.x & 63) == 0) atomicAdd(a.info + 2, c);
+  dbi_append(core && rootb[i] < 0, i, list, a.info + 4);
+}
+
+__global__ void dbi_gather_kernel(const double* __restrict__ X, long ld, int d, const int* __restrict__ ids, int m,
+                                  double* __restrict__ panel, int ldp) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)m * d) return;
+  const int r = (int)(t / d), k = (int)(t - (long)r * d);
+  panel[(long)r * ldp + k] = X[(long)ids[r] * ld + k];
+}
+
+__global__ void dbi_resolve_kernel(DbiArgs a, const int* __restrict__ rootb, int* __restrict__ root, int* __restrict__ list, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool moved = false;
+  if (i < n) {
+    if (a.count[i] >= a.min_samples) {
+      const int r = db_find(a.parent, i);
+      root[i] = r;
+      moved = r != rootb[i];
+    } else {
+      root[i] = DB_NONE;
+      const int b = a.best[i];
+      if (b != DB_NONE) a.best[i] = db_find(a.parent, b);
+    }
+  }
+  dbi_append(moved, i, list, a.info + 5);
+}
+
+__global__ void dbi_labels_kernel(const int* __restrict__ root, const int* __restrict__ best, const int* __restrict__ rank,
+                                  int* __restrict__ labels, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int r = root[i] != DB_NONE ? root[i] : best[i];
+  labels[i] = (r == DB_NONE) ? -1 : rank[r];
+}
+
+struct DbiWs {
+  int *rootb, *root, *rank, *list, *tflag, *aflag, *info;
+  double* panel;
+};
+
+static inline int dbi_ldp(int d) { return (d + 1) & ~1; }  // even: the panel's rows stay 16-byte aligned
+
+static size_t dbi_layout(long n, int d, long chunk, char* base, DbiWs* ws) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += (bytes + 255) & ~(size_t)255;
+    return p;
+  };
+  const long tiles = (n + GEMM_BM - 1) / GEMM_BM;
+  char* p0 = take(4 * (size_t)n);
+  char* p1 = take(4 * (size_t)n);
+  char* p2 = take(4 * (size_t)n);
+  char* p3 = take(4 * (size_t)n);
+  char* p4 = take(4 * (size_t)tiles);
+  char* p5 = take(4 * (size_t)tiles);
+  char* p6 = take(32);
+  char* p7 = take(8 * (size_t)chunk * dbi_ldp(d));
+  if (ws) {
+    ws->rootb = (int*)p0; ws->root = (int*)p1; ws->rank = (int*)p2; ws->list = (int*)p3; ws->tflag = (int*)p4;
+    ws->aflag = (int*)p5; ws->info = (int*)p6; ws->panel = (double*)p7;
+  }
+  return off;
+}
+
+static bool dbi_shape_ok(long n, int d, long chunk) {
+  return n >= 1 && n <= DB_MAX_ROWS && d >= 1 && d < (1 << 20) && chunk >= GEMM_BM && chunk <= DBI_MAX_CHUNK && chunk % GEMM_BM == 0;
+}
+
+template <int PASS>
+static int dbi_tile_launch(const GemmArgs& g, const DbiArgs& a, bool vec, hipStream_t st) {
+  static std::once_flag once[2];
+  static hipError_t err[2];
+  const int v = vec ? 1 : 0;
+  std::call_once(once[v], [&] {
+    const void* fn = vec ? (const void*)dbscan_incr_tile_kernel<PASS, true> : (const void*)dbscan_incr_tile_kernel<PASS, false>;
+    err[v] = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
+  });
+  MUSED_CHECK_HIP(err[v]);
+  const dim3 grid(cdiv(g.M, GEMM_BM) * cdiv(g.N, GEMM_BN)), blk(GEMM_THREADS);
+  if (vec) hipLaunchKernelGGL((dbscan_incr_tile_kernel<PASS, true>), grid, blk, GEMM_LDS_BYTES, st, g, a);
+  else hipLaunchKernelGGL((dbscan_incr_tile_kernel<PASS, false>), grid, blk, GEMM_LDS_BYTES, st, g, a);
+  MUSED_LAUNCH_CHECK();
+  return MUSED_OK;
+}
+
+// one pass over the new slice (list == nullptr) or over list[0 .. count) through the staging panel, in chunks
+template <int PASS>
+static int dbi_pass(const double* X, long ld, int d, long n, long n0, long count, const int* list, long chunk, const DbiWs& w,
+                    DbiArgs a, bool vec, hipStream_t st) {
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.B = X; g.ldb = ld; g.N = (int)n; g.K = d;
+  for (long c0 = 0; c0 < count; c0 += chunk) {
+    const long m = count - c0 < chunk ? count - c0 : chunk;
+    g.M = (int)m;
+    if (list) {
+      const long total = m * d;
+      hipLaunchKernelGGL(dbi_gather_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, X, ld, d, list + c0, (int)m, w.panel, dbi_ldp(d));
+      g.A = w.panel; g.lda = dbi_ldp(d);
+      a.ids = list + c0;
+    } else {
+      g.A = X + (n0 + c0) * ld; g.lda = ld;
+      a.ids = nullptr;
+      a.a_base = (int)(n0 + c0);
+      a.aflag = w.aflag + c0 / GEMM_BM;
+    }
+    int rc;
+    if ((rc = dbi_tile_launch<PASS>(g, a, vec, st))) return rc;
+  }
+  return MUSED_OK;
+}
+
+}  // namespace mused
+
+using namespace mused;
+
+extern "C" {
+
+// bytes of workspace mused_dbscan_incr_insert needs while the rows number at most `capacity`
+long mused_dbscan_incr_ws_bytes(long capacity, int d, long chunk) {
+  if (!dbi_shape_ok(capacity, d, chunk)) return -1;
+  return (long)dbi_layout(capacity, d, chunk, nullptr, nullptr);
+}
+
+// One insert (head of this file).  X: ALL n0 + w rows (pitch ld), the new ones already in place behind the n0 old ones.
+// Synchronises the stream (it reads the dirty counts between the phases): not enqueue-only, not for stream capture.
+int mused_dbscan_incr_insert(const double* X, long ld, int d, double* nrm, int* count, int* parent, int* best, long n0, long w,
+                             double eps, int min_samples, long chunk, int* labels_out, int* info_out, void* ws, long ws_bytes,
+                             void* stream) {
+  MUSED_REQUIRE(X && nrm && count && parent && best && labels_out && info_out && ws, "mused_dbscan_incr_insert: null argument");
+  MUSED_REQUIRE(n0 >= 0 && w >= 1 && n0 <= DB_MAX_ROWS && w <= DB_MAX_ROWS && dbi_shape_ok(n0 + w, d, chunk) && ld >= d,
+                "mused_dbscan_incr_insert: bad shape (n0=%ld w=%ld d=%d ld=%ld chunk=%ld; at most 2^19 rows in all, chunk a "
+                "multiple of 128 in [128, 65536])", n0, w, d, ld, chunk);
+  MUSED_REQUIRE(eps > 0.0 && eps * eps < 1.7976931348623157e308 && min_samples >= 1,
+                "mused_dbscan_incr_insert: need eps > 0 (finite square), min_samples >= 1");
+  const long n = n0 + w;
+  MUSED_REQUIRE(ws_bytes >= (long)dbi_layout(n, d, chunk, nullptr, nullptr), "mused_dbscan_incr_insert: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  DbiWs k;
+  dbi_layout(n, d, chunk, (char*)ws, &k);
+  const double eps2 = eps * eps;
+  const double ulp = eps2 * 2.220446049250313e-16 > 4.9406564584124654e-324 ? eps2 * 2.220446049250313e-16 : 4.9406564584124654e-324;
+  DbiArgs a{nrm, count, parent, best, k.root, nullptr, k.tflag, k.aflag, k.info, eps2, 2.0 * (d + 8) * 2.220446049250313e-16,
+            4.0 * ulp, min_samples, (int)n0, (int)n0};
+  const bool vec = vec_ok<double>(X, ld, 0);
+  const dim3 rows(cdiv(n, 256)), blk(256);
+  int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int rc;
+  MUSED_CHECK_HIP(hipMemsetAsync(k.info, 0, 32, st));
+  if ((rc = mused_row_sq_norms(X + n0 * ld, MUSED_F64, w, d, ld, nrm + n0, stream))) return rc;
+  hipLaunchKernelGGL(dbi_begin_kernel, rows, blk, 0, st, a, k.rootb, (int)n0, (int)n);
+  if ((rc = dbi_pass<DBI_COUNT>(X, ld, d, n, n0, w, nullptr, chunk, k, a, vec, st))) return rc;
+  hipLaunchKernelGGL(dbi_core_kernel, rows, blk, 0, st, a, k.rootb, k.list, k.tflag, k.aflag, (int)n0, (int)n);
+  MUSED_LAUNCH_CHECK();
+  MUSED_CHECK_HIP(hipMemcpyAsync(info, k.info, 32, hipMemcpyDeviceToHost, st));
+  MUSED_CHECK_HIP(hipStreamSynchronize(st));
+  if (info[0]) {  // a flag: the counts no longer decide the labels (or a row is not finite); nothing further is computed
+    memcpy(info_out, info, 12);
+    info_out[3] = info_out[4] = info_out[5] = 0;
+    return MUSED_OK;
+  }
+  const long n_a = info[4];
+  if ((rc = dbi_pass<DBI_UNION>(X, ld, d, n, n0, n_a, k.list, chunk, k, a, vec, st))) return rc;
+  hipLaunchKernelGGL(dbi_resolve_kernel, rows, blk, 0, st, a, k.rootb, k.root, k.list, (int)n);
+  MUSED_LAUNCH_CHECK();
+  if (min_samples > 2) {
+    MUSED_CHECK_HIP(hipMemcpyAsync(info, k.info, 32, hipMemcpyDeviceToHost, st));
+    MUSED_CHECK_HIP(hipStreamSynchronize(st));
+    if ((rc = dbi_pass<DBI_BCOL>(X, ld, d, n, n0, (long)info[5], k.list, chunk, k, a, vec, st))) return rc;
+    if ((rc = dbi_pass<DBI_BROW>(X, ld, d, n, n0, w, nullptr, chunk, k, a, vec, st))) return rc;
+  }
+  hipLaunchKernelGGL(dbscan_rank_kernel, dim3(1), dim3(DB_RANK_THREADS), 0, st, k.root, k.rank, k.info, (int)n);
+  hipLaunchKernelGGL(dbi_labels_kernel, rows, blk, 0, st, k.root, best, k.rank, labels_out, (int)n);
+  MUSED_LAUNCH_CHECK();
+  MUSED_CHECK_HIP(hipMemcpyAsync(info, k.info, 32, hipMemcpyDeviceToHost, st));
+  MUSED_CHECK_HIP(hipStreamSynchronize(st));
+  memcpy(info_out, info, 12);
+  info_out[3] = info[4] + info[5];
+  info_out[4] = info[4];
+  info_out[5] = info[5];
+  return MUSED_OK;
+}
+
+}  // extern "C"

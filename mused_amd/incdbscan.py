@@ -1,0 +1,158 @@
+"""`IncrementalDBSCAN(eps, min_pts)` with the two calls the reference's DBSCAN_incr approach makes (main.py:87-91:
+`clusterer.insert(reduced).get_cluster_labels(reduced)` per window), on the device (csrc/dbscan_incr.hip).
+
+What the labels are: after every insert, those of sklearn.cluster.DBSCAN(eps, min_samples=min_pts).fit_predict on all rows
+inserted so far, numbering included (the rule and why it is exact: mused_amd/dbscan_incr.py).  That refit is what the tests
+pin the class to, bit for bit.  It is NOT pinned to the `incdbscan` package the reference imports: the package is not
+available here, so its cluster numbers, its float labels and its choice for a border row between clusters are unchecked.
+The labels of rows inserted earlier may change with a later insert (clusters merge, numbers shift), as a refit's would.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import matrix_operations as mo
+from .dbscan import FLAG_AMBIGUOUS, FLAG_NONFINITE
+from .engine import ptr
+
+MAX_ROWS = mo.DBSCAN_MAX_ROWS   # csrc/dbscan_incr.hip: the limit of mused_dbscan
+_FIRST_CAPACITY = 4096
+
+
+class IncrementalDBSCAN:
+    """eps, min_pts: as DBSCAN's eps, min_samples.  chunk: rows per staging panel of the kernels (a multiple of 128).
+    stream: the kernels run on it (default: the current stream at each insert); an insert returns after they have finished.
+
+    The state tensors (rows, norms, counts, union-find, border minima) are owned here and grow by doubling up to 2^19 rows.
+    Host mode, in which every insert refits scikit-learn's DBSCAN on a host copy of all rows, is entered for good
+      * by an insert whose kernel raises the ambiguity flag (some pair lies within rounding of eps: mused_amd/dbscan.py); that
+        insert and every later one is counted in `matrix_operations.dbscan_incr_fallbacks`;
+      * uncounted, under MUSED_DBSCAN=host (read at construction) and beyond 2^19 rows.
+    A non-finite row raises scikit-learn's ValueError("Input contains NaN or infinity."); the object then refuses inserts."""
+
+    def __init__(self, eps=1.0, min_pts=5, chunk=4096, stream=None):
+        if not (float(eps) > 0.0) or int(min_pts) < 1:
+            raise ValueError("eps must be > 0 and min_pts >= 1")
+        self.eps, self.min_pts, self.chunk = float(eps), int(min_pts), int(chunk)
+        self._stream = stream
+        self.n, self.d = 0, None
+        self._host_mode = os.environ.get("MUSED_DBSCAN", "device") == "host" or not self.eps < 1e150
+        self._counted = False      # host mode entered through the flag: inserts are counted
+        self._host_rows = None
+        self._dead = False
+        self._X = self._nrm = self._count = self._parent = self._best = self._labels = self._ws = None
+        self._host_labels = None
+        self._last, self._last_lo = None, 0
+        self.last_info = None      # device mode: {flags, clusters, core rows, dirty rows, turned core, root moved}
+        self.dirty = []            # per device insert (rows that turned core, core rows whose root moved)
+
+    # ---- state ---------------------------------------------------------------------------------
+    def _grow(self, n, dev):
+        cap = 0 if self._X is None else self._X.shape[0]
+        if n <= cap:
+            return
+        new = max(_FIRST_CAPACITY, cap)
+        while new < n:
+            new *= 2
+        new = min(new, MAX_ROWS)
+        nbytes = int(_lib.lib().mused_dbscan_incr_ws_bytes(new, self.d, self.chunk))
+        if nbytes < 0:
+            raise ValueError(f"IncrementalDBSCAN: d = {self.d} or chunk = {self.chunk} is not taken (chunk: a multiple of 128 "
+                             "in [128, 65536])")
+
+        def moved(old, shape, dtype):
+            t = torch.empty(shape, dtype=dtype, device=dev)
+            if old is not None and self.n:
+                t[:self.n] = old[:self.n]
+            return t
+
+        self._X = moved(self._X, (new, self.d), torch.float64)
+        self._nrm = moved(self._nrm, (new,), torch.float64)
+        self._count, self._parent, self._best = (moved(t, (new,), torch.int32) for t in (self._count, self._parent, self._best))
+        self._labels = torch.empty(new, dtype=torch.int32, device=dev)
+        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+    def _to_host_mode(self, counted):
+        self._host_mode, self._counted = True, counted
+        if self._X is not None:
+            self._host_rows = self._X[:self.n].cpu().numpy()
+        self._X = self._nrm = self._count = self._parent = self._best = self._labels = self._ws = None
+
+    # ---- the reference's two calls ---------------------------------------------------------------
+    def insert(self, X):
+        """X: (w, d) ndarray or CUDA tensor (taken as fp64).  Returns self."""
+        if self._dead:
+            raise ValueError("this IncrementalDBSCAN met a non-finite row and takes no further inserts")
+        on_dev = isinstance(X, torch.Tensor)
+        rows = X.to(torch.float64) if on_dev else np.ascontiguousarray(X, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] < 1 or (self.d is not None and rows.shape[1] != self.d):
+            raise ValueError("X must be (w, d) with w, d >= 1 and the d of the earlier inserts")
+        self.d = int(rows.shape[1])
+        n0, n = self.n, self.n + int(rows.shape[0])
+        if not self._host_mode and n > MAX_ROWS:
+            self._to_host_mode(False)
+        if self._host_mode:
+            self._insert_host(rows.cpu().numpy() if on_dev else rows, n)
+        else:
+            self._insert_device(rows, n0, n)
+        self._last, self._last_lo = X, n0
+        return self
+
+    def _insert_host(self, rows, n):
+        self._host_rows = rows.copy() if self._host_rows is None else np.concatenate([self._host_rows, rows])
+        self.n = n
+        if self._counted:
+            mo._dbscan_incr_count_fallback()
+        try:
+            self._host_labels = np.asarray(mo.perform_dbscan_clustering(self._host_rows, self.eps, self.min_pts), dtype=np.int64)
+        except ValueError:
+            self._dead = True
+            raise
+
+    def _insert_device(self, rows, n0, n):
+        st = mo._match_stream(self._stream)
+        with torch.cuda.stream(st):
+            dev = rows.device if isinstance(rows, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+            self._grow(n, dev)
+            self._X[n0:n] = rows if isinstance(rows, torch.Tensor) else torch.tensor(rows, device=dev)
+            info = (C.c_int * 6)()
+            _lib.call("mused_dbscan_incr_insert", ptr(self._X), self._X.stride(0), self.d, ptr(self._nrm), ptr(self._count),
+                      ptr(self._parent), ptr(self._best), n0, n - n0, self.eps, self.min_pts, self.chunk, ptr(self._labels),
+                      info, ptr(self._ws), self._ws.numel(), C.c_void_p(st.cuda_stream))
+            self.n = n
+            self.last_info = np.array(info[:], dtype=np.int32)
+            if info[0] & FLAG_NONFINITE:
+                self._dead = True
+                raise ValueError("Input contains NaN or infinity.")
+            if info[0] & FLAG_AMBIGUOUS:
+                self.n = n0   # (the rows of this insert are appended again, on the host)
+                self._to_host_mode(True)
+                self._insert_host(rows.cpu().numpy() if isinstance(rows, torch.Tensor) else rows, n)
+                return
+            self.dirty.append((int(info[4]), int(info[5])))
+
+    def labels(self):
+        """int64 NumPy labels of all rows inserted so far (-1 = noise)."""
+        if self.n == 0:
+            return np.empty(0, dtype=np.int64)
+        if self._host_mode:
+            return self._host_labels.copy()
+        return self._labels[:self.n].cpu().numpy().astype(np.int64)
+
+    def get_cluster_labels(self, X):
+        """int64 NumPy labels of the batch just inserted.  X must BE that batch (the object handed to the last `insert`, or
+        an ndarray equal to it): rows are not looked up by value."""
+        last = self._last
+        same = X is last
+        if not same and last is not None and isinstance(X, np.ndarray) and isinstance(last, np.ndarray):
+            same = X.shape == last.shape and np.array_equal(X, last)
+        if not same:
+            raise ValueError("get_cluster_labels takes the batch of the last insert only: lookup by value is not offered")
+        if self._host_mode:
+            return self._host_labels[self._last_lo:self.n].copy()
+        return self._labels[self._last_lo:self.n].cpu().numpy().astype(np.int64)

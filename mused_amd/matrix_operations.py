@@ -743,6 +743,17 @@ def _dbscan_count_fallback():
         dbscan_fallbacks += 1
 
 
+# inserts that mused_amd.incdbscan.IncrementalDBSCAN answered with scikit-learn's refit on the host although the device was
+# asked: the insert whose kernel raised the ambiguity flag and every later insert of that object
+dbscan_incr_fallbacks = 0
+
+
+def _dbscan_incr_count_fallback():
+    global dbscan_incr_fallbacks
+    with _km_fallback_lock:
+        dbscan_incr_fallbacks += 1
+
+
 def dbscan_launch(X_dev, eps, min_samples, stream=None):
     """One mused_dbscan call on an (n, d) fp64 CUDA tensor (unit stride along the columns) -> (labels n int32 CUDA, info
     4 int32 NumPy = {flags, clusters, core rows, 0}; flags: mused_amd.dbscan.FLAG_*).  Synchronises the stream."""

@@ -8,6 +8,9 @@ Per full window (trigger rule of main.py:32):
                                         first window only, sketch transposed to (W, l)  (main.py:58-76)
     -> k-means with n_clusters = #distinct true labels in the window (main.py:41,97); "sSVDMC_mini": one MiniBatchKMeans
        (n_clusters_total) for the whole stream, partial_fit + predict per window IN WINDOW ORDER (main.py:82-86)
+       "DBSCAN_incr": one IncrementalDBSCAN(eps, min_samples) for the whole stream, insert + get_cluster_labels per window IN
+       WINDOW ORDER (main.py:87-91; mused_amd/incdbscan.py, csrc/dbscan_incr.hip: the labels of a DBSCAN refit on every row
+       inserted so far)
     -> Hungarian matching against the previous window, min_overlap = 3 (main.py:110); "sSVDMC_pot": matching by the
        Sinkhorn transport plan (main.py:111) in csrc/match.hip
     -> labels appended (main.py:118-119).
@@ -38,8 +41,8 @@ from .swfd import SeqBasedSWFD
 class StreamPipeline:
     def __init__(self, window_size, reduced_dim, k_basis, seed, approach="sSVDMC", modality_types=None,
                  step_window_ratio=1, engine=None, async_labels=True, feature_sketch=False, stream=None,
-                 assume_finite=False, window_slots=1, n_clusters_total=None):
-        if approach not in ("sSVDMC", "sSVDMC_hung", "sSVDMC_pot", "sSVDMC_mini", "SWFDMC"):
+                 assume_finite=False, window_slots=1, n_clusters_total=None, eps=0.5, min_samples=5):
+        if approach not in ("sSVDMC", "sSVDMC_hung", "sSVDMC_pot", "sSVDMC_mini", "SWFDMC", "DBSCAN_incr"):
             raise ValueError(f"approach {approach!r} is not on the device hot path")
         if approach == "sSVDMC_mini" and n_clusters_total is None:
             raise ValueError("approach 'sSVDMC_mini' needs n_clusters_total (MiniBatchKMeans(n_clusters=n_clusters_total), "
@@ -48,6 +51,11 @@ class StreamPipeline:
         # thread that clusters).  Its state is a chain over windows, so its clustering runs on the chain worker, in window
         # order, not in the parallel k-means pool; the device work of later windows (slots included) still overlaps it.
         self._mini = approach == "sSVDMC_mini"
+        # "DBSCAN_incr": embedding as "sSVDMC"; ONE mused_amd.incdbscan.IncrementalDBSCAN(eps, min_samples) for the stream takes
+        # every window's embedding in window order -- a chain like the one above, on the chain worker, with one window slot
+        self._incr = approach == "DBSCAN_incr"
+        self._chained = self._mini or self._incr
+        self.eps, self.min_samples = eps, min_samples
         # "sSVDMC_pot": embedding and k-means as "sSVDMC"; the label chain matches by the Sinkhorn plan (main.py:111), every
         # other approach by SciPy's assignment (main.py:110).  Both chains run on the device (csrc/match.hip,
         # csrc/match_hung.hip), or on the host (mused_amd/sinkhorn.py, SciPy) under MUSED_MATCH=host
@@ -73,7 +81,7 @@ class StreamPipeline:
         # 2 slots can be slower than one, the best count varies with how HIP maps the streams onto hardware queues.
         # Opt-in (default 1; MUSED_WINDOW_SLOTS for
         # process_streaming_data).  The sketch approaches carry state from window to window and keep one slot.
-        self._nslots = max(1, int(window_slots)) if (approach != "SWFDMC" and not feature_sketch) else 1
+        self._nslots = max(1, int(window_slots)) if (approach not in ("SWFDMC", "DBSCAN_incr") and not feature_sketch) else 1
         # Every engine records its eigenstep graph once, on the caller's thread, before the slot threads exist (see
         # process_window).  A modality without an edge bound ("username") re-creates an engine's handle -- frees, graph
         # destruction, allocations, a new capture -- whenever a window has more edges than the handle was sized for; the
@@ -279,6 +287,8 @@ class StreamPipeline:
         t0 = time.perf_counter()
         if self._mini:
             clusters = self._minibatch(reduced_dev, reduced_host)
+        elif self._incr:
+            clusters = self._dbscan_incr(reduced_dev, reduced_host)
         elif self._km_device and reduced_dev is not None and reduced_dev.dtype == torch.float64:
             st = getattr(self._km_local, "stream", None)
             if st is None:
@@ -295,7 +305,7 @@ class StreamPipeline:
         """A k-means window with device seeding: nothing on the host reads the embedding (the labels, sigma and the flag
         words are all the trace and the matching take), so it is not copied to the pinned buffer; a window that falls back
         fetches it itself (matrix_operations._km_host_copy)."""
-        return self._km_seed_device and not self._mini and reduced is not None and reduced.dtype == torch.float64
+        return self._km_seed_device and not self._chained and reduced is not None and reduced.dtype == torch.float64
 
     def _minibatch(self, reduced_dev, reduced_host):
         """main.py:82-86: clusterer.partial_fit(reduced).predict(reduced) on the stream's one MiniBatchKMeans.  Called in
@@ -323,8 +333,25 @@ class StreamPipeline:
         self.km_device_windows += 1
         return self.clusterer.partial_fit(X).labels_
 
+    def _dbscan_incr(self, reduced_dev, reduced_host):
+        """main.py:87-91: clusterer.insert(reduced).get_cluster_labels(reduced) on the stream's one IncrementalDBSCAN.  Called
+        in window order (chain worker, or the caller without async labels)."""
+        from .incdbscan import IncrementalDBSCAN
+
+        st = getattr(self._km_local, "stream", None)
+        if st is None:
+            st = self._km_local.stream = torch.cuda.Stream(priority=-1)
+        if self.clusterer is None:
+            self.clusterer = IncrementalDBSCAN(eps=self.eps, min_pts=self.min_samples, stream=st)
+        if reduced_dev is not None and reduced_dev.dtype == torch.float64:
+            reduced_dev.record_stream(st)  # produced on the pipeline's stream, complete (ev), consumed on the worker's
+            X = reduced_dev
+        else:
+            X = np.ascontiguousarray(reduced_host, dtype=np.float64)
+        return self.clusterer.insert(X).get_cluster_labels(X)
+
     def _cluster_chain(self, job):
-        """sSVDMC_mini: the clustering and the matching of one window, both on the chain worker (window order)."""
+        """sSVDMC_mini, DBSCAN_incr: the clustering and the matching of one window, both on the chain worker (window order)."""
         self._chain(self._cluster(job), job)
 
     def _optimistic_nnz(self):
@@ -422,7 +449,7 @@ class StreamPipeline:
 
     def _submit(self, job):
         """Hand a window to the label workers (async mode)."""
-        if self._mini:
+        if self._chained:
             return self._pool.submit(self._cluster_chain, job)
         return self._pool.submit(self._chain, self._kpool.submit(self._cluster, job), job)
 
@@ -483,7 +510,7 @@ class StreamPipeline:
         wait_ev = torch.cuda.Event()
         wait_ev.record(caller)
         fut_job = self._dpools[slot].submit(self._device_side, mods, n_clusters, trigger, t_start, eng, st, wait_ev)
-        if self._mini:
+        if self._chained:
             self._pending.append(self._pool.submit(self._cluster_chain_after, fut_job))
             return
         fut_cluster = self._kpool.submit(self._cluster_after, fut_job)
@@ -634,7 +661,8 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
     # modality types go through unchanged: "" / anything the reference does not special-case = Euclidean kNN
     # (matrix_operations.py:112), "text" and "cosine" = the cosine kernel, the other SED2012 metadata types raise
     with StreamPipeline(window_size, reduced_dim, k_basis, seed, approach, list(modality_types), step_window_ratio,
-                        window_slots=int(os.environ.get("MUSED_WINDOW_SLOTS", "1")), n_clusters_total=n_clusters_total) as pipe:
+                        window_slots=int(os.environ.get("MUSED_WINDOW_SLOTS", "1")), n_clusters_total=n_clusters_total,
+                        eps=eps, min_samples=min_samples) as pipe:
         clusters = pipe.run(data_modalities, np.asarray(complete_true_labels))
     t1 = time.time_ns()
     if score:
