@@ -470,6 +470,29 @@ int mused_dbscan_incr_insert(const double* X, long ld, int d, double* nrm, int* 
                              double eps, int min_samples, long chunk, int* labels_out, int* info_out, void* ws, long ws_bytes,
                              void* stream);
 
+/* ---- DBSCAN_incr over a sliding window: the m OLDEST of the n rows held are deleted, csrc/dbscan_incr.hip.  Afterwards the
+ * labels of the n - m rows still held equal sklearn DBSCAN(eps, min_samples, metric="euclidean").fit_predict(those rows, in
+ * their order), numbering included, after any sequence of inserts and deletes (specification: mused_amd/dbscan_incr.py,
+ * `delete_oldest`; pinned to scikit-learn's refit).  A delete runs the fp64 MFMA distance tiles of (deleted rows) x (survivors)
+ * for the counts, (surviving core rows of the components that lost a core row) x (survivors) to rebuild those components, and for
+ * min_samples >= 3 (non-core rows whose cluster may have changed) x (survivors); components the delete does not touch cost
+ * nothing.  There is no rounding flag: every pair was tested when the later of its rows was inserted.
+ * NOT enqueue-only: the call reads the two list lengths between its phases and returns after the stream has finished.
+ * X: the n rows held, fp64 (pitch ld), n <= 2^19; they are NOT modified.  Afterwards the caller's rows start at X + m * ld.
+ * nrm, count, parent, best: the state arrays of mused_dbscan_incr_insert over the n rows; on return entries [0, n - m) describe
+ *   the survivors in the new numbering (survivor i has become i - m).  They are written shifted into the workspace and copied
+ *   back, so no entry is read after it has been overwritten.  m == n leaves the empty state (the next insert has n0 = 0).
+ * m: 1 <= m <= n.  chunk: rows per staging panel, a multiple of 128 in [128, 65536].
+ * labels_out: n - m int32 (DEVICE), -1 = noise.  info_out (HOST, 6 int32) = {flags (always 0), clusters, core rows, rows that
+ *   lost core status, rows whose components were rebuilt (|R|), non-core rows taken against the core rows again (|B|)}.
+ * ws: mused_dbscan_incr_delete_ws_bytes(capacity, d, chunk) bytes for any capacity >= n (44 capacity + 4 ceil(capacity / 128)
+ *   + 8 chunk (d rounded up to even) and alignment; -1 for capacity outside [1, 2^19] or a bad d or chunk).  Scratch only.
+ *   Outside these limits (m outside [1, n], a short workspace, a bad chunk or d) the call returns an error and writes nothing. */
+long mused_dbscan_incr_delete_ws_bytes(long capacity, int d, long chunk);
+int mused_dbscan_incr_delete(const double* X, long ld, int d, double* nrm, int* count, int* parent, int* best, long n, long m,
+                             double eps, int min_samples, long chunk, int* labels_out, int* info_out, void* ws, long ws_bytes,
+                             void* stream);
+
 /* ---- HDBSCAN_batch: the exact Euclidean minimum spanning tree of n fp64 rows, csrc/emst.hip.  For
  * sklearn.cluster.HDBSCAN(min_samples <= 2, metric="euclidean") the mutual-reachability distance is the distance itself, so
  * this tree is the one its Prim loop builds; the sequential rest (Prim's edge order, single-linkage and condensed tree,

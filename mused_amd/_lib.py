@@ -101,6 +101,8 @@ _PROTOS = {
     "mused_dbscan": (_i, [_vp, _l, _i, _l, _d, _i, _vp, _vp, _vp, _l, _vp]),
     "mused_dbscan_incr_ws_bytes": (_l, [_l, _i, _l]),
     "mused_dbscan_incr_insert": (_i, [_vp, _l, _i, _vp, _vp, _vp, _vp, _l, _l, _d, _i, _l, _vp, _vp, _vp, _l, _vp]),
+    "mused_dbscan_incr_delete_ws_bytes": (_l, [_l, _i, _l]),
+    "mused_dbscan_incr_delete": (_i, [_vp, _l, _i, _vp, _vp, _vp, _vp, _l, _l, _d, _i, _l, _vp, _vp, _vp, _l, _vp]),
     "mused_emst_ws_bytes": (_l, [_l]),
     "mused_emst": (_i, [_vp, _l, _i, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "mused_score_ws_bytes": (_l, [_l, _l]),

@@ -7,6 +7,7 @@ namespace mused {
 
 constexpr int DB_NONE = 0x7fffffff;        // root of a row that no cluster has reached
 constexpr int DB_HAS_CORE = 1, DB_HAS_NONCORE = 2;
+constexpr int DB_HAS_REBUILD = 4;         // (csrc/dbscan_incr.hip, a delete: the tile holds a row whose component is rebuilt)
 constexpr long DB_MAX_ROWS = 1l << 19;     // 4096 row tiles: the tile grid, 4096 * 2049 workgroups of 256 threads, stays below the
                                            // 2^32 threads one launch may hold (reached near 740,000 rows)
 

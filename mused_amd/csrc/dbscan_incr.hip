@@ -32,6 +32,29 @@
 // order), so the passes agree with one another.  No n x n array, no neighbour list, no pass over all x all.
 // Every write to global memory is a vector store or a device-scope vector atomic; kernel boundaries are the only
 // synchronisation between workgroups.
+//
+// DELETING the m oldest of n rows (mused_dbscan_incr_delete; the rule: mused_amd/dbscan_incr.py).  D = [0, m), S = [m, n):
+//
+//   dbd_begin         rootb[i] = find(i) for the core rows, -1 for the others; best = find(best) for the non-core rows that
+//                     have one (the remembered root, kept in place); the list of affected roots is cleared
+//   tile pass UNCOUNT D x S (the slice D on the A side, column tiles that lie wholly in D return at once):
+//                     count[j] -= the rows of D within eps (column side, per-wave reduction before the atomic).  No rounding
+//                     test: every pair was tested when the later of its two rows was inserted
+//   dbd_mark          aff[rootb[i]] = 1 for the core rows of D and for the rows of S that were core and are not any more
+//                     (these are counted, and become their own parent again)
+//   dbd_select        R = the rows of S that are still core under an affected root: parent[x] = x, compacted into a list; B
+//                     (min_samples >= 3) = the rows that lost core status and the non-core rows whose best is an affected
+//                     root: best = DB_NONE, compacted into a second list; tile flags over the rows of S (DB_HAS_CORE,
+//                     DB_HAS_NONCORE, DB_HAS_REBUILD: the tile holds a row of R), the number of core rows
+//                                                                                             [the host reads |R|, |B|]
+//   tile pass REBUILD R x S through the staging panel: the UNION epilogue over the core columns of S (all of them that lie
+//                     within eps of a row of R are in R); column tiles without a row of R return before their main loop
+//   dbd_resolve       root[i] = find(i) for the core rows of S, DB_NONE for every other row
+//   tile pass BPANEL  B x S through the staging panel: the BROW epilogue, best[b] = the smallest root among the core columns
+//   dbd_shift         survivor i becomes i - m.  The four state arrays are written, shifted, INTO THE WORKSPACE and copied
+//                     back behind the kernel (no workgroup reads an entry that another has overwritten); the roots go, shifted,
+//                     into the array rootb held
+//   dbscan_rank, dbi_labels   over the n - m survivors
 #include "gemm_f64.h"
 #include "internal.h"
 #include "dbscan_common.h"
@@ -41,7 +64,8 @@ extern "C" int mused_row_sq_norms(const void* X, int dtype, long n, int d, long 
 
 namespace mused {
 
-constexpr int DBI_COUNT = 0, DBI_UNION = 1, DBI_BCOL = 2, DBI_BROW = 3;
+constexpr int DBI_COUNT = 0, DBI_UNION = 1, DBI_BCOL = 2, DBI_BROW = 3;   // an insert's passes
+constexpr int DBI_UNCOUNT = 4, DBI_REBUILD = 5, DBI_BPANEL = 6;           // a delete's: columns below a.n0 (= m) take no part
 constexpr long DBI_MAX_CHUNK = 1l << 16;  // 512 x 4096 tiles of 256 threads: far below the 2^32 threads of one launch
 
 struct DbiArgs {
@@ -49,17 +73,22 @@ struct DbiArgs {
   int *count, *parent, *best;
   const int* root;    // [n] BCOL / BROW: final root of a core row, DB_NONE for the others
   const int* ids;     // row ids of the A rows (staging panel); nullptr: a_base + local row (slice)
-  const int* tflag;   // [tiles of all rows] DB_HAS_CORE | DB_HAS_NONCORE
+  const int* tflag;   // [tiles of all rows] DB_HAS_CORE | DB_HAS_NONCORE (| DB_HAS_REBUILD)
   const int* aflag;   // BROW: the same per 128-row tile of the new slice, from this chunk's first tile on
   int* info;          // {flags, clusters, core rows, -, |dirtyA|, |dirtyB|, -, -}
   double eps2, ctau, etau;
-  int min_samples, a_base, n0;
+  int min_samples, a_base, n0;   // n0: rows before the insert; for a delete m, the first surviving row
 };
 
 // A rows [I * 128, ...) of the chunk against rows [J * 128, ...) of all rows; consecutive workgroups (one XCD's share) walk
 // the A tiles of one B tile, so the chunk stays in L2 while the rows stream by once.  Grid: tiles_a * tiles_b.
 template <int PASS, bool VEC>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_incr_tile_kernel(GemmArgs g, DbiArgs a) {
+  // the delete's passes share the epilogues: UNCOUNT the column side of COUNT (subtracting), REBUILD all of UNION, BPANEL all of
+  // BROW with the A rows in a staging panel
+  constexpr bool DEL = PASS >= DBI_UNCOUNT;
+  constexpr bool UNI = PASS == DBI_UNION || PASS == DBI_REBUILD, BRW = PASS == DBI_BROW || PASS == DBI_BPANEL;
+  constexpr bool CNT = PASS == DBI_COUNT || PASS == DBI_UNCOUNT;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tiles_a = (g.M + GEMM_BM - 1) / GEMM_BM;
   const int e = xcd_remap(blockIdx.x, gridDim.x);
@@ -67,6 +96,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_incr_tile_kernel(GemmA
   if (PASS == DBI_UNION && !(a.tflag[J] & DB_HAS_CORE)) return;
   if (PASS == DBI_BCOL && !(a.tflag[J] & DB_HAS_NONCORE)) return;
   if (PASS == DBI_BROW && (!(a.tflag[J] & DB_HAS_CORE) || !(a.aflag[I] & DB_HAS_NONCORE))) return;
+  if (PASS == DBI_UNCOUNT && (J + 1) * GEMM_BN <= a.n0) return;
+  if (PASS == DBI_REBUILD && !(a.tflag[J] & DB_HAS_REBUILD)) return;
+  if (PASS == DBI_BPANEL && !(a.tflag[J] & DB_HAS_CORE)) return;
   const int m0 = I * GEMM_BM, n0 = J * GEMM_BN;
   v4f64 acc[4][4];
   gemm_tile_mainloop<double, double, true, true, VEC>(g, reinterpret_cast<const double*>(g.A), reinterpret_cast<const double*>(g.B),
@@ -84,13 +116,13 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_incr_tile_kernel(GemmA
   for (int j = 0; j < 4; ++j) {
     const int col = n0 + wc * 64 + j * 16 + li;
     const int cc = min(col, n - 1);
-    cok[j] = col < n;
+    cok[j] = col < n && (!DEL || col >= a.n0);
     ncol[j] = a.nrm[cc];
-    corec[j] = (PASS != DBI_COUNT) && cok[j] && a.count[cc] >= a.min_samples;
-    if (PASS == DBI_COUNT) ccol[j] = 0;
-    if (PASS == DBI_UNION) ccol[j] = corec[j] ? db_find(a.parent, col) : -1;
+    corec[j] = !CNT && cok[j] && a.count[cc] >= a.min_samples;
+    if (CNT) ccol[j] = 0;
+    if (UNI) ccol[j] = corec[j] ? db_find(a.parent, col) : -1;
     if (PASS == DBI_BCOL) ccol[j] = DB_NONE;
-    if (PASS == DBI_BROW) ccol[j] = corec[j] ? a.root[cc] : DB_NONE;
+    if (BRW) ccol[j] = corec[j] ? a.root[cc] : DB_NONE;
   }
   int rsum[16];  // COUNT / BROW: the row's count / minimum over this wave's 64 columns
   int rids[16];
@@ -108,7 +140,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_incr_tile_kernel(GemmA
       // UNION, BCOL: every A row is core.  BROW: only the non-core rows of the slice take part
       const bool rtake = rok && (PASS != DBI_BROW || a.count[rid] < a.min_samples);
       const int rroot = (PASS == DBI_BCOL) ? a.root[rid] : DB_NONE;
-      int racc = (PASS == DBI_COUNT) ? 0 : (PASS == DBI_UNION ? -1 : DB_NONE);
+      int racc = CNT ? 0 : (UNI ? -1 : DB_NONE);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int col = n0 + wc * 64 + j * 16 + li;
@@ -122,16 +154,17 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_incr_tile_kernel(GemmA
           racc += in ? 1 : 0;
           ccol[j] += in ? 1 : 0;
         }
-        if (PASS == DBI_UNION) {
+        if (PASS == DBI_UNCOUNT) ccol[j] += in ? 1 : 0;
+        if (UNI) {
           if (in && !same && corec[j]) {
             if (racc < 0) racc = db_find(a.parent, rid);
             if (racc != ccol[j]) racc = ccol[j] = db_unite(a.parent, racc, ccol[j]);
           }
         }
         if (PASS == DBI_BCOL) ccol[j] = (in && !corec[j]) ? min(ccol[j], rroot) : ccol[j];
-        if (PASS == DBI_BROW) racc = (in && corec[j]) ? min(racc, ccol[j]) : racc;
+        if (BRW) racc = (in && corec[j]) ? min(racc, ccol[j]) : racc;
       }
-      if (PASS == DBI_COUNT || PASS == DBI_BROW) {
+      if (PASS == DBI_COUNT || BRW) {
         // the 16 lanes that share kq hold the 64 columns of this row in this wave
 #pragma unroll
         for (int o = 1; o < 16; o <<= 1) {
@@ -140,23 +173,23 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_incr_tile_kernel(GemmA
         }
         rsum[i * 4 + r] = racc;
         // the row's results are complete HERE (csrc/dbscan.hip: otherwise the distances of the whole patch stay alive)
-        if (PASS == DBI_BROW) asm volatile("" : "+v"(rsum[i * 4 + r]));
+        if (BRW) asm volatile("" : "+v"(rsum[i * 4 + r]));
         if (PASS == DBI_COUNT) asm volatile("" : "+v"(slack), "+v"(ccol[0]), "+v"(ccol[1]), "+v"(ccol[2]), "+v"(ccol[3]), "+v"(rsum[i * 4 + r]));
       }
-      if (PASS == DBI_BCOL) asm volatile("" : "+v"(ccol[0]), "+v"(ccol[1]), "+v"(ccol[2]), "+v"(ccol[3]));
+      if (PASS == DBI_BCOL || PASS == DBI_UNCOUNT) asm volatile("" : "+v"(ccol[0]), "+v"(ccol[1]), "+v"(ccol[2]), "+v"(ccol[3]));
     }
   }
-  if (PASS == DBI_COUNT || PASS == DBI_BROW) {
+  if (PASS == DBI_COUNT || BRW) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       const int lrow = m0 + wr * 64 + (q >> 2) * 16 + kq + 4 * (q & 3);
       if (li == 0 && lrow < ma) {
         if (PASS == DBI_COUNT && rsum[q]) atomicAdd(a.count + rids[q], rsum[q]);
-        if (PASS == DBI_BROW && rsum[q] != DB_NONE) atomicMin(a.best + rids[q], rsum[q]);
+        if (BRW && rsum[q] != DB_NONE) atomicMin(a.best + rids[q], rsum[q]);
       }
     }
   }
-  if (PASS == DBI_COUNT || PASS == DBI_BCOL) {
+  if (CNT || PASS == DBI_BCOL) {
     // the 4 lanes that share li hold the 64 rows of this column in this wave
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -164,11 +197,12 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_incr_tile_kernel(GemmA
 #pragma unroll
       for (int o = 16; o < 64; o <<= 1) {
         const int x = __shfl_xor(v, o);
-        v = (PASS == DBI_COUNT) ? v + x : min(v, x);
+        v = CNT ? v + x : min(v, x);
       }
       const int col = n0 + wc * 64 + j * 16 + li;
       if (kq == 0 && col < n) {
         if (PASS == DBI_COUNT && v && col < a.n0) atomicAdd(a.count + col, v);  // (new columns: counted from their row side)
+        if (PASS == DBI_UNCOUNT && v) atomicSub(a.count + col, v);  // (v counts columns of S only)
         if (PASS == DBI_BCOL && v != DB_NONE) atomicMin(a.best + col, v);
       }
     }
@@ -260,6 +294,81 @@ __global__ void dbi_labels_kernel(const int* __restrict__ root, const int* __res
   labels[i] = (r == DB_NONE) ? -1 : rank[r];
 }
 
+// ---- the O(n) kernels of a delete (D = [0, m), S = [m, n)) --------------------------------------------------------------
+// (behind the memset of info)
+__global__ void dbd_begin_kernel(DbiArgs a, int* __restrict__ rootb, int* __restrict__ aff, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  aff[i] = 0;
+  if (a.count[i] >= a.min_samples) {
+    rootb[i] = db_find(a.parent, i);
+  } else {
+    rootb[i] = -1;
+    const int b = a.best[i];
+    if (b != DB_NONE) a.best[i] = db_find(a.parent, b);
+  }
+}
+
+// behind UNCOUNT: the components that lose a core row
+__global__ void dbd_mark_kernel(DbiArgs a, const int* __restrict__ rootb, int* __restrict__ aff, int m, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool was = i < n && rootb[i] >= 0;
+  const bool lost = was && i >= m && a.count[i] < a.min_samples;
+  if (was && (i < m || lost)) aff[rootb[i]] = 1;   // (every writer stores the same value)
+  if (lost) a.parent[i] = i;                        // a non-core row is its own parent
+  const int c = __popcll(__ballot(lost));
+  if (c && (threadIdx.x & 63) == 0) atomicAdd(a.info + 3, c);
+}
+
+__global__ void dbd_select_kernel(DbiArgs a, const int* __restrict__ rootb, const int* __restrict__ aff, int* __restrict__ list_r,
+                                  int* __restrict__ list_b, int* __restrict__ tflag, int m, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int tiles = (n + GEMM_BM - 1) / GEMM_BM;
+  if (i < tiles) {
+    int f = 0;
+    const int hi = min(n, (i + 1) * GEMM_BM);
+    for (int r = max(m, i * GEMM_BM); r < hi; ++r) {
+      const bool core = a.count[r] >= a.min_samples;
+      f |= core ? (aff[rootb[r]] ? DB_HAS_CORE | DB_HAS_REBUILD : DB_HAS_CORE) : DB_HAS_NONCORE;
+    }
+    tflag[i] = f;
+  }
+  const bool in = i >= m && i < n;
+  const bool core = in && a.count[i] >= a.min_samples;   // (core now: core before too, counts only fell)
+  const bool reb = core && aff[rootb[i]];
+  bool bord = false;
+  if (in && !core && a.min_samples > 2) {
+    const int b = a.best[i];
+    bord = rootb[i] >= 0 || (b != DB_NONE && aff[b]);     // lost core status, or its minimum came from an affected root
+    if (bord) a.best[i] = DB_NONE;
+  }
+  if (reb) a.parent[i] = i;
+  const int c = __popcll(__ballot(core));
+  if (c && (threadIdx.x & 63) == 0) atomicAdd(a.info + 2, c);
+  dbi_append(reb, i, list_r, a.info + 4);
+  dbi_append(bord, i, list_b, a.info + 5);
+}
+
+__global__ void dbd_resolve_kernel(DbiArgs a, int* __restrict__ root, int m, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  root[i] = (i >= m && a.count[i] >= a.min_samples) ? db_find(a.parent, i) : DB_NONE;
+}
+
+// survivor m + i -> i, into the second set of arrays (nothing of the state is overwritten here)
+__global__ void dbd_shift_kernel(DbiArgs a, const int* __restrict__ root, double* __restrict__ nrm2, int* __restrict__ count2,
+                                 int* __restrict__ parent2, int* __restrict__ best2, int* __restrict__ root2, int m, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n - m) return;
+  const int s = m + i;
+  const int r = root[s], b = a.best[s];
+  nrm2[i] = a.nrm[s];
+  count2[i] = a.count[s];
+  parent2[i] = a.parent[s] - m;
+  best2[i] = (r != DB_NONE || b == DB_NONE) ? DB_NONE : b - m;   // (a core row's best is read nowhere)
+  root2[i] = r == DB_NONE ? DB_NONE : r - m;
+}
+
 struct DbiWs {
   int *rootb, *root, *rank, *list, *tflag, *aflag, *info;
   double* panel;
@@ -286,6 +395,33 @@ static size_t dbi_layout(long n, int d, long chunk, char* base, DbiWs* ws) {
   if (ws) {
     ws->rootb = (int*)p0; ws->root = (int*)p1; ws->rank = (int*)p2; ws->list = (int*)p3; ws->tflag = (int*)p4;
     ws->aflag = (int*)p5; ws->info = (int*)p6; ws->panel = (double*)p7;
+  }
+  return off;
+}
+
+struct DbdWs {
+  int *rootb, *root, *rank, *list_r, *list_b, *aff, *tflag, *info, *count2, *parent2, *best2;
+  double *nrm2, *panel;
+};
+
+static size_t dbd_layout(long n, int d, long chunk, char* base, DbdWs* ws) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += (bytes + 255) & ~(size_t)255;
+    return p;
+  };
+  const long tiles = (n + GEMM_BM - 1) / GEMM_BM;
+  char* p[9];
+  for (int i = 0; i < 9; ++i) p[i] = take(4 * (size_t)n);
+  char* pt = take(4 * (size_t)tiles);
+  char* pi = take(32);
+  char* pn = take(8 * (size_t)n);
+  char* pp = take(8 * (size_t)chunk * dbi_ldp(d));
+  if (ws) {
+    ws->rootb = (int*)p[0]; ws->root = (int*)p[1]; ws->rank = (int*)p[2]; ws->list_r = (int*)p[3]; ws->list_b = (int*)p[4];
+    ws->aff = (int*)p[5]; ws->count2 = (int*)p[6]; ws->parent2 = (int*)p[7]; ws->best2 = (int*)p[8];
+    ws->tflag = (int*)pt; ws->info = (int*)pi; ws->nrm2 = (double*)pn; ws->panel = (double*)pp;
   }
   return off;
 }
@@ -406,6 +542,67 @@ int mused_dbscan_incr_insert(const double* X, long ld, int d, double* nrm, int* 
   info_out[3] = info[4] + info[5];
   info_out[4] = info[4];
   info_out[5] = info[5];
+  return MUSED_OK;
+}
+
+// bytes of workspace mused_dbscan_incr_delete needs while the rows number at most `capacity`
+long mused_dbscan_incr_delete_ws_bytes(long capacity, int d, long chunk) {
+  if (!dbi_shape_ok(capacity, d, chunk)) return -1;
+  return (long)dbd_layout(capacity, d, chunk, nullptr, nullptr);
+}
+
+// One delete of the m oldest rows (head of this file).  X: the n rows held (pitch ld); they are not modified, the caller's rows
+// start at X + m * ld afterwards.  Synchronises the stream (it reads |R| and |B| between the phases): not enqueue-only.
+int mused_dbscan_incr_delete(const double* X, long ld, int d, double* nrm, int* count, int* parent, int* best, long n, long m,
+                             double eps, int min_samples, long chunk, int* labels_out, int* info_out, void* ws, long ws_bytes,
+                             void* stream) {
+  MUSED_REQUIRE(X && nrm && count && parent && best && labels_out && info_out && ws, "mused_dbscan_incr_delete: null argument");
+  MUSED_REQUIRE(dbi_shape_ok(n, d, chunk) && ld >= d && m >= 1 && m <= n,
+                "mused_dbscan_incr_delete: bad shape (n=%ld m=%ld d=%d ld=%ld chunk=%ld; 1 <= m <= n <= 2^19, chunk a multiple of "
+                "128 in [128, 65536])", n, m, d, ld, chunk);
+  MUSED_REQUIRE(eps > 0.0 && eps * eps < 1.7976931348623157e308 && min_samples >= 1,
+                "mused_dbscan_incr_delete: need eps > 0 (finite square), min_samples >= 1");
+  MUSED_REQUIRE(ws_bytes >= (long)dbd_layout(n, d, chunk, nullptr, nullptr), "mused_dbscan_incr_delete: workspace too small");
+  memset(info_out, 0, 24);
+  if (m == n) return MUSED_OK;  // the empty state: nothing of the arrays describes a row any more
+  hipStream_t st = (hipStream_t)stream;
+  DbdWs k;
+  dbd_layout(n, d, chunk, (char*)ws, &k);
+  const long ns = n - m;
+  DbiArgs a{nrm, count, parent, best, k.root, nullptr, k.tflag, nullptr, k.info, eps * eps, 0.0, 0.0, min_samples, 0, (int)m};
+  DbiWs w;
+  memset(&w, 0, sizeof(w));
+  w.panel = k.panel;
+  w.aflag = k.tflag;  // (the slice walk offsets it; UNCOUNT does not read it)
+  const bool vec = vec_ok<double>(X, ld, 0);
+  const dim3 rows(cdiv(n, 256)), blk(256);
+  int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int rc;
+  MUSED_CHECK_HIP(hipMemsetAsync(k.info, 0, 32, st));
+  hipLaunchKernelGGL(dbd_begin_kernel, rows, blk, 0, st, a, k.rootb, k.aff, (int)n);
+  if ((rc = dbi_pass<DBI_UNCOUNT>(X, ld, d, n, 0, m, nullptr, chunk, w, a, vec, st))) return rc;
+  hipLaunchKernelGGL(dbd_mark_kernel, rows, blk, 0, st, a, k.rootb, k.aff, (int)m, (int)n);
+  hipLaunchKernelGGL(dbd_select_kernel, rows, blk, 0, st, a, k.rootb, k.aff, k.list_r, k.list_b, k.tflag, (int)m, (int)n);
+  MUSED_LAUNCH_CHECK();
+  MUSED_CHECK_HIP(hipMemcpyAsync(info, k.info, 32, hipMemcpyDeviceToHost, st));
+  MUSED_CHECK_HIP(hipStreamSynchronize(st));
+  const long n_r = info[4], n_b = info[5];
+  if ((rc = dbi_pass<DBI_REBUILD>(X, ld, d, n, 0, n_r, k.list_r, chunk, w, a, vec, st))) return rc;
+  hipLaunchKernelGGL(dbd_resolve_kernel, rows, blk, 0, st, a, k.root, (int)m, (int)n);
+  if ((rc = dbi_pass<DBI_BPANEL>(X, ld, d, n, 0, n_b, k.list_b, chunk, w, a, vec, st))) return rc;
+  hipLaunchKernelGGL(dbd_shift_kernel, dim3(cdiv(ns, 256)), blk, 0, st, a, k.root, k.nrm2, k.count2, k.parent2, k.best2, k.rootb,
+                     (int)m, (int)n);
+  MUSED_LAUNCH_CHECK();
+  MUSED_CHECK_HIP(hipMemcpyAsync(nrm, k.nrm2, 8 * (size_t)ns, hipMemcpyDeviceToDevice, st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(count, k.count2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(parent, k.parent2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(best, k.best2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(dbscan_rank_kernel, dim3(1), dim3(DB_RANK_THREADS), 0, st, k.rootb, k.rank, k.info, (int)ns);
+  hipLaunchKernelGGL(dbi_labels_kernel, dim3(cdiv(ns, 256)), blk, 0, st, k.rootb, k.best2, k.rank, labels_out, (int)ns);
+  MUSED_LAUNCH_CHECK();
+  MUSED_CHECK_HIP(hipMemcpyAsync(info, k.info, 32, hipMemcpyDeviceToHost, st));
+  MUSED_CHECK_HIP(hipStreamSynchronize(st));
+  memcpy(info_out, info, 24);
   return MUSED_OK;
 }
 

@@ -46,6 +46,34 @@ which is the cluster scikit-learn's index-order search reaches b from first.
 
 For min_samples <= 2 a non-core row has no neighbour but itself: no border row exists, steps 4-5 are empty and every
 non-core row is noise.  Duplicate rows are ordinary rows at distance ~0, as for scikit-learn.
+
+DELETING THE m OLDEST of n rows, 1 <= m <= n (`delete_oldest`; the kernels: mused_dbscan_incr_delete).  D = [0, m) are the
+deleted rows, S = [m, n) the survivors.  The pin is the same: afterwards the labels of the rows still held equal scikit-learn's
+refit of those rows in their order (tests/test_dbscan_incr_delete_host.py, after every operation).
+
+    1 UNCOUNT  D against S: count[j] -= |{ i in D : d2(i, j) <= eps^2 }| for j in S.  No rounding test and no new flag: every
+               pair was tested against tau when the later of its two rows was inserted, so an unflagged state holds no pair
+               whose side of eps^2 depends on how d2 is evaluated, and the counts stay exact.
+    2 REMEMBER before anything moves: core_before, root_before[i] = find(i) for the core rows, find(best[i]) for the non-core
+               rows that have a best (O(n)).
+    3 AFFECTED gone = the core rows of D; lost = the rows of S that were core and have count < min_samples now.  A component
+               (old root r) is affected iff it holds a row of gone or of lost.  An unaffected component keeps every core row
+               and every edge: it stays one component with the same root.
+    4 REBUILD  R = the rows of S that are still core and whose root_before is affected: parent[x] = x for x in R, then every
+               pair of R within eps^2 is united (the smaller root wins).  No edge joins R to a core row outside R: such a row
+               was in the same component before, and a deletion adds no edge.  R against the rows of S, never S x S; the
+               components the delete does not touch cost nothing.  (A lost row gets parent[x] = x: a non-core row is its own
+               parent, which is what an insert that turns it core again starts from.)
+    5 BORDER   (min_samples >= 3)  B = lost and the non-core rows of S whose remembered best is an affected root.  For b in B:
+               best[b] = the smallest NEW root among its core neighbours in S, or NONE.  Every other non-core row keeps its
+               best: the pieces of an affected component have roots >= the old root, so a minimum that came from an
+               unaffected component is still the minimum, and a row without a best gains no neighbour.
+    6 COMPACT  survivor i becomes i - m: nrm, count, parent and best move down by m, parent and best entries drop by m (a
+               core row's best is not read anywhere and is reset to NONE).  Labels as in 6 above.  m == n leaves the empty
+               state: the next insert is a first insert.
+
+Afterwards parent[x] <= x, a root is the smallest core index of its component and best is a root as of this operation: what
+an insert relies on.
 """
 from __future__ import annotations
 
@@ -69,12 +97,18 @@ def _flatten(parent):
 class IncrementalSpec:
     """`insert(X)` -> int64 labels of all rows seen so far (the rule at the head of this module).  `flags`: FLAG_AMBIGUOUS
     once some pair of an insert lay within tau of eps^2 (the labels then hang on rounding and are no longer pinned).
-    `dirty`: per insert (|dirtyA|, |dirtyB|)."""
+    `dirty`: per insert (|dirtyA|, |dirtyB|).  `delete_oldest(m)` -> int64 labels of the rows still held; `last_delete`: its
+    (flags = 0, clusters, core rows, rows that lost core status, |R|, |B|), the info word of mused_dbscan_incr_delete.
+    max_rows: an insert that would leave more rows first deletes the surplus oldest ones."""
 
-    def __init__(self, eps, min_samples):
+    def __init__(self, eps, min_samples, max_rows=None):
         if not (float(eps) > 0.0) or int(min_samples) < 1:
             raise ValueError("eps must be > 0 and min_samples >= 1")
+        if max_rows is not None and int(max_rows) < 1:
+            raise ValueError("max_rows must be >= 1")
         self.eps, self.min_samples = float(eps), int(min_samples)
+        self.max_rows = None if max_rows is None else int(max_rows)
+        self.last_delete = None
         self.n, self.X = 0, None
         self.nrm = np.empty(0)
         self.count = np.empty(0, dtype=np.int64)
@@ -106,6 +140,11 @@ class IncrementalSpec:
             raise ValueError("Input contains NaN or infinity.")
         if self.X is not None and X.shape[1] != self.X.shape[1]:
             raise ValueError("every insert must have the same number of columns")
+        if self.max_rows is not None:
+            if X.shape[0] > self.max_rows:
+                raise ValueError(f"a window of {X.shape[0]} rows is larger than max_rows = {self.max_rows}")
+            if self.n + X.shape[0] > self.max_rows:
+                self.delete_oldest(self.n + X.shape[0] - self.max_rows)
         n0, w = self.n, X.shape[0]
         n = self.n = n0 + w
         ms = self.min_samples
@@ -155,8 +194,13 @@ class IncrementalSpec:
                 k, col = np.nonzero(within & core[None, :])
                 np.minimum.at(best, r[k], parent[col])
         self.dirty.append((len(dirty_a), len(dirty_b)))
-        # 6 LABELS
-        roots = np.flatnonzero(core & (parent == idx))
+        return self._labels()
+
+    def _labels(self):
+        """6 LABELS (parent is flat)."""
+        n, parent, best = self.n, self.parent, self.best
+        core = self.count >= self.min_samples
+        roots = np.flatnonzero(core & (parent == np.arange(n)))
         rank = np.full(n, -1, dtype=np.int64)
         rank[roots] = np.arange(len(roots))
         self.core, self.clusters = core, len(roots)
@@ -164,4 +208,67 @@ class IncrementalSpec:
         labels = np.full(n, -1, dtype=np.int64)
         labels[core] = rank[parent[core]]
         labels[border] = rank[best[border]]
+        return labels
+
+    def delete_oldest(self, m):
+        """Deletes rows 0 .. m - 1 (the rule at the head of this module) -> int64 labels of the n - m rows still held."""
+        n, m, ms = self.n, int(m), self.min_samples
+        if not 1 <= m <= n:
+            raise ValueError(f"delete_oldest: m = {m} is outside [1, {n}]")
+        if m == n:
+            self.n, self.X = 0, None
+            self.nrm = np.empty(0)
+            self.count, self.parent, self.best = (np.empty(0, dtype=np.int64) for _ in range(3))
+            self.last_delete = (0, 0, 0, 0, 0, 0)
+            return self._labels()
+        count, best, idx = self.count, self.best, np.arange(n)
+        surv = idx >= m
+        # 2 REMEMBER
+        core_before = count >= ms
+        parent = _flatten(self.parent)
+        root_before = parent.copy()
+        had_best = ~core_before & (best != NONE)
+        best_before = np.full(n, NONE, dtype=np.int64)
+        best_before[had_best] = parent[best[had_best]]
+        # 1 UNCOUNT
+        for r, within, _, _ in self._blocks(idx[:m]):
+            count[m:] -= within[:, m:].sum(axis=0)
+        # 3 AFFECTED
+        core = surv & (count >= ms)
+        lost = surv & core_before & ~core
+        affected = np.zeros(n, dtype=bool)
+        affected[root_before[core_before & ~core]] = True      # gone and lost
+        # 4 REBUILD
+        in_r = core & affected[root_before]
+        rows_r = np.flatnonzero(in_r)
+        parent[rows_r] = rows_r
+        parent[lost] = idx[lost]
+        for r, within, _, _ in self._blocks(rows_r):
+            k, col = np.nonzero(within & core[None, :])
+            assert in_r[col].all()                             # no edge joins R to a core row outside R
+            ea, eb = r[k], col
+            while True:
+                pa, pb = parent[ea], parent[eb]
+                diff = pa != pb
+                if not diff.any():
+                    break
+                np.minimum.at(parent, np.maximum(pa, pb)[diff], np.minimum(pa, pb)[diff])
+                parent = _flatten(parent)
+        # 5 BORDER
+        rows_b = np.empty(0, dtype=np.int64)
+        if ms > 2:
+            stale = surv & had_best
+            stale[stale] = affected[best_before[stale]]
+            rows_b = np.flatnonzero(lost | stale)
+            best[rows_b] = NONE
+            for r, within, _, _ in self._blocks(rows_b):
+                k, col = np.nonzero(within & core[None, :])
+                np.minimum.at(best, r[k], parent[col])
+        # 6 COMPACT
+        best[core] = NONE
+        self.n, self.X, self.nrm, self.count = n - m, self.X[m:], self.nrm[m:], count[m:]
+        self.parent = parent[m:] - m
+        self.best = np.where(best[m:] == NONE, NONE, best[m:] - m)
+        labels = self._labels()
+        self.last_delete = (0, self.clusters, int(core.sum()), int(lost.sum()), len(rows_r), len(rows_b))
         return labels

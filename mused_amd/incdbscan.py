@@ -6,6 +6,10 @@ inserted so far, numbering included (the rule and why it is exact: mused_amd/dbs
 pin the class to, bit for bit.  It is NOT pinned to the `incdbscan` package the reference imports: the package is not
 available here, so its cluster numbers, its float labels and its choice for a border row between clusters are unchecked.
 The labels of rows inserted earlier may change with a later insert (clusters merge, numbers shift), as a refit's would.
+
+A SLIDING WINDOW: `delete_oldest(m)` drops the m oldest rows on the device (mused_dbscan_incr_delete), `max_rows` lets every
+insert do so by itself, `delete(X)` is the package's call for rows that ARE the oldest ones.  The pin is the same: after any
+sequence of inserts and deletes the labels of the rows still held are those of scikit-learn's refit of these rows in their order.
 """
 from __future__ import annotations
 
@@ -28,16 +32,29 @@ class IncrementalDBSCAN:
     """eps, min_pts: as DBSCAN's eps, min_samples.  chunk: rows per staging panel of the kernels (a multiple of 128).
     stream: the kernels run on it (default: the current stream at each insert); an insert returns after they have finished.
 
+    max_rows: None (the default: the state only grows, as the reference's use of the class has it), or the most rows to hold: an
+    insert that would leave more first deletes the surplus oldest rows (deleting first keeps the insert small; the final state
+    does not depend on the order).  A window of more than max_rows rows is a ValueError.
+
     The state tensors (rows, norms, counts, union-find, border minima) are owned here and grow by doubling up to 2^19 rows.
+    The rows live in a buffer behind an offset: a delete moves no row, and when the tail of the buffer runs out the rows held
+    are copied to its front once (with deletes the buffer is sized for twice the rows held, so that this happens once per that
+    many rows).  With max_rows set the buffer never exceeds 2 max_rows rows, the other state tensors max_rows: a stream of any
+    length runs.
     Host mode, in which every insert refits scikit-learn's DBSCAN on a host copy of all rows, is entered for good
       * by an insert whose kernel raises the ambiguity flag (some pair lies within rounding of eps: mused_amd/dbscan.py); that
         insert and every later one is counted in `matrix_operations.dbscan_incr_fallbacks`;
       * uncounted, under MUSED_DBSCAN=host (read at construction) and beyond 2^19 rows.
     A non-finite row raises scikit-learn's ValueError("Input contains NaN or infinity."); the object then refuses inserts."""
 
-    def __init__(self, eps=1.0, min_pts=5, chunk=4096, stream=None):
+    def __init__(self, eps=1.0, min_pts=5, chunk=4096, stream=None, max_rows=None):
         if not (float(eps) > 0.0) or int(min_pts) < 1:
             raise ValueError("eps must be > 0 and min_pts >= 1")
+        if max_rows is not None and int(max_rows) < 1:
+            raise ValueError("max_rows must be >= 1")
+        self.max_rows = None if max_rows is None else int(max_rows)
+        self._off = 0              # the rows held are _X[_off : _off + n]
+        self.last_delete_info = None   # device mode: {0, clusters, core rows, lost core status, |R|, |B|} of the last delete
         self.eps, self.min_pts, self.chunk = float(eps), int(min_pts), int(chunk)
         self._stream = stream
         self.n, self.d = 0, None
@@ -52,35 +69,57 @@ class IncrementalDBSCAN:
         self.dirty = []            # per device insert (rows that turned core, core rows whose root moved)
 
     # ---- state ---------------------------------------------------------------------------------
+    def _rows(self):
+        return self._X[self._off:self._off + self.n]
+
     def _grow(self, n, dev):
+        """Room for n rows in all (the n - self.n new ones behind the rows held)."""
+        cap = 0 if self._nrm is None else self._nrm.shape[0]
+        if n > cap:
+            new = max(_FIRST_CAPACITY, cap)
+            while new < n:
+                new *= 2
+            new = min(new, MAX_ROWS) if self.max_rows is None else min(new, MAX_ROWS, self.max_rows)
+            L = _lib.lib()
+            nbytes = max(int(L.mused_dbscan_incr_ws_bytes(new, self.d, self.chunk)),
+                         int(L.mused_dbscan_incr_delete_ws_bytes(new, self.d, self.chunk)))
+            if nbytes < 0:
+                raise ValueError(f"IncrementalDBSCAN: d = {self.d} or chunk = {self.chunk} is not taken (chunk: a multiple of "
+                                 "128 in [128, 65536])")
+
+            def moved(old, dtype):
+                t = torch.empty((new,), dtype=dtype, device=dev)
+                if old is not None and self.n:
+                    t[:self.n] = old[:self.n]
+                return t
+
+            self._nrm = moved(self._nrm, torch.float64)
+            self._count, self._parent, self._best = (moved(t, torch.int32) for t in (self._count, self._parent, self._best))
+            self._labels = torch.empty(new, dtype=torch.int32, device=dev)
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         cap = 0 if self._X is None else self._X.shape[0]
-        if n <= cap:
+        if self._off + n <= cap:
+            return
+        # the tail has run out.  A state that deletes keeps twice the rows held, so that the copy to the front is paid once
+        # per that many rows; one that only grows keeps the capacity of the other tensors
+        slack = 2 if (self.max_rows is not None or self._off) else 1
+        if slack * n <= cap:
+            self._X[:self.n] = self._rows().clone()
+            self._off = 0
             return
         new = max(_FIRST_CAPACITY, cap)
-        while new < n:
+        while new < slack * n:
             new *= 2
-        new = min(new, MAX_ROWS)
-        nbytes = int(_lib.lib().mused_dbscan_incr_ws_bytes(new, self.d, self.chunk))
-        if nbytes < 0:
-            raise ValueError(f"IncrementalDBSCAN: d = {self.d} or chunk = {self.chunk} is not taken (chunk: a multiple of 128 "
-                             "in [128, 65536])")
-
-        def moved(old, shape, dtype):
-            t = torch.empty(shape, dtype=dtype, device=dev)
-            if old is not None and self.n:
-                t[:self.n] = old[:self.n]
-            return t
-
-        self._X = moved(self._X, (new, self.d), torch.float64)
-        self._nrm = moved(self._nrm, (new,), torch.float64)
-        self._count, self._parent, self._best = (moved(t, (new,), torch.int32) for t in (self._count, self._parent, self._best))
-        self._labels = torch.empty(new, dtype=torch.int32, device=dev)
-        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        new = min(new, MAX_ROWS) if slack == 1 else (new if self.max_rows is None else min(new, 2 * self.max_rows))
+        X = torch.empty((new, self.d), dtype=torch.float64, device=dev)
+        if self.n:
+            X[:self.n] = self._rows()
+        self._X, self._off = X, 0
 
     def _to_host_mode(self, counted):
         self._host_mode, self._counted = True, counted
         if self._X is not None:
-            self._host_rows = self._X[:self.n].cpu().numpy()
+            self._host_rows = self._rows().cpu().numpy()
         self._X = self._nrm = self._count = self._parent = self._best = self._labels = self._ws = None
 
     # ---- the reference's two calls ---------------------------------------------------------------
@@ -93,6 +132,11 @@ class IncrementalDBSCAN:
         if rows.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] < 1 or (self.d is not None and rows.shape[1] != self.d):
             raise ValueError("X must be (w, d) with w, d >= 1 and the d of the earlier inserts")
         self.d = int(rows.shape[1])
+        if self.max_rows is not None:
+            if rows.shape[0] > self.max_rows:
+                raise ValueError(f"a window of {rows.shape[0]} rows is larger than max_rows = {self.max_rows}")
+            if self.n + rows.shape[0] > self.max_rows:
+                self._delete(self.n + int(rows.shape[0]) - self.max_rows, refit=False)   # (host mode: the insert below refits)
         n0, n = self.n, self.n + int(rows.shape[0])
         if not self._host_mode and n > MAX_ROWS:
             self._to_host_mode(False)
@@ -119,9 +163,10 @@ class IncrementalDBSCAN:
         with torch.cuda.stream(st):
             dev = rows.device if isinstance(rows, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
             self._grow(n, dev)
-            self._X[n0:n] = rows if isinstance(rows, torch.Tensor) else torch.tensor(rows, device=dev)
+            held = self._X[self._off:]
+            held[n0:n] = rows if isinstance(rows, torch.Tensor) else torch.tensor(rows, device=dev)
             info = (C.c_int * 6)()
-            _lib.call("mused_dbscan_incr_insert", ptr(self._X), self._X.stride(0), self.d, ptr(self._nrm), ptr(self._count),
+            _lib.call("mused_dbscan_incr_insert", ptr(held), held.stride(0), self.d, ptr(self._nrm), ptr(self._count),
                       ptr(self._parent), ptr(self._best), n0, n - n0, self.eps, self.min_pts, self.chunk, ptr(self._labels),
                       info, ptr(self._ws), self._ws.numel(), C.c_void_p(st.cuda_stream))
             self.n = n
@@ -136,8 +181,64 @@ class IncrementalDBSCAN:
                 return
             self.dirty.append((int(info[4]), int(info[5])))
 
+    # ---- a sliding window -------------------------------------------------------------------------
+    def delete_oldest(self, m):
+        """Drops the m oldest rows held, 1 <= m <= n.  Returns self; `labels()` then covers the rows still held."""
+        if self._dead:
+            raise ValueError("this IncrementalDBSCAN met a non-finite row and takes no further calls")
+        m = int(m)
+        if not 1 <= m <= self.n:
+            raise ValueError(f"delete_oldest: m = {m} is outside [1, {self.n}] (the rows held)")
+        self._delete(m, refit=True)
+        return self
+
+    def delete(self, X):
+        """The `incdbscan` package's call, for the one case this class offers: X must be bit-equal to the oldest len(X) rows
+        held, in their order.  Anything else is a ValueError: rows are not looked up by value."""
+        on_dev = isinstance(X, torch.Tensor)
+        rows = X.to(torch.float64) if on_dev else np.ascontiguousarray(X, dtype=np.float64)
+        k = int(rows.shape[0]) if rows.ndim == 2 else 0
+        same = rows.ndim == 2 and 1 <= k <= self.n and rows.shape[1] == self.d
+        if same and self._host_mode:
+            mine = self._host_rows[:k]
+            same = np.array_equal(mine.view(np.int64), (rows.cpu().numpy() if on_dev else rows).view(np.int64))
+        elif same:
+            mine = self._X[self._off:self._off + k]
+            theirs = rows if on_dev else torch.tensor(rows, device=mine.device)
+            same = bool(torch.equal(mine.view(torch.int64), theirs.contiguous().view(torch.int64)))
+        if not same:
+            raise ValueError("delete takes the oldest rows held only, bit-equal and in their order: lookup by value is not "
+                             "offered (delete_oldest(m) drops them by number)")
+        return self.delete_oldest(k)
+
+    def _delete(self, m, refit):
+        n = self.n - m
+        if self._last is not None:
+            self._last_lo -= m
+            if self._last_lo < 0:
+                self._last = None
+        if self._host_mode:
+            self._host_rows = self._host_rows[m:]
+            self.n = n
+            if refit:
+                if self._counted:
+                    mo._dbscan_incr_count_fallback()
+                self._host_labels = (np.asarray(mo.perform_dbscan_clustering(self._host_rows, self.eps, self.min_pts), dtype=np.int64)
+                                     if n else np.empty(0, dtype=np.int64))
+            return
+        st = mo._match_stream(self._stream)
+        with torch.cuda.stream(st):
+            held = self._X[self._off:]
+            info = (C.c_int * 6)()
+            _lib.call("mused_dbscan_incr_delete", ptr(held), held.stride(0), self.d, ptr(self._nrm), ptr(self._count),
+                      ptr(self._parent), ptr(self._best), self.n, m, self.eps, self.min_pts, self.chunk, ptr(self._labels),
+                      info, ptr(self._ws), self._ws.numel(), C.c_void_p(st.cuda_stream))
+        self.n = n
+        self._off = self._off + m if n else 0
+        self.last_delete_info = np.array(info[:], dtype=np.int32)
+
     def labels(self):
-        """int64 NumPy labels of all rows inserted so far (-1 = noise)."""
+        """int64 NumPy labels of the rows held: all rows inserted so far but the deleted ones (-1 = noise)."""
         if self.n == 0:
             return np.empty(0, dtype=np.int64)
         if self._host_mode:

@@ -10,7 +10,8 @@ Per full window (trigger rule of main.py:32):
        (n_clusters_total) for the whole stream, partial_fit + predict per window IN WINDOW ORDER (main.py:82-86)
        "DBSCAN_incr": one IncrementalDBSCAN(eps, min_samples) for the whole stream, insert + get_cluster_labels per window IN
        WINDOW ORDER (main.py:87-91; mused_amd/incdbscan.py, csrc/dbscan_incr.hip: the labels of a DBSCAN refit on every row
-       inserted so far)
+       inserted so far; with `dbscan_max_rows` over a sliding window of that many rows: the oldest rows are deleted on the
+       device before each insert, and the labels are those of a refit on the rows still held)
     -> Hungarian matching against the previous window, min_overlap = 3 (main.py:110); "sSVDMC_pot": matching by the
        Sinkhorn transport plan (main.py:111) in csrc/match.hip
     -> labels appended (main.py:118-119).
@@ -41,7 +42,8 @@ from .swfd import SeqBasedSWFD
 class StreamPipeline:
     def __init__(self, window_size, reduced_dim, k_basis, seed, approach="sSVDMC", modality_types=None,
                  step_window_ratio=1, engine=None, async_labels=True, feature_sketch=False, stream=None,
-                 assume_finite=False, window_slots=1, n_clusters_total=None, eps=0.5, min_samples=5):
+                 assume_finite=False, window_slots=1, n_clusters_total=None, eps=0.5, min_samples=5,
+                 dbscan_max_rows=None):
         if approach not in ("sSVDMC", "sSVDMC_hung", "sSVDMC_pot", "sSVDMC_mini", "SWFDMC", "DBSCAN_incr"):
             raise ValueError(f"approach {approach!r} is not on the device hot path")
         if approach == "sSVDMC_mini" and n_clusters_total is None:
@@ -56,6 +58,10 @@ class StreamPipeline:
         self._incr = approach == "DBSCAN_incr"
         self._chained = self._mini or self._incr
         self.eps, self.min_samples = eps, min_samples
+        # None: the state only grows (main.py:87-91).  A number: IncrementalDBSCAN(max_rows=...), at least one window
+        self.dbscan_max_rows = None if dbscan_max_rows is None else int(dbscan_max_rows)
+        if self.dbscan_max_rows is not None and self.dbscan_max_rows < int(window_size):
+            raise ValueError(f"dbscan_max_rows = {dbscan_max_rows} is smaller than a window ({window_size} rows)")
         # "sSVDMC_pot": embedding and k-means as "sSVDMC"; the label chain matches by the Sinkhorn plan (main.py:111), every
         # other approach by SciPy's assignment (main.py:110).  Both chains run on the device (csrc/match.hip,
         # csrc/match_hung.hip), or on the host (mused_amd/sinkhorn.py, SciPy) under MUSED_MATCH=host
@@ -342,7 +348,7 @@ class StreamPipeline:
         if st is None:
             st = self._km_local.stream = torch.cuda.Stream(priority=-1)
         if self.clusterer is None:
-            self.clusterer = IncrementalDBSCAN(eps=self.eps, min_pts=self.min_samples, stream=st)
+            self.clusterer = IncrementalDBSCAN(eps=self.eps, min_pts=self.min_samples, stream=st, max_rows=self.dbscan_max_rows)
         if reduced_dev is not None and reduced_dev.dtype == torch.float64:
             reduced_dev.record_stream(st)  # produced on the pipeline's stream, complete (ev), consumed on the worker's
             X = reduced_dev
@@ -657,12 +663,14 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
     concatenated true labels of main.py:39-40, which repeat rows when step_window_ratio > 1; "processing_time" is then
     the reference's list), and "window_scores", the (K, 7) scores of the K windows from one launch
     (metrics_evaluation.score_windows)."""
+    # MUSED_DBSCAN_INCR_ROWS (read at every call; DBSCAN_incr only): the rows the stream's IncrementalDBSCAN holds at most
+    incr_rows = os.environ.get("MUSED_DBSCAN_INCR_ROWS") if approach == "DBSCAN_incr" else None
     t0 = time.time_ns()
     # modality types go through unchanged: "" / anything the reference does not special-case = Euclidean kNN
     # (matrix_operations.py:112), "text" and "cosine" = the cosine kernel, the other SED2012 metadata types raise
     with StreamPipeline(window_size, reduced_dim, k_basis, seed, approach, list(modality_types), step_window_ratio,
                         window_slots=int(os.environ.get("MUSED_WINDOW_SLOTS", "1")), n_clusters_total=n_clusters_total,
-                        eps=eps, min_samples=min_samples) as pipe:
+                        eps=eps, min_samples=min_samples, dbscan_max_rows=int(incr_rows) if incr_rows else None) as pipe:
         clusters = pipe.run(data_modalities, np.asarray(complete_true_labels))
     t1 = time.time_ns()
     if score:
