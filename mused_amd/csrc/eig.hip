@@ -62,6 +62,9 @@ struct EigPlan {
   double* Gc = nullptr;   // batch x ldn x ldn, column-major working copy
   double* lam = nullptr;  // batch x ldn column norms
   const int* rep = nullptr;  // optional: matrix b is a duplicate of matrix rep[b] != b and is not solved
+  const int* list = nullptr;  // optional: the representatives compacted (list[0] of them, list[1 ..]): the direct solver's workgroups
+                              // and the queue's set-up go through it instead of testing rep per matrix
+  const int* offs = nullptr;  // optional (direct solver of order 256): 256 - the order matrix b is solved at
   const int* jrep = nullptr;  // what the Jacobi's launch-per-round kernels test (matrix b runs when jrep[b] == b): rep, or -- behind
                               // the blocked direct solver (trdx.hip) -- the per-solve list of the matrices it rejected
   int* err_out = nullptr;  // optional device word the caller reads back: set when the queue solver gave up (results invalid)
@@ -927,8 +930,8 @@ __global__ void osjq_zero_kernel(unsigned* __restrict__ q, unsigned n, const Osj
 // (osj_begin_kernel's work, for those matrices only) -- and the queue sealed when there are none.  One workgroup.
 __global__ __launch_bounds__(1024) void osjq_prep_direct_kernel(OsjqCtl* __restrict__ ctl, unsigned* __restrict__ q, unsigned qcap,
                                                                int* __restrict__ qdone, int* __restrict__ qclean, int batch,
-                                                               int upr, const int* __restrict__ rep, const int* __restrict__ skip,
-                                                               const double* __restrict__ Gc, int ldn, int nflag,
+                                                               int upr, const int* __restrict__ rep, const int* __restrict__ list,
+                                                               const int* __restrict__ skip, const double* __restrict__ Gc, int ldn, int nflag,
                                                                double* __restrict__ trace, int* __restrict__ notconv) {
   __shared__ int s_dirty;
   const int t = threadIdx.x;
@@ -941,10 +944,15 @@ __global__ __launch_bounds__(1024) void osjq_prep_direct_kernel(OsjqCtl* __restr
     ctl->head = 0; ctl->tail = 0; ctl->finished = 0; ctl->nmat = 0; ctl->all_done = 0; ctl->error = 0; ctl->dirty = 0;
   }
   __syncthreads();
-  for (int m = t; m < batch; m += 1024) {
-    qdone[m] = 0;
-    qclean[m] = 0;
-    if (rep && rep[m] != m) continue;
+  for (int i = t; i < batch; i += 1024) {
+    qdone[i] = 0;
+    qclean[i] = 0;
+  }
+  __syncthreads();
+  const int nrun = list ? list[0] : batch;
+  for (int i = t; i < nrun; i += 1024) {
+    const int m = list ? list[1 + i] : i;
+    if (!list && rep && rep[m] != m) continue;
     if (skip && skip[m]) continue;  // solved by the direct solver
     if (trace) {
       const double* M = Gc + (long)m * ldn * ldn;
@@ -968,7 +976,7 @@ static void osjq_launch(EigPlan* p, hipStream_t st) {
   const bool behind_direct = p->c.direct == EigDirect::Trd;
   if (behind_direct) {
     hipLaunchKernelGGL(osjq_prep_direct_kernel, dim3(1), dim3(1024), 0, st, p->qctl, p->q, p->qcap, p->qdone, p->qclean, p->batch,
-                       upr, p->rep, p->trd_done, p->Gc, ldn, p->notconv ? p->sweeps * p->c.rps : 0, p->notconv ? p->trace : nullptr,
+                       upr, p->rep, p->list, p->trd_done, p->Gc, ldn, p->notconv ? p->sweeps * p->c.rps : 0, p->notconv ? p->trace : nullptr,
                        p->notconv);
   } else {
     hipLaunchKernelGGL(osjq_zero_kernel, dim3(cdiv(p->qcap, 1024)), dim3(1024), 0, st, p->q, p->qcap, p->qctl);
@@ -1256,7 +1264,7 @@ static int eig_plan_create_impl(EigPlan* p, const EigEnv& env, bool own_graph) {
 }
 
 int eig_plan_create(int n, int batch, int sweeps, bool own_graph, EigPlan** out, const int* rep, int flags, int* err_out,
-                    int need) {
+                    int need, const int* list, const int* offs) {
   MUSED_REQUIRE(n >= 2 && n % 2 == 0 && n <= 1024 && batch >= 1 && sweeps >= 1,
                 "eig_plan_create: the order must be even and <= 1024 (n=%d)", n);
   CaptureLock resource_guard(capture_mutex());  // allocations + capture: not beside another thread's capture
@@ -1266,6 +1274,12 @@ int eig_plan_create(int n, int batch, int sweeps, bool own_graph, EigPlan** out,
   p->rep = p->jrep = rep;
   p->err_out = err_out;
   p->c = eig_choose(n, batch, sweeps, flags, need, env);
+  // the list serves the register-resident direct solver and the queue behind it (the launch-per-round kernels and the
+  // blocked solver test rep); per-matrix orders exist at its layout order only
+  if (p->c.direct == EigDirect::Trd) {
+    p->list = list;
+    if (n == 256 && p->c.ldn == 256) p->offs = offs;
+  }
   const int rc = eig_plan_create_impl(p, env, own_graph);
   if (rc) {  // release what the earlier steps took (the error message of the first failure is kept)
     eig_plan_destroy(p);
@@ -1387,7 +1401,7 @@ static int eig_run_direct(EigPlan* p, hipStream_t st, bool rec) {
   int rc;
   if (p->c.direct == EigDirect::Trd) {
     rc = trd_solve(p->Gc, p->n, p->c.ldn, p->c.need, p->c.cert_all, p->batch, p->rep, p->trd_done, p->trd_ws, st, nullptr, work,
-                   after_a, p->lam);
+                   after_a, p->lam, p->list, p->offs);
   } else {
     MUSED_CHECK_HIP(hipMemsetAsync(p->trdx_nrej, 0, sizeof(int), st));
     rc = trdx_solve(p->Gc, p->c.ldn, p->c.need, p->c.cert_all, p->batch, p->rep, p->trd_done, p->trdx_act, p->trdx_jrep,

@@ -43,6 +43,10 @@ struct GemmArgs {
                // sees z = blockIdx.z (partial results, summed in split order by gemm_batched_splitk_reduce)
   int tiles_m, tiles_n;
   const int* rep;  // optional (batched launches): batch entry z is computed only if rep[z] == z
+  const int* list;  // optional, instead of rep: list[0] entries are computed, workgroup z of the batch takes entry list[1 + z]
+                    // (the workgroups that only exit lie behind the working ones in dispatch order)
+  const int* kact;  // optional (plain batched launches): entry z multiplies over k < kact[z] only -- for operands that are
+                    // exact zeros from there on: the skipped terms are fma(0, 0, acc), the result is bit-identical
   int sym;  // C = A A^T (A == B, M == N) with a symmetric epilogue: only tiles on or above the diagonal are computed,
             // each off-diagonal tile is also written mirrored (epi(z, col, row, v)): half the MFMA work
 };
@@ -255,9 +259,14 @@ template <typename TA, typename TB, bool A_KC, bool B_KC, bool VEC, typename Epi
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_f64_kernel(GemmArgs g, Epi epi) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
 
-  const int z = blockIdx.z;
-  const int zb = g.bsplit ? z / g.bsplit : z;  // batch entry
-  if (g.rep && g.rep[zb] != zb) return;  // a duplicate of entry rep[zb]: its consumer reads that one
+  int z = blockIdx.z;
+  int zb = g.bsplit ? z / g.bsplit : z;  // batch entry
+  if (g.list) {
+    if (zb >= g.list[0]) return;
+    const int e = g.list[1 + zb];
+    z += (e - zb) * (g.bsplit ? g.bsplit : 1);
+    zb = e;
+  } else if (g.rep && g.rep[zb] != zb) return;  // a duplicate of entry rep[zb]: its consumer reads that one
   int tm, tn;
   if (g.sym) {
     // C = A A^T with a symmetric epilogue: the grid holds the tiles on or above the diagonal only, row-major over
@@ -301,6 +310,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_f64_kernel(GemmArgs g, E
     if (g.bsplit) {
       k_lo = (z - zb * g.bsplit) * g.kchunk;
       k_hi = min(g.K, k_lo + g.kchunk);
+    } else if (g.kact) {
+      k_hi = min(g.K, g.kact[zb]);
     }
   }
 

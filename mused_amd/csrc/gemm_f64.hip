@@ -28,12 +28,12 @@ int gemm_f64_prepare_all() {
 
 int gemm_f64(bool a_kc, bool b_kc, const double* A, long lda, long strideA, const double* B, long ldb,
              long strideB, double* C, long ldc, long strideC, int M, int N, int K, int batch, double alpha,
-             hipStream_t stream, const int* rep) {
+             hipStream_t stream, const int* rep, const int* list, const int* kact) {
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   g.A = A; g.B = B; g.lda = lda; g.ldb = ldb; g.strideA = strideA; g.strideB = strideB;
   g.M = M; g.N = N; g.K = K; g.splitk = 0; g.kchunk = 0;
-  g.rep = rep;
+  g.rep = rep; g.list = list; g.kact = kact;
   // Gram products (A A^T: same operand, same layout, square result): tiles on or above the diagonal + mirrored stores
   g.sym = (A == B && a_kc == b_kc && lda == ldb && strideA == strideB && M == N) ? 1 : 0;
   EpiStore epi{C, ldc, strideC, alpha};
@@ -74,14 +74,14 @@ __global__ void splitk_reduce_kernel(const double* __restrict__ partial, int nsp
 // batch).  For products whose K loop is long and whose tiles do not fill the GPU (sketch Gram matrices at d = 10,000).
 int gemm_f64_batched_splitk(bool a_kc, bool b_kc, const double* A, long lda, long strideA, const double* B, long ldb, long strideB,
                             double* partial, int M, int N, int K, int batch, int kchunk, int nsplit, hipStream_t stream,
-                            const int* rep) {
+                            const int* rep, const int* list) {
   MUSED_REQUIRE(kchunk > 0 && kchunk % GEMM_BK == 0 && nsplit >= 1 && (long)kchunk * nsplit >= K,
                 "gemm_f64_batched_splitk: bad kchunk %d x %d for K=%d", kchunk, nsplit, K);
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   g.A = A; g.B = B; g.lda = lda; g.ldb = ldb; g.strideA = strideA; g.strideB = strideB;
   g.M = M; g.N = N; g.K = K; g.splitk = 0; g.kchunk = kchunk; g.bsplit = nsplit;
-  g.rep = rep;
+  g.rep = rep; g.list = list;
   g.sym = (A == B && a_kc == b_kc && lda == ldb && strideA == strideB && M == N) ? 1 : 0;
   EpiStore epi{partial, (long)N, (long)M * N, 1.0};
   const bool vec = vec_ok<double>(A, lda, strideA) && vec_ok<double>(B, ldb, strideB);
@@ -92,9 +92,12 @@ int gemm_f64_batched_splitk(bool a_kc, bool b_kc, const double* A, long lda, lon
 }
 
 __global__ void batched_splitk_reduce_kernel(const double* __restrict__ partial, int nsplit, long count, double* __restrict__ out,
-                                             const int* __restrict__ rep) {
-  const int z = blockIdx.y;
-  if (rep && rep[z] != z) return;
+                                             const int* __restrict__ rep, const int* __restrict__ list) {
+  int z = blockIdx.y;
+  if (list) {
+    if (z >= list[0]) return;
+    z = list[1 + z];
+  } else if (rep && rep[z] != z) return;
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
   const double* p = partial + (long)z * nsplit * count + i;
@@ -104,9 +107,9 @@ __global__ void batched_splitk_reduce_kernel(const double* __restrict__ partial,
 }
 
 int gemm_batched_splitk_reduce(const double* partial, int nsplit, long count, double* out, int batch, const int* rep,
-                               hipStream_t stream) {
+                               hipStream_t stream, const int* list) {
   hipLaunchKernelGGL(batched_splitk_reduce_kernel, dim3(cdiv(count, 256), batch), dim3(256), 0, stream, partial, nsplit, count, out,
-                     rep);
+                     rep, list);
   MUSED_LAUNCH_CHECK();
   return MUSED_OK;
 }
@@ -153,6 +156,14 @@ int mused_gemm_f64_batched_rep(int a_kc, int b_kc, const double* A, long lda, lo
                                double alpha, const int* rep, void* stream) {
   return mused::gemm_f64(a_kc != 0, b_kc != 0, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, M, N, K, batch,
                          alpha, (hipStream_t)stream, rep);
+}
+
+// The same with a compacted list (list[0] = count, list[1 ..] = entries; see GemmArgs) and / or a K bound per entry.
+int mused_debug_gemm_f64_batched_active(int a_kc, int b_kc, const double* A, long lda, long strideA, const double* B, long ldb,
+                                        long strideB, double* C, long ldc, long strideC, int M, int N, int K, int batch,
+                                        double alpha, const int* list, const int* kact, void* stream) {
+  return mused::gemm_f64(a_kc != 0, b_kc != 0, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, M, N, K, batch,
+                         alpha, (hipStream_t)stream, nullptr, list, kact);
 }
 
 int mused_gemm_f64_splitk(int a_kc, int b_kc, const double* A, long lda, const double* B, long ldb, double* partial,

@@ -31,15 +31,19 @@ using CaptureLock = std::lock_guard<std::recursive_mutex>;
 //   a_kc: A stored [M][K] (true) or [K][M] (false);  b_kc: B stored [N][K] (true) or [K][N] (false).
 int gemm_f64(bool a_kc, bool b_kc, const double* A, long lda, long strideA, const double* B, long ldb,
              long strideB, double* C, long ldc, long strideC, int M, int N, int K, int batch, double alpha,
-             hipStream_t stream, const int* rep = nullptr);
+             hipStream_t stream, const int* rep = nullptr, const int* list = nullptr, const int* kact = nullptr);
 // rep (device, batch ints, optional): entry z is computed only when rep[z] == z (duplicates are skipped)
+// list (device, 1 + batch ints, optional, instead of rep): the entries to compute, compacted -- list[0] of them, list[1 ..];
+//   workgroup z of the batch takes entry list[1 + z], so the workgroups with nothing to do are dispatched last
+// kact (device, batch ints, optional): entry z multiplies over k < kact[z] (a multiple of 16 keeps the vector loads) -- both operands must be exact
+//   zeros from there on, the result is then bit-identical to the full product
 
 // batched split-K (see gemm_f64.hip): partial results per (entry, split), then the fixed-order sum
 int gemm_f64_batched_splitk(bool a_kc, bool b_kc, const double* A, long lda, long strideA, const double* B, long ldb, long strideB,
                             double* partial, int M, int N, int K, int batch, int kchunk, int nsplit, hipStream_t stream,
-                            const int* rep = nullptr);
+                            const int* rep = nullptr, const int* list = nullptr);
 int gemm_batched_splitk_reduce(const double* partial, int nsplit, long count, double* out, int batch, const int* rep,
-                               hipStream_t stream);
+                               hipStream_t stream, const int* list = nullptr);
 // Sets the dynamic-LDS attribute of every plain GEMM instantiation (call before stream capture).
 int gemm_f64_prepare_all();
 
@@ -85,7 +89,11 @@ constexpr int EIG_PLAN_TOP_FD = 16;       // as TOP_HALF with an explicit `need`
 // err_out (device int, optional): OR-ed with 1 by a solve of the persistent work-queue solver that gave up waiting
 //   (timeout: the matrices are left partially rotated and the results of that solve are invalid)
 int eig_plan_create(int n, int batch, int sweeps, bool own_graph, EigPlan** out, const int* rep = nullptr, int flags = 0,
-                    int* err_out = nullptr, int need = 0);
+                    int* err_out = nullptr, int need = 0, const int* list = nullptr, const int* offs = nullptr);
+// list (device, 1 + batch ints, optional, read at every solve; plans whose direct solver is trd.hip, ignored by the others):
+//   list[0] = how many matrices have rep[b] == b, list[1 ..] = which; the solver's workgroups take their matrix from it
+// offs (device, batch ints, optional, read at every solve; order 256 with trd.hip only): matrix b is zero from row and column
+//   256 - offs[b] on and is solved at that order
 void eig_plan_destroy(EigPlan* p);
 // (batch x n x n) device buffer the caller fills with the symmetric matrices before eig_plan_run_inplace
 double* eig_plan_input(EigPlan* p);
@@ -121,7 +129,9 @@ long trd_tail_off_tg();
 int trd_tail_launch(const double* G, const int* rep, double* ws, int batch, hipStream_t st);
 int trd_solve(double* Gc, int n, int ldn, int need, bool cert_all, int batch, const int* rep, int* done, double* ws,
               hipStream_t st, long long* dbg_clk = nullptr, unsigned long long* work = nullptr, hipEvent_t after_a = nullptr,
-              double* lam_out = nullptr);  // lam_out (batch x ldn, optional): eigenvalues of the solved matrices (zeros behind them)
+              double* lam_out = nullptr,  // lam_out (batch x ldn, optional): eigenvalues of the solved matrices (zeros behind them)
+              const int* list = nullptr,  // list (1 + batch ints, optional): the matrices to solve, compacted
+              const int* offs = nullptr); // offs (batch ints, optional, n = ldn = 256): 256 - the order matrix b is solved at
 
 // trdx.hip: blocked direct solver for padded orders 320, 384, 448, 512 (need rounded up to 32 <= order / 2)
 bool trdx_supports(int ldn, int need);

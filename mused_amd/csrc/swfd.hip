@@ -38,6 +38,12 @@ struct Swfd {
   long long* qt;       // S x cap   snapshot timestamps
   int* meta;           // S x 4     {nk, qhead, qcount, dumps the next level did not make, since the last clear}
   int* rep;            // S         representative of the sketch's state class for the next rotation (see swfd_rep_kernel)
+  // the representatives of the next rotation, compacted and ordered (swfd_rep_kernel); each may be null (switched off)
+  int* list;           // 1 + S     {how many, which}: largest active order first
+  int* offs;           // S         n2 - the order the sketch's Gram matrix is solved at (order 256 only)
+  int oround;          //           offs is rounded down to a multiple of this power of two
+  int* kact;           // S         rows of the buffer in use, rounded up to 16: the K bound of the rotate product
+  long long* ostat;    // 18        {rotations, representatives, representatives by order used: (16 b, 16 b + 16]} since creation
   long long* dropped;  // S         largest timestamp of a snapshot lost to the ring capacity
   double* theta;       // S
   // rotation workspace
@@ -130,32 +136,76 @@ __global__ void swfd_set_now_kernel(long long* now, long long v) { *now = v; }
 // the epoch ends -- 55 % of the MAIN rotations on the benchmark stream (levels 0-3 after three rotations, levels 4-9
 // after ~32 of 78).  Exact: every get() returns what it would have returned; only `export_half(0)` of a dead level
 // shows the frozen state.  (Never in the first epoch of a stream, where the AUX chain borrows MAIN's solves.)
-__global__ void swfd_rep_kernel(const int* __restrict__ meta, int L, int nchains, int* __restrict__ rep, int twin,
-                                const long long* __restrict__ dropped, long long epoch_start, int skip_dead,
-                                long long* __restrict__ now_dev, long long now) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c == 0) *now_dev = now;  // (the rotation's time stamp: one launch less than a kernel of its own)
-  if (c >= nchains) return;
-  // first epoch of a stream: AUX is the twin of MAIN (both started empty) -> the AUX chain maps onto the MAIN chain
-  const int base = ((twin && (c & 1)) ? c - 1 : c) * L;  // sketch index = lane * 2L + kind * L + level = chain * L + level
-  if (twin && (c & 1)) {
+//
+// THE LIST (one workgroup does all of it).  The launches of a rotation have a grid per SKETCH, fixed on the host; a workgroup
+// that finds it has no matrix returns -- but the whole-CU workgroups of the eigensolver wait for an empty CU first, and sit
+// between the working ones in dispatch order.  list = {count, the representatives}: workgroup i takes list[1 + i], the ones
+// with nothing to do come last.  The order is by rows in use (n_act = kept + pending rows; ties by index): the longest solves
+// start first.  A buffer is zero from row n_act on, so its Gram matrix is zero from row and column n_act on: offs = n2 - max(n_act,
+// l) is the embedding offset the direct solver solves it at (its order-n path: n^3 instead of 256^3 work in the
+// tridiagonalisation), kact = n_act rounded up to the GEMM's K step bounds the K loop of the rotate product Wc buf.
+// Embedding offsets are rounded down to this multiple: a matrix within 15 rows of the full order is read in place (off = 0: no
+// copy into the workspace) -- on the benchmark stream that is 3 of 4 solves (levels 4 and up: 244 .. 251 rows in use); measured
+// against exact offsets and against 32 in DESIGN 5a.
+constexpr int SWFD_OFFS_ROUND = 16;
+__global__ __launch_bounds__(1024) void swfd_rep_kernel(const int* __restrict__ meta, int L, int nchains, int* __restrict__ rep,
+                                                        int twin, const long long* __restrict__ dropped, long long epoch_start,
+                                                        int skip_dead, long long* __restrict__ now_dev, long long now, int pend,
+                                                        int ell, int n2, int* __restrict__ list, int* __restrict__ offs,
+                                                        int* __restrict__ kact, long long* __restrict__ ostat, int oround) {
+  extern __shared__ int s_key[];  // [S] rows in use of a representative, -1 for every other sketch
+  __shared__ int s_hist[17];
+  const int t = threadIdx.x, S = nchains * L;
+  if (t == 0) *now_dev = now;  // (the rotation's time stamp: one launch less than a kernel of its own)
+  if (t < 17) s_hist[t] = 0;
+  auto put = [&](int s, int r) {
+    rep[s] = r;
+    const int na = meta[s * 4 + 0] + pend;
+    s_key[s] = (r == s) ? (na < n2 ? na : n2) : -1;
+  };
+  for (int c = t; c < nchains; c += 1024) {
+    // first epoch of a stream: AUX is the twin of MAIN (both started empty) -> the AUX chain maps onto the MAIN chain
+    const int base = ((twin && (c & 1)) ? c - 1 : c) * L;  // sketch index = lane * 2L + kind * L + level = chain * L + level
+    if (twin && (c & 1)) {
+      int r = base + L - 1;
+      put(c * L + L - 1, r);
+      for (int j = L - 2; j >= 0; --j) {
+        if (meta[(base + j) * 4 + 3] != 0) r = base + j;
+        put(c * L + j, r);
+      }
+      continue;
+    }
+    const bool dead_ok = skip_dead && !twin && (c & 1) == 0;  // MAIN chain (kind 0)
     int r = base + L - 1;
-    rep[c * L + L - 1] = r;
+    put(r, r);
     for (int j = L - 2; j >= 0; --j) {
       if (meta[(base + j) * 4 + 3] != 0) r = base + j;
-      rep[c * L + j] = r;
+      put(base + j, (dead_ok && dropped[base + j] > epoch_start) ? -1 : r);
     }
-    return;
   }
-  int r = base + L - 1;
-  rep[r] = r;
-  for (int j = L - 2; j >= 0; --j) {
-    if (meta[(base + j) * 4 + 3] != 0) r = base + j;
-    rep[base + j] = r;
+  __syncthreads();
+  if (!list) return;
+  for (int s = t; s < S; s += 1024) {
+    const int key = s_key[s];
+    if (key < 0) continue;
+    int rank = 0;
+    for (int j = 0; j < S; ++j) {
+      const int kj = s_key[j];
+      rank += (kj > key) || (kj == key && j < s);
+    }
+    list[1 + rank] = s;
+    // (the order solved: the rows in use, at least l, with the offset rounded down to a multiple of `oround`)
+    const int n = offs ? n2 - ((n2 - (key > ell ? key : ell)) & ~(oround - 1)) : n2;
+    if (offs) offs[s] = n2 - n;
+    if (kact) kact[s] = min(n2, (key + 15) & ~15);
+    atomicAdd(&s_hist[16], 1);
+    atomicAdd(&s_hist[(n - 1) >> 4 < 16 ? (n - 1) >> 4 : 15], 1);
   }
-  if (skip_dead && !twin && (c & 1) == 0)  // MAIN chain (sketch index = lane * 2L + kind * L + level, kind 0)
-    for (int j = 0; j < L - 1; ++j)
-      if (dropped[base + j] > epoch_start) rep[base + j] = -1;
+  __syncthreads();
+  if (t == 0) list[0] = s_hist[16];
+  if (t == 0) ostat[0] += 1;
+  if (t == 1) ostat[1] += s_hist[16];
+  if (t < 16) ostat[2 + t] += s_hist[t];
 }
 
 // One workgroup per sketch: expiry, eigenvalue ordering, shrink, dump/keep plan, Wc.
@@ -317,26 +367,27 @@ static int swfd_rotate_all(Swfd* h, hipStream_t st) {
   const int S = h->S, n2 = h->n2, d = h->d, ell = h->ell;
   int rc;
   if (h->rep)
-    hipLaunchKernelGGL(swfd_rep_kernel, dim3(cdiv(2 * h->lanes, 64)), dim3(64), 0, st, h->meta, h->L, 2 * h->lanes, h->rep,
+    hipLaunchKernelGGL(swfd_rep_kernel, dim3(1), dim3(1024), sizeof(int) * (size_t)S, st, h->meta, h->L, 2 * h->lanes, h->rep,
                        h->twin ? 1 : 0, h->dropped, (long long)(((h->i - 1) / h->N) * h->N), h->skip_dead, h->now_dev,
-                       (long long)h->i);
+                       (long long)h->i, h->pend, ell, n2, h->list, h->offs, h->kact, h->ostat, h->oround);
   else
     hipLaunchKernelGGL(swfd_set_now_kernel, dim3(1), dim3(1), 0, st, h->now_dev, (long long)h->i);
   if (h->gram_split > 1) {
     const int kchunk = ((d + h->gram_split - 1) / h->gram_split + 15) / 16 * 16;
     if ((rc = gemm_f64_batched_splitk(true, true, h->buf, d, (long)n2 * d, h->buf, d, (long)n2 * d, h->gpart, n2, n2, d, S, kchunk,
-                                      h->gram_split, st, h->rep)))
+                                      h->gram_split, st, h->rep, h->list)))
       return rc;
-    if ((rc = gemm_batched_splitk_reduce(h->gpart, h->gram_split, (long)n2 * n2, eig_plan_input(h->eig), S, h->rep, st))) return rc;
+    if ((rc = gemm_batched_splitk_reduce(h->gpart, h->gram_split, (long)n2 * n2, eig_plan_input(h->eig), S, h->rep, st, h->list)))
+      return rc;
   } else if ((rc = gemm_f64(true, true, h->buf, d, (long)n2 * d, h->buf, d, (long)n2 * d, eig_plan_input(h->eig), n2,
-                            (long)n2 * n2, n2, n2, d, S, 1.0, st, h->rep)))
+                            (long)n2 * n2, n2, n2, d, S, 1.0, st, h->rep, h->list)))
     return rc;
   if ((rc = eig_plan_run_inplace(h->eig, nullptr, nullptr, st, true))) return rc;
   const EigColumns e = eig_plan_columns(h->eig);
   hipLaunchKernelGGL(swfd_decide_kernel, dim3(S), dim3(1024), 0, st, e.lam, e.cols, e.ld, n2, ell, h->cap, h->N, h->now_dev,
                      h->theta, h->meta, h->qt, h->dropped, h->plan, h->keep_src, h->Wc, h->rep);
   if ((rc = gemm_f64(true, false, h->Wc, n2, (long)ell * n2, h->buf, d, (long)n2 * d, h->T, d, (long)ell * d, ell, d,
-                     n2, S, 1.0, st, h->rep)))
+                     n2, S, 1.0, st, h->rep, h->list, h->kact)))
     return rc;
   hipLaunchKernelGGL(swfd_scatter_kernel, dim3(n2, S), dim3(256), 0, st, h->T, h->plan, h->keep_src, h->meta, h->buf,
                      h->queue, n2, ell, h->cap, d, h->rep);
@@ -678,6 +729,8 @@ static int swfd_create_impl(Swfd* h, long N, double R, int d, int ell, int sweep
   h->L = lg + 1;
   h->lanes = lanes;
   h->S = 2 * h->L * lanes;
+  // (swfd_rep_kernel: one workgroup, an int of LDS per sketch; lanes <= 64 and L <= 63 keep S below this)
+  MUSED_REQUIRE(h->S <= 8192, "mused_swfd_create: %d sketches (lanes x 2 levels), at most 8192", h->S);
   h->cap = 2 * ell;
   h->n2 = 2 * ell;
   h->n4 = 4 * ell;
@@ -697,6 +750,18 @@ static int swfd_create_impl(Swfd* h, long N, double R, int d, int ell, int sweep
   {
     const char* dd = getenv("MUSED_SWFD_DEDUPE");
     if (!(dd && dd[0] == '0')) ALLOC(h->rep, 4 * S);
+    // MUSED_SWFD_LIST=0: the rotation's workgroups test rep per sketch instead of going through the compacted list;
+    // MUSED_SWFD_ORDERS=0: every Gram matrix is solved at order 2 l; MUSED_SWFD_KACT=0: the rotate product runs over all 2 l rows
+    auto off = [](const char* name) { const char* v = getenv(name); return v && v[0] == '0'; };
+    if (h->rep && !off("MUSED_SWFD_LIST")) {
+      ZALLOC(h->list, 4 * (S + 1));
+      ZALLOC(h->ostat, 8 * 18);
+      if (!off("MUSED_SWFD_ORDERS")) ZALLOC(h->offs, 4 * S);
+      const char* orr = getenv("MUSED_SWFD_ORDERS");  // 1 / 16 / 32: the embedding offsets rounded down to that multiple
+      const int rv = orr ? atoi(orr) : 0;
+      h->oround = (rv == 1 || rv == 16 || rv == 32) ? rv : SWFD_OFFS_ROUND;
+      if (!off("MUSED_SWFD_KACT")) ZALLOC(h->kact, 4 * S);
+    }
     const char* sd = getenv("MUSED_SWFD_SKIP_DEAD");
     h->skip_dead = (sd && sd[0] == '0') ? 0 : 1;
   }
@@ -728,7 +793,8 @@ static int swfd_create_impl(Swfd* h, long N, double R, int d, int ell, int sweep
   MUSED_CHECK_HIP(hipMemcpy(h->theta, th.data(), 8 * S, hipMemcpyHostToDevice));
   int rc;
   if ((rc = gemm_f64_prepare_all())) return rc;
-  if ((rc = eig_plan_create(h->n2, h->S, h->sweeps, true, &h->eig, h->rep, EIG_PLAN_TOP_HALF, h->status))) return rc;
+  if ((rc = eig_plan_create(h->n2, h->S, h->sweeps, true, &h->eig, h->rep, EIG_PLAN_TOP_HALF, h->status, 0, h->list, h->offs)))
+    return rc;
   // the query reads the l largest pairs of its stacked Gram (order 4 l, or 3 l on a rotation boundary) with the same shrink
   // rule as a rotation: orders the direct solver covers go to it
   if ((rc = eig_plan_create(h->n4, lanes, h->sweeps + 2, true, &h->eigq, nullptr, EIG_PLAN_TOP_FD, h->status, ell))) return rc;
@@ -768,7 +834,7 @@ int mused_swfd_destroy(void* handle) {
   if (h->eigp) eig_plan_destroy(h->eigp);
   void* bufs[] = {h->buf, h->queue, h->qt, h->meta, h->dropped, h->theta, h->T, h->Wc, h->plan,
                   h->keep_src, h->now_dev, h->stack, h->Wq, h->Bout, h->sig_out, h->qinfo, h->qsel,
-                  h->rep, h->pre_in, h->pre_out, h->pre_gram, h->status, h->gpart};
+                  h->rep, h->pre_in, h->pre_out, h->pre_gram, h->status, h->gpart, h->list, h->offs, h->kact, h->ostat};
   for (void* b : bufs) (void)hipFree(b);
   if (h->status_host) (void)hipHostFree(h->status_host);
   delete h;
@@ -844,6 +910,18 @@ int mused_swfd_debug_state(void* handle, int* rep_out, int* meta_out) {
   if (h->rep && rep_out) MUSED_CHECK_HIP(hipMemcpy(rep_out, h->rep, 4 * (size_t)h->S, hipMemcpyDeviceToHost));
   if (meta_out) MUSED_CHECK_HIP(hipMemcpy(meta_out, h->meta, 16 * (size_t)h->S, hipMemcpyDeviceToHost));
   return h->rep ? 1 : 0;
+}
+
+// Diagnostic (not part of the declared ABI): out[18] = {rotations, representatives, representatives by the order their Gram
+// matrix was solved at: bucket b = orders in (16 b, 16 b + 16]}, counted on the device since the handle was created.
+// Returns 1 when the handle keeps the list (and so the counts), else 0.
+int mused_swfd_debug_orders(void* handle, long long* out) {
+  Swfd* h = (Swfd*)handle;
+  if (!h || !out) return MUSED_ERR_ARG;
+  if (!h->ostat) return 0;
+  MUSED_CHECK_HIP(hipDeviceSynchronize());
+  MUSED_CHECK_HIP(hipMemcpy(out, h->ostat, 8 * 18, hipMemcpyDeviceToHost));
+  return 1;
 }
 
 // Replaces SeqBasedSWFD.get() (main.py:70): out_sketch (l x d fp64), out_sigma (l, row norms of the
@@ -957,6 +1035,7 @@ extern "C" int mused_fd_rotate(double* buf, int ell, int d, double* sigma_out, i
   const size_t bytes = sizeof(double) * (size_t)2 * ell * d;
   hipError_t e = hipMemcpyAsync(h->buf, buf, bytes, hipMemcpyDeviceToDevice, st);
   h->i = 2 * ell;
+  h->pend = 2 * ell;  // (no kept rows: the whole buffer counts as rows in use)
   if (e == hipSuccess) rc = mused::swfd_rotate_all(h, st);
   if (e == hipSuccess && !rc) e = hipMemcpyAsync(buf, h->buf, bytes, hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess && !rc) {

@@ -252,24 +252,28 @@ struct TrdDebug {
 };
 
 // ================= kernel A: tridiagonalisation (one workgroup = one CU per matrix) =================
-// EMB = false: order 256 exactly (off = 0, ldn = 256: constant addressing, every step runs); true: an embedded order.
+// EMB = false: order 256 exactly (off = 0, ldn = 256: constant addressing, every step runs); true: an embedded order -- the
+// batch's (sh.off), or with `offs` every matrix its own (offs[matrix] = 256 - order, ldn = 256: a matrix whose rows and columns
+// from its order on are zeros is solved as the smaller matrix it is; with off = 0 it is read in place, as EMB = false reads it,
+// and goes through the same steps in the same arithmetic).
 template <bool EMB>
 __global__ __launch_bounds__(TNT, 1) void trd_a_kernel(const double* __restrict__ Gc, const int* __restrict__ rep,
+                                                       const int* __restrict__ list, const int* __restrict__ offs,
                                                        double* __restrict__ ws, TrdDebug dbg, const TrdShape sh) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  const int bm = blockIdx.x;
-  if (rep && rep[bm] != bm) return;  // duplicate of another matrix / frozen sketch: nothing to solve
+  const int bm = trd_pick(rep, list, blockIdx.x);
+  if (bm < 0) return;  // duplicate of another matrix / frozen sketch / behind the list: nothing to solve
   const int t = threadIdx.x, w = t >> 6, l = t & 63;
   const int wp = w >> 2, wq = w & 3, lp = l & 7, lq = l >> 3;  // (lq in the lane bits the v_permlane swaps reach)
   const int p = wp * 8 + lp, q = wq * 8 + lq;
-  const int off = EMB ? sh.off : 0, ldn = EMB ? sh.ldn : TN;
+  const int off = EMB ? (offs ? offs[bm] : sh.off) : 0, ldn = EMB ? sh.ldn : TN;
   const double* G = Gc + (long)bm * ldn * ldn;
   double* wsm = ws + (long)bm * W_PER;
   double* Hs = wsm + W_HS;
   double* S = sm + L_S;
   double A[2][36];
   const double* Gsrc = G;
-  if constexpr (EMB) {
+  if (EMB && off > 0) {  // (off = 0: ldn = 256, the matrix lies in the 256-layout already)
     // the matrix is first copied into the 256-layout (entry (i, j) of the order-n matrix at (i + off, j + off), zeros
     // above / left of it), in the workspace region the Householder vectors will overwrite step by step -- every load below
     // has completed by then -- so that the register load keeps its constant addressing
@@ -327,12 +331,13 @@ __global__ __launch_bounds__(TNT, 1) void trd_a_kernel(const double* __restrict_
 // forward / columnwise):  T_ii = tau_i,  T(0:i, i) = -tau_i T(0:i, 0:i) (V^T v_i).  One wave per block: V^T V by 64 MFMAs
 // (both operands of an instruction are the same register: lane (kq, li) holds V[row 4 s + kq][reflector li]), then the
 // 16 columns of T one after the other, row i on lane i.
-__global__ __launch_bounds__(64) void trd_t_kernel(const int* __restrict__ rep, double* __restrict__ ws, const TrdShape sh) {
+__global__ __launch_bounds__(64) void trd_t_kernel(const int* __restrict__ rep, const int* __restrict__ list,
+                                                   const int* __restrict__ offs, double* __restrict__ ws, const TrdShape sh) {
   __shared__ double Gs[16][17];
   __shared__ double Ts[16][17];
-  const int bm = blockIdx.x >> 4, kb = blockIdx.x & 15;
-  if (rep && rep[bm] != bm) return;
-  if (16 * kb + 15 < sh.off) return;  // identity reflectors of an embedded order: kernel D skips the block as well
+  const int bm = trd_pick(rep, list, blockIdx.x >> 4), kb = blockIdx.x & 15;
+  if (bm < 0) return;
+  if (16 * kb + 15 < (offs ? offs[bm] : sh.off)) return;  // identity reflectors of an embedded order: kernel D skips the block as well
   double* wsm = ws + (long)bm * W_PER;
   const double* Hs = wsm + W_HS;
   const int l = threadIdx.x, kq = l >> 4, li = l & 15;
@@ -387,17 +392,18 @@ constexpr int DM_VB = 4096;              // [16][272]   V as [reflector][row]
 constexpr int DM_TM = DM_VB + 16 * 272;  // [16][16]    T
 constexpr int DM_TOTAL = DM_TM + 256;
 __global__ __launch_bounds__(TNT, 1) void trd_d_kernel(double* __restrict__ Gc, const int* __restrict__ rep,
+                                                       const int* __restrict__ list, const int* __restrict__ offs,
                                                        int* __restrict__ done, double* __restrict__ ws, TrdDebug dbg,
                                                        const TrdShape sh, double* __restrict__ lam_out) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  const int bm = blockIdx.x;
-  if (rep && rep[bm] != bm) {  // (the Jacobi skips it too)
-    if (threadIdx.x == 0) done[bm] = 1;
-    return;
-  }
+  // (a matrix that is not its own representative is marked by the workgroup of its own index, list or no list: the
+  // Jacobi skips it too)
+  if (rep && rep[blockIdx.x] != (int)blockIdx.x && threadIdx.x == 0) done[blockIdx.x] = 1;
+  const int bm = trd_pick(rep, list, blockIdx.x);
+  if (bm < 0) return;
   const int t = threadIdx.x, w = t >> 6, l = t & 63;
   const int kq = l >> 4, li = l & 15;
-  const int off = sh.off, ldn = sh.ldn, n = sh.n;
+  const int off = offs ? offs[bm] : sh.off, ldn = sh.ldn, n = offs ? TN - off : sh.n;
   double* G = Gc + (long)bm * ldn * ldn;
   double* wsm = ws + (long)bm * W_PER;
   const double* Hs = wsm + W_HS;
@@ -635,7 +641,8 @@ int trd_tail_launch(const double* G, const int* rep, double* ws, int batch, hipS
   TrdDebug dbg{nullptr, nullptr};
   TrdShape sh;
   sh.n = TN; sh.ldn = TN; sh.off = 0; sh.nvec = TM; sh.need = TM; sh.cert_all = 0;
-  hipLaunchKernelGGL(trd_a_kernel<false>, dim3(batch), dim3(TNT), sizeof(double) * L_A_TOTAL, st, G, rep, ws, dbg, sh);
+  hipLaunchKernelGGL(trd_a_kernel<false>, dim3(batch), dim3(TNT), sizeof(double) * L_A_TOTAL, st, G, rep, (const int*)nullptr,
+                     (const int*)nullptr, ws, dbg, sh);
   MUSED_LAUNCH_CHECK();
   return MUSED_OK;
 }
@@ -647,9 +654,14 @@ bool trd_supports(int n, int ldn, int need) { return n >= 2 && n <= TN && ldn >=
 // rounded up to a multiple of 32), every other entry zeros; done[b] = 0 -> untouched (certificate failed: solve it with the
 // Jacobi).  `need`: how many leading pairs the caller reads; cert_all: see TrdShape.  ws: trd_workspace_doubles(batch)
 // doubles.  Five launches on `st`.
+// list (device, 1 + batch ints, optional): the matrices to solve, compacted (trd_pick); rep then only says whose done word is
+// set without a solve.  offs (device, batch ints, optional; n = ldn = 256): matrix b is zero from row and column 256 - offs[b]
+// on and is solved at that order (>= need): the result is laid out as an order-n solve with ldn = 256 lays it out.
 int trd_solve(double* Gc, int n, int ldn, int need, bool cert_all, int batch, const int* rep, int* done, double* ws,
-              hipStream_t st, long long* dbg_clk, unsigned long long* work, hipEvent_t after_a, double* lam_out) {
+              hipStream_t st, long long* dbg_clk, unsigned long long* work, hipEvent_t after_a, double* lam_out,
+              const int* list, const int* offs) {
   MUSED_REQUIRE(trd_supports(n, ldn, need), "trd_solve: unsupported shape (n=%d, ld=%d, need=%d)", n, ldn, need);
+  MUSED_REQUIRE(!offs || (n == TN && ldn == TN), "trd_solve: per-matrix orders need n = ld = 256 (n=%d, ld=%d)", n, ldn);
   TrdDebug dbg{dbg_clk, work};
   TrdShape sh;
   sh.n = n; sh.ldn = ldn; sh.off = TN - n;
@@ -657,14 +669,17 @@ int trd_solve(double* Gc, int n, int ldn, int need, bool cert_all, int batch, co
   sh.need = need;
   sh.cert_all = cert_all ? 1 : 0;
   const int nch = sh.nvec / 32;
-  if (n == TN && ldn == TN) hipLaunchKernelGGL(trd_a_kernel<false>, dim3(batch), dim3(TNT), sizeof(double) * L_A_TOTAL, st, Gc, rep, ws, dbg, sh);
-  else hipLaunchKernelGGL(trd_a_kernel<true>, dim3(batch), dim3(TNT), sizeof(double) * L_A_TOTAL, st, Gc, rep, ws, dbg, sh);
+  if (n == TN && ldn == TN && !offs)
+    hipLaunchKernelGGL(trd_a_kernel<false>, dim3(batch), dim3(TNT), sizeof(double) * L_A_TOTAL, st, Gc, rep, list, offs, ws, dbg, sh);
+  else
+    hipLaunchKernelGGL(trd_a_kernel<true>, dim3(batch), dim3(TNT), sizeof(double) * L_A_TOTAL, st, Gc, rep, list, offs, ws, dbg, sh);
   if (after_a) MUSED_CHECK_HIP(hipEventRecord(after_a, st));  // profiling: the tridiagonalisation alone
-  if (batch <= 64) hipLaunchKernelGGL((trd_b_kernel<128, L256>), dim3(nch * batch), dim3(128), 0, st, rep, ws, sh);
-  else hipLaunchKernelGGL((trd_b_kernel<512, L256>), dim3(batch), dim3(512), 0, st, rep, ws, sh);
-  hipLaunchKernelGGL((trd_c_kernel<L256, 32>), dim3(nch * batch), dim3(128), sizeof(double) * C_LDS, st, rep, ws, sh);
-  hipLaunchKernelGGL(trd_t_kernel, dim3(16 * batch), dim3(64), 0, st, rep, ws, sh);
-  hipLaunchKernelGGL(trd_d_kernel, dim3(batch), dim3(TNT), sizeof(double) * L_DM_TOTAL, st, Gc, rep, done, ws, dbg, sh, lam_out);
+  if (batch <= 64) hipLaunchKernelGGL((trd_b_kernel<128, L256>), dim3(nch * batch), dim3(128), 0, st, rep, list, ws, sh);
+  else hipLaunchKernelGGL((trd_b_kernel<512, L256>), dim3(batch), dim3(512), 0, st, rep, list, ws, sh);
+  hipLaunchKernelGGL((trd_c_kernel<L256, 32>), dim3(nch * batch), dim3(128), sizeof(double) * C_LDS, st, rep, list, ws, sh);
+  hipLaunchKernelGGL(trd_t_kernel, dim3(16 * batch), dim3(64), 0, st, rep, list, offs, ws, sh);
+  hipLaunchKernelGGL(trd_d_kernel, dim3(batch), dim3(TNT), sizeof(double) * L_DM_TOTAL, st, Gc, rep, list, offs, done, ws, dbg, sh,
+                     lam_out);
   MUSED_LAUNCH_CHECK();
   return MUSED_OK;
 }
@@ -703,6 +718,38 @@ extern "C" int mused_debug_trd_n(double* G, int n, int need, int cert_all, int b
   if (!rc) hipLaunchKernelGGL(trd_export_kernel, dim3(batch), dim3(TN), 0, st, ws, out_d, out_e, out_lam, out_res);
   hipError_t e = hipStreamSynchronize(st);
   (void)hipFree(ws);
+  if (rc) return rc;
+  MUSED_CHECK_HIP(e);
+  return MUSED_OK;
+}
+
+// The same at order n = 256 with the solver's optional per-matrix inputs (device pointers, each may be null): offs (batch
+// ints: matrix b is solved at order 256 - offs[b]), list (nlist matrix indices: only these are solved, workgroup i of the batch
+// takes list[i]) and rep (batch ints: a matrix with rep[b] != b gets done = 1 and is otherwise left alone).
+extern "C" int mused_debug_trd_offs(double* G, int need, int cert_all, int batch, double* out_d, double* out_e, double* out_lam,
+                                    double* out_res, int* out_done, const int* offs, const int* list, int nlist, const int* rep,
+                                    void* stream) {
+  MUSED_REQUIRE(G && batch >= 1 && out_done && nlist >= 0 && nlist <= batch, "mused_debug_trd_offs: bad arguments");
+  int rc = trd_prepare();
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  double* ws = nullptr;
+  int* lst = nullptr;
+  MUSED_CHECK_HIP(hipMalloc((void**)&ws, sizeof(double) * trd_workspace_doubles(batch)));
+  hipError_t e = hipSuccess;
+  if (list) {
+    e = hipMalloc((void**)&lst, sizeof(int) * (size_t)(batch + 1));
+    if (e == hipSuccess) e = hipMemcpyAsync(lst, &nlist, sizeof(int), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && nlist > 0) e = hipMemcpyAsync(lst + 1, list, sizeof(int) * (size_t)nlist, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);  // (nlist lives on this frame)
+  }
+  if (e == hipSuccess) {
+    rc = trd_solve(G, TN, TN, need, cert_all != 0, batch, rep, out_done, ws, st, nullptr, nullptr, nullptr, nullptr, lst, offs);
+    if (!rc) hipLaunchKernelGGL(trd_export_kernel, dim3(batch), dim3(TN), 0, st, ws, out_d, out_e, out_lam, out_res);
+    e = hipStreamSynchronize(st);
+  }
+  (void)hipFree(ws);
+  if (lst) (void)hipFree(lst);
   if (rc) return rc;
   MUSED_CHECK_HIP(e);
   return MUSED_OK;

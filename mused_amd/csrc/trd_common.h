@@ -46,6 +46,14 @@ struct TrdShape {
                     // 0: the pairs whose energy survives the FD shrink by lam_{need-1} (discard level 1e-10 lam_0)
 };
 
+// Which matrix the workgroup(s) with batch index b serve, -1: none.  With a list (1 + batch ints: list[0] matrices, list[1 ..]) the
+// batch index counts through the list -- the workgroups that only exit then lie behind all the working ones in dispatch order
+// --, without one every matrix that is its own representative is served by its own index.
+__device__ __forceinline__ int trd_pick(const int* __restrict__ rep, const int* __restrict__ list, int b) {
+  if (list) return b < list[0] ? list[1 + b] : -1;
+  return (rep && rep[b] != b) ? -1 : b;
+}
+
 // Which of the computed pairs the certificate covers (kernels C and D / the certificate kernel agree on this).
 __device__ __forceinline__ bool trd_significant(double lc, int c, double lam0, double lamcut, const TrdShape& sh) {
   if (c >= sh.need || !(lc > 0.0)) return false;
@@ -133,7 +141,8 @@ __device__ __forceinline__ int trd_sturm(const double2* __restrict__ dd2, double
 // would leave idle; each evaluates all 512 points itself).  Both variants evaluate the same points in the same arithmetic: the
 // eigenvalues do not depend on the batch size (lock-step lanes == single sketches bit for bit).
 template <int NTB, typename LY>
-__global__ __launch_bounds__(NTB) void trd_b_kernel(const int* __restrict__ rep, double* __restrict__ ws, const TrdShape sh) {
+__global__ __launch_bounds__(NTB) void trd_b_kernel(const int* __restrict__ rep, const int* __restrict__ list,
+                                                    double* __restrict__ ws, const TrdShape sh) {
   constexpr int TNX = LY::TNX, NWV = NTB / 64;
   const int NCH = NTB == 512 ? 1 : sh.nvec / (NTB / 4);  // workgroups per matrix (NTB / 4 eigenvalues each)
   constexpr int PASSES = 19, NPT = 512;  // 5^19 x 513 > 2^53
@@ -141,8 +150,8 @@ __global__ __launch_bounds__(NTB) void trd_b_kernel(const int* __restrict__ rep,
   __shared__ double part[3 * NWV];
   __shared__ double scal[4];
   __shared__ int cnts[NPT];
-  const int bm = blockIdx.x / NCH, cq = blockIdx.x % NCH;
-  if (rep && rep[bm] != bm) return;
+  const int bm = trd_pick(rep, list, blockIdx.x / NCH), cq = blockIdx.x % NCH;
+  if (bm < 0) return;
   const int t = threadIdx.x, w = t >> 6, l = t & 63;
   double* wsm = ws + (long)bm * LY::W_PER;
   const double* dg = wsm + LY::W_TG;
@@ -223,7 +232,8 @@ template <typename LY, int VPW>
 constexpr int trd_c_lds_doubles() { return 2 * LY::TNX + LY::TNX + 4 * VPW + 2 * LY::TNX * VPW; }
 
 template <typename LY, int VPW>
-__global__ __launch_bounds__(128) void trd_c_kernel(const int* __restrict__ rep, double* __restrict__ ws, const TrdShape sh) {
+__global__ __launch_bounds__(128) void trd_c_kernel(const int* __restrict__ rep, const int* __restrict__ list,
+                                                    double* __restrict__ ws, const TrdShape sh) {
   constexpr int TNX = LY::TNX, TMX = LY::TMX;
   static_assert(TNX % 32 == 0 && (VPW == 8 || VPW == 16 || VPW == 32), "trd_c_kernel: unsupported shape");
   extern __shared__ __attribute__((aligned(16))) double smc[];  // trd_c_lds_doubles<LY, VPW>() doubles
@@ -233,8 +243,9 @@ __global__ __launch_bounds__(128) void trd_c_kernel(const int* __restrict__ rep,
   double* qp = xch + 4 * VPW;                      // forward pivots [TNX][VPW]
   double* qm = qp + TNX * VPW;                     // backward pivots [TNX][VPW]
   const int nch = sh.nvec / VPW;  // workgroups per matrix
-  const int bm = blockIdx.x / nch, cq = blockIdx.x - bm * nch;
-  if (rep && rep[bm] != bm) return;
+  const int bq = blockIdx.x / nch, cq = blockIdx.x - bq * nch;
+  const int bm = trd_pick(rep, list, bq);
+  if (bm < 0) return;
   const int t = threadIdx.x, role = t >> 6, l = t & 63;
   double* wsm = ws + (long)bm * LY::W_PER;
   double* Zg = wsm + LY::W_ZG;

@@ -885,9 +885,9 @@ static int trdx_solve_t(double* Gc, const TrdShape& sh, int batch, const int* re
   }
   hipLaunchKernelGGL(trdx_tail_merge_kernel<NX>, dim3(XTAIL, batch), dim3(256), 0, st, rep, ws, wst, trd_tail_ws_per(), trd_tail_off_hs(),
                      trd_tail_off_tg());
-  hipLaunchKernelGGL((trd_b_kernel<128, LY>), dim3(nch32 * batch), dim3(128), 0, st, rep, ws, sh);
+  hipLaunchKernelGGL((trd_b_kernel<128, LY>), dim3(nch32 * batch), dim3(128), 0, st, rep, (const int*)nullptr, ws, sh);
   constexpr size_t c_lds = sizeof(double) * trd_c_lds_doubles<LY, VPW>();
-  hipLaunchKernelGGL((trd_c_kernel<LY, VPW>), dim3(nchc * batch), dim3(128), c_lds, st, rep, ws, sh);
+  hipLaunchKernelGGL((trd_c_kernel<LY, VPW>), dim3(nchc * batch), dim3(128), c_lds, st, rep, (const int*)nullptr, ws, sh);
   hipLaunchKernelGGL(trdx_cert_kernel<LY>, dim3(batch), dim3(256), 0, st, rep, ws, done, act, jrep, nrej, work, sh);
   MUSED_LAUNCH_CHECK();
   // triangular factors of the compact-WY blocks, then Z <- H_0 H_1 ... Z (one workgroup per 32 / 16 columns of Z)
