@@ -431,6 +431,29 @@ long mused_match_hung_ws_bytes(void);
 int mused_match_hung_chain(const int* raw, int K_windows, int W, const int* prev0, int min_overlap, int* matched_out,
                            int* info_out, int* assign_out, void* ws, long ws_bytes, void* stream);
 
+/* ---- The same label chain for density labels: ANY int32 label value (the noise label -1, INT32_MIN and INT32_MAX
+ * included) and up to 4096 distinct labels a side -- what DBSCAN_incr produces and the entry above flags 4 or 8.
+ * csrc/match_wide.hip; the specification is hungarian.match_labels (mused_amd/hungarian.py).  Seven launches per window,
+ * enqueue-only: no host read or wait inside the call.  Labels are 32 bits: 64-bit labels must be narrowed by the CALLER,
+ * and a value that does not fit int32 must not be sent here.
+ * raw, prev0, matched_out: as for mused_match_hung_chain.  W in [1, 2^20] (the solver's 64-bit key is proved for overlap
+ *   counts up to 2^20 and 4096 positions; any other W is MUSED_ERR_ARG), K_windows * W < 2^31.
+ * info_out (DEVICE, 8 int32 per window), as above = {P, N, Dijkstra steps, feasible, flag word, 0, 1 when matched_t was
+ *   written, 0}.
+ * Flag word: 8 P or N beyond 4096 (that side's word then holds 4097), 16 the feasibility test passed but no complete
+ *   assignment exists (SciPy raises ValueError there), 32 the solver would take more than max_steps Dijkstra steps
+ *   (max_steps = 0: 32 min(P, N); ordinary label pairs take about 2 min(P, N), the worst case is min(P, N)^2 -- a guard
+ *   for a shared device, not a tuning knob).  There is no flag 4: every int32 is a label.  The chain ENDS at the first
+ *   flagged window as above.
+ * assign_out (DEVICE, may be NULL; diagnostic): K_windows x 4096 int32, the column of each row of the P x N matrix or -1.
+ * ws: mused_match_hung_wide_ws_bytes(W) bytes, 256-byte aligned:
+ *   256 + 8 * 2 * 16384 + 4 * 6 * 4096 + align256(4 W) + align256(4 min(W, 4096)^2)
+ *   (control block, two hash sets, value / mark / map tables, one rank per row, the dense overlap counts: 352.25 KiB + 4 W
+ *   + 4 min(W, 4096)^2, at most 68.4 MiB); -1 for W outside [1, 2^20]. */
+long mused_match_hung_wide_ws_bytes(int W);
+int mused_match_hung_wide_chain(const int* raw, int K_windows, int W, const int* prev0, int min_overlap, long max_steps,
+                                int* matched_out, int* info_out, int* assign_out, void* ws, long ws_bytes, void* stream);
+
 /* ---- DBSCAN_batch: perform_dbscan_clustering (matrix_operations.py:235-238, sklearn DBSCAN(eps, min_samples,
  * metric="euclidean").fit_predict) on fp64 rows, csrc/dbscan.hip.  scikit-learn's index-order search in closed form
  * (specification: mused_amd/dbscan.py): core rows have >= min_samples rows within eps (themselves included), clusters are the

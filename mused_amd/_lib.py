@@ -97,6 +97,8 @@ _PROTOS = {
     "mused_match_pot_chain": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _l, _vp]),
     "mused_match_hung_ws_bytes": (_l, []),
     "mused_match_hung_chain": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _l, _vp]),
+    "mused_match_hung_wide_ws_bytes": (_l, [_i]),
+    "mused_match_hung_wide_chain": (_i, [_vp, _i, _i, _vp, _i, _l, _vp, _vp, _vp, _vp, _l, _vp]),
     "mused_dbscan_ws_bytes": (_l, [_l]),
     "mused_dbscan": (_i, [_vp, _l, _i, _l, _d, _i, _vp, _vp, _vp, _l, _vp]),
     "mused_dbscan_incr_ws_bytes": (_l, [_l, _i, _l]),

@@ -79,3 +79,41 @@ def lsap(cost):
         order = np.argsort(col4row)
         return col4row[order], order, steps
     return np.arange(nr, dtype=np.int64), col4row, steps
+
+
+def overlap_counts(prev, new):
+    """(up, un, inverse of new, counts): the sorted distinct values of both sides (np.unique: -1 comes first) and the P x N
+    positional overlap counts in ONE contingency pass over the rows."""
+    up, ip = np.unique(np.asarray(prev), return_inverse=True)
+    un, iq = np.unique(np.asarray(new), return_inverse=True)
+    P, N = len(up), len(un)
+    cnt = np.bincount(ip.ravel().astype(np.int64) * N + iq.ravel(), minlength=P * N).reshape(P, N)
+    return up, un, iq.ravel(), cnt
+
+
+def costs_of(cnt, min_overlap):
+    """The cost matrix match_clusters builds: -count where the count reaches min_overlap, inf elsewhere."""
+    return np.where(cnt >= min_overlap, -cnt.astype(np.float64), np.inf)
+
+
+def is_feasible(cost) -> bool:
+    """match_clusters' own test (matrix_operations.py:176-178): every row and every column keeps a finite entry."""
+    fin = np.isfinite(cost)
+    return bool(fin.size and fin.any(axis=1).all() and fin.any(axis=0).all())
+
+
+def match_labels(prev, new, min_overlap):
+    """`match_clusters(prev, new, "hungarian", min_overlap)` restated without its P x N passes over the rows: (labels, P, N,
+    steps, feasible).  `labels` is `new` itself without a previous window or when the costs are infeasible (P, N are still
+    reported, steps = 0), the relabelled int64 array otherwise; raises lsap's ValueError where SciPy raises.  This is what
+    the wide device chain (csrc/match_wide.hip) computes, and the yardstick at sizes where the host loop takes seconds."""
+    if prev is None or len(prev) == 0:
+        return new, 0, 0, 0, False
+    up, un, iq, cnt = overlap_counts(prev, new)
+    cost = costs_of(cnt, min_overlap)
+    if not is_feasible(cost):
+        return new, len(up), len(un), 0, False
+    rows, cols, steps = lsap(cost)
+    table = un.astype(np.int64)
+    table[cols] = up[rows]   # a matched new label takes the previous value of its row, any other keeps its own
+    return table[iq], len(up), len(un), steps, True

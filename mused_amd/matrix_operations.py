@@ -32,6 +32,7 @@ ball-tree traversal) the smaller row index wins here.
 """
 from __future__ import annotations
 
+import os
 import threading
 
 import numpy as np
@@ -571,7 +572,9 @@ def match_clusters(prev_clusters, new_clusters, method="hungarian", min_overlap=
 
 # windows that match_clusters_on_device / match_chain_on_device finished with the host specification although the device was
 # asked: a flag of the kernel (a decision within rounding, a label outside [0, 1024), more than 256 distinct labels; for
-# "hungarian" also a cost matrix without a complete assignment, where the host call raises SciPy's ValueError)
+# "hungarian" also a cost matrix without a complete assignment, where the host call raises SciPy's ValueError; with
+# wide=True only what the wide Hungarian chain flags: more than 4,096 labels a side, no complete assignment, the step budget,
+# and a label that does not fit int32)
 match_fallbacks = 0
 _MATCH_WS = {}
 MATCH_FLAG_SELECT, MATCH_FLAG_STOP, MATCH_FLAG_RANGE, MATCH_FLAG_SIZE = 1, 2, 4, 8
@@ -654,68 +657,185 @@ def match_chain_launch(raw_dev, prev_dev, min_overlap, stream=None, want_plan=Fa
     return matched, info_h, plans
 
 
-def match_chain_on_device(raw_windows, prev0=None, min_overlap=3, stream=None, method="pot"):
+MATCH_WIDE_MAXC = 4096   # distinct labels a side the wide Hungarian chain takes (csrc/match_wide.hip)
+MATCH_WIDE_MAX_W = 1 << 20
+
+
+def match_wide_launch(raw_dev, prev_dev, min_overlap, stream=None, want_assign=False, max_steps=0):
+    """One mused_match_hung_wide_chain call (csrc/match_wide.hip: any int32 label values, up to 4,096 distinct labels a side)
+    over raw_dev (K x W int32 CUDA, the TRUE label values) against prev_dev (W int32 CUDA or None) -> (matched K x W int32
+    CUDA, info K x 8 int32 NumPy, and with want_assign the K x 4096 int32 CUDA columns of each row or -1, else None).
+    max_steps: the solver's step budget per window (0: 32 min(P, N)).  Synchronises the stream."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+
+    K, W = raw_dev.shape
+    dev = raw_dev.device
+    st = stream if stream is not None else torch.cuda.current_stream()
+    with torch.cuda.stream(st):
+        need = int(_lib.lib().mused_match_hung_wide_ws_bytes(int(W)))
+        if need < 0:
+            raise ValueError(f"match_wide_launch: W = {W} outside [1, 2^20]")
+        key = (dev, st.cuda_stream, "hungarian_wide")
+        ws = _MATCH_WS.get(key)
+        if ws is None or ws.numel() < need:
+            if len(_MATCH_WS) > 16:
+                _MATCH_WS.clear()
+            ws = _MATCH_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+        matched = torch.empty((K, W), dtype=torch.int32, device=dev)
+        info = torch.empty((K, 8), dtype=torch.int32, device=dev)
+        assign = torch.empty((K, MATCH_WIDE_MAXC), dtype=torch.int32, device=dev) if want_assign else None
+        _lib.call("mused_match_hung_wide_chain", _eng.ptr(raw_dev), K, W, _eng.ptr(prev_dev) if prev_dev is not None else None,
+                  int(min_overlap), int(max_steps), _eng.ptr(matched), _eng.ptr(info), _eng.ptr(assign) if want_assign else None,
+                  _eng.ptr(ws), ws.numel(), C.c_void_p(st.cuda_stream))
+        info_h = info.cpu().numpy()
+    return matched, info_h, assign
+
+
+def _labels_to_device_wide(x, device):
+    """int32 CUDA labels with their TRUE values (no clamp: the wide chain takes every int32), or None when a value does not
+    fit int32 -- such a window is the host's."""
+    import torch
+
+    lo, hi = -(1 << 31), (1 << 31) - 1
+    if isinstance(x, torch.Tensor):
+        if x.dtype != torch.int32 and x.numel() and (int(x.min()) < lo or int(x.max()) > hi):
+            return None
+        return x.to(device).to(torch.int32).contiguous()
+    a = np.asarray(x)
+    if a.dtype != np.int32:
+        if a.dtype.kind not in "iub" or (a.size and (int(a.min()) < lo or int(a.max()) > hi)):
+            return None
+        a = a.astype(np.int32)
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
+def _wide_mode(wide, method):
+    """The `wide` keyword of the public functions -> False, True (the narrow chain first, what it flags 4 or 8 to the wide
+    one) or "only" (straight to the wide chain: labels known to hold -1).  MUSED_MATCH_WIDE=host, read per call, turns it
+    off: flagged windows take the host route as they did before the wide chain existed."""
+    if not wide:
+        return False
+    if method != "hungarian":
+        raise ValueError("wide=True is for method 'hungarian' only (the Sinkhorn chain has no wide entry)")
+    if os.environ.get("MUSED_MATCH_WIDE", "device") == "host":
+        return False
+    return "only" if wide == "only" else True
+
+
+def match_chain_on_device(raw_windows, prev0=None, min_overlap=3, stream=None, method="pot", wide=False, max_steps=0):
     """`distributed.replay_label_chain(raw_windows, match_clusters, method=method)` with the whole chain in one launch of
     csrc/match.hip ("pot") or csrc/match_hung.hip ("hungarian"): matched_t = match_clusters(matched_{t-1}, raw_t, method,
     min_overlap), window 0 against prev0 (None: it passes through).  raw_windows: (K, W) NumPy array or int32 / int64 CUDA
     tensor.  Returns the K * W matched labels (NumPy int64).  A window the kernel flags (head of the kernel's source file) is
     matched by the host `match_clusters` and counted in `match_fallbacks`; the chain is launched again behind it.  Where
-    SciPy finds no complete assignment (flag 16) that host call raises its ValueError, as the host chain does."""
+    SciPy finds no complete assignment (flag 16) that host call raises its ValueError, as the host chain does.
+
+    wide=True ("hungarian" only): a window the narrow chain flags 4 (a label outside [0, 1024)) or 8 (more than 256 labels
+    a side) goes to the wide chain (csrc/match_wide.hip: any int32 value, 4,096 labels a side), which then runs the rest of
+    the chain; only what THAT flags (8, 16, 32) or a label that does not fit int32 goes to the host and is counted.
+    wide="only" skips the narrow launch.  max_steps: the wide solver's step budget (0: 32 min(P, N))."""
     import torch
 
     _match_entry(method)
+    wide = _wide_mode(wide, method)
     dev = raw_windows.device if isinstance(raw_windows, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
     stream = _match_stream(stream)
     with torch.cuda.stream(stream):
-        return _match_chain(raw_windows, prev0, min_overlap, stream, dev, method)
+        return _match_chain(raw_windows, prev0, min_overlap, stream, dev, method, wide, max_steps)
 
 
-def _match_chain(raw_windows, prev0, min_overlap, stream, dev, method):
-    raw_dev = _labels_to_device(raw_windows, dev)
-    if raw_dev.dim() != 2:
+def _narrow_flags_only(word) -> bool:
+    """The narrow chain gave the window up for its own limits alone (flags 4 and 8), not for a missing assignment."""
+    word = int(word)
+    return bool(word & (MATCH_FLAG_RANGE | MATCH_FLAG_SIZE)) and not word & ~(MATCH_FLAG_RANGE | MATCH_FLAG_SIZE)
+
+
+def _match_chain(raw_windows, prev0, min_overlap, stream, dev, method, wide=False, max_steps=0):
+    import torch
+
+    if not isinstance(raw_windows, torch.Tensor):
+        raw_windows = np.asarray(raw_windows)
+    if raw_windows.ndim != 2:
         raise ValueError("raw_windows must be (K, W)")
-    K, W = raw_dev.shape
+    raw_dev = _labels_to_device(raw_windows, dev) if wide != "only" else None
+    K, W = raw_windows.shape
     out = np.empty((K, W), dtype=np.int64)
     if K == 0 or W == 0:
         return out.ravel()
     raw_host = None
     prev_host = None if prev0 is None or len(prev0) == 0 else prev0
-    prev_dev = None if prev_host is None else _labels_to_device(prev_host, dev)
+    on_wide = wide == "only"   # once a window went to the wide chain the rest of the chain stays there
     t0 = 0
     while t0 < K:
-        matched, info, _ = match_chain_launch(raw_dev[t0:], prev_dev, min_overlap, stream, method=method)
-        done = int(np.argmin(info[:, 6])) if not info[:, 6].all() else K - t0
+        host_now = False
+        if on_wide:
+            # the wide upload keeps the true values: the windows up to the first one with a label that does not fit int32
+            stop, block = K, _labels_to_device_wide(raw_windows[t0:], dev)
+            if block is None:
+                if raw_host is None:
+                    raw_host = _labels_to_host(raw_windows)
+                stop = next(t for t in range(t0, K) if _labels_to_device_wide(raw_host[t], dev) is None)
+                block = _labels_to_device_wide(raw_host[t0:stop], dev) if stop > t0 else None
+            prev_w = None if prev_host is None else _labels_to_device_wide(prev_host, dev)
+            if block is None or (prev_host is not None and prev_w is None) or W > MATCH_WIDE_MAX_W:
+                done, host_now = 0, True
+            else:
+                matched, info, _ = match_wide_launch(block, prev_w, min_overlap, stream, max_steps=max_steps)
+                done = int(np.argmin(info[:, 6])) if not info[:, 6].all() else stop - t0
+                host_now = t0 + done < K
+        else:
+            prev_dev = None if prev_host is None else _labels_to_device(prev_host, dev)
+            matched, info, _ = match_chain_launch(raw_dev[t0:], prev_dev, min_overlap, stream, method=method)
+            done = int(np.argmin(info[:, 6])) if not info[:, 6].all() else K - t0
+            if done < K - t0:
+                if wide and _narrow_flags_only(info[done, 4]):
+                    on_wide = True
+                else:
+                    host_now = True
         if done:
             out[t0:t0 + done] = matched[:done].cpu().numpy()
             prev_host = out[t0 + done - 1]
         t0 += done
-        if t0 < K:   # the flagged window: host specification, then on from the next one
+        if host_now and t0 < K:   # the flagged window: host specification, then on from the next one
             if raw_host is None:
                 raw_host = _labels_to_host(raw_windows)
             _match_count_fallback()
             out[t0] = match_clusters(None if prev_host is None else _labels_to_host(prev_host), raw_host[t0], method, min_overlap)
             prev_host = out[t0]
-            prev_dev = _labels_to_device(prev_host, dev)
             t0 += 1
     return out.ravel()
 
 
-def match_clusters_on_device(prev_clusters, new_clusters, min_overlap=3, stream=None, method="pot"):
+def match_clusters_on_device(prev_clusters, new_clusters, min_overlap=3, stream=None, method="pot", wide=False, max_steps=0):
     """`match_clusters(prev_clusters, new_clusters, method, min_overlap)` on the device (csrc/match.hip for "pot",
     csrc/match_hung.hip for "hungarian"; NumPy arrays or int32 / int64 CUDA tensors).  Returns what match_clusters returns:
     `new_clusters` itself without a previous window or when the overlap costs are infeasible, the relabelled array
     otherwise.  A window the kernel flags is matched by the host `match_clusters` (which raises SciPy's ValueError where no
-    complete assignment exists) and counted in `match_fallbacks`."""
+    complete assignment exists) and counted in `match_fallbacks`.  wide, max_steps: as for match_chain_on_device -- with
+    wide=True a window flagged 4 or 8 goes to csrc/match_wide.hip, and only what that flags goes to the host."""
     import torch
 
     _match_entry(method)
+    wide = _wide_mode(wide, method)
     if prev_clusters is None or len(prev_clusters) == 0:
         return new_clusters
     dev = new_clusters.device if isinstance(new_clusters, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
     stream = _match_stream(stream)
+    info = None
     with torch.cuda.stream(stream):
-        matched, info, _ = match_chain_launch(_labels_to_device(new_clusters, dev).reshape(1, -1),
-                                              _labels_to_device(prev_clusters, dev), min_overlap, stream, method=method)
+        if wide != "only":
+            matched, info, _ = match_chain_launch(_labels_to_device(new_clusters, dev).reshape(1, -1),
+                                                  _labels_to_device(prev_clusters, dev), min_overlap, stream, method=method)
+        if wide and (info is None or (not info[0, 6] and _narrow_flags_only(info[0, 4]))):
+            new_w, prev_w = _labels_to_device_wide(new_clusters, dev), _labels_to_device_wide(prev_clusters, dev)
+            if new_w is None or prev_w is None or new_w.numel() > MATCH_WIDE_MAX_W:
+                info = np.zeros((1, 8), dtype=np.int32)   # not the device's: the host route below
+            else:
+                matched, info, _ = match_wide_launch(new_w.reshape(1, -1), prev_w, min_overlap, stream, max_steps=max_steps)
     if not info[0, 6]:
         _match_count_fallback()
         return match_clusters(_labels_to_host(prev_clusters), _labels_to_host(new_clusters), method, min_overlap)

@@ -401,7 +401,11 @@ class StreamPipeline:
             st = getattr(self._km_local, "stream", None)
             if st is None:
                 st = self._km_local.stream = torch.cuda.Stream(priority=-1)
-            matched = mo.match_clusters_on_device(self.prev, clusters, min_overlap=3, stream=st, method=method)
+            # Hungarian approaches: what the narrow chain cannot take (a label outside [0, 1024), more than 256 labels a side)
+            # goes to csrc/match_wide.hip, not to the host.  DBSCAN_incr's windows hold the noise label -1, which the narrow
+            # chain would only flag: straight to the wide one.  MUSED_MATCH_WIDE=host (read per call): the former host route
+            wide = False if self._pot else ("only" if self._incr else True)
+            matched = mo.match_clusters_on_device(self.prev, clusters, min_overlap=3, stream=st, method=method, wide=wide)
         else:
             matched = mo.match_clusters(self.prev, clusters, method=method, min_overlap=3)
         if matched is None or len(matched) == 0:  # main.py:114-116
@@ -875,7 +879,7 @@ class SwfdmcLanes:
         self.sigma = {tr["trigger"]: tr["sigma"] for tr in self.pipe.trace}
         raw = np.array([raw[t] for t in range(K)], dtype=np.int64)
         if self.pipe._match_device:   # the whole chain in one launch (csrc/match_hung.hip); MUSED_MATCH=host: SciPy per window
-            return mo.match_chain_on_device(raw, method="hungarian")
+            return mo.match_chain_on_device(raw, method="hungarian", wide=True)
         return mdist.replay_label_chain(raw, mo.match_clusters)
 
     def close(self):

@@ -12,6 +12,9 @@ of a pass beyond the rows themselves.
     python tools/dbscan_incr_time.py --min-samples 5
     python tools/dbscan_incr_time.py --rows 40000          # a shorter stream
     python tools/dbscan_incr_time.py --no-refit --repeats 1   # ONE pass of the chain alone (for a kernel trace of its own)
+    python tools/dbscan_incr_time.py --match --rows 40000  # the label matching of every window (what the pipeline records as
+                                                           # host_ms["match"]): the wide chain (csrc/match_wide.hip) against the
+                                                           # former host route (MUSED_MATCH_WIDE=host), same raw labels
 """
 import argparse, json, os, sys
 import numpy as np
@@ -95,6 +98,46 @@ def measure(n, ms, repeats, refits):
     return out
 
 
+def measure_match(n, ms):
+    """The pipeline's matching step (StreamPipeline._chain: match_clusters_on_device(prev, labels, 3, "hungarian",
+    wide="only")) on the raw labels of every window of one pass, by both routes: wall ms per window as host_ms["match"]."""
+    import time
+
+    import torch
+    from mused_amd import hungarian as hg
+    from mused_amd import matrix_operations as mo
+    from mused_amd.incdbscan import IncrementalDBSCAN
+
+    Xd = torch.from_numpy(rows(n)).cuda()
+    c, raws = IncrementalDBSCAN(EPS, ms), []
+    for lo in range(0, n - W + 1, W):
+        c.insert(Xd[lo:lo + W])
+        raws.append(c.labels()[-W:])
+    out = dict(n=n, W=W, eps=EPS, min_samples=ms, windows=len(raws), labels_a_side=[int(len(np.unique(r))) for r in raws])
+    chains = {}
+    for route in ("host", "device"):
+        os.environ["MUSED_MATCH_WIDE"] = route
+        for timed in (False, True):   # one warm pass
+            prev, t_ms, chain = None, [], []
+            before = mo.match_fallbacks
+            for r in raws:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                prev = mo.match_clusters_on_device(prev, r, 3, method="hungarian", wide="only")
+                t_ms.append(1e3 * (time.perf_counter() - t0))
+                chain.extend(np.asarray(prev).tolist())
+        chains[route] = chain
+        out[route] = dict(match_ms=t_ms, match_ms_total=float(sum(t_ms)), match_ms_median=float(np.median(t_ms[1:])),
+                          fallbacks=mo.match_fallbacks - before)
+    os.environ.pop("MUSED_MATCH_WIDE")
+    prev, spec = None, []
+    for r in raws:
+        prev = hg.match_labels(prev, r, 3)[0]
+        spec.extend(np.asarray(prev).tolist())
+    out["same_labels"] = chains["host"] == chains["device"] == spec
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=150000)
@@ -102,5 +145,9 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--refits", type=int, default=3)
     ap.add_argument("--no-refit", action="store_true")
+    ap.add_argument("--match", action="store_true")
     a = ap.parse_args()
+    if a.match:
+        print(json.dumps(measure_match(a.rows, a.min_samples), indent=1))
+        sys.exit(0)
     print(json.dumps(measure(a.rows, a.min_samples, a.repeats, 0 if a.no_refit else a.refits), indent=1))
