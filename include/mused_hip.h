@@ -516,6 +516,44 @@ int mused_dbscan_incr_delete(const double* X, long ld, int d, double* nrm, int* 
                              double eps, int min_samples, long chunk, int* labels_out, int* info_out, void* ws, long ws_bytes,
                              void* stream);
 
+/* ---- DBSCAN_incr, ANY rows deleted: the rows at the m positions dele[] of the n rows held, csrc/dbscan_incr.hip.  The pin is
+ * that of mused_dbscan_incr_delete: afterwards the labels of the n - m rows still held equal sklearn DBSCAN(eps, min_samples,
+ * metric="euclidean").fit_predict(those rows, in their order), numbering included (specification: mused_amd/dbscan_incr.py,
+ * `delete_rows`).  The same three tile passes with the deleted rows gathered into the staging panel: (deleted rows) x (all
+ * rows) for the counts, then the rebuild and the border pass over the survivors.  dele = 0 .. m - 1 leaves the state, labels
+ * and info of mused_dbscan_incr_delete(m), bit for bit (parent[] up to the shape of its trees: the roots are the same).
+ * NOT enqueue-only: the call reads the list's flag and the two list lengths between its phases.
+ * X: the n rows held, fp64 (pitch ld), n <= 2^19; NOT modified.  X_out (pitch ld_out >= d): receives the n - m surviving rows,
+ *   packed in their order; it must not overlap the rows held (an error).
+ * nrm, count, parent, best: as mused_dbscan_incr_delete; on return entries [0, n - m) describe the survivors in the new
+ *   numbering: survivor i has become i - |{ j in dele : j < i }|, parent and best entries are renumbered through the same map.
+ * dele: m int32 (DEVICE), strictly ascending, in [0, n); 1 <= m <= n.  A kernel checks the list before anything is written:
+ *   a list that is not so sets flag 4 in info_out[0] and every array is left untouched.
+ * labels_out: n - m int32 (DEVICE).  info_out (HOST, 6 int32) = {flags (0 or 4), clusters, core rows, rows that lost core
+ *   status, |R|, |B|} as mused_dbscan_incr_delete.
+ * ws: mused_dbscan_incr_delete_rows_ws_bytes(capacity, d, chunk) bytes for any capacity >= n (56 capacity + 4 ceil(capacity /
+ *   128) + 4 ceil(capacity / 1024) + 8 chunk (d rounded up to even) and alignment; -1 as mused_dbscan_incr_delete_ws_bytes).
+ *   Outside these limits (m outside [1, n], a short workspace, a bad chunk, d or pitch, an overlap) the call returns an
+ *   error and writes nothing. */
+long mused_dbscan_incr_delete_rows_ws_bytes(long capacity, int d, long chunk);
+int mused_dbscan_incr_delete_rows(const double* X, long ld, int d, double* X_out, long ld_out, double* nrm, int* count, int* parent,
+                                  int* best, long n, const int* dele, long m, double eps, int min_samples, long chunk,
+                                  int* labels_out, int* info_out, void* ws, long ws_bytes, void* stream);
+
+/* ---- Rows looked up by value, csrc/rows_find.hip: the position of each of q query rows among n held rows, or -1
+ * (specification: mused_amd/rows_find.py, which the tests pin it to).  Two rows are equal when all d fp64 values have the same
+ * bits: -0.0 is not +0.0, and a NaN row finds a row with the same NaN bits.  A value held at positions h1 < h2 < ... and asked
+ * for at query positions q1 < q2 < ...: query q_k gets h_k, and -1 beyond the last held occurrence.  All rows go into one
+ * open-addressing table keyed by their bytes (the hash only places a row, the d words identify it), the elements are
+ * radix-sorted by the table slot of their value and ranked inside each slot.  Enqueue-only; no pass over values on the host.
+ * X: n x d fp64 (pitch ld), Q: q x d fp64 (pitch ldq); n, q >= 0, n + q <= 2^24.
+ * idx_out: q int32 (DEVICE).  info_out (DEVICE, 4 int32) = {found, not found, 0, 0}.
+ * ws: mused_rows_find_ws_bytes(n, q, d) bytes (40 (n + q) + 1024 ceil((n + q) / 1024) and alignment; -1 outside the limits).
+ *   Scratch only.  Outside the limits the call returns an error and writes nothing. */
+long mused_rows_find_ws_bytes(long n, long q, int d);
+int mused_rows_find(const double* X, long ld, long n, const double* Q, long ldq, long q, int d, int* idx_out, int* info_out,
+                    void* ws, long ws_bytes, void* stream);
+
 /* ---- HDBSCAN_batch: the exact Euclidean minimum spanning tree of n fp64 rows, csrc/emst.hip.  For
  * sklearn.cluster.HDBSCAN(min_samples <= 2, metric="euclidean") the mutual-reachability distance is the distance itself, so
  * this tree is the one its Prim loop builds; the sequential rest (Prim's edge order, single-linkage and condensed tree,

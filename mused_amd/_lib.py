@@ -105,6 +105,11 @@ _PROTOS = {
     "mused_dbscan_incr_insert": (_i, [_vp, _l, _i, _vp, _vp, _vp, _vp, _l, _l, _d, _i, _l, _vp, _vp, _vp, _l, _vp]),
     "mused_dbscan_incr_delete_ws_bytes": (_l, [_l, _i, _l]),
     "mused_dbscan_incr_delete": (_i, [_vp, _l, _i, _vp, _vp, _vp, _vp, _l, _l, _d, _i, _l, _vp, _vp, _vp, _l, _vp]),
+    "mused_dbscan_incr_delete_rows_ws_bytes": (_l, [_l, _i, _l]),
+    "mused_dbscan_incr_delete_rows": (_i, [_vp, _l, _i, _vp, _l, _vp, _vp, _vp, _vp, _l, _vp, _l, _d, _i, _l, _vp, _vp, _vp, _l,
+                                           _vp]),
+    "mused_rows_find_ws_bytes": (_l, [_l, _l, _i]),
+    "mused_rows_find": (_i, [_vp, _l, _l, _vp, _l, _l, _i, _vp, _vp, _vp, _l, _vp]),
     "mused_emst_ws_bytes": (_l, [_l]),
     "mused_emst": (_i, [_vp, _l, _i, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "mused_score_ws_bytes": (_l, [_l, _l]),

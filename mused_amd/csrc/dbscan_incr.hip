@@ -55,10 +55,28 @@
 //                     back behind the kernel (no workgroup reads an entry that another has overwritten); the roots go, shifted,
 //                     into the array rootb held
 //   dbscan_rank, dbi_labels   over the n - m survivors
+//
+// DELETING ANY ROWS (mused_dbscan_incr_delete_rows; the rule: `delete_rows` of mused_amd/dbscan_incr.py).  D = the m positions
+// dele[] (strictly ascending), S = the rest.  The same passes and no further instance of the tile kernel: with m = 0 every
+// column takes part, and the dead mark lives in the state -- count[D] = 0 behind UNCOUNT -- so that a dead row is a non-core
+// column to REBUILD and BPANEL, which read core columns only:
+//
+//   dbr_check         dele[] strictly ascending in [0, n), or flag 4: the host reads it and returns before anything is written
+//   dbr_begin, dbr_dead   dbd_begin, and dead[i] = 1 for the rows of D
+//   tile pass UNCOUNT D x ALL rows, D gathered into the staging panel: a dead column is subtracted from as well, and dropped
+//   dbr_mark          dbd_mark with "i < m" read from dead[]; then count[D] = 0
+//   dbr_select        dbd_select over the rows that are not dead (tile flags over S)               [the host reads |R|, |B|]
+//   REBUILD, dbd_resolve (m = 0), BPANEL   as above
+//   dbr_scan, blockscan   pos[i] = number of survivors below i: block totals, their scan in one workgroup, the positions
+//   dbr_compact       survivor i becomes pos[i]: the four state arrays INTO THE WORKSPACE and copied back as in dbd_shift,
+//                     parent, best and the roots renumbered through pos[] (which keeps the order: parent[x] <= x still holds)
+//   dbi_gather        the surviving rows, packed, into X_out (the rows do have to move here)
+//   dbscan_rank, dbi_labels   over the n - m survivors
 #include "gemm_f64.h"
 #include "internal.h"
 #include "dbscan_common.h"
 #include "union_find.h"
+#include "block_scan.h"
 
 extern "C" int mused_row_sq_norms(const void* X, int dtype, long n, int d, long ld, double* out, void* stream);
 
@@ -369,6 +387,128 @@ __global__ void dbd_shift_kernel(DbiArgs a, const int* __restrict__ root, double
   root2[i] = r == DB_NONE ? DB_NONE : r - m;
 }
 
+// ---- the O(n) kernels of a delete of ANY rows (D = dele[0 .. m), marked in dead[]; S = the rest) -----------------------------
+// The tile passes are the delete's own instances with m = 0: every column takes part.  UNCOUNT also subtracts from the dead
+// columns, which are dropped; dbr_mark then zeroes count[D], so that a dead row is a non-core column to REBUILD and BPANEL,
+// which read core columns only.  The kernels below are those of the prefix delete with "i < m" read from dead[].
+constexpr int DBR_FLAG_LIST = 4;   // dele[] is not strictly ascending in [0, n)
+
+// (behind the memset of info; writes nothing else)
+__global__ void dbr_check_kernel(const int* __restrict__ dele, int m, int n, int* __restrict__ info) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  bool bad = false;
+  if (t < m) {
+    const int v = dele[t];
+    bad = v < 0 || v >= n || (t > 0 && dele[t - 1] >= v);
+  }
+  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(info, DBR_FLAG_LIST);
+}
+
+__global__ void dbr_begin_kernel(DbiArgs a, int* __restrict__ rootb, int* __restrict__ aff, int* __restrict__ dead, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  aff[i] = 0;
+  dead[i] = 0;
+  if (a.count[i] >= a.min_samples) {
+    rootb[i] = db_find(a.parent, i);
+  } else {
+    rootb[i] = -1;
+    const int b = a.best[i];
+    if (b != DB_NONE) a.best[i] = db_find(a.parent, b);
+  }
+}
+
+__global__ void dbr_dead_kernel(const int* __restrict__ dele, int m, int* __restrict__ dead) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < m) dead[dele[t]] = 1;
+}
+
+// behind UNCOUNT: the components that lose a core row; from here on a dead row has count 0
+__global__ void dbr_mark_kernel(DbiArgs a, const int* __restrict__ rootb, int* __restrict__ aff, const int* __restrict__ dead, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool gone = i < n && dead[i];
+  const bool was = i < n && rootb[i] >= 0;
+  const bool lost = was && !gone && a.count[i] < a.min_samples;
+  if (was && (gone || lost)) aff[rootb[i]] = 1;   // (every writer stores the same value)
+  if (lost) a.parent[i] = i;                       // a non-core row is its own parent
+  if (gone) a.count[i] = 0;
+  const int c = __popcll(__ballot(lost));
+  if (c && (threadIdx.x & 63) == 0) atomicAdd(a.info + 3, c);
+}
+
+__global__ void dbr_select_kernel(DbiArgs a, const int* __restrict__ rootb, const int* __restrict__ aff, const int* __restrict__ dead,
+                                  int* __restrict__ list_r, int* __restrict__ list_b, int* __restrict__ tflag, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int tiles = (n + GEMM_BM - 1) / GEMM_BM;
+  if (i < tiles) {
+    int f = 0;
+    const int hi = min(n, (i + 1) * GEMM_BM);
+    for (int r = i * GEMM_BM; r < hi; ++r) {
+      if (dead[r]) continue;
+      const bool core = a.count[r] >= a.min_samples;
+      f |= core ? (aff[rootb[r]] ? DB_HAS_CORE | DB_HAS_REBUILD : DB_HAS_CORE) : DB_HAS_NONCORE;
+    }
+    tflag[i] = f;
+  }
+  const bool in = i < n && !dead[i];
+  const bool core = in && a.count[i] >= a.min_samples;   // (core now: core before too, counts only fell)
+  const bool reb = core && aff[rootb[i]];
+  bool bord = false;
+  if (in && !core && a.min_samples > 2) {
+    const int b = a.best[i];
+    bord = rootb[i] >= 0 || (b != DB_NONE && aff[b]);     // lost core status, or its minimum came from an affected root
+    if (bord) a.best[i] = DB_NONE;
+  }
+  if (reb) a.parent[i] = i;
+  const int c = __popcll(__ballot(core));
+  if (c && (threadIdx.x & 63) == 0) atomicAdd(a.info + 2, c);
+  dbi_append(reb, i, list_r, a.info + 4);
+  dbi_append(bord, i, list_b, a.info + 5);
+}
+
+// pos[i] = number of survivors below i: the exclusive scan of the keep mask in three launches (the pattern of csrc/tokenise.hip):
+// the totals of blocks of 1024 rows, their scan in one workgroup, the positions
+constexpr int DBR_SCAN_THREADS = 1024;
+template <bool WRITE>
+__global__ __launch_bounds__(DBR_SCAN_THREADS) void dbr_scan_kernel(const int* __restrict__ dead, int* __restrict__ blk,
+                                                                   int* __restrict__ pos, int n) {
+  __shared__ int wtot[DBR_SCAN_THREADS / 64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int i = blockIdx.x * DBR_SCAN_THREADS + t;
+  const unsigned long long bal = __ballot(i < n && !dead[i]);
+  if (lane == 0) wtot[wave] = __popcll(bal);
+  __syncthreads();
+  int before = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < DBR_SCAN_THREADS / 64; ++w) {
+    const int c = wtot[w];
+    total += c;
+    before += w < wave ? c : 0;
+  }
+  if (!WRITE) {
+    if (t == 0) blk[blockIdx.x] = total;
+  } else if (i < n) {
+    pos[i] = blk[blockIdx.x] + before + __popcll(bal & ((1ull << lane) - 1ull));
+  }
+}
+
+// survivor i -> pos[i], into the second set of arrays (nothing of the state is overwritten here); parent, best and the roots
+// are renumbered through the same map, which keeps the order: parent[x] <= x still holds.  surv[pos[i]] = i for the row gather
+__global__ void dbr_compact_kernel(DbiArgs a, const int* __restrict__ root, const int* __restrict__ dead, const int* __restrict__ pos,
+                                   double* __restrict__ nrm2, int* __restrict__ count2, int* __restrict__ parent2,
+                                   int* __restrict__ best2, int* __restrict__ root2, int* __restrict__ surv, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || dead[i]) return;
+  const int p = pos[i];
+  const int r = root[i], b = a.best[i];
+  nrm2[p] = a.nrm[i];
+  count2[p] = a.count[i];
+  parent2[p] = pos[a.parent[i]];
+  best2[p] = (r != DB_NONE || b == DB_NONE) ? DB_NONE : pos[b];   // (a core row's best is read nowhere)
+  root2[p] = r == DB_NONE ? DB_NONE : pos[r];
+  surv[p] = i;
+}
+
 struct DbiWs {
   int *rootb, *root, *rank, *list, *tflag, *aflag, *info;
   double* panel;
@@ -422,6 +562,28 @@ static size_t dbd_layout(long n, int d, long chunk, char* base, DbdWs* ws) {
     ws->rootb = (int*)p[0]; ws->root = (int*)p[1]; ws->rank = (int*)p[2]; ws->list_r = (int*)p[3]; ws->list_b = (int*)p[4];
     ws->aff = (int*)p[5]; ws->count2 = (int*)p[6]; ws->parent2 = (int*)p[7]; ws->best2 = (int*)p[8];
     ws->tflag = (int*)pt; ws->info = (int*)pi; ws->nrm2 = (double*)pn; ws->panel = (double*)pp;
+  }
+  return off;
+}
+
+// a delete of any rows: the prefix delete's workspace and, behind it, dead[], pos[], surv[] and the scan's block totals
+struct DbrWs {
+  DbdWs k;
+  int *dead, *pos, *surv, *blk;
+};
+
+static size_t dbr_layout(long n, int d, long chunk, char* base, DbrWs* ws) {
+  size_t off = dbd_layout(n, d, chunk, base, ws ? &ws->k : nullptr);
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += (bytes + 255) & ~(size_t)255;
+    return p;
+  };
+  char* p[3];
+  for (int i = 0; i < 3; ++i) p[i] = take(4 * (size_t)n);
+  char* pb = take(4 * (size_t)((n + DBR_SCAN_THREADS - 1) / DBR_SCAN_THREADS));
+  if (ws) {
+    ws->dead = (int*)p[0]; ws->pos = (int*)p[1]; ws->surv = (int*)p[2]; ws->blk = (int*)pb;
   }
   return off;
 }
@@ -592,6 +754,85 @@ int mused_dbscan_incr_delete(const double* X, long ld, int d, double* nrm, int* 
   if ((rc = dbi_pass<DBI_BPANEL>(X, ld, d, n, 0, n_b, k.list_b, chunk, w, a, vec, st))) return rc;
   hipLaunchKernelGGL(dbd_shift_kernel, dim3(cdiv(ns, 256)), blk, 0, st, a, k.root, k.nrm2, k.count2, k.parent2, k.best2, k.rootb,
                      (int)m, (int)n);
+  MUSED_LAUNCH_CHECK();
+  MUSED_CHECK_HIP(hipMemcpyAsync(nrm, k.nrm2, 8 * (size_t)ns, hipMemcpyDeviceToDevice, st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(count, k.count2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(parent, k.parent2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(best, k.best2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(dbscan_rank_kernel, dim3(1), dim3(DB_RANK_THREADS), 0, st, k.rootb, k.rank, k.info, (int)ns);
+  hipLaunchKernelGGL(dbi_labels_kernel, dim3(cdiv(ns, 256)), blk, 0, st, k.rootb, k.best2, k.rank, labels_out, (int)ns);
+  MUSED_LAUNCH_CHECK();
+  MUSED_CHECK_HIP(hipMemcpyAsync(info, k.info, 32, hipMemcpyDeviceToHost, st));
+  MUSED_CHECK_HIP(hipStreamSynchronize(st));
+  memcpy(info_out, info, 24);
+  return MUSED_OK;
+}
+
+// bytes of workspace mused_dbscan_incr_delete_rows needs while the rows number at most `capacity`
+long mused_dbscan_incr_delete_rows_ws_bytes(long capacity, int d, long chunk) {
+  if (!dbi_shape_ok(capacity, d, chunk)) return -1;
+  return (long)dbr_layout(capacity, d, chunk, nullptr, nullptr);
+}
+
+// One delete of the rows at positions dele[0 .. m) (DEVICE, strictly ascending, in [0, n)) of the n rows held.  X: the rows held
+// (pitch ld), not modified; X_out (pitch ld_out, no overlap with the rows held) receives the n - m survivors, packed in order.
+// A list that is not strictly ascending in [0, n) sets DBR_FLAG_LIST in info_out[0] and nothing else is written.  Synchronises
+// the stream (it reads the list's flag, then |R| and |B|, between the phases): not enqueue-only.
+int mused_dbscan_incr_delete_rows(const double* X, long ld, int d, double* X_out, long ld_out, double* nrm, int* count, int* parent,
+                                  int* best, long n, const int* dele, long m, double eps, int min_samples, long chunk,
+                                  int* labels_out, int* info_out, void* ws, long ws_bytes, void* stream) {
+  MUSED_REQUIRE(X && X_out && nrm && count && parent && best && dele && labels_out && info_out && ws,
+                "mused_dbscan_incr_delete_rows: null argument");
+  MUSED_REQUIRE(dbi_shape_ok(n, d, chunk) && ld >= d && ld_out >= d && ld_out < (1l << 31) && m >= 1 && m <= n,
+                "mused_dbscan_incr_delete_rows: bad shape (n=%ld m=%ld d=%d ld=%ld ld_out=%ld chunk=%ld; 1 <= m <= n <= 2^19, chunk a "
+                "multiple of 128 in [128, 65536])", n, m, d, ld, ld_out, chunk);
+  MUSED_REQUIRE(eps > 0.0 && eps * eps < 1.7976931348623157e308 && min_samples >= 1,
+                "mused_dbscan_incr_delete_rows: need eps > 0 (finite square), min_samples >= 1");
+  MUSED_REQUIRE(ws_bytes >= (long)dbr_layout(n, d, chunk, nullptr, nullptr), "mused_dbscan_incr_delete_rows: workspace too small");
+  const long ns = n - m;
+  MUSED_REQUIRE(ns == 0 || X_out + ((ns - 1) * ld_out + d) <= X || X + ((n - 1) * ld + d) <= X_out,
+                "mused_dbscan_incr_delete_rows: X_out overlaps the rows held");
+  hipStream_t st = (hipStream_t)stream;
+  DbrWs r;
+  dbr_layout(n, d, chunk, (char*)ws, &r);
+  const DbdWs& k = r.k;
+  DbiArgs a{nrm, count, parent, best, k.root, nullptr, k.tflag, nullptr, k.info, eps * eps, 0.0, 0.0, min_samples, 0, 0};
+  DbiWs w;
+  memset(&w, 0, sizeof(w));
+  w.panel = k.panel;
+  const bool vec = vec_ok<double>(X, ld, 0);
+  const dim3 rows(cdiv(n, 256)), blk(256), scan(cdiv(n, DBR_SCAN_THREADS));
+  int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int rc;
+  memset(info_out, 0, 24);
+  MUSED_CHECK_HIP(hipMemsetAsync(k.info, 0, 32, st));
+  hipLaunchKernelGGL(dbr_check_kernel, dim3(cdiv(m, 256)), blk, 0, st, dele, (int)m, (int)n, k.info);
+  MUSED_LAUNCH_CHECK();
+  MUSED_CHECK_HIP(hipMemcpyAsync(info, k.info, 32, hipMemcpyDeviceToHost, st));
+  MUSED_CHECK_HIP(hipStreamSynchronize(st));
+  if (info[0]) {  // a bad list: no array has been written
+    info_out[0] = info[0];
+    return MUSED_OK;
+  }
+  if (m == n) return MUSED_OK;  // the empty state: nothing of the arrays describes a row any more
+  hipLaunchKernelGGL(dbr_begin_kernel, rows, blk, 0, st, a, k.rootb, k.aff, r.dead, (int)n);
+  hipLaunchKernelGGL(dbr_dead_kernel, dim3(cdiv(m, 256)), blk, 0, st, dele, (int)m, r.dead);
+  if ((rc = dbi_pass<DBI_UNCOUNT>(X, ld, d, n, 0, m, dele, chunk, w, a, vec, st))) return rc;
+  hipLaunchKernelGGL(dbr_mark_kernel, rows, blk, 0, st, a, k.rootb, k.aff, r.dead, (int)n);
+  hipLaunchKernelGGL(dbr_select_kernel, rows, blk, 0, st, a, k.rootb, k.aff, r.dead, k.list_r, k.list_b, k.tflag, (int)n);
+  MUSED_LAUNCH_CHECK();
+  MUSED_CHECK_HIP(hipMemcpyAsync(info, k.info, 32, hipMemcpyDeviceToHost, st));
+  MUSED_CHECK_HIP(hipStreamSynchronize(st));
+  const long n_r = info[4], n_b = info[5];
+  if ((rc = dbi_pass<DBI_REBUILD>(X, ld, d, n, 0, n_r, k.list_r, chunk, w, a, vec, st))) return rc;
+  hipLaunchKernelGGL(dbd_resolve_kernel, rows, blk, 0, st, a, k.root, 0, (int)n);  // (a dead row has count 0: DB_NONE)
+  if ((rc = dbi_pass<DBI_BPANEL>(X, ld, d, n, 0, n_b, k.list_b, chunk, w, a, vec, st))) return rc;
+  hipLaunchKernelGGL(dbr_scan_kernel<false>, scan, dim3(DBR_SCAN_THREADS), 0, st, r.dead, r.blk, r.pos, (int)n);
+  hipLaunchKernelGGL(blockscan_kernel, dim3(1), dim3(BLOCKSCAN_THREADS), 0, st, r.blk, (int)scan.x);
+  hipLaunchKernelGGL(dbr_scan_kernel<true>, scan, dim3(DBR_SCAN_THREADS), 0, st, r.dead, r.blk, r.pos, (int)n);
+  hipLaunchKernelGGL(dbr_compact_kernel, rows, blk, 0, st, a, k.root, r.dead, r.pos, k.nrm2, k.count2, k.parent2, k.best2, k.rootb,
+                     r.surv, (int)n);
+  hipLaunchKernelGGL(dbi_gather_kernel, dim3(cdiv(ns * d, 256)), blk, 0, st, X, ld, d, r.surv, (int)ns, X_out, (int)ld_out);
   MUSED_LAUNCH_CHECK();
   MUSED_CHECK_HIP(hipMemcpyAsync(nrm, k.nrm2, 8 * (size_t)ns, hipMemcpyDeviceToDevice, st));
   MUSED_CHECK_HIP(hipMemcpyAsync(count, k.count2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));

@@ -74,6 +74,23 @@ refit of those rows in their order (tests/test_dbscan_incr_delete_host.py, after
 
 Afterwards parent[x] <= x, a root is the smallest core index of its component and best is a root as of this operation: what
 an insert relies on.
+
+DELETING ANY ROWS (`delete_rows`; the kernels: mused_dbscan_incr_delete_rows).  D is a non-empty set of distinct positions among
+the n rows held, S the rest in their order.  The pin is unchanged: afterwards the labels of S equal scikit-learn's refit of those
+rows in their order (tests/test_dbscan_incr_delete_rows_host.py, after every operation).  Steps 1-5 are those above with
+"i < m" read as "i in D":
+
+    1 UNCOUNT  D against ALL rows.  Subtracting from a dead column is harmless: the column is dropped in step 6.  No rounding
+               flag, for the reason above.
+    2 REMEMBER as above.
+    3 AFFECTED gone = the core rows of D; lost = the rows of S that were core and are below min_samples now.
+    4 REBUILD  R = the still-core rows of S under an affected root.  A dead row is never core in it.
+    5 BORDER   (min_samples >= 3)  B = lost and the non-core rows of S whose remembered best is an affected root.
+    6 COMPACT  the one real difference: survivor i becomes pos[i] = i - |{ j in D : j < i }|, and parent and best entries are
+               renumbered through the same map.  The map keeps the order, so parent[x] <= x still holds and a root is still the
+               smallest core index of its component.  A core row's best is reset to NONE.  D = everything leaves the empty state.
+
+`delete_rows(range(m))` leaves exactly the state and `last_delete` of `delete_oldest(m)`.
 """
 from __future__ import annotations
 
@@ -99,6 +116,7 @@ class IncrementalSpec:
     once some pair of an insert lay within tau of eps^2 (the labels then hang on rounding and are no longer pinned).
     `dirty`: per insert (|dirtyA|, |dirtyB|).  `delete_oldest(m)` -> int64 labels of the rows still held; `last_delete`: its
     (flags = 0, clusters, core rows, rows that lost core status, |R|, |B|), the info word of mused_dbscan_incr_delete.
+    `delete_rows(idx)` -> the same for the rows at any distinct positions, with the same `last_delete`.
     max_rows: an insert that would leave more rows first deletes the surplus oldest ones."""
 
     def __init__(self, eps, min_samples, max_rows=None):
@@ -269,6 +287,75 @@ class IncrementalSpec:
         self.n, self.X, self.nrm, self.count = n - m, self.X[m:], self.nrm[m:], count[m:]
         self.parent = parent[m:] - m
         self.best = np.where(best[m:] == NONE, NONE, best[m:] - m)
+        labels = self._labels()
+        self.last_delete = (0, self.clusters, int(core.sum()), int(lost.sum()), len(rows_r), len(rows_b))
+        return labels
+
+    def delete_rows(self, idx):
+        """Deletes the rows at the distinct positions `idx` (any order; the rule at the head of this module) -> int64 labels of
+        the rows still held.  `delete_rows(range(m))` leaves the state and `last_delete` of `delete_oldest(m)`."""
+        n, ms = self.n, self.min_samples
+        dele = np.asarray(idx, dtype=np.int64).reshape(-1)
+        if len(dele) < 1 or dele.min() < 0 or dele.max() >= n or len(np.unique(dele)) != len(dele):
+            raise ValueError(f"delete_rows: needs 1 to {n} distinct positions in [0, {n})")
+        dead = np.zeros(n, dtype=bool)
+        dead[dele] = True
+        if dead.all():
+            self.n, self.X = 0, None
+            self.nrm = np.empty(0)
+            self.count, self.parent, self.best = (np.empty(0, dtype=np.int64) for _ in range(3))
+            self.last_delete = (0, 0, 0, 0, 0, 0)
+            return self._labels()
+        count, best, idx = self.count, self.best, np.arange(n)
+        surv = ~dead
+        # 2 REMEMBER
+        core_before = count >= ms
+        parent = _flatten(self.parent)
+        root_before = parent.copy()
+        had_best = ~core_before & (best != NONE)
+        best_before = np.full(n, NONE, dtype=np.int64)
+        best_before[had_best] = parent[best[had_best]]
+        # 1 UNCOUNT (D against all rows; the dead columns are dropped below)
+        for r, within, _, _ in self._blocks(idx[dead]):
+            count -= within.sum(axis=0)
+        # 3 AFFECTED
+        core = surv & (count >= ms)
+        lost = surv & core_before & ~core
+        affected = np.zeros(n, dtype=bool)
+        affected[root_before[core_before & ~core]] = True      # gone and lost
+        # 4 REBUILD
+        in_r = core & affected[root_before]
+        rows_r = np.flatnonzero(in_r)
+        parent[rows_r] = rows_r
+        parent[lost] = idx[lost]
+        for r, within, _, _ in self._blocks(rows_r):
+            k, col = np.nonzero(within & core[None, :])
+            assert in_r[col].all()                             # no edge joins R to a core row outside R
+            ea, eb = r[k], col
+            while True:
+                pa, pb = parent[ea], parent[eb]
+                diff = pa != pb
+                if not diff.any():
+                    break
+                np.minimum.at(parent, np.maximum(pa, pb)[diff], np.minimum(pa, pb)[diff])
+                parent = _flatten(parent)
+        # 5 BORDER
+        rows_b = np.empty(0, dtype=np.int64)
+        if ms > 2:
+            stale = surv & had_best
+            stale[stale] = affected[best_before[stale]]
+            rows_b = np.flatnonzero(lost | stale)
+            best[rows_b] = NONE
+            for r, within, _, _ in self._blocks(rows_b):
+                k, col = np.nonzero(within & core[None, :])
+                np.minimum.at(best, r[k], parent[col])
+        # 6 COMPACT: survivor i becomes pos[i] = i - |{ j in D : j < i }|, an order-preserving map
+        best[core] = NONE
+        pos = np.cumsum(surv) - 1
+        self.n, self.X, self.nrm, self.count = int(surv.sum()), self.X[surv], self.nrm[surv], count[surv]
+        self.parent = pos[parent[surv]]
+        bs = best[surv]
+        self.best = np.where(bs == NONE, NONE, pos[np.minimum(bs, n - 1)])
         labels = self._labels()
         self.last_delete = (0, self.clusters, int(core.sum()), int(lost.sum()), len(rows_r), len(rows_b))
         return labels

@@ -10,11 +10,18 @@ The labels of rows inserted earlier may change with a later insert (clusters mer
 A SLIDING WINDOW: `delete_oldest(m)` drops the m oldest rows on the device (mused_dbscan_incr_delete), `max_rows` lets every
 insert do so by itself, `delete(X)` is the package's call for rows that ARE the oldest ones.  The pin is the same: after any
 sequence of inserts and deletes the labels of the rows still held are those of scikit-learn's refit of these rows in their order.
+
+ANY ROWS: `delete_rows(idx)` drops the rows at any positions among the rows held (mused_dbscan_incr_delete_rows; the rule:
+`IncrementalSpec.delete_rows`, the same pin), `find(X)` looks rows up by value (mused_rows_find; pinned to the NumPy rule of
+mused_amd/rows_find.py: bit equality, duplicates handed out in order of position) and `labels_of(X)` returns their labels.
+With `by_value=True`, `delete(X)` and `get_cluster_labels(X)` take any rows, as the package describes its own calls: rows not
+held are skipped with a warning, or get NaN.  These two are UNPINNED against the package, like its numbering and its float labels.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import warnings
 
 import numpy as np
 import torch
@@ -23,6 +30,7 @@ from . import _lib
 from . import matrix_operations as mo
 from .dbscan import FLAG_AMBIGUOUS, FLAG_NONFINITE
 from .engine import ptr
+from .rows_find import rows_find
 
 MAX_ROWS = mo.DBSCAN_MAX_ROWS   # csrc/dbscan_incr.hip: the limit of mused_dbscan
 _FIRST_CAPACITY = 4096
@@ -45,15 +53,26 @@ class IncrementalDBSCAN:
       * by an insert whose kernel raises the ambiguity flag (some pair lies within rounding of eps: mused_amd/dbscan.py); that
         insert and every later one is counted in `matrix_operations.dbscan_incr_fallbacks`;
       * uncounted, under MUSED_DBSCAN=host (read at construction) and beyond 2^19 rows.
-    A non-finite row raises scikit-learn's ValueError("Input contains NaN or infinity."); the object then refuses inserts."""
+    A non-finite row raises scikit-learn's ValueError("Input contains NaN or infinity."); the object then refuses inserts.
 
-    def __init__(self, eps=1.0, min_pts=5, chunk=4096, stream=None, max_rows=None):
+    by_value: False (the default) keeps `delete(X)` to the oldest rows and `get_cluster_labels(X)` to the batch of the last
+    insert, with their errors.  True: both look X up by value (`find`); `delete` skips rows that are not held, with one
+    UserWarning that gives their number, and `get_cluster_labels` returns float64 labels with NaN for them.
+    A delete of any rows packs the survivors into a second row buffer and the two change places.  From the first such delete
+    on, with max_rows set, each of the two holds at most max_rows rows (2 max_rows in all, as before), and the rows held are
+    copied to the front whenever the tail runs out."""
+
+    def __init__(self, eps=1.0, min_pts=5, chunk=4096, stream=None, max_rows=None, by_value=False):
         if not (float(eps) > 0.0) or int(min_pts) < 1:
             raise ValueError("eps must be > 0 and min_pts >= 1")
         if max_rows is not None and int(max_rows) < 1:
             raise ValueError("max_rows must be >= 1")
         self.max_rows = None if max_rows is None else int(max_rows)
+        self.by_value = bool(by_value)
         self._off = 0              # the rows held are _X[_off : _off + n]
+        self._X2 = None            # the buffer a delete of any rows packs the survivors into; it then becomes _X
+        self._two = False          # such a delete has happened
+        self._find_ws = None
         self.last_delete_info = None   # device mode: {0, clusters, core rows, lost core status, |R|, |B|} of the last delete
         self.eps, self.min_pts, self.chunk = float(eps), int(min_pts), int(chunk)
         self._stream = stream
@@ -82,7 +101,8 @@ class IncrementalDBSCAN:
             new = min(new, MAX_ROWS) if self.max_rows is None else min(new, MAX_ROWS, self.max_rows)
             L = _lib.lib()
             nbytes = max(int(L.mused_dbscan_incr_ws_bytes(new, self.d, self.chunk)),
-                         int(L.mused_dbscan_incr_delete_ws_bytes(new, self.d, self.chunk)))
+                         int(L.mused_dbscan_incr_delete_ws_bytes(new, self.d, self.chunk)),
+                         int(L.mused_dbscan_incr_delete_rows_ws_bytes(new, self.d, self.chunk)))
             if nbytes < 0:
                 raise ValueError(f"IncrementalDBSCAN: d = {self.d} or chunk = {self.chunk} is not taken (chunk: a multiple of "
                                  "128 in [128, 65536])")
@@ -102,7 +122,8 @@ class IncrementalDBSCAN:
             return
         # the tail has run out.  A state that deletes keeps twice the rows held, so that the copy to the front is paid once
         # per that many rows; one that only grows keeps the capacity of the other tensors
-        slack = 2 if (self.max_rows is not None or self._off) else 1
+        two = self._two and self.max_rows is not None   # two buffers of at most max_rows rows each
+        slack = 1 if two else 2 if (self.max_rows is not None or self._off) else 1
         if slack * n <= cap:
             self._X[:self.n] = self._rows().clone()
             self._off = 0
@@ -110,7 +131,10 @@ class IncrementalDBSCAN:
         new = max(_FIRST_CAPACITY, cap)
         while new < slack * n:
             new *= 2
-        new = min(new, MAX_ROWS) if slack == 1 else (new if self.max_rows is None else min(new, 2 * self.max_rows))
+        if two:
+            new = min(new, self.max_rows)
+        else:
+            new = min(new, MAX_ROWS) if slack == 1 else (new if self.max_rows is None else min(new, 2 * self.max_rows))
         X = torch.empty((new, self.d), dtype=torch.float64, device=dev)
         if self.n:
             X[:self.n] = self._rows()
@@ -121,6 +145,7 @@ class IncrementalDBSCAN:
         if self._X is not None:
             self._host_rows = self._rows().cpu().numpy()
         self._X = self._nrm = self._count = self._parent = self._best = self._labels = self._ws = None
+        self._X2 = self._find_ws = None
 
     # ---- the reference's two calls ---------------------------------------------------------------
     def insert(self, X):
@@ -193,8 +218,16 @@ class IncrementalDBSCAN:
         return self
 
     def delete(self, X):
-        """The `incdbscan` package's call, for the one case this class offers: X must be bit-equal to the oldest len(X) rows
-        held, in their order.  Anything else is a ValueError: rows are not looked up by value."""
+        """The `incdbscan` package's call.  by_value=False: for the oldest rows only: X must be bit-equal to the oldest len(X)
+        rows held, in their order; anything else is a ValueError.  by_value=True: the rows that `find(X)` returns are deleted,
+        rows not held are skipped with one UserWarning that gives their number."""
+        if self.by_value:
+            pos = self.find(X)
+            missing = int((pos < 0).sum())
+            if missing:
+                warnings.warn(f"IncrementalDBSCAN.delete: {missing} of {len(pos)} rows are not held and were skipped", UserWarning,
+                              stacklevel=2)
+            return self.delete_rows(pos[pos >= 0]) if missing < len(pos) else self
         on_dev = isinstance(X, torch.Tensor)
         rows = X.to(torch.float64) if on_dev else np.ascontiguousarray(X, dtype=np.float64)
         k = int(rows.shape[0]) if rows.ndim == 2 else 0
@@ -237,6 +270,116 @@ class IncrementalDBSCAN:
         self._off = self._off + m if n else 0
         self.last_delete_info = np.array(info[:], dtype=np.int32)
 
+    # ---- any rows ---------------------------------------------------------------------------------
+    def delete_rows(self, idx):
+        """Drops the rows at the positions `idx` among the rows held: an int array or a bool mask over the rows held, NumPy
+        (or a sequence) or a CUDA tensor.  Positions that repeat or lie outside [0, n) are a ValueError and leave the state
+        untouched, as does an empty set.  Returns self; `labels()` then covers the rows still held, in their order."""
+        if self._dead:
+            raise ValueError("this IncrementalDBSCAN met a non-finite row and takes no further calls")
+        n = self.n
+        if isinstance(idx, torch.Tensor):
+            t = idx.reshape(-1)
+            if t.dtype == torch.bool:
+                if t.numel() != n:
+                    raise ValueError(f"delete_rows: a mask must have one entry per row held ({n})")
+                t = torch.nonzero(t).reshape(-1)
+            elif t.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+                raise ValueError("delete_rows: positions must be integers or a bool mask")
+            t = torch.sort(t.to(torch.int64)).values
+            bad = t.numel() < 1 or bool((t[0] < 0) | (t[-1] >= n) | (t[1:] == t[:-1]).any())
+            below = 0 if bad else int((t < self._last_lo).sum())
+            last_hit = not bad and int(t[-1]) >= self._last_lo
+        else:
+            t = np.asarray(idx).reshape(-1)
+            if t.dtype == np.bool_:
+                if t.size != n:
+                    raise ValueError(f"delete_rows: a mask must have one entry per row held ({n})")
+                t = np.flatnonzero(t)
+            elif t.size and not np.issubdtype(t.dtype, np.integer):
+                raise ValueError("delete_rows: positions must be integers or a bool mask")
+            t = np.sort(t.astype(np.int64))
+            bad = t.size < 1 or t[0] < 0 or t[-1] >= n or bool((t[1:] == t[:-1]).any())
+            below = 0 if bad else int((t < self._last_lo).sum())
+            last_hit = not bad and int(t[-1]) >= self._last_lo
+        if bad:
+            raise ValueError(f"delete_rows: needs 1 to {n} distinct positions in [0, {n})")
+        m = int(t.shape[0])
+        if m == n:                                          # everything goes: the empty state
+            self._delete(n, refit=True)
+            return self
+        if self._last is not None:
+            self._last_lo -= below
+            if last_hit:
+                self._last = None
+        if self._host_mode:
+            keep = np.ones(n, dtype=bool)
+            keep[t.cpu().numpy() if isinstance(t, torch.Tensor) else t] = False
+            self._host_rows = self._host_rows[keep]
+            self.n = n - m
+            if self._counted:
+                mo._dbscan_incr_count_fallback()
+            self._host_labels = np.asarray(mo.perform_dbscan_clustering(self._host_rows, self.eps, self.min_pts), dtype=np.int64)
+            return self
+        st = mo._match_stream(self._stream)
+        with torch.cuda.stream(st):
+            dev = self._X.device
+            dele = (t.to(dev) if isinstance(t, torch.Tensor) else torch.from_numpy(t).to(dev)).to(torch.int32).contiguous()
+            if self._X2 is None or self._X2.shape[0] < n - m:
+                cap = self._X.shape[0] if self.max_rows is None else min(self._X.shape[0], self.max_rows)
+                self._X2 = torch.empty((cap, self.d), dtype=torch.float64, device=dev)
+            held, out = self._X[self._off:], self._X2
+            info = (C.c_int * 6)()
+            _lib.call("mused_dbscan_incr_delete_rows", ptr(held), held.stride(0), self.d, ptr(out), out.stride(0), ptr(self._nrm),
+                      ptr(self._count), ptr(self._parent), ptr(self._best), n, ptr(dele), m, self.eps, self.min_pts, self.chunk,
+                      ptr(self._labels), info, ptr(self._ws), self._ws.numel(), C.c_void_p(st.cuda_stream))
+        if info[0]:
+            raise RuntimeError(f"mused_dbscan_incr_delete_rows refused a checked list (flags {info[0]})")
+        self._X, self._X2, self._off, self.n, self._two = out, self._X, 0, n - m, True
+        if self.max_rows is not None and self._X2.shape[0] > self.max_rows:
+            self._X2 = None                                 # (the buffer of 2 max_rows rows of the sliding window)
+        self.last_delete_info = np.array(info[:], dtype=np.int32)
+        return self
+
+    def _queries(self, X):
+        on_dev = isinstance(X, torch.Tensor)
+        rows = X.to(torch.float64) if on_dev else np.ascontiguousarray(X, dtype=np.float64)
+        if rows.ndim != 2 or (self.d is not None and rows.shape[1] != self.d):
+            raise ValueError("X must be (q, d) with the d of the inserts")
+        return rows, on_dev
+
+    def find(self, X):
+        """int64 NumPy positions of the rows of X among the rows held, -1 for rows that are not held (the rule:
+        mused_amd/rows_find.py: bit equality; a value held several times is handed out in order of position)."""
+        rows, on_dev = self._queries(X)
+        q = int(rows.shape[0])
+        if q == 0 or self.n == 0:
+            return np.full(q, -1, dtype=np.int64)
+        if self._host_mode:
+            return rows_find(self._host_rows, rows.cpu().numpy() if on_dev else rows)
+        st = mo._match_stream(self._stream)
+        with torch.cuda.stream(st):
+            dev = self._X.device
+            Q = (rows.to(dev) if on_dev else torch.tensor(rows, device=dev)).contiguous()
+            nbytes = int(_lib.lib().mused_rows_find_ws_bytes(self.n, q, self.d))
+            if nbytes < 0:
+                raise ValueError(f"find: {self.n} rows held and {q} asked for are more than mused_rows_find takes")
+            if self._find_ws is None or self._find_ws.numel() < nbytes:
+                self._find_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            idx = torch.empty(q, dtype=torch.int32, device=dev)
+            info = torch.empty(4, dtype=torch.int32, device=dev)
+            held = self._rows()
+            _lib.call("mused_rows_find", ptr(held), held.stride(0), self.n, ptr(Q), Q.stride(0), q, self.d, ptr(idx), ptr(info),
+                      ptr(self._find_ws), self._find_ws.numel(), C.c_void_p(st.cuda_stream))
+            return idx.cpu().numpy().astype(np.int64)
+
+    def labels_of(self, X):
+        """int64 NumPy labels of the rows of X, which must all be held (`find`); ValueError otherwise."""
+        pos = self.find(X)
+        if (pos < 0).any():
+            raise ValueError(f"labels_of: {int((pos < 0).sum())} of {len(pos)} rows are not held")
+        return self.labels()[pos] if len(pos) else np.empty(0, dtype=np.int64)
+
     def labels(self):
         """int64 NumPy labels of the rows held: all rows inserted so far but the deleted ones (-1 = noise)."""
         if self.n == 0:
@@ -246,8 +389,14 @@ class IncrementalDBSCAN:
         return self._labels[:self.n].cpu().numpy().astype(np.int64)
 
     def get_cluster_labels(self, X):
-        """int64 NumPy labels of the batch just inserted.  X must BE that batch (the object handed to the last `insert`, or
-        an ndarray equal to it): rows are not looked up by value."""
+        """by_value=False: int64 NumPy labels of the batch just inserted.  X must BE that batch (the object handed to the last
+        `insert`, or an ndarray equal to it).  by_value=True: float64 labels of any rows, NaN for rows that are not held."""
+        if self.by_value:
+            pos = self.find(X)
+            out = np.full(len(pos), np.nan)
+            if (pos >= 0).any():
+                out[pos >= 0] = self.labels()[pos[pos >= 0]]
+            return out
         last = self._last
         same = X is last
         if not same and last is not None and isinstance(X, np.ndarray) and isinstance(last, np.ndarray):
