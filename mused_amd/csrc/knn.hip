@@ -14,32 +14,41 @@
 namespace mused {
 
 // ---- row squared norms (HBM-bound: one wave per row, 16-B loads) ------------
+// One lane's share of a row's sum.  The norm is a function of the row's values, d and T alone: lane L adds the V = 16 /
+// sizeof(T) columns of every 64th 16-byte group (their squares summed first), then the columns behind the last whole group
+// at stride 64, whether the row starts on a 16-byte line (ALIGNED: one 16-byte load per group) or not (V element loads of
+// the same columns).  The arithmetic is the same text for both, so duplicate rows get the same bits wherever they lie and
+// the scores built on the norms tie exactly (selection then goes by column).
+template <typename T, bool ALIGNED>
+__device__ __forceinline__ double row_sqnorm_lane(const T* __restrict__ p, int d, int lane) {
+  constexpr int V = 16 / sizeof(T);
+  double s = 0.0;
+  for (int c = lane * V; c + V <= d; c += 64 * V) {
+    if constexpr (sizeof(T) == 4) {
+      float4 v;
+      if constexpr (ALIGNED) v = *reinterpret_cast<const float4*>(p + c);
+      else v = make_float4(p[c], p[c + 1], p[c + 2], p[c + 3]);
+      s += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+    } else {
+      double2 v;
+      if constexpr (ALIGNED) v = *reinterpret_cast<const double2*>(p + c);
+      else v = make_double2(p[c], p[c + 1]);
+      s += v.x * v.x + v.y * v.y;
+    }
+  }
+  // tail columns (d not a multiple of V), from the first uncovered column
+  for (int t = (d / V) * V + lane; t < d; t += 64) s += (double)p[t] * (double)p[t];
+  return s;
+}
+
 template <typename T>
 __global__ void row_sqnorm_kernel(const T* __restrict__ X, long n, int d, long ld, double* __restrict__ out) {
   const long row = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= n) return;
   const int lane = threadIdx.x & 63;
   const T* p = X + row * ld;
-  double s = 0.0;
-  constexpr int V = 16 / sizeof(T);
-  const bool vec = ((uintptr_t)p % 16 == 0);
-  int c = 0;
-  if (vec) {
-    for (c = lane * V; c + V <= d; c += 64 * V) {
-      if (sizeof(T) == 4) {
-        const float4 v = *reinterpret_cast<const float4*>(p + c);
-        s += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
-      } else {
-        const double2 v = *reinterpret_cast<const double2*>(p + c);
-        s += v.x * v.x + v.y * v.y;
-      }
-    }
-    // tail columns (d not a multiple of V): handled below from the first uncovered column
-    c = (d / V) * V;
-    for (int t = c + lane; t < d; t += 64) s += (double)p[t] * (double)p[t];
-  } else {
-    for (int t = lane; t < d; t += 64) s += (double)p[t] * (double)p[t];
-  }
+  const bool vec = ((uintptr_t)p % 16 == 0);  // wave-uniform: one row per wave
+  double s = vec ? row_sqnorm_lane<T, true>(p, d, lane) : row_sqnorm_lane<T, false>(p, d, lane);
   s = wave_sum(s);
   if (lane == 0) out[row] = s;
 }

@@ -161,12 +161,81 @@ def test_select_k_long_rows_uncached(L):
     rng = np.random.default_rng(5)
     n, k = 16500, 50
     Smat = (rng.standard_normal((n, n)).astype(np.float32) * 30 + 1000).astype(np.float64)
-    idx, _ = _select(L, Smat, k)
+    dS = dev(Smat)
+    idx, _ = _select_outputs(L, dS, n, n, k, True, True, (n + 63) // 64)
     rows = rng.integers(0, n, size=64)
     ref = _select_k_smallest_mask(Smat[rows], k)
     got = np.zeros((64, n), dtype=bool)
     np.put_along_axis(got, idx[rows].astype(np.int64), True, axis=1)
     assert np.array_equal(got, ref)
+    # the mask alone (what the engine asks for), from the matrix already on the device: the same rows, self column cleared
+    _, mask = _select_outputs(L, dS, n, n, k, False, True, (n + 63) // 64)
+    ref_noself = ref.copy()
+    ref_noself[np.arange(64), rows] = False
+    assert np.array_equal(_mask_to_bool(mask[rows], n), ref_noself)
+    assert not (mask[:, -1] >> np.uint64(n % 64)).any()
+
+
+def _select_outputs(L, dS, n, ld, k, want_idx, want_mask, words):
+    """mused_select_k_smallest on a matrix already on the device, with either output left out (NULL)."""
+    idx = torch.full((n + 1, k), -1, dtype=torch.int32, device="cuda") if want_idx else None
+    mask = torch.full((n + 1, words), -1, dtype=torch.int64, device="cuda") if want_mask else None
+    L.call("mused_select_k_smallest", P(dS), ld, n, k, P(idx), P(mask), words, S())
+    sync()
+    idx = idx.cpu().numpy() if want_idx else None
+    mask = mask.cpu().numpy().view(np.uint64) if want_mask else None
+    assert idx is None or (idx[n] == -1).all(), "written past the lists"
+    assert mask is None or (mask[n] == ~np.uint64(0)).all(), "written past the mask"
+    return (idx[:n] if want_idx else None), (mask[:n] if want_mask else None)
+
+
+def _select_keys(kind, n, rng):
+    """(scores, k).  distinct: no two keys of a row equal, so every row can emit its mask by ballots alone.  cut: six values,
+    the tie at the k-th key is cut in nearly every row (prefix sums decide which of the equal keys go).  uncut: every
+    value four times in shuffled places and k a multiple of four, so a whole group of equal keys ends every selection."""
+    if kind == "distinct":
+        return rng.permuted(np.tile(np.arange(n, dtype=np.float64), (n, 1)), axis=1) * 0.37 - 11.0, 37
+    if kind == "cut":
+        return rng.integers(0, 6, size=(n, n)).astype(np.float64), 37
+    if kind == "uncut":
+        return rng.permuted(np.tile((np.arange(n) // 4).astype(np.float64), (n, 1)), axis=1), 36
+    raise KeyError(kind)
+
+
+@pytest.mark.parametrize("padded", [False, True])
+@pytest.mark.parametrize("kind", ["distinct", "cut", "uncut"])
+@pytest.mark.parametrize("n", [65, 1024, 1025, 2049])
+def test_select_k_output_combinations(L, n, kind, padded):
+    """Lists alone, mask alone (its own emit path where no tie is cut: ballots, no scans) and both, from the same device
+    matrix: the lists are the oracle's, the mask is the list minus the row's own column, in all three.  padded: the score
+    matrix has pitch n + 5 with -inf behind every row (it would win every selection if it were read) and the mask two words
+    more than it needs (they come back zero)."""
+    from oracle.mo_oracle import _select_k_smallest_mask
+
+    rng = np.random.default_rng(n * 7 + len(kind))
+    Smat, k = _select_keys(kind, n, rng)
+    ld, words = (n + 5, (n + 63) // 64 + 2) if padded else (n, (n + 63) // 64)
+    host = np.full((n, ld), -np.inf)
+    host[:, :n] = Smat
+    dS = dev(host)
+    ref = _select_k_smallest_mask(Smat, k)
+    assert (ref.sum(1) == k).all()
+    ref_noself = ref.copy()
+    np.fill_diagonal(ref_noself, False)
+    want_words = np.zeros((n, words * 8), dtype=np.uint8)
+    packed = np.packbits(ref_noself, axis=1, bitorder="little")
+    want_words[:, :packed.shape[1]] = packed
+    want_words = want_words.view(np.uint64)
+    i_only, _ = _select_outputs(L, dS, n, ld, k, True, False, 0)
+    _, m_only = _select_outputs(L, dS, n, ld, k, False, True, words)
+    i_both, m_both = _select_outputs(L, dS, n, ld, k, True, True, words)
+    for idx in (i_only, i_both):
+        got = np.zeros((n, n), dtype=bool)
+        assert idx.min() >= 0 and idx.max() < n and np.all(np.diff(idx, axis=1) > 0)
+        np.put_along_axis(got, idx.astype(np.int64), True, axis=1)
+        assert np.array_equal(got, ref)
+    assert np.array_equal(m_only, want_words), "mask alone"
+    assert np.array_equal(m_both, want_words), "mask with the lists"
 
 
 # ---------------------------------------------------------------- adjacency ops -------
