@@ -42,6 +42,19 @@ void set_error(const char* fmt, ...);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Carves a workspace into arrays, each starting on a multiple of 256 bytes, in the order of the take() calls; `off` is the
+// bytes taken so far.  A null base only sizes: every pointer is null then
+struct WsCarver {
+  char* base;
+  size_t off = 0;
+  template <typename T>
+  T* take(size_t count) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += (count * sizeof(T) + 255) & ~(size_t)255;
+    return p;
+  }
+};
+
 // order-preserving map double -> uint64 (ascending)
 __device__ __forceinline__ unsigned long long f64_key(double v) {
   unsigned long long u = (unsigned long long)__double_as_longlong(v);

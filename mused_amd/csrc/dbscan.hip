@@ -246,25 +246,17 @@ struct DbWs {
 };
 
 static size_t db_layout(long n, char* base, DbWs* ws) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return p;
-  };
-  const long tiles = (n + GEMM_BM - 1) / GEMM_BM;
-  char* p0 = take(8 * (size_t)n);
-  char* p1 = take(4 * (size_t)n);
-  char* p2 = take(4 * (size_t)n);
-  char* p3 = take(4 * (size_t)n);
-  char* p4 = take(4 * (size_t)n);
-  char* p5 = take(4 * (size_t)tiles);
-  char* p6 = take(16);
-  if (ws) {
-    ws->nrm = (double*)p0; ws->count = (int*)p1; ws->parent = (int*)p2; ws->root = (int*)p3; ws->rank = (int*)p4;
-    ws->tflag = (int*)p5; ws->info = (int*)p6;
-  }
-  return off;
+  DbWs sizing;
+  DbWs& w = ws ? *ws : sizing;
+  WsCarver c{base};
+  w.nrm = c.take<double>(n);
+  w.count = c.take<int>(n);
+  w.parent = c.take<int>(n);
+  w.root = c.take<int>(n);
+  w.rank = c.take<int>(n);
+  w.tflag = c.take<int>((n + GEMM_BM - 1) / GEMM_BM);
+  w.info = c.take<int>(4);
+  return c.off;
 }
 
 template <int PASS>

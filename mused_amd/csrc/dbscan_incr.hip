@@ -33,15 +33,25 @@
 // Every write to global memory is a vector store or a device-scope vector atomic; kernel boundaries are the only
 // synchronisation between workgroups.
 //
-// DELETING the m oldest of n rows (mused_dbscan_incr_delete; the rule: mused_amd/dbscan_incr.py).  D = [0, m), S = [m, n):
+// DELETING a set D of m of the n rows held; S = the rest (the rule: mused_amd/dbscan_incr.py).  The O(n) kernels below take
+// "is row i deleted, and where does a survivor go" as a policy passed by value; the two entries differ in nothing else but how
+// D reaches UNCOUNT and in what the list needs:
 //
+//   prefix (DelPrefix; mused_dbscan_incr_delete)     D = [0, m): dead(i) = i < m, pos(i) = i - m; no array
+//   mask (DelMask; mused_dbscan_incr_delete_rows)    D = the positions dele[] (strictly ascending): dead(i) = dead[i],
+//                                                    pos(i) = pos[i] = the survivors below i
+//
+//   dbr_check         (mask) dele[] strictly ascending in [0, n), or flag 4: the host reads it and returns before anything is written
 //   dbd_begin         rootb[i] = find(i) for the core rows, -1 for the others; best = find(best) for the non-core rows that
-//                     have one (the remembered root, kept in place); the list of affected roots is cleared
-//   tile pass UNCOUNT D x S (the slice D on the A side, column tiles that lie wholly in D return at once):
-//                     count[j] -= the rows of D within eps (column side, per-wave reduction before the atomic).  No rounding
-//                     test: every pair was tested when the later of its two rows was inserted
+//                     have one (the remembered root, kept in place); the list of affected roots is cleared (mask: dead[] too)
+//   dbr_dead          (mask) dead[i] = 1 for the rows of D
+//   tile pass UNCOUNT count[j] -= the rows of D within eps (column side, per-wave reduction before the atomic).  No rounding
+//                     test: every pair was tested when the later of its two rows was inserted.  prefix: the slice D on the A
+//                     side with a.n0 = m: columns below m take no part, column tiles that lie wholly in D return at once.
+//                     mask: D gathered into the staging panel, a.n0 = 0: a dead column is subtracted from as well, and dropped
 //   dbd_mark          aff[rootb[i]] = 1 for the core rows of D and for the rows of S that were core and are not any more
-//                     (these are counted, and become their own parent again)
+//                     (these are counted, and become their own parent again).  mask: then count[D] = 0, so that a dead row is
+//                     a non-core column to REBUILD and BPANEL, which read core columns only
 //   dbd_select        R = the rows of S that are still core under an affected root: parent[x] = x, compacted into a list; B
 //                     (min_samples >= 3) = the rows that lost core status and the non-core rows whose best is an affected
 //                     root: best = DB_NONE, compacted into a second list; tile flags over the rows of S (DB_HAS_CORE,
@@ -51,26 +61,12 @@
 //                     within eps of a row of R are in R); column tiles without a row of R return before their main loop
 //   dbd_resolve       root[i] = find(i) for the core rows of S, DB_NONE for every other row
 //   tile pass BPANEL  B x S through the staging panel: the BROW epilogue, best[b] = the smallest root among the core columns
-//   dbd_shift         survivor i becomes i - m.  The four state arrays are written, shifted, INTO THE WORKSPACE and copied
-//                     back behind the kernel (no workgroup reads an entry that another has overwritten); the roots go, shifted,
-//                     into the array rootb held
-//   dbscan_rank, dbi_labels   over the n - m survivors
-//
-// DELETING ANY ROWS (mused_dbscan_incr_delete_rows; the rule: `delete_rows` of mused_amd/dbscan_incr.py).  D = the m positions
-// dele[] (strictly ascending), S = the rest.  The same passes and no further instance of the tile kernel: with m = 0 every
-// column takes part, and the dead mark lives in the state -- count[D] = 0 behind UNCOUNT -- so that a dead row is a non-core
-// column to REBUILD and BPANEL, which read core columns only:
-//
-//   dbr_check         dele[] strictly ascending in [0, n), or flag 4: the host reads it and returns before anything is written
-//   dbr_begin, dbr_dead   dbd_begin, and dead[i] = 1 for the rows of D
-//   tile pass UNCOUNT D x ALL rows, D gathered into the staging panel: a dead column is subtracted from as well, and dropped
-//   dbr_mark          dbd_mark with "i < m" read from dead[]; then count[D] = 0
-//   dbr_select        dbd_select over the rows that are not dead (tile flags over S)               [the host reads |R|, |B|]
-//   REBUILD, dbd_resolve (m = 0), BPANEL   as above
-//   dbr_scan, blockscan   pos[i] = number of survivors below i: block totals, their scan in one workgroup, the positions
-//   dbr_compact       survivor i becomes pos[i]: the four state arrays INTO THE WORKSPACE and copied back as in dbd_shift,
-//                     parent, best and the roots renumbered through pos[] (which keeps the order: parent[x] <= x still holds)
-//   dbi_gather        the surviving rows, packed, into X_out (the rows do have to move here)
+//   dbr_scan, blockscan   (mask) pos[]: block totals, their scan in one workgroup, the positions
+//   dbd_compact       survivor i becomes pos(i).  The four state arrays are written, renumbered, INTO THE WORKSPACE and copied
+//                     back behind the kernel (no workgroup reads an entry that another has overwritten); the roots go,
+//                     renumbered, into the array rootb held.  pos keeps the order: parent[x] <= x still holds.  mask:
+//                     surv[pos[i]] = i
+//   dbi_gather        (mask) the surviving rows, packed, into X_out (the rows do have to move here; the prefix leaves them)
 //   dbscan_rank, dbi_labels   over the n - m survivors
 #include "gemm_f64.h"
 #include "internal.h"
@@ -312,12 +308,34 @@ __global__ void dbi_labels_kernel(const int* __restrict__ root, const int* __res
   labels[i] = (r == DB_NONE) ? -1 : rank[r];
 }
 
-// ---- the O(n) kernels of a delete (D = [0, m), S = [m, n)) --------------------------------------------------------------
+// ---- the O(n) kernels of a delete -------------------------------------------------------------------------------------
+// Which rows are deleted and where a survivor goes: a policy, passed by value.  DelPrefix: D = [0, m).  DelMask: D = dele[0 .. m),
+// marked in mark[]; map[i] = the survivors below i; surv[map[i]] = i feeds the row gather.  The tile passes are the same
+// instances for both: with a.n0 = 0 every column takes part, UNCOUNT also subtracts from the dead columns, which are dropped,
+// and dbd_mark then stores count[D] = 0, so that a dead row is a non-core column to REBUILD and BPANEL, which read core columns only.
+struct DelPrefix {
+  static constexpr bool MASK = false;
+  int m;
+  __device__ __forceinline__ bool dead(int i) const { return i < m; }
+  __device__ __forceinline__ int pos(int i) const { return i - m; }
+};
+
+struct DelMask {
+  static constexpr bool MASK = true;
+  int* mark;
+  const int* map;
+  int* surv;
+  __device__ __forceinline__ bool dead(int i) const { return mark[i] != 0; }
+  __device__ __forceinline__ int pos(int i) const { return map[i]; }
+};
+
 // (behind the memset of info)
-__global__ void dbd_begin_kernel(DbiArgs a, int* __restrict__ rootb, int* __restrict__ aff, int n) {
+template <class P>
+__global__ void dbd_begin_kernel(DbiArgs a, P del, int* __restrict__ rootb, int* __restrict__ aff, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   aff[i] = 0;
+  if constexpr (P::MASK) del.mark[i] = 0;
   if (a.count[i] >= a.min_samples) {
     rootb[i] = db_find(a.parent, i);
   } else {
@@ -327,31 +345,38 @@ __global__ void dbd_begin_kernel(DbiArgs a, int* __restrict__ rootb, int* __rest
   }
 }
 
-// behind UNCOUNT: the components that lose a core row
-__global__ void dbd_mark_kernel(DbiArgs a, const int* __restrict__ rootb, int* __restrict__ aff, int m, int n) {
+// behind UNCOUNT: the components that lose a core row; under a mask a dead row has count 0 from here on
+template <class P>
+__global__ void dbd_mark_kernel(DbiArgs a, P del, const int* __restrict__ rootb, int* __restrict__ aff, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool gone = i < n && del.dead(i);
   const bool was = i < n && rootb[i] >= 0;
-  const bool lost = was && i >= m && a.count[i] < a.min_samples;
-  if (was && (i < m || lost)) aff[rootb[i]] = 1;   // (every writer stores the same value)
-  if (lost) a.parent[i] = i;                        // a non-core row is its own parent
+  const bool lost = was && !gone && a.count[i] < a.min_samples;
+  if (was && (gone || lost)) aff[rootb[i]] = 1;   // (every writer stores the same value)
+  if (lost) a.parent[i] = i;                       // a non-core row is its own parent
+  if constexpr (P::MASK) {
+    if (gone) a.count[i] = 0;
+  }
   const int c = __popcll(__ballot(lost));
   if (c && (threadIdx.x & 63) == 0) atomicAdd(a.info + 3, c);
 }
 
-__global__ void dbd_select_kernel(DbiArgs a, const int* __restrict__ rootb, const int* __restrict__ aff, int* __restrict__ list_r,
-                                  int* __restrict__ list_b, int* __restrict__ tflag, int m, int n) {
+template <class P>
+__global__ void dbd_select_kernel(DbiArgs a, P del, const int* __restrict__ rootb, const int* __restrict__ aff,
+                                  int* __restrict__ list_r, int* __restrict__ list_b, int* __restrict__ tflag, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int tiles = (n + GEMM_BM - 1) / GEMM_BM;
   if (i < tiles) {
     int f = 0;
     const int hi = min(n, (i + 1) * GEMM_BM);
-    for (int r = max(m, i * GEMM_BM); r < hi; ++r) {
+    for (int r = i * GEMM_BM; r < hi; ++r) {
+      if (del.dead(r)) continue;
       const bool core = a.count[r] >= a.min_samples;
       f |= core ? (aff[rootb[r]] ? DB_HAS_CORE | DB_HAS_REBUILD : DB_HAS_CORE) : DB_HAS_NONCORE;
     }
     tflag[i] = f;
   }
-  const bool in = i >= m && i < n;
+  const bool in = i < n && !del.dead(i);
   const bool core = in && a.count[i] >= a.min_samples;   // (core now: core before too, counts only fell)
   const bool reb = core && aff[rootb[i]];
   bool bord = false;
@@ -367,30 +392,31 @@ __global__ void dbd_select_kernel(DbiArgs a, const int* __restrict__ rootb, cons
   dbi_append(bord, i, list_b, a.info + 5);
 }
 
+// (m: the first column that takes part, a.n0 of the tile passes)
 __global__ void dbd_resolve_kernel(DbiArgs a, int* __restrict__ root, int m, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   root[i] = (i >= m && a.count[i] >= a.min_samples) ? db_find(a.parent, i) : DB_NONE;
 }
 
-// survivor m + i -> i, into the second set of arrays (nothing of the state is overwritten here)
-__global__ void dbd_shift_kernel(DbiArgs a, const int* __restrict__ root, double* __restrict__ nrm2, int* __restrict__ count2,
-                                 int* __restrict__ parent2, int* __restrict__ best2, int* __restrict__ root2, int m, int n) {
+// survivor i -> pos(i), into the second set of arrays (nothing of the state is overwritten here); parent, best and the roots
+// are renumbered through the same map, which keeps the order: parent[x] <= x still holds
+template <class P>
+__global__ void dbd_compact_kernel(DbiArgs a, P del, const int* __restrict__ root, double* __restrict__ nrm2, int* __restrict__ count2,
+                                   int* __restrict__ parent2, int* __restrict__ best2, int* __restrict__ root2, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n - m) return;
-  const int s = m + i;
-  const int r = root[s], b = a.best[s];
-  nrm2[i] = a.nrm[s];
-  count2[i] = a.count[s];
-  parent2[i] = a.parent[s] - m;
-  best2[i] = (r != DB_NONE || b == DB_NONE) ? DB_NONE : b - m;   // (a core row's best is read nowhere)
-  root2[i] = r == DB_NONE ? DB_NONE : r - m;
+  if (i >= n || del.dead(i)) return;
+  const int p = del.pos(i);
+  const int r = root[i], b = a.best[i];
+  nrm2[p] = a.nrm[i];
+  count2[p] = a.count[i];
+  parent2[p] = del.pos(a.parent[i]);
+  best2[p] = (r != DB_NONE || b == DB_NONE) ? DB_NONE : del.pos(b);   // (a core row's best is read nowhere)
+  root2[p] = r == DB_NONE ? DB_NONE : del.pos(r);
+  if constexpr (P::MASK) del.surv[p] = i;
 }
 
-// ---- the O(n) kernels of a delete of ANY rows (D = dele[0 .. m), marked in dead[]; S = the rest) -----------------------------
-// The tile passes are the delete's own instances with m = 0: every column takes part.  UNCOUNT also subtracts from the dead
-// columns, which are dropped; dbr_mark then zeroes count[D], so that a dead row is a non-core column to REBUILD and BPANEL,
-// which read core columns only.  The kernels below are those of the prefix delete with "i < m" read from dead[].
+// ---- a delete of any rows alone: the list's check, the mask, the positions ----------------------------------------------------------
 constexpr int DBR_FLAG_LIST = 4;   // dele[] is not strictly ascending in [0, n)
 
 // (behind the memset of info; writes nothing else)
@@ -404,66 +430,9 @@ __global__ void dbr_check_kernel(const int* __restrict__ dele, int m, int n, int
   if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(info, DBR_FLAG_LIST);
 }
 
-__global__ void dbr_begin_kernel(DbiArgs a, int* __restrict__ rootb, int* __restrict__ aff, int* __restrict__ dead, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  aff[i] = 0;
-  dead[i] = 0;
-  if (a.count[i] >= a.min_samples) {
-    rootb[i] = db_find(a.parent, i);
-  } else {
-    rootb[i] = -1;
-    const int b = a.best[i];
-    if (b != DB_NONE) a.best[i] = db_find(a.parent, b);
-  }
-}
-
 __global__ void dbr_dead_kernel(const int* __restrict__ dele, int m, int* __restrict__ dead) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < m) dead[dele[t]] = 1;
-}
-
-// behind UNCOUNT: the components that lose a core row; from here on a dead row has count 0
-__global__ void dbr_mark_kernel(DbiArgs a, const int* __restrict__ rootb, int* __restrict__ aff, const int* __restrict__ dead, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool gone = i < n && dead[i];
-  const bool was = i < n && rootb[i] >= 0;
-  const bool lost = was && !gone && a.count[i] < a.min_samples;
-  if (was && (gone || lost)) aff[rootb[i]] = 1;   // (every writer stores the same value)
-  if (lost) a.parent[i] = i;                       // a non-core row is its own parent
-  if (gone) a.count[i] = 0;
-  const int c = __popcll(__ballot(lost));
-  if (c && (threadIdx.x & 63) == 0) atomicAdd(a.info + 3, c);
-}
-
-__global__ void dbr_select_kernel(DbiArgs a, const int* __restrict__ rootb, const int* __restrict__ aff, const int* __restrict__ dead,
-                                  int* __restrict__ list_r, int* __restrict__ list_b, int* __restrict__ tflag, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int tiles = (n + GEMM_BM - 1) / GEMM_BM;
-  if (i < tiles) {
-    int f = 0;
-    const int hi = min(n, (i + 1) * GEMM_BM);
-    for (int r = i * GEMM_BM; r < hi; ++r) {
-      if (dead[r]) continue;
-      const bool core = a.count[r] >= a.min_samples;
-      f |= core ? (aff[rootb[r]] ? DB_HAS_CORE | DB_HAS_REBUILD : DB_HAS_CORE) : DB_HAS_NONCORE;
-    }
-    tflag[i] = f;
-  }
-  const bool in = i < n && !dead[i];
-  const bool core = in && a.count[i] >= a.min_samples;   // (core now: core before too, counts only fell)
-  const bool reb = core && aff[rootb[i]];
-  bool bord = false;
-  if (in && !core && a.min_samples > 2) {
-    const int b = a.best[i];
-    bord = rootb[i] >= 0 || (b != DB_NONE && aff[b]);     // lost core status, or its minimum came from an affected root
-    if (bord) a.best[i] = DB_NONE;
-  }
-  if (reb) a.parent[i] = i;
-  const int c = __popcll(__ballot(core));
-  if (c && (threadIdx.x & 63) == 0) atomicAdd(a.info + 2, c);
-  dbi_append(reb, i, list_r, a.info + 4);
-  dbi_append(bord, i, list_b, a.info + 5);
 }
 
 // pos[i] = number of survivors below i: the exclusive scan of the keep mask in three launches (the pattern of csrc/tokenise.hip):
@@ -492,23 +461,6 @@ __global__ __launch_bounds__(DBR_SCAN_THREADS) void dbr_scan_kernel(const int* _
   }
 }
 
-// survivor i -> pos[i], into the second set of arrays (nothing of the state is overwritten here); parent, best and the roots
-// are renumbered through the same map, which keeps the order: parent[x] <= x still holds.  surv[pos[i]] = i for the row gather
-__global__ void dbr_compact_kernel(DbiArgs a, const int* __restrict__ root, const int* __restrict__ dead, const int* __restrict__ pos,
-                                   double* __restrict__ nrm2, int* __restrict__ count2, int* __restrict__ parent2,
-                                   int* __restrict__ best2, int* __restrict__ root2, int* __restrict__ surv, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || dead[i]) return;
-  const int p = pos[i];
-  const int r = root[i], b = a.best[i];
-  nrm2[p] = a.nrm[i];
-  count2[p] = a.count[i];
-  parent2[p] = pos[a.parent[i]];
-  best2[p] = (r != DB_NONE || b == DB_NONE) ? DB_NONE : pos[b];   // (a core row's best is read nowhere)
-  root2[p] = r == DB_NONE ? DB_NONE : pos[r];
-  surv[p] = i;
-}
-
 struct DbiWs {
   int *rootb, *root, *rank, *list, *tflag, *aflag, *info;
   double* panel;
@@ -517,26 +469,19 @@ struct DbiWs {
 static inline int dbi_ldp(int d) { return (d + 1) & ~1; }  // even: the panel's rows stay 16-byte aligned
 
 static size_t dbi_layout(long n, int d, long chunk, char* base, DbiWs* ws) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return p;
-  };
-  const long tiles = (n + GEMM_BM - 1) / GEMM_BM;
-  char* p0 = take(4 * (size_t)n);
-  char* p1 = take(4 * (size_t)n);
-  char* p2 = take(4 * (size_t)n);
-  char* p3 = take(4 * (size_t)n);
-  char* p4 = take(4 * (size_t)tiles);
-  char* p5 = take(4 * (size_t)tiles);
-  char* p6 = take(32);
-  char* p7 = take(8 * (size_t)chunk * dbi_ldp(d));
-  if (ws) {
-    ws->rootb = (int*)p0; ws->root = (int*)p1; ws->rank = (int*)p2; ws->list = (int*)p3; ws->tflag = (int*)p4;
-    ws->aflag = (int*)p5; ws->info = (int*)p6; ws->panel = (double*)p7;
-  }
-  return off;
+  DbiWs sizing;
+  DbiWs& w = ws ? *ws : sizing;
+  WsCarver c{base};
+  const size_t tiles = (n + GEMM_BM - 1) / GEMM_BM;
+  w.rootb = c.take<int>(n);
+  w.root = c.take<int>(n);
+  w.rank = c.take<int>(n);
+  w.list = c.take<int>(n);
+  w.tflag = c.take<int>(tiles);
+  w.aflag = c.take<int>(tiles);
+  w.info = c.take<int>(8);
+  w.panel = c.take<double>((size_t)chunk * dbi_ldp(d));
+  return c.off;
 }
 
 struct DbdWs {
@@ -545,25 +490,15 @@ struct DbdWs {
 };
 
 static size_t dbd_layout(long n, int d, long chunk, char* base, DbdWs* ws) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return p;
-  };
-  const long tiles = (n + GEMM_BM - 1) / GEMM_BM;
-  char* p[9];
-  for (int i = 0; i < 9; ++i) p[i] = take(4 * (size_t)n);
-  char* pt = take(4 * (size_t)tiles);
-  char* pi = take(32);
-  char* pn = take(8 * (size_t)n);
-  char* pp = take(8 * (size_t)chunk * dbi_ldp(d));
-  if (ws) {
-    ws->rootb = (int*)p[0]; ws->root = (int*)p[1]; ws->rank = (int*)p[2]; ws->list_r = (int*)p[3]; ws->list_b = (int*)p[4];
-    ws->aff = (int*)p[5]; ws->count2 = (int*)p[6]; ws->parent2 = (int*)p[7]; ws->best2 = (int*)p[8];
-    ws->tflag = (int*)pt; ws->info = (int*)pi; ws->nrm2 = (double*)pn; ws->panel = (double*)pp;
-  }
-  return off;
+  DbdWs sizing;
+  DbdWs& w = ws ? *ws : sizing;
+  WsCarver c{base};
+  for (int** p : {&w.rootb, &w.root, &w.rank, &w.list_r, &w.list_b, &w.aff, &w.count2, &w.parent2, &w.best2}) *p = c.take<int>(n);
+  w.tflag = c.take<int>((n + GEMM_BM - 1) / GEMM_BM);
+  w.info = c.take<int>(8);
+  w.nrm2 = c.take<double>(n);
+  w.panel = c.take<double>((size_t)chunk * dbi_ldp(d));
+  return c.off;
 }
 
 // a delete of any rows: the prefix delete's workspace and, behind it, dead[], pos[], surv[] and the scan's block totals
@@ -573,19 +508,14 @@ struct DbrWs {
 };
 
 static size_t dbr_layout(long n, int d, long chunk, char* base, DbrWs* ws) {
-  size_t off = dbd_layout(n, d, chunk, base, ws ? &ws->k : nullptr);
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return p;
-  };
-  char* p[3];
-  for (int i = 0; i < 3; ++i) p[i] = take(4 * (size_t)n);
-  char* pb = take(4 * (size_t)((n + DBR_SCAN_THREADS - 1) / DBR_SCAN_THREADS));
-  if (ws) {
-    ws->dead = (int*)p[0]; ws->pos = (int*)p[1]; ws->surv = (int*)p[2]; ws->blk = (int*)pb;
-  }
-  return off;
+  DbrWs sizing;
+  DbrWs& w = ws ? *ws : sizing;
+  WsCarver c{base, dbd_layout(n, d, chunk, base, &w.k)};
+  w.dead = c.take<int>(n);
+  w.pos = c.take<int>(n);
+  w.surv = c.take<int>(n);
+  w.blk = c.take<int>((n + DBR_SCAN_THREADS - 1) / DBR_SCAN_THREADS);
+  return c.off;
 }
 
 static bool dbi_shape_ok(long n, int d, long chunk) {
@@ -633,6 +563,50 @@ static int dbi_pass(const double* X, long ld, int d, long n, long n0, long count
     int rc;
     if ((rc = dbi_tile_launch<PASS>(g, a, vec, st))) return rc;
   }
+  return MUSED_OK;
+}
+
+// A delete from begin to BPANEL (behind the memset of info).  UNCOUNT takes D as the slice [0, m) (ids == nullptr; a.n0 = m) or
+// through the staging panel with ids[0 .. m) as the row ids (a.n0 = 0).  Synchronises the stream once, to read |R| and |B|
+template <class P>
+static int dbd_front(P del, const DbdWs& k, const DbiArgs& a, const double* X, long ld, int d, long n, const int* ids, long m,
+                     long chunk, hipStream_t st) {
+  DbiWs w;
+  memset(&w, 0, sizeof(w));
+  w.panel = k.panel;
+  w.aflag = k.tflag;  // (the slice walk offsets it; UNCOUNT does not read it)
+  const bool vec = vec_ok<double>(X, ld, 0);
+  const dim3 rows(cdiv(n, 256)), blk(256);
+  int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int rc;
+  hipLaunchKernelGGL(dbd_begin_kernel<P>, rows, blk, 0, st, a, del, k.rootb, k.aff, (int)n);
+  if constexpr (P::MASK) hipLaunchKernelGGL(dbr_dead_kernel, dim3(cdiv(m, 256)), blk, 0, st, ids, (int)m, del.mark);
+  if ((rc = dbi_pass<DBI_UNCOUNT>(X, ld, d, n, 0, m, ids, chunk, w, a, vec, st))) return rc;
+  hipLaunchKernelGGL(dbd_mark_kernel<P>, rows, blk, 0, st, a, del, k.rootb, k.aff, (int)n);
+  hipLaunchKernelGGL(dbd_select_kernel<P>, rows, blk, 0, st, a, del, k.rootb, k.aff, k.list_r, k.list_b, k.tflag, (int)n);
+  MUSED_LAUNCH_CHECK();
+  MUSED_CHECK_HIP(hipMemcpyAsync(info, k.info, 32, hipMemcpyDeviceToHost, st));
+  MUSED_CHECK_HIP(hipStreamSynchronize(st));
+  const long n_r = info[4], n_b = info[5];
+  if ((rc = dbi_pass<DBI_REBUILD>(X, ld, d, n, 0, n_r, k.list_r, chunk, w, a, vec, st))) return rc;
+  hipLaunchKernelGGL(dbd_resolve_kernel, rows, blk, 0, st, a, k.root, a.n0, (int)n);  // (a dead row under a mask has count 0: DB_NONE)
+  return dbi_pass<DBI_BPANEL>(X, ld, d, n, 0, n_b, k.list_b, chunk, w, a, vec, st);
+}
+
+// Behind the compact kernel: the ns survivors' state back from the workspace, their labels, the info word.  Synchronises the stream
+static int dbd_finish(const DbdWs& k, const DbiArgs& a, double* nrm, long ns, int* labels_out, int* info_out, hipStream_t st) {
+  int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  MUSED_LAUNCH_CHECK();
+  MUSED_CHECK_HIP(hipMemcpyAsync(nrm, k.nrm2, 8 * (size_t)ns, hipMemcpyDeviceToDevice, st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(a.count, k.count2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(a.parent, k.parent2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(a.best, k.best2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(dbscan_rank_kernel, dim3(1), dim3(DB_RANK_THREADS), 0, st, k.rootb, k.rank, k.info, (int)ns);
+  hipLaunchKernelGGL(dbi_labels_kernel, dim3(cdiv(ns, 256)), dim3(256), 0, st, k.rootb, k.best2, k.rank, labels_out, (int)ns);
+  MUSED_LAUNCH_CHECK();
+  MUSED_CHECK_HIP(hipMemcpyAsync(info, k.info, 32, hipMemcpyDeviceToHost, st));
+  MUSED_CHECK_HIP(hipStreamSynchronize(st));
+  memcpy(info_out, info, 24);
   return MUSED_OK;
 }
 
@@ -730,42 +704,14 @@ int mused_dbscan_incr_delete(const double* X, long ld, int d, double* nrm, int* 
   hipStream_t st = (hipStream_t)stream;
   DbdWs k;
   dbd_layout(n, d, chunk, (char*)ws, &k);
-  const long ns = n - m;
-  DbiArgs a{nrm, count, parent, best, k.root, nullptr, k.tflag, nullptr, k.info, eps * eps, 0.0, 0.0, min_samples, 0, (int)m};
-  DbiWs w;
-  memset(&w, 0, sizeof(w));
-  w.panel = k.panel;
-  w.aflag = k.tflag;  // (the slice walk offsets it; UNCOUNT does not read it)
-  const bool vec = vec_ok<double>(X, ld, 0);
-  const dim3 rows(cdiv(n, 256)), blk(256);
-  int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const DbiArgs a{nrm, count, parent, best, k.root, nullptr, k.tflag, nullptr, k.info, eps * eps, 0.0, 0.0, min_samples, 0, (int)m};
+  const DelPrefix del{(int)m};
   int rc;
   MUSED_CHECK_HIP(hipMemsetAsync(k.info, 0, 32, st));
-  hipLaunchKernelGGL(dbd_begin_kernel, rows, blk, 0, st, a, k.rootb, k.aff, (int)n);
-  if ((rc = dbi_pass<DBI_UNCOUNT>(X, ld, d, n, 0, m, nullptr, chunk, w, a, vec, st))) return rc;
-  hipLaunchKernelGGL(dbd_mark_kernel, rows, blk, 0, st, a, k.rootb, k.aff, (int)m, (int)n);
-  hipLaunchKernelGGL(dbd_select_kernel, rows, blk, 0, st, a, k.rootb, k.aff, k.list_r, k.list_b, k.tflag, (int)m, (int)n);
-  MUSED_LAUNCH_CHECK();
-  MUSED_CHECK_HIP(hipMemcpyAsync(info, k.info, 32, hipMemcpyDeviceToHost, st));
-  MUSED_CHECK_HIP(hipStreamSynchronize(st));
-  const long n_r = info[4], n_b = info[5];
-  if ((rc = dbi_pass<DBI_REBUILD>(X, ld, d, n, 0, n_r, k.list_r, chunk, w, a, vec, st))) return rc;
-  hipLaunchKernelGGL(dbd_resolve_kernel, rows, blk, 0, st, a, k.root, (int)m, (int)n);
-  if ((rc = dbi_pass<DBI_BPANEL>(X, ld, d, n, 0, n_b, k.list_b, chunk, w, a, vec, st))) return rc;
-  hipLaunchKernelGGL(dbd_shift_kernel, dim3(cdiv(ns, 256)), blk, 0, st, a, k.root, k.nrm2, k.count2, k.parent2, k.best2, k.rootb,
-                     (int)m, (int)n);
-  MUSED_LAUNCH_CHECK();
-  MUSED_CHECK_HIP(hipMemcpyAsync(nrm, k.nrm2, 8 * (size_t)ns, hipMemcpyDeviceToDevice, st));
-  MUSED_CHECK_HIP(hipMemcpyAsync(count, k.count2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
-  MUSED_CHECK_HIP(hipMemcpyAsync(parent, k.parent2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
-  MUSED_CHECK_HIP(hipMemcpyAsync(best, k.best2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(dbscan_rank_kernel, dim3(1), dim3(DB_RANK_THREADS), 0, st, k.rootb, k.rank, k.info, (int)ns);
-  hipLaunchKernelGGL(dbi_labels_kernel, dim3(cdiv(ns, 256)), blk, 0, st, k.rootb, k.best2, k.rank, labels_out, (int)ns);
-  MUSED_LAUNCH_CHECK();
-  MUSED_CHECK_HIP(hipMemcpyAsync(info, k.info, 32, hipMemcpyDeviceToHost, st));
-  MUSED_CHECK_HIP(hipStreamSynchronize(st));
-  memcpy(info_out, info, 24);
-  return MUSED_OK;
+  if ((rc = dbd_front(del, k, a, X, ld, d, n, nullptr, m, chunk, st))) return rc;
+  hipLaunchKernelGGL(dbd_compact_kernel<DelPrefix>, dim3(cdiv(n, 256)), dim3(256), 0, st, a, del, k.root, k.nrm2, k.count2, k.parent2,
+                     k.best2, k.rootb, (int)n);
+  return dbd_finish(k, a, nrm, n - m, labels_out, info_out, st);
 }
 
 // bytes of workspace mused_dbscan_incr_delete_rows needs while the rows number at most `capacity`
@@ -796,11 +742,8 @@ int mused_dbscan_incr_delete_rows(const double* X, long ld, int d, double* X_out
   DbrWs r;
   dbr_layout(n, d, chunk, (char*)ws, &r);
   const DbdWs& k = r.k;
-  DbiArgs a{nrm, count, parent, best, k.root, nullptr, k.tflag, nullptr, k.info, eps * eps, 0.0, 0.0, min_samples, 0, 0};
-  DbiWs w;
-  memset(&w, 0, sizeof(w));
-  w.panel = k.panel;
-  const bool vec = vec_ok<double>(X, ld, 0);
+  const DbiArgs a{nrm, count, parent, best, k.root, nullptr, k.tflag, nullptr, k.info, eps * eps, 0.0, 0.0, min_samples, 0, 0};
+  const DelMask del{r.dead, r.pos, r.surv};
   const dim3 rows(cdiv(n, 256)), blk(256), scan(cdiv(n, DBR_SCAN_THREADS));
   int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int rc;
@@ -815,36 +758,13 @@ int mused_dbscan_incr_delete_rows(const double* X, long ld, int d, double* X_out
     return MUSED_OK;
   }
   if (m == n) return MUSED_OK;  // the empty state: nothing of the arrays describes a row any more
-  hipLaunchKernelGGL(dbr_begin_kernel, rows, blk, 0, st, a, k.rootb, k.aff, r.dead, (int)n);
-  hipLaunchKernelGGL(dbr_dead_kernel, dim3(cdiv(m, 256)), blk, 0, st, dele, (int)m, r.dead);
-  if ((rc = dbi_pass<DBI_UNCOUNT>(X, ld, d, n, 0, m, dele, chunk, w, a, vec, st))) return rc;
-  hipLaunchKernelGGL(dbr_mark_kernel, rows, blk, 0, st, a, k.rootb, k.aff, r.dead, (int)n);
-  hipLaunchKernelGGL(dbr_select_kernel, rows, blk, 0, st, a, k.rootb, k.aff, r.dead, k.list_r, k.list_b, k.tflag, (int)n);
-  MUSED_LAUNCH_CHECK();
-  MUSED_CHECK_HIP(hipMemcpyAsync(info, k.info, 32, hipMemcpyDeviceToHost, st));
-  MUSED_CHECK_HIP(hipStreamSynchronize(st));
-  const long n_r = info[4], n_b = info[5];
-  if ((rc = dbi_pass<DBI_REBUILD>(X, ld, d, n, 0, n_r, k.list_r, chunk, w, a, vec, st))) return rc;
-  hipLaunchKernelGGL(dbd_resolve_kernel, rows, blk, 0, st, a, k.root, 0, (int)n);  // (a dead row has count 0: DB_NONE)
-  if ((rc = dbi_pass<DBI_BPANEL>(X, ld, d, n, 0, n_b, k.list_b, chunk, w, a, vec, st))) return rc;
+  if ((rc = dbd_front(del, k, a, X, ld, d, n, dele, m, chunk, st))) return rc;
   hipLaunchKernelGGL(dbr_scan_kernel<false>, scan, dim3(DBR_SCAN_THREADS), 0, st, r.dead, r.blk, r.pos, (int)n);
   hipLaunchKernelGGL(blockscan_kernel, dim3(1), dim3(BLOCKSCAN_THREADS), 0, st, r.blk, (int)scan.x);
   hipLaunchKernelGGL(dbr_scan_kernel<true>, scan, dim3(DBR_SCAN_THREADS), 0, st, r.dead, r.blk, r.pos, (int)n);
-  hipLaunchKernelGGL(dbr_compact_kernel, rows, blk, 0, st, a, k.root, r.dead, r.pos, k.nrm2, k.count2, k.parent2, k.best2, k.rootb,
-                     r.surv, (int)n);
+  hipLaunchKernelGGL(dbd_compact_kernel<DelMask>, rows, blk, 0, st, a, del, k.root, k.nrm2, k.count2, k.parent2, k.best2, k.rootb, (int)n);
   hipLaunchKernelGGL(dbi_gather_kernel, dim3(cdiv(ns * d, 256)), blk, 0, st, X, ld, d, r.surv, (int)ns, X_out, (int)ld_out);
-  MUSED_LAUNCH_CHECK();
-  MUSED_CHECK_HIP(hipMemcpyAsync(nrm, k.nrm2, 8 * (size_t)ns, hipMemcpyDeviceToDevice, st));
-  MUSED_CHECK_HIP(hipMemcpyAsync(count, k.count2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
-  MUSED_CHECK_HIP(hipMemcpyAsync(parent, k.parent2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
-  MUSED_CHECK_HIP(hipMemcpyAsync(best, k.best2, 4 * (size_t)ns, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(dbscan_rank_kernel, dim3(1), dim3(DB_RANK_THREADS), 0, st, k.rootb, k.rank, k.info, (int)ns);
-  hipLaunchKernelGGL(dbi_labels_kernel, dim3(cdiv(ns, 256)), blk, 0, st, k.rootb, k.best2, k.rank, labels_out, (int)ns);
-  MUSED_LAUNCH_CHECK();
-  MUSED_CHECK_HIP(hipMemcpyAsync(info, k.info, 32, hipMemcpyDeviceToHost, st));
-  MUSED_CHECK_HIP(hipStreamSynchronize(st));
-  memcpy(info_out, info, 24);
-  return MUSED_OK;
+  return dbd_finish(k, a, nrm, ns, labels_out, info_out, st);
 }
 
 }  // extern "C"

@@ -353,31 +353,22 @@ struct EmWs {
 };
 
 static size_t em_layout(long n, char* base, EmWs* ws) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return p;
-  };
-  const long tiles = (n + GEMM_BM - 1) / GEMM_BM;
-  char* p0 = take(8 * (size_t)n);
-  char* p1 = take(8 * (size_t)n);
-  char* p2 = take(8 * (size_t)n);
-  char* p3 = take(8 * (size_t)n);
-  char* p4 = take(8 * (size_t)n);
-  char* p5 = take(4 * (size_t)n);
-  char* p6 = take(4 * (size_t)n);
-  char* p7 = take(4 * (size_t)n);
-  char* p8 = take(4 * (size_t)n);
-  char* p9 = take(4 * (size_t)tiles);
-  char* p10 = take(16);
-  char* p11 = take(8);
-  if (ws) {
-    ws->nrm = (double*)p0; ws->best = (em_u64*)p1; ws->second = (em_u64*)p2; ws->cbest = (em_u64*)p3; ws->ckey = (em_u64*)p4;
-    ws->bcol = (int*)p5; ws->bcol2 = (int*)p6; ws->comp = (int*)p7; ws->parent = (int*)p8; ws->tcomp = (int*)p9;
-    ws->info = (int*)p10; ws->ctl = (int*)p11;
-  }
-  return off;
+  EmWs sizing;
+  EmWs& w = ws ? *ws : sizing;
+  WsCarver c{base};
+  w.nrm = c.take<double>(n);
+  w.best = c.take<em_u64>(n);
+  w.second = c.take<em_u64>(n);
+  w.cbest = c.take<em_u64>(n);
+  w.ckey = c.take<em_u64>(n);
+  w.bcol = c.take<int>(n);
+  w.bcol2 = c.take<int>(n);
+  w.comp = c.take<int>(n);
+  w.parent = c.take<int>(n);
+  w.tcomp = c.take<int>((n + GEMM_BM - 1) / GEMM_BM);
+  w.info = c.take<int>(4);
+  w.ctl = c.take<int>(2);
+  return c.off;
 }
 
 template <int PASS>

@@ -443,28 +443,18 @@ struct KnnFusedWs {
   int *taucol, *count, *ccol, *overflow;
 };
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static size_t knn_fused_layout(long n, int cap, char* base, KnnFusedWs* ws) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align256(bytes);
-    return p;
-  };
-  char* p0 = take(8 * (size_t)n);
-  char* p1 = take(8 * (size_t)n);
-  char* p2 = take(4 * (size_t)n);
-  char* p2b = take(4 * (size_t)n);
-  char* p3 = take(256);
-  char* p4 = take(8 * (size_t)n * cap);
-  char* p5 = take(4 * (size_t)n * cap);
-  if (ws) {
-    ws->norms = (double*)p0; ws->tau = (double*)p1; ws->count = (int*)p2; ws->taucol = (int*)p2b;
-    ws->overflow = (int*)p3;
-    ws->cscore = (double*)p4; ws->ccol = (int*)p5;
-  }
-  return off;
+  KnnFusedWs sizing;
+  KnnFusedWs& w = ws ? *ws : sizing;
+  WsCarver c{base};
+  w.norms = c.take<double>(n);
+  w.tau = c.take<double>(n);
+  w.count = c.take<int>(n);
+  w.taucol = c.take<int>(n);
+  w.overflow = c.take<int>(64);
+  w.cscore = c.take<double>((size_t)n * cap);
+  w.ccol = c.take<int>((size_t)n * cap);
+  return c.off;
 }
 
 int inv_norms_launch(double* norms, long n, hipStream_t st);  // knn.hip: sq norms -> 1 / norm (zero norms -> 1)

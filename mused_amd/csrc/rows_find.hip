@@ -157,24 +157,19 @@ struct RfWs {
 static long rf_slots(long total) { return 2 * total + 1; }
 
 static size_t rf_layout(long total, char* base, RfWs* ws) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return p;
-  };
+  RfWs sizing;
+  RfWs& w = ws ? *ws : sizing;
+  WsCarver c{base};
   const long slots = rf_slots(total), nb = (total + RF_TILE - 1) / RF_TILE;
-  char* pt[3];
-  for (int i = 0; i < 3; ++i) pt[i] = take(4 * (size_t)slots);
-  char* pe[4];
-  for (int i = 0; i < 4; ++i) pe[i] = take(4 * (size_t)total);
-  char* ph = take(4 * 256 * (size_t)nb);
-  if (ws) {
-    ws->table = (int*)pt[0]; ws->first = (int*)pt[1]; ws->firstq = (int*)pt[2];
-    ws->key[0] = (int*)pe[0]; ws->val[0] = (int*)pe[1]; ws->key[1] = (int*)pe[2]; ws->val[1] = (int*)pe[3];
-    ws->hist = (int*)ph;
+  w.table = c.take<int>(slots);
+  w.first = c.take<int>(slots);
+  w.firstq = c.take<int>(slots);
+  for (int i = 0; i < 2; ++i) {
+    w.key[i] = c.take<int>(total);
+    w.val[i] = c.take<int>(total);
   }
-  return off;
+  w.hist = c.take<int>(256 * (size_t)nb);
+  return c.off;
 }
 
 static bool rf_shape_ok(long n, long q, int d) { return n >= 0 && q >= 0 && n + q <= RF_MAX_ELEMS && d >= 1 && d < (1 << 20); }

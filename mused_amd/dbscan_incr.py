@@ -47,50 +47,39 @@ which is the cluster scikit-learn's index-order search reaches b from first.
 For min_samples <= 2 a non-core row has no neighbour but itself: no border row exists, steps 4-5 are empty and every
 non-core row is noise.  Duplicate rows are ordinary rows at distance ~0, as for scikit-learn.
 
-DELETING THE m OLDEST of n rows, 1 <= m <= n (`delete_oldest`; the kernels: mused_dbscan_incr_delete).  D = [0, m) are the
-deleted rows, S = [m, n) the survivors.  The pin is the same: afterwards the labels of the rows still held equal scikit-learn's
-refit of those rows in their order (tests/test_dbscan_incr_delete_host.py, after every operation).
+DELETING a non-empty set D of distinct positions among the n rows held; S = the rest, in their order (`_delete`, reached through
+`delete_rows(idx)` and `delete_oldest(m)`; the kernels: mused_dbscan_incr_delete_rows, mused_dbscan_incr_delete).  The pin is the
+same: afterwards the labels of S equal scikit-learn's refit of those rows in their order (tests/test_dbscan_incr_delete_host.py,
+tests/test_dbscan_incr_delete_rows_host.py, after every operation).
 
-    1 UNCOUNT  D against S: count[j] -= |{ i in D : d2(i, j) <= eps^2 }| for j in S.  No rounding test and no new flag: every
-               pair was tested against tau when the later of its two rows was inserted, so an unflagged state holds no pair
-               whose side of eps^2 depends on how d2 is evaluated, and the counts stay exact.
+    1 UNCOUNT  D against ALL rows: count[j] -= |{ i in D : d2(i, j) <= eps^2 }|.  Subtracting from a dead column is harmless: the
+               column is dropped in step 6.  No rounding test and no new flag: every pair was tested against tau when the later
+               of its two rows was inserted, so an unflagged state holds no pair whose side of eps^2 depends on how d2 is
+               evaluated, and the counts stay exact.
     2 REMEMBER before anything moves: core_before, root_before[i] = find(i) for the core rows, find(best[i]) for the non-core
                rows that have a best (O(n)).
     3 AFFECTED gone = the core rows of D; lost = the rows of S that were core and have count < min_samples now.  A component
                (old root r) is affected iff it holds a row of gone or of lost.  An unaffected component keeps every core row
                and every edge: it stays one component with the same root.
     4 REBUILD  R = the rows of S that are still core and whose root_before is affected: parent[x] = x for x in R, then every
-               pair of R within eps^2 is united (the smaller root wins).  No edge joins R to a core row outside R: such a row
-               was in the same component before, and a deletion adds no edge.  R against the rows of S, never S x S; the
-               components the delete does not touch cost nothing.  (A lost row gets parent[x] = x: a non-core row is its own
-               parent, which is what an insert that turns it core again starts from.)
+               pair of R within eps^2 is united (the smaller root wins).  A dead row is never core in it.  No edge joins R to a
+               core row outside R: such a row was in the same component before, and a deletion adds no edge.  R against the rows
+               of S, never S x S; the components the delete does not touch cost nothing.  (A lost row gets parent[x] = x: a
+               non-core row is its own parent, which is what an insert that turns it core again starts from.)
     5 BORDER   (min_samples >= 3)  B = lost and the non-core rows of S whose remembered best is an affected root.  For b in B:
                best[b] = the smallest NEW root among its core neighbours in S, or NONE.  Every other non-core row keeps its
                best: the pieces of an affected component have roots >= the old root, so a minimum that came from an
                unaffected component is still the minimum, and a row without a best gains no neighbour.
-    6 COMPACT  survivor i becomes i - m: nrm, count, parent and best move down by m, parent and best entries drop by m (a
-               core row's best is not read anywhere and is reset to NONE).  Labels as in 6 above.  m == n leaves the empty
-               state: the next insert is a first insert.
+    6 COMPACT  survivor i becomes pos[i] = i - |{ j in D : j < i }|: nrm, count, parent and best are packed, and parent and best
+               entries are renumbered through the same map (a core row's best is not read anywhere and is reset to NONE).  The
+               map keeps the order, so parent[x] <= x still holds and a root is still the smallest core index of its component.
+               Labels as in 6 above.  D = everything leaves the empty state: the next insert is a first insert.
 
-Afterwards parent[x] <= x, a root is the smallest core index of its component and best is a root as of this operation: what
-an insert relies on.
+Afterwards best is a root as of this operation: with the two invariants of step 6, what an insert relies on.
 
-DELETING ANY ROWS (`delete_rows`; the kernels: mused_dbscan_incr_delete_rows).  D is a non-empty set of distinct positions among
-the n rows held, S the rest in their order.  The pin is unchanged: afterwards the labels of S equal scikit-learn's refit of those
-rows in their order (tests/test_dbscan_incr_delete_rows_host.py, after every operation).  Steps 1-5 are those above with
-"i < m" read as "i in D":
-
-    1 UNCOUNT  D against ALL rows.  Subtracting from a dead column is harmless: the column is dropped in step 6.  No rounding
-               flag, for the reason above.
-    2 REMEMBER as above.
-    3 AFFECTED gone = the core rows of D; lost = the rows of S that were core and are below min_samples now.
-    4 REBUILD  R = the still-core rows of S under an affected root.  A dead row is never core in it.
-    5 BORDER   (min_samples >= 3)  B = lost and the non-core rows of S whose remembered best is an affected root.
-    6 COMPACT  the one real difference: survivor i becomes pos[i] = i - |{ j in D : j < i }|, and parent and best entries are
-               renumbered through the same map.  The map keeps the order, so parent[x] <= x still holds and a root is still the
-               smallest core index of its component.  A core row's best is reset to NONE.  D = everything leaves the empty state.
-
-`delete_rows(range(m))` leaves exactly the state and `last_delete` of `delete_oldest(m)`.
+THE m OLDEST ROWS are the case D = [0, m): pos[i] = i - m, and the device skips the columns of D in step 1 (they are dropped
+anyway).  `delete_rows(range(m))` and `delete_oldest(m)` are one path here; that the two device entries agree is pinned on the
+device (tests/test_gpu_dbscan_incr_delete_rows.py).
 """
 from __future__ import annotations
 
@@ -230,76 +219,25 @@ class IncrementalSpec:
 
     def delete_oldest(self, m):
         """Deletes rows 0 .. m - 1 (the rule at the head of this module) -> int64 labels of the n - m rows still held."""
-        n, m, ms = self.n, int(m), self.min_samples
+        n, m = self.n, int(m)
         if not 1 <= m <= n:
             raise ValueError(f"delete_oldest: m = {m} is outside [1, {n}]")
-        if m == n:
-            self.n, self.X = 0, None
-            self.nrm = np.empty(0)
-            self.count, self.parent, self.best = (np.empty(0, dtype=np.int64) for _ in range(3))
-            self.last_delete = (0, 0, 0, 0, 0, 0)
-            return self._labels()
-        count, best, idx = self.count, self.best, np.arange(n)
-        surv = idx >= m
-        # 2 REMEMBER
-        core_before = count >= ms
-        parent = _flatten(self.parent)
-        root_before = parent.copy()
-        had_best = ~core_before & (best != NONE)
-        best_before = np.full(n, NONE, dtype=np.int64)
-        best_before[had_best] = parent[best[had_best]]
-        # 1 UNCOUNT
-        for r, within, _, _ in self._blocks(idx[:m]):
-            count[m:] -= within[:, m:].sum(axis=0)
-        # 3 AFFECTED
-        core = surv & (count >= ms)
-        lost = surv & core_before & ~core
-        affected = np.zeros(n, dtype=bool)
-        affected[root_before[core_before & ~core]] = True      # gone and lost
-        # 4 REBUILD
-        in_r = core & affected[root_before]
-        rows_r = np.flatnonzero(in_r)
-        parent[rows_r] = rows_r
-        parent[lost] = idx[lost]
-        for r, within, _, _ in self._blocks(rows_r):
-            k, col = np.nonzero(within & core[None, :])
-            assert in_r[col].all()                             # no edge joins R to a core row outside R
-            ea, eb = r[k], col
-            while True:
-                pa, pb = parent[ea], parent[eb]
-                diff = pa != pb
-                if not diff.any():
-                    break
-                np.minimum.at(parent, np.maximum(pa, pb)[diff], np.minimum(pa, pb)[diff])
-                parent = _flatten(parent)
-        # 5 BORDER
-        rows_b = np.empty(0, dtype=np.int64)
-        if ms > 2:
-            stale = surv & had_best
-            stale[stale] = affected[best_before[stale]]
-            rows_b = np.flatnonzero(lost | stale)
-            best[rows_b] = NONE
-            for r, within, _, _ in self._blocks(rows_b):
-                k, col = np.nonzero(within & core[None, :])
-                np.minimum.at(best, r[k], parent[col])
-        # 6 COMPACT
-        best[core] = NONE
-        self.n, self.X, self.nrm, self.count = n - m, self.X[m:], self.nrm[m:], count[m:]
-        self.parent = parent[m:] - m
-        self.best = np.where(best[m:] == NONE, NONE, best[m:] - m)
-        labels = self._labels()
-        self.last_delete = (0, self.clusters, int(core.sum()), int(lost.sum()), len(rows_r), len(rows_b))
-        return labels
+        return self._delete(np.arange(n) < m)
 
     def delete_rows(self, idx):
         """Deletes the rows at the distinct positions `idx` (any order; the rule at the head of this module) -> int64 labels of
         the rows still held.  `delete_rows(range(m))` leaves the state and `last_delete` of `delete_oldest(m)`."""
-        n, ms = self.n, self.min_samples
+        n = self.n
         dele = np.asarray(idx, dtype=np.int64).reshape(-1)
         if len(dele) < 1 or dele.min() < 0 or dele.max() >= n or len(np.unique(dele)) != len(dele):
             raise ValueError(f"delete_rows: needs 1 to {n} distinct positions in [0, {n})")
         dead = np.zeros(n, dtype=bool)
         dead[dele] = True
+        return self._delete(dead)
+
+    def _delete(self, dead):
+        """Steps 1-6 of the delete's rule for D = the rows marked in the bool mask `dead` (not empty)."""
+        n, ms = self.n, self.min_samples
         if dead.all():
             self.n, self.X = 0, None
             self.nrm = np.empty(0)
