@@ -94,7 +94,9 @@ int mused_group_mask(const int* ids, int n, unsigned long long* out_mask, int ma
 /* The same selections as mused_record_scores / mused_jaccard_scores followed by mused_select_k_smallest, WITHOUT the
  * n x n score matrix: the scores of a row are computed into LDS by the selection kernel itself (n <= 16384 records,
  * n <= 15000 tag sets).  Outputs as
- * mused_select_k_smallest (out_idx and out_mask may each be NULL; ties to the smaller row; own column cleared). */
+ * mused_select_k_smallest (ties to the smaller row; own column cleared).  Either of out_idx and out_mask may be NULL, not
+ * both; with a mask, mask_words >= ceil(n / 64) (words past the last column are written as zero).  Error, nothing
+ * launched: both outputs NULL, a mask with a smaller mask_words, k < 1, k > n, n beyond the cap. */
 int mused_record_knn(const double* rec, int n, int kind, int k, int* out_idx, unsigned long long* out_mask, int mask_words,
                      void* stream);
 int mused_jaccard_knn(const int* rowptr, const int* tags, const int* postptr, const int* postrow, int n, int n_tags, int k,

@@ -139,6 +139,8 @@ int mused_record_knn(const double* rec, int n, int kind, int k, int* out_idx, un
                      void* stream) {
   MUSED_REQUIRE(rec && n > 0 && (kind == 0 || kind == 1) && k >= 1 && k <= n && n <= select_max_fused_rows(false),
                 "mused_record_knn: bad arguments (n=%d kind=%d k=%d)", n, kind, k);
+  MUSED_REQUIRE(out_idx || out_mask, "mused_record_knn: out_idx and out_mask are both null");
+  MUSED_REQUIRE(!out_mask || mask_words >= (n + 63) / 64, "mused_record_knn: mask_words %d (n=%d)", mask_words, n);
   return select_from_records(rec, n, kind, k, out_idx, out_mask, mask_words, (hipStream_t)stream);
 }
 
@@ -146,6 +148,8 @@ int mused_jaccard_knn(const int* rowptr, const int* tags, const int* postptr, co
                       int* out_idx, unsigned long long* out_mask, int mask_words, void* stream) {
   MUSED_REQUIRE(rowptr && postptr && n > 0 && n_tags >= 0 && k >= 1 && k <= n && n <= select_max_fused_rows(true),
                 "mused_jaccard_knn: bad arguments (n=%d k=%d)", n, k);
+  MUSED_REQUIRE(out_idx || out_mask, "mused_jaccard_knn: out_idx and out_mask are both null");
+  MUSED_REQUIRE(!out_mask || mask_words >= (n + 63) / 64, "mused_jaccard_knn: mask_words %d (n=%d)", mask_words, n);
   return select_from_tag_sets(rowptr, tags, postptr, postrow, n, k, out_idx, out_mask, mask_words, (hipStream_t)stream);
 }
 

@@ -121,7 +121,10 @@ __global__ __launch_bounds__(CS_THREADS) void chunk_select_kernel(int n, int k, 
           const double v = src.vals[t];
           for (int q = lo + tid; q < hi; q += CS_THREADS) {
             double* acc = reinterpret_cast<double*>(ck + (src.postrow[q] - c0));
-            *acc = __dadd_rn(*acc, __dmul_rn(v, src.postval[q]));
+            // a product and a sum, each rounded, written out under this file's `fp contract(off)`: __dadd_rn(*acc,
+            // __dmul_rn(...)) fuses into one v_fmac_f64 once the header's inline bodies are inlined (tfidf.hip)
+            const double prod = v * src.postval[q];
+            *acc = *acc + prod;
           }
         }
         __syncthreads();
