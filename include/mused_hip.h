@@ -624,9 +624,19 @@ int mused_swfd_counters(void* handle, long* rows_seen, int* pending); /* HOST ou
 /* BLOCKING (synchronises `stream`): *status_out (HOST) != 0 -> an eigensolve of this sketch gave up (bit 0: timeout of the
  * persistent work-queue solver); everything it has returned since is invalid.  Sticky. */
 int mused_swfd_status(void* handle, int* status_out, void* stream);
-/* state exchange between ranks (one half = the L sketches of kind 0 MAIN / 1 AUX) */
+/* state exchange between ranks (one half = the L sketches of kind 0 MAIN / 1 AUX; single-lane handles) */
 long mused_swfd_half_bytes(void* handle);
+/* Packs one half into dst (device, mused_swfd_half_bytes bytes).  THE EXCHANGE FORMAT, with L = mused_swfd_levels,
+ * l = sketch_dim, every part level-major and without padding:
+ *   [ buffers     L x 2l x d  f64 | snapshot rings  L x 2l x d  f64 | timestamps  L x 2l  i64 | meta  L x 4  i32 | dropped  L  i64 ]
+ * buffer of a level: rows 0 .. nk - 1 the kept rows, then the rows appended since the last rotation, then zeros;
+ * meta = {nk, ring head, ring count, dumps the next level did not make}: the live snapshots are the ring slots
+ * (head + q) mod 2l, q < count, oldest first, timestamps (row numbers, from 1) at the same slots -- slots outside that
+ * range hold stale data; dropped = the largest timestamp of a snapshot lost to the ring capacity (0: none).
+ * A MAIN level below the top that has lost a snapshot of the current epoch is frozen until the epoch ends (it cannot be
+ * selected before AUX replaces it): its exported state is the one of its last rotation. */
 int mused_swfd_export_half(void* handle, int kind, void* dst, void* stream);
+/* the inverse: overwrites one half with a blob of the same N, R, d, sketch_dim (row counter and pending rows untouched) */
 int mused_swfd_import_half(void* handle, int kind, const void* src, void* stream);
 int mused_swfd_begin_epoch(void* handle, long rows_seen, const void* main_half, void* stream);
 /* BLOCKING unit primitive: one FD rotation of a (2 l x d) buffer in place */

@@ -999,6 +999,8 @@ int mused_swfd_import_half(void* handle, int kind, const void* src, void* stream
 int mused_swfd_begin_epoch(void* handle, long rows_seen, const void* main_half, void* stream) {
   Swfd* h = (Swfd*)handle;
   MUSED_REQUIRE(h && rows_seen >= 0 && rows_seen % h->N == 0, "mused_swfd_begin_epoch: rows_seen must be a multiple of N");
+  // (checked before anything is cleared: an argument error leaves the handle as it was)
+  MUSED_REQUIRE(!main_half || h->lanes == 1, "mused_swfd_begin_epoch: a state blob can only be imported into a single-lane handle");
   hipStream_t st = (hipStream_t)stream;
   const size_t S = h->S, L = h->L;
   MUSED_CHECK_HIP(hipMemsetAsync(h->buf, 0, 8 * S * (size_t)h->n2 * h->d, st));
@@ -1007,7 +1009,6 @@ int mused_swfd_begin_epoch(void* handle, long rows_seen, const void* main_half, 
   MUSED_CHECK_HIP(hipMemsetAsync(h->qt, 0, 8 * S * h->cap, st));
   (void)L;
   if (main_half) {
-    MUSED_REQUIRE(h->lanes == 1, "mused_swfd_begin_epoch: a state blob can only be imported into a single-lane handle");
     int rc = half_copy(h, 0, (char*)main_half, false, st);
     if (rc) return rc;
   }

@@ -188,6 +188,15 @@ class SeqBasedSWFD:
         call("mused_swfd_export_half", self._h, int(kind), ptr(blob), stream_ptr())
         return blob
 
+    def import_half(self, kind: int, blob: torch.Tensor):
+        """Overwrite the MAIN (0) or AUX (1) half of the state with a blob `export_half` packed (same N, R, d, l)."""
+        self._flush()
+        if blob.numel() != self.half_bytes() or blob.dtype != torch.uint8 or not blob.is_cuda:
+            raise ValueError("state blob has the wrong size")
+        blob = blob.contiguous()
+        call("mused_swfd_import_half", self._h, int(kind), ptr(blob), stream_ptr())
+        self._keepalive = blob
+
     def begin_epoch(self, rows_seen: int, main_half: torch.Tensor | None = None):
         """Start the epoch that begins after `rows_seen` rows (a multiple of N) with MAIN taken from
         `main_half` (the AUX half of whoever sketched the previous window) and AUX empty."""
