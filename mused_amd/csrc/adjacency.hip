@@ -8,6 +8,7 @@
 // lists derived from the bitmask (rows in ascending column order -> reproducible sums).
 // Every kernel here is HBM-bound integer/bit work.
 #include "internal.h"
+#include "scan.h"
 
 namespace mused {
 
@@ -48,39 +49,21 @@ __global__ __launch_bounds__(1024) void degree_scan_kernel(const int* __restrict
                                                           int* __restrict__ stats, long cap = 0,
                                                           int* __restrict__ overflow = nullptr) {
   __shared__ int wsum[16];
-  __shared__ int carry;
   __shared__ int smax;
-  if (threadIdx.x == 0) { carry = 0; smax = 0; }
+  if (threadIdx.x == 0) smax = 0;
   __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int carry = 0;
   for (int base = 0; base < n; base += 1024) {
     const int i = base + threadIdx.x;
     const int v = (i < n) ? deg[i] : 0;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(x, o);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[w] = x;
     int m = v;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
-    if (lane == 0) atomicMax(&smax, m);
-    __syncthreads();
-    int b = carry, tot = 0;
-    for (int j = 0; j < 16; ++j) {
-      const int c = wsum[j];
-      b += (j < w) ? c : 0;
-      tot += c;
-    }
-    if (i < n) {
-      const int rp = b + x - v;
-      rowptr[i] = (cap > 0 && rp > cap) ? (int)cap : rp;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) carry += tot;
-    __syncthreads();
+    if ((threadIdx.x & 63) == 0) atomicMax(&smax, m);  // read behind the barriers of the scan
+    int tot;
+    const int rp = carry + block_excl_scan(v, wsum, tot);
+    if (i < n) rowptr[i] = (cap > 0 && rp > cap) ? (int)cap : rp;
+    carry += tot;
   }
   if (threadIdx.x == 0) {
     rowptr[n] = (cap > 0 && carry > cap) ? (int)cap : carry;
@@ -102,12 +85,7 @@ __global__ void mask_to_csr_kernel(const unsigned long long* __restrict__ mask, 
     const int w = w0 + lane;
     unsigned long long bits = (w < words) ? mask[(long)row * words + w] : 0ull;
     const int c = __popcll(bits);
-    int x = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(x, o);
-      if (lane >= o) x += y;
-    }
+    const int x = wave_incl_scan(c);
     int pos = base + x - c;
     while (bits) {
       const int b = __ffsll((long long)bits) - 1;

@@ -1,38 +1,25 @@
-// a[0 .. m) <- its exclusive prefix sums, by ONE workgroup: shared by csrc/dbscan_incr.hip (the block totals of a keep mask) and
-// csrc/rows_find.hip (the histograms of a radix pass).  Chunks of 1024 consecutive entries (coalesced): shuffles scan a wave,
-// the 16 wave totals and a running carry give the rest.
+// The scan of an array by ONE workgroup, in chunks of 1024 consecutive entries (coalesced): the block counts of a compaction
+// (csrc/dbscan_incr.hip, csrc/tokenise.hip) and the histograms of a radix pass (radix_sort.h).  Each .hip is compiled on its
+// own, so the kernel is static.
 #pragma once
-#include "common.h"
+#include "scan.h"
 
 namespace mused {
 
 constexpr int BLOCKSCAN_THREADS = 1024;
-static __global__ __launch_bounds__(BLOCKSCAN_THREADS) void blockscan_kernel(int* __restrict__ a, int m) {
-  __shared__ int wtot[BLOCKSCAN_THREADS / 64];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+// a[0 .. m) <- its exclusive prefix sums; *total <- the sum unless total is null (it may be a + m)
+static __global__ __launch_bounds__(BLOCKSCAN_THREADS) void blockscan_kernel(int* __restrict__ a, int m, int* total) {
+  __shared__ int ws[16];
   int carry = 0;
   for (int base = 0; base < m; base += BLOCKSCAN_THREADS) {
-    const int i = base + t;
+    const int i = base + threadIdx.x;
     const int v = i < m ? a[i] : 0;
-    int x = v;  // inclusive over the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(x, o);
-      x += lane >= o ? y : 0;
-    }
-    if (lane == 63) wtot[wave] = x;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < BLOCKSCAN_THREADS / 64; ++w) {
-      const int c = wtot[w];
-      total += c;
-      before += w < wave ? c : 0;
-    }
-    if (i < m) a[i] = carry + before + x - v;
-    carry += total;
-    __syncthreads();  // wtot is rewritten by the next chunk
+    int tot;
+    const int x = carry + block_excl_scan(v, ws, tot);
+    if (i < m) a[i] = x;
+    carry += tot;
   }
+  if (total && threadIdx.x == 0) *total = carry;
 }
 
 }  // namespace mused

@@ -760,7 +760,7 @@ int mused_dbscan_incr_delete_rows(const double* X, long ld, int d, double* X_out
   if (m == n) return MUSED_OK;  // the empty state: nothing of the arrays describes a row any more
   if ((rc = dbd_front(del, k, a, X, ld, d, n, dele, m, chunk, st))) return rc;
   hipLaunchKernelGGL(dbr_scan_kernel<false>, scan, dim3(DBR_SCAN_THREADS), 0, st, r.dead, r.blk, r.pos, (int)n);
-  hipLaunchKernelGGL(blockscan_kernel, dim3(1), dim3(BLOCKSCAN_THREADS), 0, st, r.blk, (int)scan.x);
+  hipLaunchKernelGGL(blockscan_kernel, dim3(1), dim3(BLOCKSCAN_THREADS), 0, st, r.blk, (int)scan.x, (int*)nullptr);
   hipLaunchKernelGGL(dbr_scan_kernel<true>, scan, dim3(DBR_SCAN_THREADS), 0, st, r.dead, r.blk, r.pos, (int)n);
   hipLaunchKernelGGL(dbd_compact_kernel<DelMask>, rows, blk, 0, st, a, del, k.root, k.nrm2, k.count2, k.parent2, k.best2, k.rootb, (int)n);
   hipLaunchKernelGGL(dbi_gather_kernel, dim3(cdiv(ns * d, 256)), blk, 0, st, X, ld, d, r.surv, (int)ns, X_out, (int)ld_out);

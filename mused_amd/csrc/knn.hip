@@ -10,6 +10,7 @@
 #include "gemm_f64.h"
 #include "internal.h"
 #include "meta_scores.h"
+#include "radix_select.h"
 
 namespace mused {
 
@@ -121,38 +122,11 @@ static int scores_launch(const T* X, long n, int d, long ld, int metric, double*
 
 // ---- k-smallest selection -------------------------------------------------------
 // One 1024-thread workgroup per row.  Exact radix select on order-preserving 64-bit
-// keys: bits above the highest bit in which the row's min and max keys differ are
-// skipped; each pass histograms one digit (<= 8 bits) of the still-undecided keys
-// in LDS; when the bin holding the k-th key has shrunk to <= 256 keys the rest is
-// finished by ranking those candidates against each other.  Selected columns are
-// emitted in ascending column order (block prefix sums) -> deterministic output.
-constexpr int SEL_THREADS = 1024;
-constexpr int SEL_WAVES = SEL_THREADS / 64;
+// keys (radix_select.h).  Selected columns are emitted in ascending column order
+// (block prefix sums) -> deterministic output.
+constexpr int SEL_THREADS = SELECT_THREADS;
 constexpr int SEL_MAX_LDS_KEYS = 16384;  // 128 KiB of keys cached in LDS; longer rows re-read global
 constexpr int SEL_MAX_JACCARD_ROWS = 15000;  // keys + 16-bit intersection counters of one row: 150 KB of the 160 KB
-
-__device__ __forceinline__ int block_excl_scan(int v, int* ws /*[SEL_WAVES]*/, int& total) {
-  // exclusive prefix sum over the workgroup; ws in LDS
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) ws[w] = x;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < SEL_WAVES; ++i) {
-    const int c = ws[i];
-    base += (i < w) ? c : 0;
-    tot += c;
-  }
-  total = tot;
-  __syncthreads();
-  return base + x - v;
-}
 
 // Where a row of scores comes from.  SRC_MATRIX: row `row` of S (the classic path).  The others compute the row on the
 // fly (rows of at most SEL_MAX_LDS_KEYS scores, kept as keys in LDS) -- the metadata modality types of meta.hip without
@@ -181,13 +155,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_k_kernel(const double* __r
                                                              unsigned long long* __restrict__ out_mask, int mask_words,
                                                              SelSource src) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long sel_smem[];
-  __shared__ int hist[256];
-  __shared__ int ws[SEL_WAVES];
-  __shared__ unsigned long long s_red[2 * SEL_WAVES];
-  __shared__ unsigned long long s_prefix, s_maskbits;
-  __shared__ int s_remaining, s_shift, s_done, s_ncand, s_eqcount;
-  __shared__ unsigned long long cand_key[256];
-  __shared__ int cand_idx[256];
+  __shared__ SelectLds lds;
 
   const int row = blockIdx.x;
   const int tid = threadIdx.x;
@@ -243,14 +211,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_k_kernel(const double* __r
     for (int t = t0; t < t1; ++t) {
       const int tag = src.tags[t];
       const int p1 = src.postptr[tag + 1];
-      if (tid == 0) {
-        int lo = src.postptr[tag], hi = p1;
-        while (lo < hi) {
-          const int mid = lo + ((hi - lo) >> 1);
-          if (src.postrow[mid] < ws0) lo = mid + 1; else hi = mid;
-        }
-        s_lb[(t - t0) & 1] = lo;
-      }
+      if (tid == 0) s_lb[(t - t0) & 1] = lower_bound(src.postrow, src.postptr[tag], p1, ws0);
       __syncthreads();
       for (int q = s_lb[(t - t0) & 1] + tid; q < p1; q += SEL_THREADS) {
         const int r = src.postrow[q];
@@ -298,120 +259,16 @@ __global__ __launch_bounds__(SEL_THREADS) void select_k_kernel(const double* __r
     kmin = key < kmin ? key : kmin;
     kmax = key > kmax ? key : kmax;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long a = __shfl_xor(kmin, o), b = __shfl_xor(kmax, o);
-    kmin = a < kmin ? a : kmin;
-    kmax = b > kmax ? b : kmax;
-  }
-  if ((tid & 63) == 0) {
-    s_red[tid >> 6] = kmin;
-    s_red[SEL_WAVES + (tid >> 6)] = kmax;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    unsigned long long mn = s_red[0], mx = s_red[SEL_WAVES];
-    for (int i = 1; i < SEL_WAVES; ++i) {
-      mn = s_red[i] < mn ? s_red[i] : mn;
-      mx = s_red[SEL_WAVES + i] > mx ? s_red[SEL_WAVES + i] : mx;
-    }
-    const unsigned long long diff = mn ^ mx;
-    s_remaining = k;
-    if (diff == 0) {  // all keys equal: threshold = that key, every needed element is "equal"
-      s_prefix = mn;
-      s_maskbits = ~0ull;
-      s_shift = -1;
-    } else {
-      const int hb = 63 - __clzll(diff);       // highest differing bit
-      const int top = hb + 1;                  // bits [top, 64) are common
-      s_maskbits = (top >= 64) ? 0ull : (~0ull << top);
-      s_prefix = mn & s_maskbits;
-      s_shift = top;                           // next digit covers [max(0, top-8), top)
-    }
-    s_done = 0;
-    s_ncand = 0;
-  }
-  __syncthreads();
-
   auto key_at = [&](int i) -> unsigned long long { return cached ? keys[i] : f64_key(srow[i]); };
-
-  // radix passes
-  while (true) {
-    const int top = s_shift;
-    if (top <= 0 || s_done) break;
-    const int lo = top >= 8 ? top - 8 : 0;
-    const int width = top - lo;
-    const unsigned long long pmask = s_maskbits, prefix = s_prefix;
-    for (int i = tid; i < 256; i += SEL_THREADS) hist[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < n; i += SEL_THREADS) {
-      const unsigned long long key = key_at(i);
-      if ((key & pmask) == prefix) atomicAdd(&hist[(int)((key >> lo) & ((1u << width) - 1))], 1);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int rem = s_remaining, cum = 0, dsel = 0;
-      const int nb = 1 << width;
-      for (int b = 0; b < nb; ++b) {
-        if (cum + hist[b] >= rem) { dsel = b; break; }
-        cum += hist[b];
-      }
-      s_remaining = rem - cum;
-      s_prefix = prefix | ((unsigned long long)dsel << lo);
-      s_maskbits = pmask | ((((unsigned long long)1 << width) - 1) << lo);
-      s_shift = lo;
-      if (hist[dsel] <= 256 && lo > 0) s_done = 1;  // finish by ranking the bin's members
-    }
-    __syncthreads();
-  }
-
-  unsigned long long thr;  // k-th smallest key
-  int need_eq;             // how many keys == thr are selected (smallest indices first)
-  if (s_done) {
-    // gather the undecided bin (<= 256 keys) with an LDS atomic append; the order does not matter,
-    // the ranking below is by (key, column)
-    const unsigned long long pmask = s_maskbits, prefix = s_prefix;
-    for (int i = tid; i < n; i += SEL_THREADS) {
-      const unsigned long long key = key_at(i);
-      if ((key & pmask) == prefix) {
-        const int pos = atomicAdd(&s_ncand, 1);
-        cand_key[pos] = key;
-        cand_idx[pos] = i;
-      }
-    }
-    __syncthreads();
-    const int nc = s_ncand, rem = s_remaining;  // the rem-th smallest (1-based) of the candidates
-    if (tid < nc) {
-      const unsigned long long mk = cand_key[tid];
-      const int mi = cand_idx[tid];
-      int rank = 0, eq_before = 0, eq_all = 0;
-      for (int j = 0; j < nc; ++j) {
-        const unsigned long long kj = cand_key[j];
-        const bool same = (kj == mk);
-        const bool before = same && cand_idx[j] < mi;
-        rank += (kj < mk) || before;
-        eq_before += before;
-        eq_all += same;
-      }
-      if (rank == rem - 1) {
-        s_prefix = mk;
-        s_remaining = eq_before + 1;
-        s_eqcount = eq_all;
-      }
-    }
-    __syncthreads();
-  } else if (tid == 0) {
-    s_eqcount = -1;  // unknown: the general emit path counts
-  }
-  __syncthreads();
-  thr = s_prefix;
-  need_eq = s_remaining;
+  const SelectThreshold th = block_select_threshold(lds, n, k, key_at, kmin, kmax);
+  const unsigned long long thr = th.thr;  // k-th smallest key
+  const int need_eq = th.need_eq;         // how many keys == thr are selected (smallest indices first)
 
   // emit: keys < thr, plus the first need_eq keys == thr in index order
   unsigned long long* mrow = out_mask ? out_mask + (long)row * mask_words : nullptr;
   // LDS bitmask staging reuses hist/cand arrays is awkward for large n; write mask words with
   // wave ballots instead: each group of 64 consecutive columns is one word owned by one wave.
-  if (!out_idx && s_eqcount == need_eq) {
+  if (!out_idx && th.eq_count == need_eq) {
     // common case: every key equal to the threshold is selected (no tie is cut) and only the bitmask
     // is wanted -> one ballot per 64 columns, no prefix sums, no barriers
     for (int base = 0; base < n; base += SEL_THREADS) {
@@ -436,10 +293,10 @@ __global__ __launch_bounds__(SEL_THREADS) void select_k_kernel(const double* __r
       is_eq = key == thr;
     }
     int tot_eq;
-    const int eq_pos = block_excl_scan(is_eq, ws, tot_eq);
+    const int eq_pos = block_excl_scan(is_eq, lds.ws, tot_eq);
     const int sel = is_lt || (is_eq && (eq_seen + eq_pos) < need_eq);
     int tot_sel;
-    const int pos = block_excl_scan(sel, ws, tot_sel);
+    const int pos = block_excl_scan(sel, lds.ws, tot_sel);
     if (sel && out_idx) out_idx[(long)row * k + emitted + pos] = i;
     if (mrow) {
       const unsigned long long bal = __ballot(sel && i != row);  // self edge dropped (matrix_operations.py:128)

@@ -19,13 +19,13 @@
 #include "common.h"
 #include "internal.h"
 #include "meta_scores.h"
+#include "radix_select.h"
 
 #pragma clang fp contract(off)
 
 namespace mused {
 
-constexpr int CS_THREADS = 1024;
-constexpr int CS_WAVES = CS_THREADS / 64;
+constexpr int CS_THREADS = SELECT_THREADS;
 constexpr int CS_MAX_K = 1024;
 constexpr int CS_MAX_CHUNK = 16384;
 constexpr int CS_LDS_DYN = 152 * 1024;  // dynamic LDS: (k + chunk) keys + k columns; the static arrays take ~4.5 KB more
@@ -42,49 +42,11 @@ struct ChunkSource {
   const double* postval;  // SPCOS: the values of the posting entries
 };
 
-__device__ __forceinline__ int cs_excl_scan(int v, int* ws, int& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) ws[w] = x;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < CS_WAVES; ++i) {
-    const int c = ws[i];
-    base += (i < w) ? c : 0;
-    tot += c;
-  }
-  total = tot;
-  __syncthreads();
-  return base + x - v;
-}
-
-// first position p in [lo, hi) with a[p] >= v (hi if none)
-__device__ __forceinline__ int cs_lower_bound(const int* __restrict__ a, int lo, int hi, int v) {
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 template <int SRC>
 __global__ __launch_bounds__(CS_THREADS) void chunk_select_kernel(int n, int k, int chunk, ChunkSource src,
                                                                  int* __restrict__ out_idx) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long cs_smem[];
-  __shared__ int hist[256];
-  __shared__ int ws[CS_WAVES];
-  __shared__ unsigned long long s_red[2 * CS_WAVES];
-  __shared__ unsigned long long s_prefix, s_maskbits;
-  __shared__ int s_remaining, s_shift, s_done, s_ncand;
-  __shared__ unsigned long long cand_key[256];
-  __shared__ int cand_idx[256];
+  __shared__ SelectLds lds;
 
   const int row = blockIdx.x;
   const int tid = threadIdx.x;
@@ -113,8 +75,8 @@ __global__ __launch_bounds__(CS_THREADS) void chunk_select_kernel(int n, int k, 
       for (int t = t0; t < t1; ++t) {
         const int term = src.cols[t];
         const int p1 = src.postptr[term + 1];
-        const int lo = cs_lower_bound(src.postrow, src.postptr[term], p1, c0);
-        const int hi = cs_lower_bound(src.postrow, lo, p1, c1);
+        const int lo = lower_bound(src.postrow, src.postptr[term], p1, c0);
+        const int hi = lower_bound(src.postrow, lo, p1, c1);
         if constexpr (SRC == CS_JACCARD) {
           for (int q = lo + tid; q < hi; q += CS_THREADS) ck[src.postrow[q] - c0] += 1ull;
         } else {
@@ -157,105 +119,16 @@ __global__ __launch_bounds__(CS_THREADS) void chunk_select_kernel(int n, int k, 
     unsigned long long thr = ~0ull;
     int need_eq = m;  // m <= k: every entry is kept
     if (m > k) {
-      // ---- exact radix select of the kk-th smallest (key, position) among keys[0, m) (select_k_kernel, knn.hip) ----
+      // the kk-th smallest (key, position) among keys[0, m)
       unsigned long long kmin = ~0ull, kmax = 0ull;
       for (int i = tid; i < m; i += CS_THREADS) {
         const unsigned long long key = keys[i];
         kmin = key < kmin ? key : kmin;
         kmax = key > kmax ? key : kmax;
       }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long a = __shfl_xor(kmin, o), b = __shfl_xor(kmax, o);
-        kmin = a < kmin ? a : kmin;
-        kmax = b > kmax ? b : kmax;
-      }
-      if ((tid & 63) == 0) {
-        s_red[tid >> 6] = kmin;
-        s_red[CS_WAVES + (tid >> 6)] = kmax;
-      }
-      __syncthreads();
-      if (tid == 0) {
-        unsigned long long mn = s_red[0], mx = s_red[CS_WAVES];
-        for (int i = 1; i < CS_WAVES; ++i) {
-          mn = s_red[i] < mn ? s_red[i] : mn;
-          mx = s_red[CS_WAVES + i] > mx ? s_red[CS_WAVES + i] : mx;
-        }
-        const unsigned long long diff = mn ^ mx;
-        s_remaining = kk;
-        if (diff == 0) {
-          s_prefix = mn;
-          s_maskbits = ~0ull;
-          s_shift = -1;
-        } else {
-          const int top = 64 - __clzll(diff);
-          s_maskbits = (top >= 64) ? 0ull : (~0ull << top);
-          s_prefix = mn & s_maskbits;
-          s_shift = top;
-        }
-        s_done = 0;
-        s_ncand = 0;
-      }
-      __syncthreads();
-      while (true) {
-        const int top = s_shift;
-        if (top <= 0 || s_done) break;
-        const int lo = top >= 8 ? top - 8 : 0;
-        const int width = top - lo;
-        const unsigned long long pmask = s_maskbits, prefix = s_prefix;
-        for (int i = tid; i < 256; i += CS_THREADS) hist[i] = 0;
-        __syncthreads();
-        for (int i = tid; i < m; i += CS_THREADS) {
-          const unsigned long long key = keys[i];
-          if ((key & pmask) == prefix) atomicAdd(&hist[(int)((key >> lo) & ((1u << width) - 1))], 1);
-        }
-        __syncthreads();
-        if (tid == 0) {
-          int rem = s_remaining, cum = 0, dsel = 0;
-          const int nb = 1 << width;
-          for (int b = 0; b < nb; ++b) {
-            if (cum + hist[b] >= rem) { dsel = b; break; }
-            cum += hist[b];
-          }
-          s_remaining = rem - cum;
-          s_prefix = prefix | ((unsigned long long)dsel << lo);
-          s_maskbits = pmask | ((((unsigned long long)1 << width) - 1) << lo);
-          s_shift = lo;
-          if (hist[dsel] <= 256 && lo > 0) s_done = 1;
-        }
-        __syncthreads();
-      }
-      if (s_done) {
-        const unsigned long long pmask = s_maskbits, prefix = s_prefix;
-        for (int i = tid; i < m; i += CS_THREADS) {
-          const unsigned long long key = keys[i];
-          if ((key & pmask) == prefix) {
-            const int pos = atomicAdd(&s_ncand, 1);
-            cand_key[pos] = key;
-            cand_idx[pos] = i;
-          }
-        }
-        __syncthreads();
-        const int nc = s_ncand, rem = s_remaining;
-        if (tid < nc) {
-          const unsigned long long mk = cand_key[tid];
-          const int mi = cand_idx[tid];
-          int rank = 0, eq_before = 0;
-          for (int j = 0; j < nc; ++j) {
-            const unsigned long long kj = cand_key[j];
-            const bool before = (kj == mk) && cand_idx[j] < mi;
-            rank += (kj < mk) || before;
-            eq_before += before;
-          }
-          if (rank == rem - 1) {
-            s_prefix = mk;
-            s_remaining = eq_before + 1;
-          }
-        }
-      }
-      __syncthreads();
-      thr = s_prefix;
-      need_eq = s_remaining;
+      const SelectThreshold th = block_select_threshold(lds, m, kk, [&](int i) { return keys[i]; }, kmin, kmax);
+      thr = th.thr;
+      need_eq = th.need_eq;
     }
 
     // ---- keep: keys < thr plus the first need_eq keys == thr in position (= column) order, compacted in place ----
@@ -272,10 +145,10 @@ __global__ __launch_bounds__(CS_THREADS) void chunk_select_kernel(int n, int k, 
         is_eq = key == thr;
       }
       int tot_eq;
-      const int eq_pos = cs_excl_scan(is_eq, ws, tot_eq);
+      const int eq_pos = block_excl_scan(is_eq, lds.ws, tot_eq);
       const int sel = is_lt || (is_eq && (eq_seen + eq_pos) < need_eq);
       int tot_sel;
-      const int pos = cs_excl_scan(sel, ws, tot_sel);
+      const int pos = block_excl_scan(sel, lds.ws, tot_sel);
       if (sel) {
         keys[emitted + pos] = key;
         run_col[emitted + pos] = col;

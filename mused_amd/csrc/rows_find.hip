@@ -7,21 +7,19 @@
 //               2 (n + q) + 1 slots keyed by their bytes.  The hash only places a row, the d words identify it: the slot
 //               that holds an equal row (or the free slot the row claims with a compare-and-swap) is the row's GROUP.  Which
 //               slot a value ends in depends on the order of the claims; the groups do not
-//   rf_hist, rf_scatter   a stable LSD radix sort of the elements by group, 8 bits a pass (the sort of csrc/tokenise.hip: a
-//               histogram per tile of 1024 elements, one scan (block_scan.h), ranks by wave ballots).  The elements start
-//               in the order (held by position, queries by position) and the sort is stable: inside a group the held
-//               positions ascend, then the query positions ascend
+//   sort        a stable LSD radix sort of the elements by group, 8 bits a pass (radix_sort.h).  The elements start in the
+//               order (held by position, queries by position) and the sort is stable: inside a group the held positions
+//               ascend, then the query positions ascend
 //   rf_heads    per group the sorted index of its first element and of its first query
 //   rf_assign   the k-th query of a group takes the k-th held element of it
 //
 // O(n + q) workspace, no pass over the values on the host, enqueue-only.  Every write to global memory is a vector store or
 // a device-scope vector atomic.
 #include "internal.h"
-#include "block_scan.h"
+#include "radix_sort.h"
 
 namespace mused {
 
-constexpr int RF_TILE = 1024;          // elements per wave of the radix passes
 constexpr long RF_MAX_ELEMS = 1l << 24;
 
 struct RfRows {
@@ -61,58 +59,6 @@ __global__ __launch_bounds__(256) void rf_insert_kernel(RfRows a, int* __restric
       return;
     }
     slot = slot + 1 == slots ? 0 : slot + 1;
-  }
-}
-
-__device__ __forceinline__ int rf_digit(int key, int shift) { return (key >> shift) & 255; }
-
-// hist[digit * nb + tile] <- elements of the tile with that digit
-__global__ __launch_bounds__(64) void rf_hist_kernel(const int* __restrict__ key, int total, int shift, int* __restrict__ hist, int nb) {
-  __shared__ int c[256];
-  const int lane = threadIdx.x;
-  for (int j = lane; j < 256; j += 64) c[j] = 0;
-  __syncthreads();
-  const long t0 = (long)blockIdx.x * RF_TILE;
-  for (int q = 0; q < RF_TILE; q += 64) {
-    const long i = t0 + q + lane;
-    if (i < total) atomicAdd(&c[rf_digit(key[i], shift)], 1);
-  }
-  __syncthreads();
-  for (int j = lane; j < 256; j += 64) hist[(long)j * nb + blockIdx.x] = c[j];
-}
-
-// hist scanned (digit-major): element i of tile b goes to hist[digit][b] + its rank among the tile's earlier elements of the
-// digit.  val == nullptr: the element is its own index (the first pass)
-__global__ __launch_bounds__(64) void rf_scatter_kernel(const int* __restrict__ key, const int* __restrict__ val, int total, int shift,
-                                                       const int* __restrict__ hist, int nb, int* __restrict__ key_out,
-                                                       int* __restrict__ val_out) {
-  __shared__ int run[256];
-  const int lane = threadIdx.x;
-  for (int j = lane; j < 256; j += 64) run[j] = hist[(long)j * nb + blockIdx.x];
-  __syncthreads();
-  const long t0 = (long)blockIdx.x * RF_TILE;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  for (int q = 0; q < RF_TILE; q += 64) {
-    const long i = t0 + q + lane;
-    const bool live = i < total;
-    const int k = live ? key[i] : 0;
-    const int dg = rf_digit(k, shift);
-    unsigned long long peers = __ballot(live);
-#pragma unroll
-    for (int bit = 0; bit < 8; ++bit) {
-      const bool on = (dg >> bit) & 1;
-      const unsigned long long m = __ballot(live && on);
-      peers &= on ? m : ~m;
-    }
-    const int ahead = __popcll(peers & below);
-    const int p = live ? run[dg] + ahead : 0;
-    __syncthreads();
-    if (live && ahead == 0) run[dg] += __popcll(peers);  // one lane per digit present in the chunk
-    __syncthreads();
-    if (live && (unsigned)p < (unsigned)total) {
-      key_out[p] = k;
-      val_out[p] = val ? val[i] : (int)i;
-    }
   }
 }
 
@@ -160,7 +106,7 @@ static size_t rf_layout(long total, char* base, RfWs* ws) {
   RfWs sizing;
   RfWs& w = ws ? *ws : sizing;
   WsCarver c{base};
-  const long slots = rf_slots(total), nb = (total + RF_TILE - 1) / RF_TILE;
+  const long slots = rf_slots(total), nb = (total + RADIX_TILE - 1) / RADIX_TILE;
   w.table = c.take<int>(slots);
   w.first = c.take<int>(slots);
   w.firstq = c.take<int>(slots);
@@ -201,17 +147,15 @@ int mused_rows_find(const double* X, long ld, long n, const double* Q, long ldq,
   RfWs k;
   rf_layout(total, (char*)ws, &k);
   const long slots = rf_slots(total);
-  const int nb = (int)cdiv(total, RF_TILE);
   RfRows a{reinterpret_cast<const unsigned long long*>(X), reinterpret_cast<const unsigned long long*>(Q), ld, ldq, (int)n, (int)total, d};
   const dim3 elems(cdiv(total, 256)), blk(256);
   MUSED_CHECK_HIP(hipMemsetAsync(k.table, 0xff, 4 * (size_t)slots, st));   // -1: a free slot
   hipLaunchKernelGGL(rf_insert_kernel, elems, blk, 0, st, a, k.table, (int)slots, k.key[0]);
   int cur = 0;
   for (int shift = 0; shift < 32 && ((slots - 1) >> shift) != 0; shift += 8) {
-    hipLaunchKernelGGL(rf_hist_kernel, dim3(nb), dim3(64), 0, st, k.key[cur], (int)total, shift, k.hist, nb);
-    hipLaunchKernelGGL(blockscan_kernel, dim3(1), dim3(BLOCKSCAN_THREADS), 0, st, k.hist, 256 * nb);
-    hipLaunchKernelGGL(rf_scatter_kernel, dim3(nb), dim3(64), 0, st, k.key[cur], shift ? k.val[cur] : (const int*)nullptr, (int)total,
-                       shift, k.hist, nb, k.key[cur ^ 1], k.val[cur ^ 1]);
+    const int rc = radix_sort_pass(k.key[cur], shift ? k.val[cur] : nullptr, (int)total, RadixCount{(int)total, nullptr}, shift,
+                                   k.hist, k.key[cur ^ 1], k.val[cur ^ 1], nullptr, nullptr, st);
+    if (rc) return rc;
     cur ^= 1;
   }
   hipLaunchKernelGGL(rf_heads_kernel, elems, blk, 0, st, k.key[cur], k.val[cur], (int)n, (int)total, k.first, k.firstq);

@@ -19,6 +19,7 @@
 // The idf table comes from the host (NumPy's log; the device never calls log).
 #include "common.h"
 #include "internal.h"
+#include "scan.h"
 
 #pragma clang fp contract(off)
 
@@ -32,23 +33,13 @@ struct TfCorpus {
   const int *rowptr, *term, *cnt, *pos, *vrank, *vrow, *gpostptr, *gpostrow, *gpostent;
 };
 
-// first position p in [lo, hi) with a[p] >= v (hi if none)
-__device__ __forceinline__ int tf_lower_bound(const int* __restrict__ a, int lo, int hi, int v) {
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(256) void tfidf_terms_kernel(TfCorpus c, int n_terms, int s, int e, int* __restrict__ df,
                                                          unsigned long long* __restrict__ key, int* __restrict__ start) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= n_terms) return;
   const int p1 = c.gpostptr[t + 1];
-  const int lo = tf_lower_bound(c.gpostrow, c.gpostptr[t], p1, s);
-  const int hi = tf_lower_bound(c.gpostrow, lo, p1, e);
+  const int lo = lower_bound(c.gpostrow, c.gpostptr[t], p1, s);
+  const int hi = lower_bound(c.gpostrow, lo, p1, e);
   df[t] = hi - lo;
   start[t] = lo;
   key[t] = hi > lo ? ((unsigned long long)(unsigned)(c.gpostrow[lo] - s) << 32) | (unsigned)c.pos[c.gpostent[lo]] : ~0ull;
@@ -62,30 +53,6 @@ __device__ __forceinline__ double tf_add_square(double s, double v) {
   return s + q;
 }
 
-// exclusive prefix sum over the workgroup of 1024 (cs_excl_scan of meta_stream.hip on 64-bit words)
-__device__ __forceinline__ unsigned long long tf_excl_scan(unsigned long long v, unsigned long long* ws,
-                                                          unsigned long long& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  unsigned long long x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) ws[w] = x;
-  __syncthreads();
-  unsigned long long base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < TF_SCAN_THREADS / 64; ++i) {
-    const unsigned long long c = ws[i];
-    base += (i < w) ? c : 0;
-    tot += c;
-  }
-  total = tot;
-  __syncthreads();
-  return base + x - v;
-}
-
 // df < 2^31 summed and at most 2^31 flags: the two sums share a 64-bit word without a carry between them
 __global__ __launch_bounds__(TF_SCAN_THREADS) void tfidf_scan_kernel(const int* __restrict__ df, int n_terms,
                                                                     int* __restrict__ postptr, int* __restrict__ colid,
@@ -96,7 +63,7 @@ __global__ __launch_bounds__(TF_SCAN_THREADS) void tfidf_scan_kernel(const int* 
     const int t = base + threadIdx.x;
     const int d = t < n_terms ? df[t] : 0;
     unsigned long long total;
-    const unsigned long long x = carry + tf_excl_scan(((unsigned long long)d << 32) | (d > 0 ? 1u : 0u), ws, total);
+    const unsigned long long x = carry + block_excl_scan(((unsigned long long)d << 32) | (d > 0 ? 1u : 0u), ws, total);
     if (t < n_terms) {
       postptr[t] = (int)(x >> 32);
       colid[t] = (int)(x & 0xffffffffu);
@@ -175,7 +142,7 @@ __global__ __launch_bounds__(64) void tfidf_rows_kernel(TfCorpus c, int s, int e
   for (int i = lane; i < L; i += 64) {
     const int t = c.term[a0 + i];
     const int st = start[t], d = df[t];
-    const int q = tf_lower_bound(c.gpostrow, st, st + d, row) - st;
+    const int q = lower_bound(c.gpostrow, st, st + d, row) - st;
     const int slot = postptr[t] + q;
     if (q < d && slot < nnz_w) {
       out_postrow[slot] = r;

@@ -26,9 +26,8 @@
 //              between): (term << 32 | position) of its tokens to LDS, bitonic sort; equal terms collapse to one entry: cnt =
 //              run length, first position = the run's smallest; pos = rank of the first position among the entries
 //              (a second sort, of first position << 16 | entry)
-//     postings stable LSD radix sort of the entries by term, 8 bits a pass (histogram per tile of 1024, one exclusive scan
-//              of the digit-major table, scatter in tile order -- one wave per tile, ranks inside a chunk of 64 from
-//              ballots): entries are row-major, so rows ascend inside a term.  gpostptr[t] = first sorted entry >= t.
+//     postings stable LSD radix sort of the entries by term, 8 bits a pass (radix_sort.h; the last pass also gathers the
+//              entries' rows): entries are row-major, so rows ascend inside a term.  gpostptr[t] = first sorted entry >= t.
 // No float anywhere and no result that depends on arrival order: two calls on the same input give identical bytes.
 //
 // Text that is not pure ASCII takes the same steps on CODE POINTS (mused_tokenise_cp_scan / _cp_build; the rule:
@@ -46,14 +45,13 @@
 // Two tokens may touch ("aİbİ" holds "ai" and "bi"), so a buffer of n code points holds up to n / 2 tokens.
 #include "common.h"
 #include "internal.h"
+#include "radix_sort.h"
 
 namespace mused {
 
 constexpr int TK_MAX_DOC_TOKENS = 8192;  // keys (8 B), second keys (4 B), run heads (4 B) of one document in LDS: 128 KiB + 80 B
 constexpr int TK_SCAN_THREADS = 256;
 constexpr int TK_SCAN_TILE = TK_SCAN_THREADS * 16;  // bytes per workgroup of the scan
-constexpr int TK_BLOCKSCAN_THREADS = 1024;
-constexpr int TK_RADIX_TILE = 1024;  // entries per wave of the radix passes
 constexpr int TK_FLAG_DOC = 1;       // a document holds more tokens than the caller's cap
 constexpr int TK_FLAG_TABLE = 2;     // more tokens than table slots: nothing was inserted
 constexpr int TK_FLAG_STATE = 4;     // the workspace is not what mused_tokenise_scan left (ids or slices out of range)
@@ -63,39 +61,6 @@ __device__ __forceinline__ bool tk_is_word(unsigned c) {
   return (c - '0' < 10u) | ((c | 32u) - 'a' < 26u) | (c == '_');
 }
 __device__ __forceinline__ unsigned char tk_lower(unsigned c) { return (unsigned char)(c - 'A' < 26u ? c + 32u : c); }
-
-// exclusive prefix sum over the workgroup (any multiple of 64 threads up to 1024); ws: 16 ints of LDS
-__device__ __forceinline__ int tk_excl_scan(int v, int* ws, int& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) ws[w] = x;
-  __syncthreads();
-  int base = 0, tot = 0;
-  for (int i = 0; i < nw; ++i) {
-    const int c = ws[i];
-    base += (i < w) ? c : 0;
-    tot += c;
-  }
-  total = tot;
-  __syncthreads();
-  return base + x - v;
-}
-
-// first position p in [0, n) with a[p] >= v (n if none)
-__device__ __forceinline__ int tk_lower_bound(const int* __restrict__ a, int n, int v) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // WRITE = false: lower-cased bytes -> low, token starts per block -> blk[block]
 // WRITE = true:  blk holds the exclusive scan of those counts; tok_start / tok_len in text order (reads `low`)
@@ -137,7 +102,7 @@ __global__ __launch_bounds__(TK_SCAN_THREADS) void tk_scan_kernel(const unsigned
     }
   }
   int total;
-  const int before = tk_excl_scan(mine, ws, total);
+  const int before = block_excl_scan(mine, ws, total);
   if (!WRITE) {
     if (threadIdx.x == 0) blk[blockIdx.x] = total;
     return;
@@ -157,27 +122,12 @@ __global__ __launch_bounds__(TK_SCAN_THREADS) void tk_scan_kernel(const unsigned
   }
 }
 
-// one workgroup: a[0 .. m) <- its exclusive prefix sums, *total <- the sum
-__global__ __launch_bounds__(TK_BLOCKSCAN_THREADS) void tk_blockscan_kernel(int* __restrict__ a, int m, int* __restrict__ total) {
-  __shared__ int ws[16];
-  int carry = 0;
-  for (int base = 0; base < m; base += TK_BLOCKSCAN_THREADS) {
-    const int i = base + threadIdx.x;
-    const int v = i < m ? a[i] : 0;
-    int tot;
-    const int x = carry + tk_excl_scan(v, ws, tot);
-    if (i < m) a[i] = x;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) *total = carry;
-}
-
 __global__ __launch_bounds__(256) void tk_docs_kernel(const int* __restrict__ docptr, int n_docs, const int* __restrict__ tok_start,
                                                      int max_doc_tokens, int* __restrict__ info) {
   const int d = blockIdx.x * 256 + threadIdx.x;
   const int T = info[0];
   int nt = 0;
-  if (d < n_docs) nt = tk_lower_bound(tok_start, T, docptr[d + 1]) - tk_lower_bound(tok_start, T, docptr[d]);
+  if (d < n_docs) nt = lower_bound(tok_start, 0, T, docptr[d + 1]) - lower_bound(tok_start, 0, T, docptr[d]);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) nt = max(nt, __shfl_xor(nt, o));
   if ((threadIdx.x & 63) == 0) {
@@ -283,7 +233,7 @@ __global__ __launch_bounds__(TK_SCAN_THREADS) void tk_cp_scan_kernel(const unsig
   const unsigned starts = ((cbits >> 1) & ~cbits & (wbits >> 2)) & ((1u << P) - 1u);
   const int mine = __popc(starts);
   int total;
-  const int before = tk_excl_scan(mine, ws, total);
+  const int before = block_excl_scan(mine, ws, total);
   if (!WRITE) {
     if (threadIdx.x == 0) blk[blockIdx.x] = total;
     return;
@@ -346,7 +296,7 @@ __global__ __launch_bounds__(256) void tk_compact_kernel(int* __restrict__ table
   const long slot = (long)blockIdx.x * 256 + threadIdx.x;
   const int t = slot < slots ? table[slot] : -1;
   int total;
-  const int before = tk_excl_scan(t >= 0 ? 1 : 0, ws, total);
+  const int before = block_excl_scan(t >= 0 ? 1 : 0, ws, total);
   if (!WRITE) {
     if (threadIdx.x == 0) blk[blockIdx.x] = total;
     return;
@@ -394,8 +344,8 @@ __global__ __launch_bounds__(256) void tk_rows_kernel(TkRows a, int* __restrict_
   unsigned* k2 = reinterpret_cast<unsigned*>(keys + n);    // [n]
   int* ws = reinterpret_cast<int*>(k2 + n);                // [16]
   int* hidx = ws + 16;                                     // [n + 1]
-  const int t0 = tk_lower_bound(a.tok_start, a.T, a.docptr[d]);
-  const int nt = tk_lower_bound(a.tok_start, a.T, a.docptr[d + 1]) - t0;
+  const int t0 = lower_bound(a.tok_start, 0, a.T, a.docptr[d]);
+  const int nt = lower_bound(a.tok_start, 0, a.T, a.docptr[d + 1]) - t0;
   if (nt < 0 || nt > n) {  // uniform over the workgroup
     if (tid == 0) {
       atomicOr(&info[2], TK_FLAG_STATE);
@@ -425,7 +375,7 @@ __global__ __launch_bounds__(256) void tk_rows_kernel(TkRows a, int* __restrict_
     const int i = base + tid;
     const bool head = i < nt && (i == 0 || (unsigned)(keys[i] >> 32) != (unsigned)(keys[i - 1] >> 32));
     int tot;
-    const int e = L + tk_excl_scan(head ? 1 : 0, ws, tot);
+    const int e = L + block_excl_scan(head ? 1 : 0, ws, tot);
     if (head) hidx[e] = i;
     L += tot;
   }
@@ -453,118 +403,58 @@ __global__ __launch_bounds__(256) void tk_rows_kernel(TkRows a, int* __restrict_
   for (int r = tid; r < L; r += bd) pos[o0 + (k2[r] & 0xffffu)] = r;
 }
 
-__device__ __forceinline__ int tk_digit(int key, int shift) { return (key >> shift) & 255; }
-
-// hist[digit * nb + tile] <- entries of the tile with that digit
-__global__ __launch_bounds__(64) void tk_radix_hist_kernel(const int* __restrict__ key, const int* __restrict__ nnz_p, int shift,
-                                                          int* __restrict__ hist, int nb) {
-  __shared__ int c[256];
-  const int lane = threadIdx.x, nnz = *nnz_p;
-  for (int j = lane; j < 256; j += 64) c[j] = 0;
-  __syncthreads();
-  const long t0 = (long)blockIdx.x * TK_RADIX_TILE;
-  for (int q = 0; q < TK_RADIX_TILE; q += 64) {
-    const long i = t0 + q + lane;
-    if (i < nnz) atomicAdd(&c[tk_digit(key[i], shift)], 1);
-  }
-  __syncthreads();
-  for (int j = lane; j < 256; j += 64) hist[(long)j * nb + blockIdx.x] = c[j];
-}
-
-// hist scanned (digit-major): entry i of tile b goes to hist[digit][b] + its rank among the tile's earlier entries of the digit
-__global__ __launch_bounds__(64) void tk_radix_scatter_kernel(const int* __restrict__ key, const int* __restrict__ val,
-                                                             const int* __restrict__ nnz_p, int shift,
-                                                             const int* __restrict__ hist, int nb, int* __restrict__ key_out,
-                                                             int* __restrict__ val_out, const int* __restrict__ ent_row,
-                                                             int* __restrict__ row_out) {
-  __shared__ int run[256];
-  const int lane = threadIdx.x, nnz = *nnz_p;
-  for (int j = lane; j < 256; j += 64) run[j] = hist[(long)j * nb + blockIdx.x];
-  __syncthreads();
-  const long t0 = (long)blockIdx.x * TK_RADIX_TILE;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  for (int q = 0; q < TK_RADIX_TILE; q += 64) {
-    const long i = t0 + q + lane;
-    const bool live = i < nnz;
-    const int k = live ? key[i] : 0;
-    const int dg = tk_digit(k, shift);
-    unsigned long long peers = __ballot(live);
-#pragma unroll
-    for (int bit = 0; bit < 8; ++bit) {
-      const bool on = (dg >> bit) & 1;
-      const unsigned long long m = __ballot(live && on);
-      peers &= on ? m : ~m;
-    }
-    const int ahead = __popcll(peers & below);
-    const int p = live ? run[dg] + ahead : 0;
-    __syncthreads();
-    if (live && ahead == 0) run[dg] += __popcll(peers);  // one lane per digit present in the chunk
-    __syncthreads();
-    if (live && (unsigned)p < (unsigned)nnz) {
-      const int v = val ? val[i] : (int)i;
-      key_out[p] = k;
-      val_out[p] = v;
-      if (row_out) row_out[p] = ent_row[v];
-    }
-  }
-}
-
 __global__ __launch_bounds__(256) void tk_postptr_kernel(const int* __restrict__ sorted_key, const int* __restrict__ nnz_p, int V,
                                                         int* __restrict__ gpostptr) {
   const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t <= V) gpostptr[t] = tk_lower_bound(sorted_key, *nnz_p, t);
+  if (t <= V) gpostptr[t] = lower_bound(sorted_key, 0, *nnz_p, t);
 }
 
-static long tk_align(long b) { return (b + 15) / 16 * 16; }
-
-struct TkLayout {
-  long tok_cap, nb_scan, nb_tab, nb_radix;
-  long low, docptr, blk, tok_start, tok_len, tok_slot, table, blk2, ent_row, ka, va, kb, vb, hist, scratch, bytes;
+// the workspace both calls carve alike: the build reads what the scan left
+struct TkWs {
+  long tok_cap, nb_scan, nb_tab, bytes;
+  unsigned char* low;  // bytes: the lower-cased text ...
+  unsigned* low_cp;    // ... code points: the class-table entries
+  int *docptr, *blk, *tok_start, *tok_len, *tok_slot, *table, *blk2, *ent_row, *key[2], *val[2], *hist;
 };
 
 static long tk_default_slots(long n_bytes) { return 2 * (n_bytes / 3 + 1); }
 
-// n elements of `elem` bytes, at most tok_cap tokens, `tile` elements per workgroup of the scan
-static TkLayout tk_layout_of(long n, long n_docs, long slots, long elem, long tok_cap, long tile) {
-  TkLayout l;
+// n elements (code points if `cp`, else bytes), at most tok_cap tokens, `tile` elements per workgroup of the scan.  A null
+// base only sizes
+static TkWs tk_layout_of(long n, long n_docs, long slots, bool cp, long tok_cap, long tile, void* base) {
+  TkWs l{};
+  WsCarver c{static_cast<char*>(base)};
   l.tok_cap = tok_cap;
   l.nb_scan = (n + tile - 1) / tile;
   l.nb_tab = (slots + 255) / 256;
-  l.nb_radix = (l.tok_cap + TK_RADIX_TILE - 1) / TK_RADIX_TILE;
-  long o = 0;
-  auto take = [&](long bytes) {
-    const long at = o;
-    o += tk_align(bytes);
-    return at;
-  };
-  l.low = take(elem * n);
-  l.docptr = take(4 * (n_docs + 1));
-  l.blk = take(4 * l.nb_scan);
-  l.tok_start = take(4 * l.tok_cap);
-  l.tok_len = take(4 * l.tok_cap);
-  l.tok_slot = take(4 * l.tok_cap);
-  l.table = take(4 * slots);
-  l.blk2 = take(4 * l.nb_tab);
-  l.ent_row = take(4 * l.tok_cap);
-  l.ka = take(4 * l.tok_cap);
-  l.va = take(4 * l.tok_cap);
-  l.kb = take(4 * l.tok_cap);
-  l.vb = take(4 * l.tok_cap);
-  l.hist = take(4 * 256 * l.nb_radix);
-  l.scratch = take(16);
-  l.bytes = o;
+  if (cp) l.low_cp = c.take<unsigned>(n);
+  else l.low = c.take<unsigned char>(n);
+  l.docptr = c.take<int>(n_docs + 1);
+  l.blk = c.take<int>(l.nb_scan);
+  l.tok_start = c.take<int>(tok_cap);
+  l.tok_len = c.take<int>(tok_cap);
+  l.tok_slot = c.take<int>(tok_cap);
+  l.table = c.take<int>(slots);
+  l.blk2 = c.take<int>(l.nb_tab);
+  l.ent_row = c.take<int>(tok_cap);
+  for (int i = 0; i < 2; ++i) {
+    l.key[i] = c.take<int>(tok_cap);
+    l.val[i] = c.take<int>(tok_cap);
+  }
+  l.hist = c.take<int>(256 * (size_t)cdiv(tok_cap, RADIX_TILE));
+  l.bytes = (long)c.off;
   return l;
 }
 
 // a token is two word bytes or more and a non-word byte (or the end of the buffer) behind them
-static TkLayout tk_layout(long n_bytes, long n_docs, long slots) {
-  return tk_layout_of(n_bytes, n_docs, slots, 1, n_bytes / 3 + 1, TK_SCAN_TILE);
+static TkWs tk_layout(long n_bytes, long n_docs, long slots, void* base) {
+  return tk_layout_of(n_bytes, n_docs, slots, false, n_bytes / 3 + 1, TK_SCAN_TILE, base);
 }
 
 // code points: two tokens may touch, so a token is two elements or more and nothing else
 static long tk_cp_default_slots(long n_cp) { return 2 * (n_cp / 2 + 1); }
-static TkLayout tk_cp_layout(long n_cp, long n_docs, long slots) {
-  return tk_layout_of(n_cp, n_docs, slots, 4, n_cp / 2 + 1, TK_CP_TILE);
+static TkWs tk_cp_layout(long n_cp, long n_docs, long slots, void* base) {
+  return tk_layout_of(n_cp, n_docs, slots, true, n_cp / 2 + 1, TK_CP_TILE, base);
 }
 // below 2^30 code points every element offset, token count and block count is an int and the workspace stays below 2^36 bytes
 static bool tk_cp_sizes_ok(long n_cp, long n_docs, long slots) {
@@ -575,44 +465,38 @@ static bool tk_sizes_ok(long n_bytes, long n_docs, long slots) {
   return n_bytes >= 1 && n_bytes < (1l << 31) && n_docs >= 1 && n_docs <= n_bytes && slots >= 1 && slots < (1l << 31);
 }
 
-static size_t tk_rows_lds(int n) { return (size_t)tk_align(8l * n + 4l * n + 4 * 16 + 4l * (n + 1)); }
+static size_t tk_rows_lds(int n) { return (size_t)(8l * n + 4l * n + 4 * 16 + 4l * (n + 1) + 15) / 16 * 16; }
 
 // what follows the scan on either kind of element: docs, insert, compact (the vocabulary's spans and provisional ids)
-static int tk_vocab_launch(const TkLayout& l, char* w, bool cp, long n_docs, long slots, int max_doc_tokens, int* voc_start,
-                           int* voc_len, long voc_cap, int* info, hipStream_t st) {
-  int* docptr = reinterpret_cast<int*>(w + l.docptr);
-  int* tok_start = reinterpret_cast<int*>(w + l.tok_start);
-  int* tok_len = reinterpret_cast<int*>(w + l.tok_len);
-  int* tok_slot = reinterpret_cast<int*>(w + l.tok_slot);
-  int* table = reinterpret_cast<int*>(w + l.table);
-  int* blk2 = reinterpret_cast<int*>(w + l.blk2);
-  hipLaunchKernelGGL(tk_docs_kernel, dim3(cdiv(n_docs, 256)), dim3(256), 0, st, docptr, (int)n_docs, tok_start, max_doc_tokens,
-                     info);
+static int tk_vocab_launch(const TkWs& l, long n_docs, long slots, int max_doc_tokens, int* voc_start, int* voc_len,
+                           long voc_cap, int* info, hipStream_t st) {
+  hipLaunchKernelGGL(tk_docs_kernel, dim3(cdiv(n_docs, 256)), dim3(256), 0, st, l.docptr, (int)n_docs, l.tok_start,
+                     max_doc_tokens, info);
   MUSED_LAUNCH_CHECK();
-  if (cp)
-    hipLaunchKernelGGL(tk_cp_insert_kernel, dim3(cdiv(l.tok_cap, 256)), dim3(256), 0, st, reinterpret_cast<const unsigned*>(w + l.low),
-                       tok_start, tok_len, table, (int)slots, tok_slot, info);
+  if (l.low_cp)
+    hipLaunchKernelGGL(tk_cp_insert_kernel, dim3(cdiv(l.tok_cap, 256)), dim3(256), 0, st, l.low_cp, l.tok_start, l.tok_len,
+                       l.table, (int)slots, l.tok_slot, info);
   else
-    hipLaunchKernelGGL(tk_insert_kernel, dim3(cdiv(l.tok_cap, 256)), dim3(256), 0, st,
-                       reinterpret_cast<const unsigned char*>(w + l.low), tok_start, tok_len, table, (int)slots, tok_slot, info);
+    hipLaunchKernelGGL(tk_insert_kernel, dim3(cdiv(l.tok_cap, 256)), dim3(256), 0, st, l.low, l.tok_start, l.tok_len, l.table,
+                       (int)slots, l.tok_slot, info);
   MUSED_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tk_compact_kernel<false>, dim3((unsigned)l.nb_tab), dim3(256), 0, st, table, (int)slots, blk2, tok_start,
-                     tok_len, voc_start, voc_len, (int)(voc_cap < (1l << 31) ? voc_cap : (1l << 31) - 1));
+  const int cap = (int)(voc_cap < (1l << 31) ? voc_cap : (1l << 31) - 1);
+  hipLaunchKernelGGL(tk_compact_kernel<false>, dim3((unsigned)l.nb_tab), dim3(256), 0, st, l.table, (int)slots, l.blk2,
+                     l.tok_start, l.tok_len, voc_start, voc_len, cap);
   MUSED_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tk_blockscan_kernel, dim3(1), dim3(TK_BLOCKSCAN_THREADS), 0, st, blk2, (int)l.nb_tab, info + 1);
+  hipLaunchKernelGGL(blockscan_kernel, dim3(1), dim3(BLOCKSCAN_THREADS), 0, st, l.blk2, (int)l.nb_tab, info + 1);
   MUSED_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tk_compact_kernel<true>, dim3((unsigned)l.nb_tab), dim3(256), 0, st, table, (int)slots, blk2, tok_start,
-                     tok_len, voc_start, voc_len, (int)(voc_cap < (1l << 31) ? voc_cap : (1l << 31) - 1));
+  hipLaunchKernelGGL(tk_compact_kernel<true>, dim3((unsigned)l.nb_tab), dim3(256), 0, st, l.table, (int)slots, l.blk2,
+                     l.tok_start, l.tok_len, voc_start, voc_len, cap);
   MUSED_LAUNCH_CHECK();
   return MUSED_OK;
 }
 
 // rows and postings: nothing here reads text, so bytes and code points share it
-static int tk_build_launch(const TkLayout& l, long n_docs, long slots, int n_tokens, int n_terms, int doc_tokens, const int* rank,
+static int tk_build_launch(const TkWs& l, long n_docs, long slots, int n_tokens, int n_terms, int doc_tokens, const int* rank,
                            const int* vrow, int* doc_rowptr, int* term, int* cnt, int* pos, int* gpostptr, int* gpostrow,
-                           int* gpostent, int* info, void* ws, void* stream) {
+                           int* gpostent, int* info, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  char* w = reinterpret_cast<char*>(ws);
   int n = 1;
   while (n < doc_tokens) n <<= 1;
   const size_t lds = tk_rows_lds(n);
@@ -626,45 +510,33 @@ static int tk_build_launch(const TkLayout& l, long n_docs, long slots, int n_tok
       aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(tk_rows_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
   });
   MUSED_CHECK_HIP(aerr);
-  TkRows a{reinterpret_cast<int*>(w + l.docptr), reinterpret_cast<int*>(w + l.tok_start), reinterpret_cast<int*>(w + l.tok_slot),
-           reinterpret_cast<int*>(w + l.table), rank, vrow, (int)n_docs, n_tokens, n_terms, (int)slots, n};
-  int* ent_row = reinterpret_cast<int*>(w + l.ent_row);
-  int* hist = reinterpret_cast<int*>(w + l.hist);
-  int* scratch = reinterpret_cast<int*>(w + l.scratch);
+  TkRows a{l.docptr, l.tok_start, l.tok_slot, l.table, rank, vrow, (int)n_docs, n_tokens, n_terms, (int)slots, n};
   const int threads = n / 2 < 64 ? 64 : (n / 2 > 256 ? 256 : n / 2);
   hipLaunchKernelGGL(tk_rows_kernel<false>, dim3((unsigned)n_docs), dim3(threads), lds, st, a, doc_rowptr, doc_rowptr, term, cnt,
-                     pos, ent_row, info);
+                     pos, l.ent_row, info);
   MUSED_LAUNCH_CHECK();
   // doc_rowptr[n_docs] <- the sum: the scan's total lands where the exclusive scan of n_docs + 1 counts would put it
-  hipLaunchKernelGGL(tk_blockscan_kernel, dim3(1), dim3(TK_BLOCKSCAN_THREADS), 0, st, doc_rowptr, (int)n_docs, doc_rowptr + n_docs);
+  hipLaunchKernelGGL(blockscan_kernel, dim3(1), dim3(BLOCKSCAN_THREADS), 0, st, doc_rowptr, (int)n_docs, doc_rowptr + n_docs);
   MUSED_LAUNCH_CHECK();
   hipLaunchKernelGGL(tk_rows_kernel<true>, dim3((unsigned)n_docs), dim3(threads), lds, st, a, doc_rowptr, doc_rowptr, term, cnt,
-                     pos, ent_row, info);
+                     pos, l.ent_row, info);
   MUSED_LAUNCH_CHECK();
-  const int* nnz_p = doc_rowptr + n_docs;  // at most n_tokens: the grids below cover that many
-  const int nb = cdiv(n_tokens, TK_RADIX_TILE);
+  const RadixCount nnz{0, doc_rowptr + n_docs};  // at most n_tokens: the grids cover that many
   int bits = 0;
   while (bits < 24 && (1 << bits) < n_terms) ++bits;
   const int passes = bits <= 8 ? 1 : (bits <= 16 ? 2 : 3);
-  int* kbuf[2] = {reinterpret_cast<int*>(w + l.ka), reinterpret_cast<int*>(w + l.kb)};
-  int* vbuf[2] = {reinterpret_cast<int*>(w + l.va), reinterpret_cast<int*>(w + l.vb)};
   const int* kin = term;
   const int* vin = nullptr;
   for (int p = 0; p < passes; ++p) {
-    const bool last = p == passes - 1;
-    int* kout = kbuf[p & 1];
-    int* vout = last ? gpostent : vbuf[p & 1];
-    hipLaunchKernelGGL(tk_radix_hist_kernel, dim3(nb), dim3(64), 0, st, kin, nnz_p, 8 * p, hist, nb);
-    MUSED_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tk_blockscan_kernel, dim3(1), dim3(TK_BLOCKSCAN_THREADS), 0, st, hist, 256 * nb, scratch);
-    MUSED_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tk_radix_scatter_kernel, dim3(nb), dim3(64), 0, st, kin, vin, nnz_p, 8 * p, hist, nb, kout, vout, ent_row,
-                       last ? gpostrow : (int*)nullptr);
-    MUSED_LAUNCH_CHECK();
-    kin = kout;
+    const bool last = p == passes - 1;  // the last pass also gathers the entries' rows
+    int* vout = last ? gpostent : l.val[p & 1];
+    const int rc = radix_sort_pass(kin, vin, n_tokens, nnz, 8 * p, l.hist, l.key[p & 1], vout, last ? l.ent_row : nullptr,
+                                   last ? gpostrow : nullptr, st);
+    if (rc) return rc;
+    kin = l.key[p & 1];
     vin = vout;
   }
-  hipLaunchKernelGGL(tk_postptr_kernel, dim3(cdiv((long)n_terms + 1, 256)), dim3(256), 0, st, kin, nnz_p, n_terms, gpostptr);
+  hipLaunchKernelGGL(tk_postptr_kernel, dim3(cdiv((long)n_terms + 1, 256)), dim3(256), 0, st, kin, nnz.ptr, n_terms, gpostptr);
   MUSED_LAUNCH_CHECK();
   return MUSED_OK;
 }
@@ -677,7 +549,7 @@ extern "C" {
 
 long mused_tokenise_ws_bytes(long n_bytes, long n_docs, long table_slots) {
   const long slots = table_slots == 0 && n_bytes >= 1 ? tk_default_slots(n_bytes) : table_slots;
-  return tk_sizes_ok(n_bytes, n_docs, slots) ? tk_layout(n_bytes, n_docs, slots).bytes : -1;
+  return tk_sizes_ok(n_bytes, n_docs, slots) ? tk_layout(n_bytes, n_docs, slots, nullptr).bytes : -1;
 }
 
 int mused_tokenise_scan(const unsigned char* buf, long n_bytes, const int* docptr_host, long n_docs, long table_slots,
@@ -698,31 +570,24 @@ int mused_tokenise_scan(const unsigned char* buf, long n_bytes, const int* docpt
   MUSED_REQUIRE(max_doc_tokens >= 1 && max_doc_tokens <= TK_MAX_DOC_TOKENS,
                 "mused_tokenise_scan: max_doc_tokens=%d outside [1, %d] (one document is sorted in LDS)", max_doc_tokens,
                 TK_MAX_DOC_TOKENS);
-  const TkLayout l = tk_layout(n_bytes, n_docs, slots);
+  const TkWs l = tk_layout(n_bytes, n_docs, slots, ws);
   MUSED_REQUIRE(voc_cap >= 1, "mused_tokenise_scan: voc_cap=%ld", voc_cap);
   MUSED_REQUIRE(ws && ws_bytes >= l.bytes && ((uintptr_t)ws & 15) == 0,
                 "mused_tokenise_scan: workspace of %ld bytes, need %ld (16-byte aligned)", ws_bytes, l.bytes);
   hipStream_t st = (hipStream_t)stream;
-  char* w = reinterpret_cast<char*>(ws);
-  unsigned char* low = reinterpret_cast<unsigned char*>(w + l.low);
-  int* docptr = reinterpret_cast<int*>(w + l.docptr);
-  int* blk = reinterpret_cast<int*>(w + l.blk);
-  int* tok_start = reinterpret_cast<int*>(w + l.tok_start);
-  int* tok_len = reinterpret_cast<int*>(w + l.tok_len);
-  int* table = reinterpret_cast<int*>(w + l.table);
   MUSED_CHECK_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int), st));
-  MUSED_CHECK_HIP(hipMemsetAsync(table, 0xff, (size_t)slots * sizeof(int), st));
-  MUSED_CHECK_HIP(hipMemcpyAsync(docptr, docptr_host, (size_t)(n_docs + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+  MUSED_CHECK_HIP(hipMemsetAsync(l.table, 0xff, (size_t)slots * sizeof(int), st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(l.docptr, docptr_host, (size_t)(n_docs + 1) * sizeof(int), hipMemcpyHostToDevice, st));
   const int cap = (int)l.tok_cap;
-  hipLaunchKernelGGL(tk_scan_kernel<false>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, buf, n_bytes, low, blk,
-                     tok_start, tok_len, cap);
+  hipLaunchKernelGGL(tk_scan_kernel<false>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, buf, n_bytes, l.low, l.blk,
+                     l.tok_start, l.tok_len, cap);
   MUSED_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tk_blockscan_kernel, dim3(1), dim3(TK_BLOCKSCAN_THREADS), 0, st, blk, (int)l.nb_scan, info + 0);
+  hipLaunchKernelGGL(blockscan_kernel, dim3(1), dim3(BLOCKSCAN_THREADS), 0, st, l.blk, (int)l.nb_scan, info + 0);
   MUSED_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tk_scan_kernel<true>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, low, n_bytes, low, blk,
-                     tok_start, tok_len, cap);
+  hipLaunchKernelGGL(tk_scan_kernel<true>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, l.low, n_bytes, l.low, l.blk,
+                     l.tok_start, l.tok_len, cap);
   MUSED_LAUNCH_CHECK();
-  return tk_vocab_launch(l, w, false, n_docs, slots, max_doc_tokens, voc_start, voc_len, voc_cap, info, st);
+  return tk_vocab_launch(l, n_docs, slots, max_doc_tokens, voc_start, voc_len, voc_cap, info, st);
 }
 
 int mused_tokenise_build(long n_bytes, long n_docs, long table_slots, int n_tokens, int n_terms, int doc_tokens,
@@ -732,7 +597,7 @@ int mused_tokenise_build(long n_bytes, long n_docs, long table_slots, int n_toke
   MUSED_REQUIRE(tk_sizes_ok(n_bytes, n_docs, slots),
                 "mused_tokenise_build: bad sizes (bytes=%ld in [1, 2^31), docs=%ld in [1, bytes], table slots=%ld in [1, 2^31))",
                 n_bytes, n_docs, table_slots);
-  const TkLayout l = tk_layout(n_bytes, n_docs, slots);
+  const TkWs l = tk_layout(n_bytes, n_docs, slots, ws);
   MUSED_REQUIRE(n_tokens >= 1 && n_tokens <= l.tok_cap && n_tokens <= slots && n_terms >= 1 && n_terms <= n_tokens &&
                     n_terms < (1 << 24),
                 "mused_tokenise_build: %d tokens (at most %ld and the table's %ld slots), %d terms (at most 2^24 - 1: three "
@@ -744,12 +609,12 @@ int mused_tokenise_build(long n_bytes, long n_docs, long table_slots, int n_toke
   MUSED_REQUIRE(ws && ws_bytes >= l.bytes && ((uintptr_t)ws & 15) == 0,
                 "mused_tokenise_build: workspace of %ld bytes, need %ld (16-byte aligned)", ws_bytes, l.bytes);
   return tk_build_launch(l, n_docs, slots, n_tokens, n_terms, doc_tokens, rank, vrow, doc_rowptr, term, cnt, pos, gpostptr, gpostrow,
-                         gpostent, info, ws, stream);
+                         gpostent, info, stream);
 }
 
 long mused_tokenise_cp_ws_bytes(long n_cp, long n_docs, long table_slots) {
   const long slots = table_slots == 0 && n_cp >= 1 ? tk_cp_default_slots(n_cp) : table_slots;
-  return tk_cp_sizes_ok(n_cp, n_docs, slots) ? tk_cp_layout(n_cp, n_docs, slots).bytes : -1;
+  return tk_cp_sizes_ok(n_cp, n_docs, slots) ? tk_cp_layout(n_cp, n_docs, slots, nullptr).bytes : -1;
 }
 
 int mused_tokenise_cp_scan(const unsigned* buf, long n_cp, const unsigned* cls, long n_cls, const int* docptr_host, long n_docs,
@@ -772,30 +637,24 @@ int mused_tokenise_cp_scan(const unsigned* buf, long n_cp, const unsigned* cls, 
   MUSED_REQUIRE(max_doc_tokens >= 1 && max_doc_tokens <= TK_MAX_DOC_TOKENS,
                 "mused_tokenise_cp_scan: max_doc_tokens=%d outside [1, %d] (one document is sorted in LDS)", max_doc_tokens,
                 TK_MAX_DOC_TOKENS);
-  const TkLayout l = tk_cp_layout(n_cp, n_docs, slots);
+  const TkWs l = tk_cp_layout(n_cp, n_docs, slots, ws);
   MUSED_REQUIRE(voc_cap >= 1, "mused_tokenise_cp_scan: voc_cap=%ld", voc_cap);
   MUSED_REQUIRE(ws && ws_bytes >= l.bytes && ((uintptr_t)ws & 15) == 0,
                 "mused_tokenise_cp_scan: workspace of %ld bytes, need %ld (16-byte aligned)", ws_bytes, l.bytes);
   hipStream_t st = (hipStream_t)stream;
-  char* w = reinterpret_cast<char*>(ws);
-  unsigned* low = reinterpret_cast<unsigned*>(w + l.low);
-  int* docptr = reinterpret_cast<int*>(w + l.docptr);
-  int* blk = reinterpret_cast<int*>(w + l.blk);
-  int* tok_start = reinterpret_cast<int*>(w + l.tok_start);
-  int* tok_len = reinterpret_cast<int*>(w + l.tok_len);
   MUSED_CHECK_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int), st));
-  MUSED_CHECK_HIP(hipMemsetAsync(w + l.table, 0xff, (size_t)slots * sizeof(int), st));
-  MUSED_CHECK_HIP(hipMemcpyAsync(docptr, docptr_host, (size_t)(n_docs + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+  MUSED_CHECK_HIP(hipMemsetAsync(l.table, 0xff, (size_t)slots * sizeof(int), st));
+  MUSED_CHECK_HIP(hipMemcpyAsync(l.docptr, docptr_host, (size_t)(n_docs + 1) * sizeof(int), hipMemcpyHostToDevice, st));
   const int cap = (int)l.tok_cap;
   hipLaunchKernelGGL(tk_cp_scan_kernel<false>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, buf, n_cp, cls,
-                     (unsigned)n_cls, low, blk, tok_start, tok_len, cap);
+                     (unsigned)n_cls, l.low_cp, l.blk, l.tok_start, l.tok_len, cap);
   MUSED_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tk_blockscan_kernel, dim3(1), dim3(TK_BLOCKSCAN_THREADS), 0, st, blk, (int)l.nb_scan, info + 0);
+  hipLaunchKernelGGL(blockscan_kernel, dim3(1), dim3(BLOCKSCAN_THREADS), 0, st, l.blk, (int)l.nb_scan, info + 0);
   MUSED_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tk_cp_scan_kernel<true>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, low, n_cp, cls,
-                     (unsigned)n_cls, low, blk, tok_start, tok_len, cap);
+  hipLaunchKernelGGL(tk_cp_scan_kernel<true>, dim3((unsigned)l.nb_scan), dim3(TK_SCAN_THREADS), 0, st, l.low_cp, n_cp, cls,
+                     (unsigned)n_cls, l.low_cp, l.blk, l.tok_start, l.tok_len, cap);
   MUSED_LAUNCH_CHECK();
-  return tk_vocab_launch(l, w, true, n_docs, slots, max_doc_tokens, voc_start, voc_len, voc_cap, info, st);
+  return tk_vocab_launch(l, n_docs, slots, max_doc_tokens, voc_start, voc_len, voc_cap, info, st);
 }
 
 int mused_tokenise_cp_build(long n_cp, long n_docs, long table_slots, int n_tokens, int n_terms, int doc_tokens, const int* rank,
@@ -805,7 +664,7 @@ int mused_tokenise_cp_build(long n_cp, long n_docs, long table_slots, int n_toke
   MUSED_REQUIRE(tk_cp_sizes_ok(n_cp, n_docs, slots),
                 "mused_tokenise_cp_build: bad sizes (code points=%ld in [1, 2^30), docs=%ld in [1, code points], table slots=%ld "
                 "in [1, 2^31))", n_cp, n_docs, table_slots);
-  const TkLayout l = tk_cp_layout(n_cp, n_docs, slots);
+  const TkWs l = tk_cp_layout(n_cp, n_docs, slots, ws);
   MUSED_REQUIRE(n_tokens >= 1 && n_tokens <= l.tok_cap && n_tokens <= slots && n_terms >= 1 && n_terms <= n_tokens &&
                     n_terms < (1 << 24),
                 "mused_tokenise_cp_build: %d tokens (at most %ld and the table's %ld slots), %d terms (at most 2^24 - 1: three "
@@ -817,7 +676,7 @@ int mused_tokenise_cp_build(long n_cp, long n_docs, long table_slots, int n_toke
   MUSED_REQUIRE(ws && ws_bytes >= l.bytes && ((uintptr_t)ws & 15) == 0,
                 "mused_tokenise_cp_build: workspace of %ld bytes, need %ld (16-byte aligned)", ws_bytes, l.bytes);
   return tk_build_launch(l, n_docs, slots, n_tokens, n_terms, doc_tokens, rank, vrow, doc_rowptr, term, cnt, pos, gpostptr, gpostrow,
-                         gpostent, info, ws, stream);
+                         gpostent, info, stream);
 }
 
 }  // extern "C"

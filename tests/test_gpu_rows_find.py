@@ -59,9 +59,12 @@ def _held(n, d):
     return X
 
 
-@pytest.mark.parametrize("q", [1, 127, 128, 129])
-@pytest.mark.parametrize("d", [1, 2, 50])
-@pytest.mark.parametrize("n", [1, 300, 20000])
+# the sort's edges, d = 1: n + q = 1024 and 1025 (one tile of the radix passes exactly, and one element into the second); a
+# table of 65,535 and of 65,539 slots (the largest group id crosses 2^16: two passes, then three)
+SORT_EDGES = [(1023, 1, 1), (1024, 1, 1), (32766, 1, 1), (32768, 1, 1)]
+
+
+@pytest.mark.parametrize("n,d,q", [(n, d, q) for q in [1, 127, 128, 129] for d in [1, 2, 50] for n in [1, 300, 20000]] + SORT_EDGES)
 def test_against_the_rule(n, d, q):
     from mused_amd.rows_find import rows_find
 

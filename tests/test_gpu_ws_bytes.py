@@ -57,3 +57,22 @@ def test_rows_find(n, q, d):
     slots, nb = 2 * total + 1, (total + 1023) // 1024
     # table, first, firstq (one int per slot); two key / value pairs (one int per element); 256 counters per block of 1,024
     assert _lib().mused_rows_find_ws_bytes(n, q, d) == 3 * A(4 * slots) + 4 * A(4 * total) + A(4 * 256 * nb)
+
+
+def tokenise_bytes(n, docs, slots, elem, cap, tile):
+    # the lowered text; docptr; token starts per block of the scan; tok_start, tok_len, tok_slot; the table; occupied slots per
+    # block of 256; ent_row; two key / value pairs of the sort; 256 counters per tile of 1,024 entries
+    return (A(elem * n) + A(4 * (docs + 1)) + A(4 * ((n + tile - 1) // tile)) + 3 * A(4 * cap) + A(4 * slots)
+            + A(4 * ((slots + 255) // 256)) + A(4 * cap) + 4 * A(4 * cap) + A(4 * 256 * ((cap + 1023) // 1024)))
+
+
+@pytest.mark.parametrize("slots", [0, 1, 4099])
+@pytest.mark.parametrize("n,docs", [(1, 1), (4097, 3), (10 ** 6, 2000)])
+def test_tokenise(n, docs, slots):
+    L = _lib()
+    # bytes: a token takes three bytes or more, 4,096 bytes per block of the scan, by default two slots per possible token
+    cap = n // 3 + 1
+    assert L.mused_tokenise_ws_bytes(n, docs, slots) == tokenise_bytes(n, docs, slots or 2 * cap, 1, cap, 4096)
+    # code points (4 bytes each): a token takes two or more, 2,048 per block
+    cap = n // 2 + 1
+    assert L.mused_tokenise_cp_ws_bytes(n, docs, slots) == tokenise_bytes(n, docs, slots or 2 * cap, 4, cap, 2048)
