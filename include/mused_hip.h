@@ -306,6 +306,12 @@ int mused_rsvd_select(void* handle, const double* evals, const double* U, const 
                       double* V_out, double* sigma_out, void* stream);
 int mused_spmm_binary(const int* rowptr, const int* colidx, int n, const double* Q, long ldq, int r, double* Y,
                       long ldy, void* stream);
+/* Which kernel mused_spmm_binary runs for these arguments: 0 rows (any shape), 1 wide (r even, rows of Q 16-byte aligned).
+ * q_align / y_align: the base pointers of Q and Y modulo 16 bytes. */
+int mused_spmm_binary_path(int n, int r, long ldq, long ldy, int q_align, int y_align);
+/* Test-facing: force that kernel wherever the shape can take it, as MUSED_SPMM=rows|wide does; -1: the default.
+ * An eigenstep handle records its kernels when it first runs a shape. */
+int mused_spmm_force_path(int path);
 /* ws_int: n + ceil(n/16) ints, ws_f64: 4 * (r + n) doubles */
 int mused_lu_permute_l(double* Y, int n, int r, long ld, int* ws_int, double* ws_f64, void* stream);
 /* ws_f64: r + ceil(n/512) * r + 2 n doubles; n >= r */

@@ -72,6 +72,8 @@ _PROTOS = {
     "mused_rsvd_cholqr": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mused_rsvd_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "mused_spmm_binary": (_i, [_vp, _vp, _i, _vp, _l, _i, _vp, _l, _vp]),
+    "mused_spmm_binary_path": (_i, [_i, _i, _l, _l, _i, _i]),
+    "mused_spmm_force_path": (_i, [_i]),
     "mused_lu_permute_l": (_i, [_vp, _i, _i, _l, _vp, _vp, _vp]),
     "mused_qr_economic": (_i, [_vp, _i, _i, _l, _vp, _l, _vp, _vp]),
     "mused_syevj_batched": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),

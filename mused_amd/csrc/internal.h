@@ -60,9 +60,9 @@ int lu_permute_l(double* Y, int n, int r, long ld, int* pivstep, double* prow, l
 // run_if (optional, device int): the whole chain is a no-op unless *run_if != 0 (fallback of the Cholesky-QR path)
 int qr_economic(double* Y, int n, int r, long ldy, double* Q, long ldq, double* tau, double* wpart, hipStream_t st,
                 const int* run_if = nullptr);
-// Y = A Q for binary CSR A
+// Y = A Q for binary CSR A; col_sign (optional, r doubles of +-1): Y = A Q diag(col_sign), bit for bit
 int spmm_binary(const int* rowptr, const int* colidx, int n, const double* Q, long ldq, int r, double* Y, long ldy,
-                hipStream_t stream);
+                hipStream_t stream, const double* col_sign = nullptr);
 
 // bitmask -> (deg, rowptr, colidx ascending); stats[0] = max degree, stats[1] = nnz; entries beyond
 // `cap` (if cap > 0) are dropped and *overflow set.

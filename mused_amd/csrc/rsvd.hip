@@ -37,6 +37,7 @@ struct Rsvd {
   int mode;  // mused_rsvd_set_mode: 0 Cholesky-QR + Householder fallback recorded in the graph, 1 Cholesky-QR only (the caller
              // reads flags[2]), 2 the reference's LU / Householder chain, launched kernel by kernel
   int g_n, g_r, g_ncomp, g_iter;
+  bool g_comps;  // the recorded graph leaves the signed components in Vsel (out_components was asked for)
   int q0_n, q0_r;
 };
 
@@ -385,19 +386,21 @@ static int rsvd_normalise(Rsvd* h, const double* Y, double* dst, int n, int r, i
 }
 
 // The selection tail: eigenpairs (evals, U: order h->eig_n) of the Gram of Bt (n x rc, pitch ld) -> h->sigma (n_comp, descending)
-// and h->Vsel (n x n_comp) = Bt U[:, order] S^-1 with the signs of svd_flip.
+// and h->Vsel (n x n_comp) = Bt U[:, order] S^-1 with the signs of svd_flip -- or, with apply_signs false, without them: the
+// signs stay in h->signs for the caller (one pass over Vsel less).
 static int rsvd_select(Rsvd* h, const double* evals, const double* U, const double* Bt, long ld, int n, int rc, int n_comp,
-                       hipStream_t st) {
+                       hipStream_t st, bool apply_signs = true) {
   int e;
   hipLaunchKernelGGL(rsvd_decide_kernel, dim3(1), dim3(1024), 0, st, evals, U, h->eig_n, rc, n_comp, h->Cm, h->sigma);
   if ((e = gemm_f64(true, false, Bt, ld, 0, h->Cm, n_comp, 0, h->Vsel, n_comp, 0, n, n_comp, rc, 1, 1.0, st))) return e;
   hipLaunchKernelGGL(col_sign_kernel, dim3(n_comp), dim3(256), 0, st, h->Vsel, n, n_comp, n_comp, h->signs);
-  hipLaunchKernelGGL(col_scale_kernel, dim3(cdiv((long)n * n_comp, 256)), dim3(256), 0, st, h->Vsel, (long)n * n_comp,
-                     n_comp, h->signs);
+  if (apply_signs)
+    hipLaunchKernelGGL(col_scale_kernel, dim3(cdiv((long)n * n_comp, 256)), dim3(256), 0, st, h->Vsel, (long)n * n_comp,
+                       n_comp, h->signs);
   return MUSED_OK;
 }
 
-static int rsvd_enqueue(Rsvd* h, int n, int r, int n_comp, int n_iter, hipStream_t st, bool capturing) {
+static int rsvd_enqueue(Rsvd* h, int n, int r, int n_comp, int n_iter, bool want_comps, hipStream_t st, bool capturing) {
   const int words = (n + 63) / 64;
   const long ld = r;
   int rc_;
@@ -479,8 +482,10 @@ static int rsvd_enqueue(Rsvd* h, int n, int r, int n_comp, int n_iter, hipStream
   hipLaunchKernelGGL(gram_reduce_pad_kernel, dim3(cdiv((long)en * en, 256)), dim3(256), 0, st, h->gpart, nsplit, rc,
                      eig_plan_input(ep), en);
   RC(eig_plan_run_inplace(ep, h->evals, h->U, st, false));
-  RC(rsvd_select(h, h->evals, h->U, h->Bt, ld, n, rc, n_comp, st));
-  RC(spmm_binary(h->rowptr, h->colidx, n, h->Vsel, n_comp, n_comp, h->embed, n_comp, st));
+  // X_new = A V.  Nobody reads V itself unless the components are asked for: its svd_flip signs then go into the stores of
+  // this product (a sign per column commutes exactly with the sum) instead of a pass of their own over Vsel
+  RC(rsvd_select(h, h->evals, h->U, h->Bt, ld, n, rc, n_comp, st, want_comps));
+  RC(spmm_binary(h->rowptr, h->colidx, n, h->Vsel, n_comp, n_comp, h->embed, n_comp, st, want_comps ? nullptr : h->signs));
   MUSED_LAUNCH_CHECK();
 #undef RC
   return MUSED_OK;
@@ -618,15 +623,16 @@ int mused_rsvd_reduce(void* handle, int n, int n_comp, int r, int n_iter, double
   MUSED_REQUIRE(h->q0_n == n && h->q0_r == r, "mused_rsvd_reduce: Q0 was set for (%d, %d), need (%d, %d)", h->q0_n,
                 h->q0_r, n, r);
   hipStream_t st = (hipStream_t)stream;
+  const bool want_comps = out_components != nullptr;
   int rc;
   if (h->use_graph && h->mode != 2) {
-    if (!h->have_graph || h->g_n != n || h->g_r != r || h->g_ncomp != n_comp || h->g_iter != n_iter) {
+    if (!h->have_graph || h->g_n != n || h->g_r != r || h->g_ncomp != n_comp || h->g_iter != n_iter || h->g_comps != want_comps) {
       CaptureLock capture_guard(capture_mutex());  // one capture at a time, and no resource call of this library beside it
       rsvd_drop_graph(h);
       // the capture stream lives only while it records: every live HIP stream competes for the hardware queues
       if (!h->cap_stream) MUSED_CHECK_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
       MUSED_CHECK_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-      rc = rsvd_enqueue(h, n, r, n_comp, n_iter, h->cap_stream, true);
+      rc = rsvd_enqueue(h, n, r, n_comp, n_iter, want_comps, h->cap_stream, true);
       hipError_t e = hipStreamEndCapture(h->cap_stream, &h->graph);
       (void)hipStreamDestroy(h->cap_stream);
       h->cap_stream = nullptr;
@@ -636,11 +642,11 @@ int mused_rsvd_reduce(void* handle, int n, int n_comp, int r, int n_iter, double
       }
       MUSED_CHECK_HIP(hipGraphInstantiate(&h->exec, h->graph, nullptr, nullptr, 0));
       h->have_graph = true;
-      h->g_n = n; h->g_r = r; h->g_ncomp = n_comp; h->g_iter = n_iter;
+      h->g_n = n; h->g_r = r; h->g_ncomp = n_comp; h->g_iter = n_iter; h->g_comps = want_comps;
     }
     MUSED_CHECK_HIP(hipGraphLaunch(h->exec, st));
   } else {
-    if ((rc = rsvd_enqueue(h, n, r, n_comp, n_iter, st, false))) return rc;
+    if ((rc = rsvd_enqueue(h, n, r, n_comp, n_iter, want_comps, st, false))) return rc;
   }
   MUSED_CHECK_HIP(hipMemcpyAsync(out_embed, h->embed, sizeof(double) * (size_t)n * n_comp, hipMemcpyDeviceToDevice, st));
   MUSED_CHECK_HIP(hipMemcpyAsync(out_sigma, h->sigma, sizeof(double) * (size_t)n_comp, hipMemcpyDeviceToDevice, st));
