@@ -256,6 +256,18 @@ int mused_adj_to_dense(const unsigned long long* mask, int n, int words, int dty
 /* dense import (nonzero -> edge); *nonbinary (device int, pre-zeroed) set if an entry is not 0/1 */
 int mused_adj_from_dense(const void* dense, int dtype, int n, long ld, int words, unsigned long long* mask,
                          int* nonbinary, void* stream);
+/* A value per entry of CSR lists, for mused_spmm_valued.  Weighted fusion S = sum_m w_m A_m of M (1 .. 8) bitmasks whose OR
+ * gave the lists (`masks`, `weights`: HOST arrays; every weight finite and > 0): vals[e] = the fp64 sum from 0.0, in modality
+ * order, of w_m over the modalities whose bit (i, colidx[e]) is set, e in rowptr[i] .. rowptr[i + 1].  transposed = 1: the
+ * lists are those of the transposed mask, the bit read is (colidx[e], i).  Nothing is written behind rowptr[n].
+ * Bad arguments (M, a null pointer, a weight <= 0 or not finite): MUSED_ERR_ARG, nothing enqueued. */
+int mused_adj_csr_values(const unsigned long long* const* masks, const double* weights, int M, int n, int words,
+                         const int* rowptr, const int* colidx, int transposed, double* vals, void* stream);
+/* The same from a dense n x n matrix (MUSED_F32 / F64 / I64, row pitch ld) whose nonzeros gave the lists: vals[e] =
+ * (double)dense[i][colidx[e]], or dense[colidx[e]][i] with transposed = 1.  *nonfinite (device int, pre-zeroed) is set when a
+ * value is NaN or infinite. */
+int mused_adj_csr_values_dense(const void* dense, int dtype, int n, long ld, const int* rowptr, const int* colidx,
+                               int transposed, double* vals, int* nonfinite, void* stream);
 
 /* ---- f3: hopping windows (step_window_ratio > 1, main.py:32) with reuse across consecutive windows --------------------
  * The same outputs as mused_knn_fused for the window whose row 0 is stream row lo_abs, computed from what the previous call
@@ -280,8 +292,23 @@ int mused_rsvd_set_q0(void* handle, const double* Q0, int n, int r, void* stream
  * may be NULL) = Vt.T after svd_flip. */
 int mused_rsvd_reduce(void* handle, int n, int n_comp, int r, int n_iter, double* out_embed, double* out_sigma,
                       double* out_components, void* stream);
-/* device int[4] raised by mused_rsvd_reduce (flags[0] != 0: more than nnz_cap edges -> lists truncated, result
- * invalid but memory-safe; flags[2]: weak Cholesky pivot, see mused_rsvd_set_mode; flags[3] != 0: the r x r eigensolve
+/* mused_rsvd_reduce for the weighted fusion S = sum_m w_m A_m of M (1 .. 8) modality bitmasks (n rows of words =
+ * ceil(n/64); `masks`, `weights`: HOST arrays, every weight finite and > 0, else MUSED_ERR_ARG).  The pattern is the OR of
+ * the masks, which this call writes into the handle's mask buffer itself; the value of an edge is what
+ * mused_adj_csr_values gives.  The handle allocates 16 * nnz_cap bytes for the values at its first valued call.  Masks and
+ * weights may change from call to call. */
+int mused_rsvd_reduce_weighted(void* handle, int n, int n_comp, int r, int n_iter,
+                               const unsigned long long* const* masks, const double* weights, int M, int words,
+                               double* out_embed, double* out_sigma, double* out_components, void* stream);
+/* mused_rsvd_reduce for any square real matrix: dense n x n (MUSED_F32 / F64 / I64, row pitch ld, device).  Its nonzeros
+ * are the pattern (built here, in the handle's mask buffer; at most nnz_cap < 2^31 of them), its entries as fp64 the values:
+ * TruncatedSVD(n_comp, random_state -> Q0).fit_transform(dense).  A NaN, an infinity or a magnitude outside
+ * [2^-200, 2^200] raises flags[1]; a matrix without a nonzero is not taken (the caller answers it: all zeros). */
+int mused_rsvd_reduce_dense(void* handle, const void* dense, int dtype, long ld, int n, int n_comp, int r, int n_iter,
+                            double* out_embed, double* out_sigma, double* out_components, void* stream);
+/* device int[4] raised by mused_rsvd_reduce and its valued forms (flags[0] != 0: more than nnz_cap edges -> lists truncated,
+ * result invalid but memory-safe; flags[1] != 0, valued calls only: a value was NaN or infinite (bit 0) or its magnitude outside
+ * [2^-200, 2^200], beyond which the fp64 chain over- or underflows (bit 1) -- result invalid; flags[2]: weak Cholesky pivot, see mused_rsvd_set_mode; flags[3] != 0: the r x r eigensolve
  * gave up (work-queue timeout), result invalid); copy it on the same stream behind the call for a sync-free check */
 const int* mused_rsvd_flags(void* handle);
 /* How the eigenstep builds its bases.  0 (default): Cholesky-QR (Gram + Cholesky + triangular solve) with the
@@ -306,6 +333,13 @@ int mused_rsvd_select(void* handle, const double* evals, const double* U, const 
                       double* V_out, double* sigma_out, void* stream);
 int mused_spmm_binary(const int* rowptr, const int* colidx, int n, const double* Q, long ldq, int r, double* Y,
                       long ldy, void* stream);
+/* Y = S Q for lists with one fp64 value per entry (mused_adj_csr_values): every Y[i][c] is accumulated by one lane over row
+ * i's list, in list order, from 0.0, acc = acc + (vals[e] * Q[colidx[e]][c]) with the product rounded before the add (no
+ * fused multiply-add).  With every value 1.0 the result is mused_spmm_binary's, bit for bit.  The shape rule and
+ * mused_spmm_force_path / MUSED_SPMM apply as for mused_spmm_binary (a forced kernel: mused_spmm_binary_path); unforced, the
+ * wide kernel runs wherever the shape can take it.  Both kernels give the same bits. */
+int mused_spmm_valued(const int* rowptr, const int* colidx, const double* vals, int n, const double* Q, long ldq, int r,
+                      double* Y, long ldy, void* stream);
 /* Which kernel mused_spmm_binary runs for these arguments: 0 rows (any shape), 1 wide (r even, rows of Q 16-byte aligned).
  * q_align / y_align: the base pointers of Q and Y modulo 16 bytes. */
 int mused_spmm_binary_path(int n, int r, long ldq, long ldy, int q_align, int y_align);

@@ -61,17 +61,22 @@ _PROTOS = {
     "mused_adj_transpose": (_i, [_vp, _i, _i, _vp, _vp]),
     "mused_adj_to_dense": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mused_adj_from_dense": (_i, [_vp, _i, _i, _l, _i, _vp, _vp, _vp]),
+    "mused_adj_csr_values": (_i, [C.POINTER(_vp), C.POINTER(_d), _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "mused_adj_csr_values_dense": (_i, [_vp, _i, _i, _l, _vp, _vp, _i, _vp, _vp, _vp]),
     "mused_rsvd_create": (_i, [_i, _i, _l, _i, C.POINTER(_vp)]),
     "mused_rsvd_set_mode": (_i, [_vp, _i]),
     "mused_rsvd_destroy": (_i, [_vp]),
     "mused_rsvd_mask_buffer": (_vp, [_vp]),
     "mused_rsvd_set_q0": (_i, [_vp, _vp, _i, _i, _vp]),
     "mused_rsvd_reduce": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "mused_rsvd_reduce_weighted": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_vp), C.POINTER(_d), _i, _i, _vp, _vp, _vp, _vp]),
+    "mused_rsvd_reduce_dense": (_i, [_vp, _vp, _i, _l, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mused_rsvd_flags": (_vp, [_vp]),
     "mused_rsvd_status": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), _vp]),
     "mused_rsvd_cholqr": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mused_rsvd_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "mused_spmm_binary": (_i, [_vp, _vp, _i, _vp, _l, _i, _vp, _l, _vp]),
+    "mused_spmm_valued": (_i, [_vp, _vp, _vp, _i, _vp, _l, _i, _vp, _l, _vp]),
     "mused_spmm_binary_path": (_i, [_i, _i, _l, _l, _i, _i]),
     "mused_spmm_force_path": (_i, [_i]),
     "mused_lu_permute_l": (_i, [_vp, _i, _i, _l, _vp, _vp, _vp]),

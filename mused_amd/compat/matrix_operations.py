@@ -3,6 +3,7 @@
 from mused_amd.matrix_operations import (  # noqa: F401
     create_adjacency_matrix,
     fuse_matrices,
+    fuse_matrices_weighted,
     match_clusters,
     perform_clustering,
     perform_dbscan_clustering,
@@ -10,4 +11,5 @@ from mused_amd.matrix_operations import (  # noqa: F401
     perform_hdbscan_clustering,
     perform_hdbscan_clustering_on_device,
     perform_svd_reduction,
+    perform_svd_reduction_valued,
 )

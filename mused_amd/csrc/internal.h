@@ -64,6 +64,31 @@ int qr_economic(double* Y, int n, int r, long ldy, double* Q, long ldq, double* 
 int spmm_binary(const int* rowptr, const int* colidx, int n, const double* Q, long ldq, int r, double* Y, long ldy,
                 hipStream_t stream, const double* col_sign = nullptr);
 
+// Y = S Q for CSR lists with one fp64 value per entry (spmm_valued.hip): acc = acc + (val * q), product rounded first, in
+// list order from 0.0; the kernel choice and col_sign as for spmm_binary
+int spmm_valued(const int* rowptr, const int* colidx, const double* vals, int n, const double* Q, long ldq, int r, double* Y,
+                long ldy, hipStream_t stream, const double* col_sign = nullptr);
+
+// adj_values.hip: where the values of CSR lists come from.  M >= 1: the weighted sum of M bitmasks p[0 .. M - 1] (weights w);
+// M == 0: the dense matrix p[0] (dtype, row pitch ld)
+constexpr int ADJ_VAL_MAX_M = 8;
+struct AdjValSrc {
+  const void* p[ADJ_VAL_MAX_M];
+  double w[ADJ_VAL_MAX_M];
+  long ld;
+  int M, dtype;
+};
+// the C entries' HOST arrays / dense arguments, checked (MUSED_ERR_ARG, MUSED_ERR_UNSUPPORTED) -> *out; `who` names the entry
+int adj_val_src_masks(const unsigned long long* const* masks, const double* weights, int M, AdjValSrc* out, const char* who);
+int adj_val_src_dense(const void* dense, int dtype, int n, long ld, AdjValSrc* out, const char* who);
+// *dst (device) = src, stream-ordered (the description travels in the launch, not through host memory)
+int adj_val_src_store(const AdjValSrc& src, AdjValSrc* dst, hipStream_t st);
+// vals[e] for every entry of the lists, the description read from DEVICE memory at run time (safe to record in a graph);
+// a value that is not finite (bit 0 of *flag) or outside [2^-200, 2^200] in magnitude (bit 1) is flagged and stored as 1.0:
+// nothing that could become a NaN inside the eigenstep reaches it (adj_values.hip, GUARD)
+int adj_csr_values_dev(const AdjValSrc* src_dev, bool dense, int n, int words, const int* rowptr, const int* colidx,
+                       int transposed, double* vals, int* flag, hipStream_t st);
+
 // bitmask -> (deg, rowptr, colidx ascending); stats[0] = max degree, stats[1] = nnz; entries beyond
 // `cap` (if cap > 0) are dropped and *overflow set.
 int adj_csr_from_mask(const unsigned long long* mask, int n, int words, int* deg, int* rowptr, int* colidx,

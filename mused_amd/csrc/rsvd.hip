@@ -38,6 +38,13 @@ struct Rsvd {
              // reads flags[2]), 2 the reference's LU / Householder chain, launched kernel by kernel
   int g_n, g_r, g_ncomp, g_iter;
   bool g_comps;  // the recorded graph leaves the signed components in Vsel (out_components was asked for)
+  int g_valued;  // the recorded graph's products: 0 binary, 1 valued from masks and weights, 2 valued from a dense matrix
+  // valued calls only (allocated at the first one: 16 nnz_cap bytes that binary users do not pay): a value per entry of the
+  // lists of A and of A^T, the description of their source, which the recorded value kernels read at run time, and a word
+  // for the pattern kernel's 0/1 check, which nobody reads
+  double *vals, *valsT;
+  AdjValSrc* vsrc;
+  int* vscratch;
   int q0_n, q0_r;
 };
 
@@ -328,6 +335,7 @@ __global__ __launch_bounds__(256) void col_sign_kernel(const double* __restrict_
   if (threadIdx.x == 0) {
     for (int w = 1; w < 4; ++w)
       if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+    if (bi >= n) bi = 0;  // a column of NaN wins no comparison: read a row that exists (the result is flagged elsewhere)
     const double v = V[(long)bi * ld + c];
     signs[c] = v < 0.0 ? -1.0 : 1.0;
   }
@@ -400,7 +408,10 @@ static int rsvd_select(Rsvd* h, const double* evals, const double* U, const doub
   return MUSED_OK;
 }
 
-static int rsvd_enqueue(Rsvd* h, int n, int r, int n_comp, int n_iter, bool want_comps, hipStream_t st, bool capturing) {
+// valued: 0 the 0/1 adjacency of h->mask; 1 / 2 a value per entry, from what h->vsrc describes (masks and weights / a dense
+// matrix) -- the pattern is h->mask either way
+static int rsvd_enqueue(Rsvd* h, int n, int r, int n_comp, int n_iter, bool want_comps, int valued, hipStream_t st,
+                        bool capturing) {
   const int words = (n + 63) / 64;
   const long ld = r;
   int rc_;
@@ -421,6 +432,17 @@ static int rsvd_enqueue(Rsvd* h, int n, int r, int n_comp, int n_iter, bool want
   RC(adj_csr_from_mask(h->mask, n, words, h->deg, h->rowptr, h->colidx, h->stats, h->nnz_cap, h->flags, st));
   RC(adj_transpose(h->mask, n, words, h->mask_t, st));
   RC(adj_csr_from_mask(h->mask_t, n, words, h->degT, h->rowptrT, h->colidxT, h->stats + 2, h->nnz_cap, h->flags, st));
+  if (valued) {
+    RC(adj_csr_values_dev(h->vsrc, valued == 2, n, words, h->rowptr, h->colidx, 0, h->vals, h->flags + 1, st));
+    RC(adj_csr_values_dev(h->vsrc, valued == 2, n, words, h->rowptrT, h->colidxT, 1, h->valsT, h->flags + 1, st));
+  }
+  // the seven products of the chain: A X (tr false) or A^T X (tr true), binary or valued
+  auto mul = [&](bool tr, const double* X, long ldx, int cols, double* Y, long ldy, const double* col_sign) -> int {
+    const int* rp = tr ? h->rowptrT : h->rowptr;
+    const int* ci = tr ? h->colidxT : h->colidx;
+    if (valued) return spmm_valued(rp, ci, tr ? h->valsT : h->vals, n, X, ldx, cols, Y, ldy, st, col_sign);
+    return spmm_binary(rp, ci, n, X, ldx, cols, Y, ldy, st, col_sign);
+  };
 
   int rc = r;
   const double* Qcur = h->Q0;
@@ -435,25 +457,25 @@ static int rsvd_enqueue(Rsvd* h, int n, int r, int n_comp, int n_iter, bool want
     // (1e-11 of the largest pivot is the alarm level), and the subspace is the same (goldens: sigma 1e-15, labels equal)
     for (int it = 0; it < n_iter; ++it) {
       double* X = (Qcur == h->Qa) ? h->Qb : h->Qa;
-      RC(spmm_binary(h->rowptr, h->colidx, n, Qcur, ld, rc, X, ld, st));
+      RC(mul(false, Qcur, ld, rc, X, ld, nullptr));
       double* Z = (X == h->Qa) ? h->Qb : h->Qa;  // (the buffer of the old basis, unless that is Q0)
-      RC(spmm_binary(h->rowptrT, h->colidxT, n, X, ld, rc, Z, ld, st));
+      RC(mul(true, X, ld, rc, Z, ld, nullptr));
       RC(rsvd_normalise(h, Z, X, n, r, nullptr, st));
       Qcur = X;
     }
   } else {
     for (int it = 0; it < n_iter; ++it) {
-      RC(spmm_binary(h->rowptr, h->colidx, n, Qcur, ld, rc, h->Qa, ld, st));
+      RC(mul(false, Qcur, ld, rc, h->Qa, ld, nullptr));
       RC(lu_permute_l(h->Qa, n, rc, ld, h->pivstep, h->prow, h->prow_len, st));
       rc = n < rc ? n : rc;
-      RC(spmm_binary(h->rowptrT, h->colidxT, n, h->Qa, ld, rc, h->Qb, ld, st));
+      RC(mul(true, h->Qa, ld, rc, h->Qb, ld, nullptr));
       RC(lu_permute_l(h->Qb, n, rc, ld, h->pivstep, h->prow, h->prow_len, st));
       Qcur = h->Qb;
     }
   }
   double* Yf = (Qcur == h->Qa) ? h->Qb : h->Qa;  // Y = A Q of the last step
   double* Yt = (Yf == h->Qa) ? h->Qb : h->Qa;
-  RC(spmm_binary(h->rowptr, h->colidx, n, Qcur, ld, rc, Yf, ld, st));
+  RC(mul(false, Qcur, ld, rc, Yf, ld, nullptr));
   rc = n < rc ? n : rc;
   if (cholqr) {
     // final orthonormal basis: Cholesky-QR twice (Yf -> Yt -> Qf); a weak pivot in either pass raises flags[2] (mode 0:
@@ -468,7 +490,7 @@ static int rsvd_enqueue(Rsvd* h, int n, int r, int n_comp, int n_iter, bool want
   } else {
     RC(qr_economic(Yf, n, rc, ld, h->Qf, ld, h->tau, h->wpart, st));
   }
-  RC(spmm_binary(h->rowptrT, h->colidxT, n, h->Qf, ld, rc, h->Bt, ld, st));
+  RC(mul(true, h->Qf, ld, rc, h->Bt, ld, nullptr));
 
   const int nsplit = cdiv(n, GRAM_KCHUNK);
   RC(gemm_f64_splitk(false, false, h->Bt, ld, h->Bt, ld, h->gpart, rc, rc, n, GRAM_KCHUNK, nsplit, st));
@@ -485,7 +507,7 @@ static int rsvd_enqueue(Rsvd* h, int n, int r, int n_comp, int n_iter, bool want
   // X_new = A V.  Nobody reads V itself unless the components are asked for: its svd_flip signs then go into the stores of
   // this product (a sign per column commutes exactly with the sum) instead of a pass of their own over Vsel
   RC(rsvd_select(h, h->evals, h->U, h->Bt, ld, n, rc, n_comp, st, want_comps));
-  RC(spmm_binary(h->rowptr, h->colidx, n, h->Vsel, n_comp, n_comp, h->embed, n_comp, st, want_comps ? nullptr : h->signs));
+  RC(mul(false, h->Vsel, n_comp, n_comp, h->embed, n_comp, want_comps ? nullptr : h->signs));
   MUSED_LAUNCH_CHECK();
 #undef RC
   return MUSED_OK;
@@ -510,6 +532,9 @@ extern "C" {
 // (0 -> default 12).
 static int rsvd_create_impl(Rsvd* h, int n_max, int r_max, long nnz_cap, int sweeps);
 int mused_rsvd_destroy(void* handle);
+int mused_adj_fuse(const unsigned long long* const* masks, int M, int n, int words, unsigned long long* out, void* stream);
+int mused_adj_from_dense(const void* dense, int dtype, int n, long ld, int words, unsigned long long* mask, int* nonbinary,
+                         void* stream);
 
 int mused_rsvd_create(int n_max, int r_max, long nnz_cap, int sweeps, void** out) {
   MUSED_REQUIRE(out && n_max >= 2 && r_max >= 1 && r_max <= 1022 && nnz_cap >= 1, "mused_rsvd_create: bad arguments");
@@ -589,7 +614,7 @@ int mused_rsvd_destroy(void* handle) {
   if (h->eig_top) eig_plan_destroy(h->eig_top);
   void* bufs[] = {h->mask, h->mask_t, h->deg, h->degT, h->rowptr, h->rowptrT, h->colidx, h->colidxT, h->stats,
                   h->flags, h->pivstep, h->Q0, h->Qa, h->Qb, h->Qf, h->Bt, h->Vsel, h->embed, h->prow, h->tau,
-                  h->wpart, h->gpart, h->evals, h->U, h->Cm, h->sigma, h->signs};
+                  h->wpart, h->gpart, h->evals, h->U, h->Cm, h->sigma, h->signs, h->vals, h->valsT, h->vsrc, h->vscratch};
   for (void* b : bufs) (void)hipFree(b);
   delete h;
   return MUSED_OK;
@@ -614,25 +639,30 @@ int mused_rsvd_set_q0(void* handle, const double* Q0, int n, int r, void* stream
 // bitmask in the handle's mask buffer.  n_comp = min(reduced_dim, n - 1), r = n_comp + 10 must
 // match the Q0 set before.  out_embed: n x n_comp fp64 (X @ Vt.T), out_sigma: n_comp singular
 // values (TruncatedSVD.singular_values_), out_components (optional): n x n_comp = Vt[:n_comp].T.
-int mused_rsvd_reduce(void* handle, int n, int n_comp, int r, int n_iter, double* out_embed, double* out_sigma,
-                      double* out_components, void* stream) {
-  Rsvd* h = (Rsvd*)handle;
-  MUSED_REQUIRE(h && out_embed && out_sigma, "mused_rsvd_reduce: null pointer");
+static int rsvd_reduce_check(Rsvd* h, int n, int n_comp, int r, int n_iter, const double* out_embed, const double* out_sigma,
+                             const char* who) {
+  MUSED_REQUIRE(h && out_embed && out_sigma, "%s: null pointer", who);
   MUSED_REQUIRE(n >= 2 && n <= h->n_max && r <= h->r_max && n_comp >= 1 && n_comp <= r && n_comp <= n && n_iter >= 0,
-                "mused_rsvd_reduce: bad sizes n=%d n_comp=%d r=%d", n, n_comp, r);
-  MUSED_REQUIRE(h->q0_n == n && h->q0_r == r, "mused_rsvd_reduce: Q0 was set for (%d, %d), need (%d, %d)", h->q0_n,
-                h->q0_r, n, r);
-  hipStream_t st = (hipStream_t)stream;
+                "%s: bad sizes n=%d n_comp=%d r=%d", who, n, n_comp, r);
+  MUSED_REQUIRE(h->q0_n == n && h->q0_r == r, "%s: Q0 was set for (%d, %d), need (%d, %d)", who, h->q0_n, h->q0_r, n, r);
+  return MUSED_OK;
+}
+
+// The chain on what h->mask (and, valued, h->vsrc) holds on the stream; whether the products are valued is part of the
+// recorded graph's key, as want_comps is.
+static int rsvd_reduce_run(Rsvd* h, int n, int n_comp, int r, int n_iter, int valued, double* out_embed, double* out_sigma,
+                           double* out_components, hipStream_t st) {
   const bool want_comps = out_components != nullptr;
   int rc;
   if (h->use_graph && h->mode != 2) {
-    if (!h->have_graph || h->g_n != n || h->g_r != r || h->g_ncomp != n_comp || h->g_iter != n_iter || h->g_comps != want_comps) {
+    if (!h->have_graph || h->g_n != n || h->g_r != r || h->g_ncomp != n_comp || h->g_iter != n_iter || h->g_comps != want_comps ||
+        h->g_valued != valued) {
       CaptureLock capture_guard(capture_mutex());  // one capture at a time, and no resource call of this library beside it
       rsvd_drop_graph(h);
       // the capture stream lives only while it records: every live HIP stream competes for the hardware queues
       if (!h->cap_stream) MUSED_CHECK_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
       MUSED_CHECK_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-      rc = rsvd_enqueue(h, n, r, n_comp, n_iter, want_comps, h->cap_stream, true);
+      rc = rsvd_enqueue(h, n, r, n_comp, n_iter, want_comps, valued, h->cap_stream, true);
       hipError_t e = hipStreamEndCapture(h->cap_stream, &h->graph);
       (void)hipStreamDestroy(h->cap_stream);
       h->cap_stream = nullptr;
@@ -642,11 +672,11 @@ int mused_rsvd_reduce(void* handle, int n, int n_comp, int r, int n_iter, double
       }
       MUSED_CHECK_HIP(hipGraphInstantiate(&h->exec, h->graph, nullptr, nullptr, 0));
       h->have_graph = true;
-      h->g_n = n; h->g_r = r; h->g_ncomp = n_comp; h->g_iter = n_iter; h->g_comps = want_comps;
+      h->g_n = n; h->g_r = r; h->g_ncomp = n_comp; h->g_iter = n_iter; h->g_comps = want_comps; h->g_valued = valued;
     }
     MUSED_CHECK_HIP(hipGraphLaunch(h->exec, st));
   } else {
-    if ((rc = rsvd_enqueue(h, n, r, n_comp, n_iter, want_comps, st, false))) return rc;
+    if ((rc = rsvd_enqueue(h, n, r, n_comp, n_iter, want_comps, valued, st, false))) return rc;
   }
   MUSED_CHECK_HIP(hipMemcpyAsync(out_embed, h->embed, sizeof(double) * (size_t)n * n_comp, hipMemcpyDeviceToDevice, st));
   MUSED_CHECK_HIP(hipMemcpyAsync(out_sigma, h->sigma, sizeof(double) * (size_t)n_comp, hipMemcpyDeviceToDevice, st));
@@ -654,6 +684,66 @@ int mused_rsvd_reduce(void* handle, int n, int n_comp, int r, int n_iter, double
     MUSED_CHECK_HIP(hipMemcpyAsync(out_components, h->Vsel, sizeof(double) * (size_t)n * n_comp,
                                    hipMemcpyDeviceToDevice, st));
   return MUSED_OK;
+}
+
+int mused_rsvd_reduce(void* handle, int n, int n_comp, int r, int n_iter, double* out_embed, double* out_sigma,
+                      double* out_components, void* stream) {
+  Rsvd* h = (Rsvd*)handle;
+  int rc;
+  if ((rc = rsvd_reduce_check(h, n, n_comp, r, n_iter, out_embed, out_sigma, "mused_rsvd_reduce"))) return rc;
+  return rsvd_reduce_run(h, n, n_comp, r, n_iter, 0, out_embed, out_sigma, out_components, (hipStream_t)stream);
+}
+
+// The value buffers of a handle, allocated at its first valued call.
+static int rsvd_valued_prepare(Rsvd* h) {
+  if (h->vals) return MUSED_OK;
+  CaptureLock resource_guard(capture_mutex());
+  MUSED_CHECK_HIP(hipMalloc((void**)&h->vsrc, sizeof(AdjValSrc)));
+  MUSED_CHECK_HIP(hipMalloc((void**)&h->vscratch, sizeof(int)));
+  MUSED_CHECK_HIP(hipMalloc((void**)&h->valsT, 8 * (size_t)h->nnz_cap));
+  MUSED_CHECK_HIP(hipMalloc((void**)&h->vals, 8 * (size_t)h->nnz_cap));  // (last: its pointer marks the set complete)
+  return MUSED_OK;
+}
+
+// mused_rsvd_reduce for the weighted fusion S = sum_m w_m A_m of M <= 8 modality bitmasks (n rows of `words` =
+// ceil(n / 64) words each; `masks`, `weights`: HOST arrays, every weight finite and > 0): the pattern is the OR of the masks,
+// which this call writes into the handle's mask buffer itself, the value of an entry the sum of the weights of the
+// modalities that have it, in modality order (adj_values.hip), and the seven products of the chain multiply by it
+// (spmm_valued.hip).  Masks and weights may change from call to call: the recorded graph reads them through the handle.
+int mused_rsvd_reduce_weighted(void* handle, int n, int n_comp, int r, int n_iter, const unsigned long long* const* masks,
+                               const double* weights, int M, int words, double* out_embed, double* out_sigma,
+                               double* out_components, void* stream) {
+  Rsvd* h = (Rsvd*)handle;
+  int rc;
+  if ((rc = rsvd_reduce_check(h, n, n_comp, r, n_iter, out_embed, out_sigma, "mused_rsvd_reduce_weighted"))) return rc;
+  AdjValSrc src;
+  if ((rc = adj_val_src_masks(masks, weights, M, &src, "mused_rsvd_reduce_weighted"))) return rc;
+  MUSED_REQUIRE(words == (n + 63) / 64, "mused_rsvd_reduce_weighted: words = %d, the handle's mask buffer has pitch ceil(n / 64) = %d",
+                words, (n + 63) / 64);
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = rsvd_valued_prepare(h))) return rc;
+  if ((rc = mused_adj_fuse(masks, M, n, words, h->mask, stream))) return rc;
+  if ((rc = adj_val_src_store(src, h->vsrc, st))) return rc;
+  return rsvd_reduce_run(h, n, n_comp, r, n_iter, 1, out_embed, out_sigma, out_components, st);
+}
+
+// mused_rsvd_reduce for any square real matrix: dense n x n, row pitch ld, MUSED_F32 / F64 / I64 (device).  Its nonzeros are
+// the pattern, which this call builds in the handle's mask buffer itself, its entries as fp64 the values.  An entry that is
+// not finite raises bit 0 of flags[1] (mused_rsvd_flags), one outside [2^-200, 2^200] in magnitude bit 1: the result is
+// invalid then (the chain ran with 1.0 in that entry's place: adj_values.hip).  More nonzeros than the handle's nnz_cap
+// raise flags[0], as ever.
+int mused_rsvd_reduce_dense(void* handle, const void* dense, int dtype, long ld, int n, int n_comp, int r, int n_iter,
+                            double* out_embed, double* out_sigma, double* out_components, void* stream) {
+  Rsvd* h = (Rsvd*)handle;
+  int rc;
+  if ((rc = rsvd_reduce_check(h, n, n_comp, r, n_iter, out_embed, out_sigma, "mused_rsvd_reduce_dense"))) return rc;
+  AdjValSrc src;
+  if ((rc = adj_val_src_dense(dense, dtype, n, ld, &src, "mused_rsvd_reduce_dense"))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = rsvd_valued_prepare(h))) return rc;
+  if ((rc = mused_adj_from_dense(dense, dtype, n, ld, (n + 63) / 64, h->mask, h->vscratch, stream))) return rc;
+  if ((rc = adj_val_src_store(src, h->vsrc, st))) return rc;
+  return rsvd_reduce_run(h, n, n_comp, r, n_iter, 2, out_embed, out_sigma, out_components, st);
 }
 
 // ---- test-facing entries: one Cholesky-QR pass and the selection tail on their own, on the handle's scratch, launched
@@ -718,7 +808,8 @@ int mused_rsvd_set_mode(void* handle, int mode) {
 }
 
 // Device int[4] the eigenstep raises its flags in (flags[0] != 0: the adjacency had more than nnz_cap edges, the
-// neighbour lists were truncated and the result of that mused_rsvd_reduce is INVALID; flags[2]: weak Cholesky pivot, see
+// neighbour lists were truncated and the result of that mused_rsvd_reduce is INVALID; flags[1] != 0 (valued calls): a value
+// was not finite (bit 0) or outside [2^-200, 2^200] in magnitude (bit 1), result INVALID; flags[2]: weak Cholesky pivot, see
 // mused_rsvd_set_mode; flags[3] != 0: the r x r eigensolve timed out, result INVALID).  Rewritten by every
 // mused_rsvd_reduce on its stream: copy it behind the call (same stream) to read it without a host sync.
 const int* mused_rsvd_flags(void* handle) { return handle ? ((Rsvd*)handle)->flags : nullptr; }

@@ -21,16 +21,9 @@
 #include <atomic>
 #include <stdlib.h>
 
-#include "common.h"
+#include "spmm_common.h"
 
 namespace mused {
-
-enum { SPMM_ROWS = 0, SPMM_WIDE = 1 };
-
-__device__ __forceinline__ double spmm_signed(double s, double v) {
-  const double x = s * v;
-  return x == 0.0 ? 0.0 : x;
-}
 
 __global__ void spmm_binary_kernel(const int* __restrict__ rowptr, const int* __restrict__ colidx, int n,
                                    const double* __restrict__ Q, long ldq, int r, double* __restrict__ Y,
@@ -68,26 +61,6 @@ __global__ void spmm_binary_kernel(const int* __restrict__ rowptr, const int* __
     if (hb) y[cb] = a1;
     if (hc) y[cc] = a2;
   }
-}
-
-// the pair (c, c + 1) of one output row: c even, c + 1 < r.  Y16: y + c is 16-byte aligned (a template argument, not a flag:
-// behind a run-time flag the compiler merges the two forms into 8-byte stores)
-template <bool Y16>
-__device__ __forceinline__ void spmm_store_pair(double* __restrict__ y, int c, double2 a, const double* __restrict__ col_sign) {
-  if (col_sign) {
-    a.x = spmm_signed(col_sign[c], a.x);
-    a.y = spmm_signed(col_sign[c + 1], a.y);
-  }
-  if (Y16) {
-    *reinterpret_cast<double2*>(y + c) = a;
-  } else {
-    y[c] = a.x;
-    y[c + 1] = a.y;
-  }
-}
-
-__device__ __forceinline__ double2 spmm_load_pair(const double* __restrict__ q) {
-  return *reinterpret_cast<const double2*>(q);
 }
 
 // One wave per output row.  A trip covers 192 columns: lane l the pair at 2 l of the first 128 and, for l < 32, the pair at
@@ -147,7 +120,7 @@ __global__ __launch_bounds__(256) void spmm_wide_kernel(const int* __restrict__ 
 // MUSED_SPMM=rows|wide (diagnostic, read once) or mused_spmm_force_path; -1: the measured default per shape
 static std::atomic<int> g_spmm_forced{-2};  // -2: the environment has not been read
 
-static int spmm_forced_path() {
+int spmm_forced_path() {
   int f = g_spmm_forced.load(std::memory_order_relaxed);
   if (f == -2) {
     const char* e = getenv("MUSED_SPMM");

@@ -132,6 +132,70 @@ class Adjacency:
         return Adjacency(mask, n, fused=(t.dtype == torch.int64))
 
 
+MAX_WEIGHTED_PARTS = 8   # csrc/adj_values.hip: modalities of one weighted fusion
+
+
+def check_weights(weights, count=None):
+    """The weights of a weighted fusion as a list of floats: one per modality, finite and > 0 (anything else: ValueError)."""
+    try:
+        w = [float(x) for x in weights]
+    except (TypeError, ValueError):
+        raise ValueError(f"modality weights must be a sequence of numbers, got {weights!r}") from None
+    if count is not None and len(w) != count:
+        raise ValueError(f"{len(w)} modality weights for {count} modalities")
+    if not 1 <= len(w) <= MAX_WEIGHTED_PARTS:
+        raise ValueError(f"a weighted fusion takes 1 .. {MAX_WEIGHTED_PARTS} modalities, got {len(w)}")
+    for x in w:
+        if not (np.isfinite(x) and x > 0.0):
+            raise ValueError(f"modality weights must be finite and > 0, got {x!r}")
+    return w
+
+
+class WeightedAdjacency:
+    """The weighted fusion S = sum_m w_m A_m of M <= 8 modality adjacencies on the device: the masks of its parts and their
+    weights.  Its pattern is the OR of the parts (`.mask`, fused on first use, an `Adjacency` as `.pattern`); the value of
+    edge (i, j) is the fp64 sum, from 0.0 and in modality order, of w_m over the parts that have the edge."""
+
+    def __init__(self, parts, weights):
+        parts = list(parts)
+        if not parts or not all(isinstance(a, Adjacency) for a in parts):
+            raise ValueError("a weighted fusion needs at least one Adjacency")
+        self.weights = check_weights(weights, len(parts))
+        self.parts = parts
+        self.n, self.words = parts[0].n, parts[0].words
+        for a in parts:
+            if a.n != self.n or a.words != self.words:
+                raise ValueError("adjacency shapes differ")
+        self._pattern = None
+
+    @property
+    def pattern(self) -> Adjacency:
+        if self._pattern is None:
+            out = torch.empty_like(self.parts[0].mask)
+            arr = (C.c_void_p * len(self.parts))(*[a.mask.data_ptr() for a in self.parts])
+            call("mused_adj_fuse", arr, len(self.parts), self.n, self.words, ptr(out), stream_ptr())
+            self._pattern = Adjacency(out, self.n, fused=len(self.parts) > 1)
+        return self._pattern
+
+    @property
+    def mask(self) -> torch.Tensor:
+        return self.pattern.mask
+
+    def degrees(self):
+        return self.pattern.degrees()
+
+    def to_dense(self) -> torch.Tensor:
+        """S as an (n, n) fp64 device tensor (the additions in modality order, as the edge values are formed)."""
+        out = torch.zeros((self.n, self.n), dtype=torch.float64, device=self.parts[0].mask.device)
+        for a, w in zip(self.parts, self.weights):
+            d = a.to_dense(torch.float64)
+            out = torch.where(d != 0, out + w, out)
+        return out
+
+    def to_numpy(self) -> np.ndarray:
+        return self.to_dense().cpu().numpy()
+
+
 class DeviceTfidf:
     """The TF-IDF of one text window on the device (`WindowEngine.tfidf_window`): n documents, nnz entries, n_terms
     global terms.  Window CSR in scikit-learn's stored order -- rowptr[n + 1], term[nnz] (global ids), col[nnz] (window
@@ -631,6 +695,10 @@ class WindowEngine:
         call("mused_adj_fuse", arr, len(adjs), n, w, ptr(out), stream_ptr())
         return Adjacency(out, n, fused=len(adjs) > 1)
 
+    def fuse_weighted(self, adjs, weights) -> WeightedAdjacency:
+        """The weighted fusion sum_m w_m A_m of the modality adjacencies (at most 8; weights finite and > 0)."""
+        return WeightedAdjacency(adjs, weights)
+
     @staticmethod
     def max_row_sq_norm(adj: Adjacency) -> float:
         """main.py:61 for a 0/1 matrix: max_i ||row_i||^2 = largest out-degree.  Blocking (.item())."""
@@ -663,8 +731,99 @@ class WindowEngine:
             self._rsvd_fb, self._rsvd_fb_key = h, (max(n, self.n_max), r, nnz_cap)
         return self._rsvd_fb
 
-    def svd_reduce(self, adj: Adjacency, reduced_dim: int, seed: int, n_iter: int = 5, n_oversamples: int = 10,
+    def svd_reduce(self, adj, reduced_dim: int, seed: int, n_iter: int = 5, n_oversamples: int = 10,
                    nnz_cap: int | None = None, want_components: bool = False, want_flags: bool = False):
+        """`adj`: an Adjacency (the 0/1 eigenstep, below) or a WeightedAdjacency (`_svd_reduce_valued`: the same chain with
+        the products multiplying by the edge values)."""
+        if isinstance(adj, WeightedAdjacency):
+            return self._svd_reduce_valued(adj, None, reduced_dim, seed, n_iter, n_oversamples, nnz_cap, want_components,
+                                           want_flags)
+        return self._svd_reduce_binary(adj, reduced_dim, seed, n_iter, n_oversamples, nnz_cap, want_components, want_flags)
+
+    def svd_reduce_dense(self, matrix, reduced_dim: int, seed: int, n_iter: int = 5, n_oversamples: int = 10,
+                         nnz_cap: int | None = None, want_components: bool = False, want_flags: bool = False):
+        """TruncatedSVD(n_components=min(reduced_dim, n - 1), random_state=seed).fit_transform(matrix) for any square real
+        matrix (NumPy or torch; float32, float64 or int64, anything else is converted to float64), through the neighbour
+        lists of its nonzeros: (embedding, sigma) fp64 device tensors.  A NaN or an infinity raises scikit-learn's
+        ValueError (one blocking read of the flag word; with `want_flags` the word is returned unread instead);
+        a matrix that is not square raises ValueError.  `nnz_cap`: a bound on the nonzeros (counted on the device, blocking,
+        when not given); the lists are int32, so at most 2^31 - 1 nonzeros."""
+        if isinstance(matrix, torch.Tensor):
+            t = matrix.to(self.device)
+        else:
+            a = np.asarray(matrix)
+            if a.dtype == np.bool_:
+                a = a.astype(np.int64)
+            if a.dtype not in (np.float32, np.float64, np.int64):
+                a = a.astype(np.float64)
+            t = torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        if t.dtype not in _DT:
+            t = t.to(torch.float64)
+        if t.dim() != 2 or t.shape[0] != t.shape[1]:
+            raise ValueError(f"the valued eigenstep takes a square matrix, got shape {tuple(t.shape)}")
+        if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+            t = t.contiguous()
+        if nnz_cap is None:
+            nnz_cap = int(torch.count_nonzero(t).item())
+            if nnz_cap == 0:   # TruncatedSVD of the zero matrix; there are no lists to run the chain on
+                n_comp = min(int(reduced_dim), t.shape[0] - 1)
+                if n_comp < 1:
+                    raise ValueError("need at least 2 columns")
+                out = (torch.zeros((t.shape[0], n_comp), dtype=torch.float64, device=self.device),
+                       torch.zeros(n_comp, dtype=torch.float64, device=self.device))
+                if want_components:
+                    out = out + (torch.zeros((t.shape[0], n_comp), dtype=torch.float64, device=self.device),)
+                return out + (torch.zeros(4, dtype=torch.int32, device=self.device),) if want_flags else out
+        return self._svd_reduce_valued(None, t, reduced_dim, seed, n_iter, n_oversamples, nnz_cap, want_components,
+                                       want_flags)
+
+    def _svd_reduce_valued(self, wadj, dense, reduced_dim, seed, n_iter, n_oversamples, nnz_cap, want_components, want_flags):
+        n = wadj.n if wadj is not None else dense.shape[0]
+        n_comp = min(int(reduced_dim), n - 1)
+        if n_comp < 1:
+            raise ValueError("need at least 2 columns")  # TruncatedSVD: ensure_min_features=2
+        r = n_comp + n_oversamples
+        if nnz_cap is None:
+            nnz_cap = int(wadj.degrees()[2][1].item())  # blocking; callers on the fast path pass a bound
+        nnz_cap = max(int(nnz_cap), 1)
+        if nnz_cap >= 2 ** 31:
+            raise MusedError(f"{nnz_cap} entries: the eigenstep's neighbour lists are int32 (< 2^31)")
+        emb = torch.empty((n, n_comp), dtype=torch.float64, device=self.device)
+        sig = torch.empty(n_comp, dtype=torch.float64, device=self.device)
+        comp = torch.empty((n, n_comp), dtype=torch.float64, device=self.device) if want_components else None
+        flags = torch.empty(4, dtype=torch.int32, device=self.device)
+
+        def run(h, set_q0):
+            if set_q0:  # Q0 as sklearn draws it, cached in the handle per (n, r, seed)
+                q0_dev = torch.from_numpy(np.random.RandomState(seed).normal(size=(n, r))).to(self.device)
+                call("mused_rsvd_set_q0", h, ptr(q0_dev), n, r, stream_ptr())  # stream-ordered copy
+            tail = (ptr(emb), ptr(sig), ptr(comp) if want_components else None, stream_ptr())
+            if wadj is not None:
+                masks = (C.c_void_p * len(wadj.parts))(*[a.mask.data_ptr() for a in wadj.parts])
+                weights = (C.c_double * len(wadj.parts))(*wadj.weights)
+                call("mused_rsvd_reduce_weighted", h, n, n_comp, r, n_iter, masks, weights, len(wadj.parts), wadj.words, *tail)
+            else:
+                call("mused_rsvd_reduce_dense", h, ptr(dense), _DT[dense.dtype], dense.stride(0), n, n_comp, r, n_iter, *tail)
+            _hip_memcpy_d2d(flags.data_ptr(), _lib.lib().mused_rsvd_flags(h), 16)
+
+        h = self._rsvd_handle(n, r, nnz_cap)
+        run(h, self._q0_key != (n, r, seed))
+        self._q0_key = (n, r, seed)
+        if not self.defer:
+            f = flags.cpu().numpy()  # one small blocking read per call, behind the eigenstep
+            if f[1] and not want_flags:
+                self.raise_value_flag(f[1])
+            if self.rsvd_mode == "cholqr" and f[2] and not f[1]:
+                # weak Cholesky pivot of the final basis (numerically rank-deficient panel): repeat on the reference's chain
+                self.rsvd_fallbacks += 1
+                run(self._rsvd_fallback_handle(n, r, nnz_cap), True)
+        out = (emb, sig, comp) if want_components else (emb, sig)
+        if want_flags:
+            out = out + (flags,)
+        return out
+
+    def _svd_reduce_binary(self, adj: Adjacency, reduced_dim: int, seed: int, n_iter: int = 5, n_oversamples: int = 10,
+                           nnz_cap: int | None = None, want_components: bool = False, want_flags: bool = False):
         """perform_svd_reduction on a device adjacency: (embedding (n, n_comp), sigma (n_comp,)) fp64
         device tensors.  Q0 is generated on the host exactly as sklearn does and cached per (n, r, seed).
         `nnz_cap` is a caller-supplied bound on the number of edges (no host sync); if the adjacency has more, the
@@ -712,6 +871,14 @@ class WindowEngine:
         return out
 
     @staticmethod
+    def raise_value_flag(word) -> None:
+        """flags[1] of a valued eigenstep: bit 0 a NaN or an infinity among the values (scikit-learn's message), bit 1 a
+        magnitude outside [2^-200, 2^200], beyond which the fp64 chain over- or underflows."""
+        if int(word) & 1:
+            raise ValueError("Input contains NaN or infinity.")
+        raise ValueError("the valued eigenstep takes nonzero magnitudes within [2^-200, 2^200]")
+
+    @staticmethod
     def check_rsvd_flags(flags) -> None:
         """Raise if the flag word of an eigenstep (host copy, >= 4 ints) reports truncated neighbour lists or an
         eigensolve that gave up."""
@@ -720,6 +887,8 @@ class WindowEngine:
                 "randomized-SVD eigenstep: the fused adjacency has more edges than the nnz_cap it was given; "
                 "its neighbour lists were truncated and the embedding is invalid"
             )
+        if int(flags[1]) != 0:
+            WindowEngine.raise_value_flag(flags[1])
         if int(flags[3]) != 0:
             raise MusedError("randomized-SVD eigenstep: the r x r eigensolve gave up (work-queue timeout); the embedding "
                              "is invalid")

@@ -346,6 +346,24 @@ def fuse_matrices(matrices):
     return eng.fuse(adjs).to_dense().cpu().numpy()
 
 
+def fuse_matrices_weighted(matrices, weights):
+    """Fusion by weighted sum instead of OR: S = sum_m w_m (A_m != 0), at most 8 modalities, every weight finite and > 0
+    (ValueError otherwise).  A list of `Adjacency` objects gives a `WeightedAdjacency` (nothing is computed until the
+    eigenstep reads it); a list of ndarrays gives S as a float64 array, each entry the sum in modality order from 0.0."""
+    if len(matrices) == 0:
+        raise IndexError("list index out of range")
+    if all(isinstance(m, _eng.Adjacency) for m in matrices):
+        return _eng.WeightedAdjacency(list(matrices), weights)
+    w = _eng.check_weights(weights, len(matrices))
+    mats = [np.asarray(m.to_numpy() if isinstance(m, _eng.Adjacency) else m) for m in matrices]
+    out = np.zeros(mats[0].shape, dtype=np.float64)
+    for a, wm in zip(mats, w):
+        if a.shape != out.shape:
+            raise ValueError("adjacency shapes differ")
+        out = np.where(a != 0, out + wm, out)
+    return out
+
+
 def max_row_sq_norm(fused) -> float:
     """R of main.py:61: max_i ||fused[i, :]||^2."""
     if isinstance(fused, _eng.Adjacency):
@@ -354,8 +372,8 @@ def max_row_sq_norm(fused) -> float:
 
 
 def svd_reduce_on_device(matrix, reduced_dim, seed, nnz_cap=None, engine=None):
-    """(embedding, singular_values) as fp64 CUDA tensors; `matrix` an Adjacency or a dense 0/1 matrix."""
-    adj = matrix if isinstance(matrix, _eng.Adjacency) else _eng.Adjacency.from_dense(matrix)
+    """(embedding, singular_values) as fp64 CUDA tensors; `matrix` an Adjacency, a WeightedAdjacency or a dense 0/1 matrix."""
+    adj = matrix if isinstance(matrix, (_eng.Adjacency, _eng.WeightedAdjacency)) else _eng.Adjacency.from_dense(matrix)
     eng = engine or _eng.default_engine(adj.n)
     return eng.svd_reduce(adj, reduced_dim, seed, nnz_cap=nnz_cap)
 
@@ -364,6 +382,23 @@ def perform_svd_reduction(matrix, reduced_dim, seed):
     """matrix_operations.py:143-147: TruncatedSVD(n_components=min(reduced_dim, n_cols - 1),
     random_state=seed).fit_transform(matrix) for the 0/1 fused adjacency -> (n, n_comp) float64."""
     emb, _ = svd_reduce_on_device(matrix, reduced_dim, seed)
+    return emb.cpu().numpy()
+
+
+def perform_svd_reduction_valued(matrix, reduced_dim, seed):
+    """TruncatedSVD(n_components=min(reduced_dim, n - 1), random_state=seed).fit_transform(matrix) -> (n, n_comp) float64
+    for ANY square real matrix (its nonzeros become neighbour lists with a value per entry: csrc/adj_values.hip,
+    csrc/spmm_valued.hip) or a `WeightedAdjacency`.  ValueError for a matrix that is not square and, with scikit-learn's
+    message, for a NaN or an infinity.  `perform_svd_reduction` keeps its 0/1 contract."""
+    if isinstance(matrix, _eng.WeightedAdjacency):
+        emb, _ = _eng.default_engine(matrix.n).svd_reduce(matrix, reduced_dim, seed)
+    else:
+        if isinstance(matrix, _eng.Adjacency):
+            matrix = matrix.to_dense()
+        shape = tuple(matrix.shape) if hasattr(matrix, "shape") else np.shape(matrix)
+        if len(shape) != 2 or shape[0] != shape[1]:
+            raise ValueError(f"the valued eigenstep takes a square matrix, got shape {shape}")
+        emb, _ = _eng.default_engine(shape[0]).svd_reduce_dense(matrix, reduced_dim, seed)
     return emb.cpu().numpy()
 
 

@@ -2,7 +2,8 @@
 built on the device engine.
 
 Per full window (trigger rule of main.py:32):
-    per-modality kNN adjacency (device bitmask)  ->  OR-fusion  ->
+    per-modality kNN adjacency (device bitmask)  ->  OR-fusion (or, with `modality_weights`, the weighted sum
+    sum_m w_m A_m: the eigenstep then multiplies by a value per edge; the sketch approaches take bit rows and refuse it)  ->
         approach "sSVDMC"/"sSVDMC_hung"/"sSVDMC_pot"/"sSVDMC_mini": randomized-SVD embedding (main.py:79)
         approach "SWFDMC"             : SeqBasedSWFD over the rows of the fused matrix, R from the
                                         first window only, sketch transposed to (W, l)  (main.py:58-76)
@@ -35,7 +36,7 @@ from . import matrix_operations as mo
 from . import meta as _meta
 from . import text as _text
 from ._lib import MusedError
-from .engine import WindowEngine
+from .engine import WindowEngine, check_weights
 from .swfd import SeqBasedSWFD
 
 
@@ -43,9 +44,17 @@ class StreamPipeline:
     def __init__(self, window_size, reduced_dim, k_basis, seed, approach="sSVDMC", modality_types=None,
                  step_window_ratio=1, engine=None, async_labels=True, feature_sketch=False, stream=None,
                  assume_finite=False, window_slots=1, n_clusters_total=None, eps=0.5, min_samples=5,
-                 dbscan_max_rows=None):
+                 dbscan_max_rows=None, modality_weights=None):
         if approach not in ("sSVDMC", "sSVDMC_hung", "sSVDMC_pot", "sSVDMC_mini", "SWFDMC", "DBSCAN_incr"):
             raise ValueError(f"approach {approach!r} is not on the device hot path")
+        # None: OR-fusion, today's path exactly.  M weights (finite, > 0): the modalities are fused by weighted sum and the
+        # eigenstep runs valued.  The sketches ingest bit rows: weighted rows for them are not built
+        self.weights = None
+        if modality_weights is not None:
+            if approach == "SWFDMC" or feature_sketch:
+                raise ValueError("modality_weights: the SWFD sketch ingests the bit rows of the OR-fused adjacency; weighted "
+                                 "fusion covers the approaches that go through the eigenstep")
+            self.weights = check_weights(modality_weights, len(modality_types) if modality_types else None)
         if approach == "sSVDMC_mini" and n_clusters_total is None:
             raise ValueError("approach 'sSVDMC_mini' needs n_clusters_total (MiniBatchKMeans(n_clusters=n_clusters_total), "
                              "main.py:84)")
@@ -188,9 +197,14 @@ class StreamPipeline:
         # candidate lists across windows (engine.knn_adjacency_hop).  `lo` = stream row of the window's row 0.
         reuse = lo is not None and self._hop_reuse and eng is self.eng
         adjs = [self._adjacency(m, t, eng, hop=((i, lo) if reuse else None)) for i, (m, t) in enumerate(zip(mods, types))]
-        fused = eng.fuse(adjs) if len(adjs) > 1 else adjs[0]
-        if len(adjs) == 1:
-            fused.fused = False
+        if self.weights is not None:
+            if len(self.weights) != len(adjs):
+                raise ValueError(f"{len(self.weights)} modality weights for {len(adjs)} modalities")
+            fused = eng.fuse_weighted(adjs, self.weights)   # the pattern is the OR mask: every edge bound below holds
+        else:
+            fused = eng.fuse(adjs) if len(adjs) > 1 else adjs[0]
+            if len(adjs) == 1:
+                fused.fused = False
         if self.feature_sketch:
             X = mods[0] if len(mods) == 1 else torch.cat(mods, dim=1)
             if self.fswfd is None:
@@ -660,8 +674,9 @@ class StreamPipeline:
 
 def process_streaming_data(results, data_modalities, modality_types, window_size, reduced_dim, k_basis, n_clusters_total,
                            seed, approach, complete_true_labels, step_window_ratio, noise_rate, label_mode, sorting,
-                           eps, min_samples, score=False):
-    """Same positional parameters as main.py:13.  Returns `results` with the label arrays ("all_clusters") and the wall
+                           eps, min_samples, score=False, modality_weights=None):
+    """Same positional parameters as main.py:13.  `modality_weights` (one weight per modality, finite and > 0): fusion by
+    weighted sum instead of OR for the approaches that go through the eigenstep ("SWFDMC": ValueError); None: OR.  Returns `results` with the label arrays ("all_clusters") and the wall
     time ("processing_time").  `score=True`: `results` (get_initial_results()'s lists when none is given) also receives
     what the reference's compute_all_metrics appends (main.py:128: the concatenated window labels against the
     concatenated true labels of main.py:39-40, which repeat rows when step_window_ratio > 1; "processing_time" is then
@@ -674,7 +689,8 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
     # (matrix_operations.py:112), "text" and "cosine" = the cosine kernel, the other SED2012 metadata types raise
     with StreamPipeline(window_size, reduced_dim, k_basis, seed, approach, list(modality_types), step_window_ratio,
                         window_slots=int(os.environ.get("MUSED_WINDOW_SLOTS", "1")), n_clusters_total=n_clusters_total,
-                        eps=eps, min_samples=min_samples, dbscan_max_rows=int(incr_rows) if incr_rows else None) as pipe:
+                        eps=eps, min_samples=min_samples, dbscan_max_rows=int(incr_rows) if incr_rows else None,
+                        modality_weights=modality_weights) as pipe:
         clusters = pipe.run(data_modalities, np.asarray(complete_true_labels))
     t1 = time.time_ns()
     if score:
@@ -714,13 +730,17 @@ def _scored(results, clusters, true_labels, variables, t1, t0, window_size=None)
 BATCH_APPROACHES = ("SVDMC_batch", "DBSCAN_batch", "HDBSCAN_batch")
 
 
-def batch_embedding(data_modalities, modality_types, reduced_dim, k_basis, seed, engine=None, timings=None):
+def batch_embedding(data_modalities, modality_types, reduced_dim, k_basis, seed, engine=None, timings=None,
+                    modality_weights=None):
     """Device part of process_batch_data (main.py:138-147): per-modality kNN adjacency of all rows, OR-fused into one
     bitmask as it arrives (one modality mask alive beside the fused one), then the randomized-SVD embedding at n = subset
     size.  Returns (embedding (n, m) fp64 CUDA tensor, sigma, number of fused edges).  `timings`: a dict that receives
     the seconds of every phase (synchronised) and, as "peak_bytes", the most device memory in use beyond what was in
-    use on entry at the end of any phase."""
+    use on entry at the end of any phase.  `modality_weights`: fusion by weighted sum (every modality's mask then stays alive
+    until the eigenstep has read it, and the eigenstep holds 16 bytes of values per edge)."""
     n = len(data_modalities[0])
+    weights = None if modality_weights is None else check_weights(modality_weights, len(data_modalities))
+    parts = []
     base = torch.cuda.mem_get_info()[1] - torch.cuda.mem_get_info()[0] if timings is not None else 0
     eng = engine or WindowEngine(max(n, 2))
 
@@ -743,9 +763,14 @@ def batch_embedding(data_modalities, modality_types, reduced_dim, k_basis, seed,
                 t = tick(f"tokenise[{i}]", t)
             adj = mo.adjacency_on_device(m, ty, k_basis, engine=eng)
             t = tick(f"knn[{i}:{ty or 'l2'}]", t)
-            fused = adj if fused is None else eng.fuse_into(fused, adj)
+            if weights is not None:
+                parts.append(adj)
+            else:
+                fused = adj if fused is None else eng.fuse_into(fused, adj)
             del adj
             t = tick("fusion", t)
+        if weights is not None:
+            fused = eng.fuse_weighted(parts, weights)
         deg, _, _ = fused.degrees()
         nnz = int(deg.to(torch.int64).sum().item())
         if nnz >= 2 ** 31:
@@ -762,8 +787,9 @@ def batch_embedding(data_modalities, modality_types, reduced_dim, k_basis, seed,
 
 def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_basis, n_clusters, seed, approach,
                        complete_true_labels, noise_rate, label_mode, sorting, eps, min_samples, min_cluster_size,
-                       window_size, timings=None, score=False):
-    """Same positional parameters as main.py:132: the whole subset as one window -- kNN adjacency per modality, fusion,
+                       window_size, timings=None, score=False, modality_weights=None):
+    """`modality_weights`: as for process_streaming_data (every batch approach goes through the eigenstep).
+    Same positional parameters as main.py:132: the whole subset as one window -- kNN adjacency per modality, fusion,
     randomized-SVD embedding on the device (`batch_embedding`), then "SVDMC_batch": k-means with n_clusters on the device
     (perform_clustering_on_device: scikit-learn's labels); "DBSCAN_batch": DBSCAN on the device embedding
     (perform_dbscan_clustering_on_device: scikit-learn's labels, csrc/dbscan.hip); "HDBSCAN_batch": MUSED_HDBSCAN, read at every call --
@@ -780,7 +806,8 @@ def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_
     if hd_mode == "package":
         import hdbscan  # noqa: F401  (the reference imports it at module level: without it nothing runs)
     t0 = time.time_ns()
-    emb, _, nnz = batch_embedding(data_modalities, list(modality_types), reduced_dim, k_basis, seed, timings=timings)
+    emb, _, nnz = batch_embedding(data_modalities, list(modality_types), reduced_dim, k_basis, seed, timings=timings,
+                                  modality_weights=modality_weights)
     t1 = time.perf_counter()
     if hd_mode == "device":
         clusters = mo.perform_hdbscan_clustering_on_device(emb, min_cluster_size=min_cluster_size, min_samples=min_samples)
@@ -819,8 +846,11 @@ class SwfdmcLanes:
         out = lanes.run(windows, labels)                     # windows[t] = list of modality tensors of stream window t
     """
 
-    def __init__(self, W, ell, k, seed, lanes, R, modality_types=None, stream=None, assume_finite=False):
+    def __init__(self, W, ell, k, seed, lanes, R, modality_types=None, stream=None, assume_finite=False, modality_weights=None):
         from .swfd import SeqBasedSWFD
+
+        if modality_weights is not None:
+            raise ValueError("modality_weights: the SWFD sketch ingests the bit rows of the OR-fused adjacency")
 
         self.W, self.ell, self.k, self.seed, self.lanes = int(W), int(ell), int(k), int(seed), int(lanes)
         self.types = list(modality_types) if modality_types else None
