@@ -245,6 +245,22 @@ int mused_tokenise_cp_build(long n_cp, long n_docs, long table_slots, int n_toke
 /* Replaces fuse_matrices (matrix_operations.py:134-141).  `masks`: HOST array of M device pointers. */
 int mused_adj_fuse(const unsigned long long* const* masks, int M, int n, int words, unsigned long long* out,
                    void* stream);
+/* Fusion by a truth table (not in the reference).  A subset s in [0, 2^M) has bit m set when modality m has the edge; the
+ * table T is 256 bits (4 uint64, bit s of the table = bit s & 63 of word s >> 6).
+ * out = T(masks): bit (i, j) of out = table bit s, s = sum_m bit_m(i, j) << m.  masks: HOST array of M (1 .. 8) device
+ * pointers, n rows of `words` uint64 each; table: HOST, 4 uint64 (256 bits), bit 0 clear and no bit at or above 2^M set,
+ * else MUSED_ERR_ARG.  ONE launch; every input word is read once, every output word written once; out may be any of the
+ * inputs (a thread reads all of its inputs before it writes).  words >= ceil(n/64); all masks and out share the pitch.  T[0] = 0
+ * keeps padding words and columns >= n clear for inputs that keep them clear.  Enqueue-only.  Bad arguments: MUSED_ERR_ARG,
+ * nothing enqueued, out untouched. */
+int mused_adj_fuse_table(const unsigned long long* const* masks, int M, const unsigned long long* table, int n, int words,
+                         unsigned long long* out, void* stream);
+/* The table of (weights, tau) built on the host, then the call above.  weights: HOST, M values finite and > 0, may be NULL = all
+ * 1.0.  score(s) = the fp64 sum, from 0.0 and IN MODALITY ORDER, of w_m over the set bits of s (plain additions, nothing
+ * reassociated); T[s] = 1 iff s != 0 and score(s) >= tau.  tau must be finite, > 0 and <= score(2^M - 1), else MUSED_ERR_ARG
+ * with nothing enqueued: the table always accepts at least the full subset. */
+int mused_adj_fuse_threshold(const unsigned long long* const* masks, const double* weights, int M, double tau, int n,
+                             int words, unsigned long long* out, void* stream);
 /* deg[n], rowptr[n+1] (exclusive scan), stats = {max degree, nnz}; max degree = R of main.py:61. */
 int mused_adj_degrees(const unsigned long long* mask, int n, int words, int* deg, int* rowptr, int* stats,
                       void* stream);

@@ -56,6 +56,8 @@ _PROTOS = {
     "mused_tokenise_cp_scan": (_i, [_vp, _l, _vp, _l, _vp, _l, _l, _i, _vp, _vp, _l, _vp, _vp, _l, _vp]),
     "mused_tokenise_cp_build": (_i, [_l, _l, _l, _i, _i, _i] + [_vp] * 10 + [_vp, _l, _vp]),
     "mused_adj_fuse": (_i, [C.POINTER(_vp), _i, _i, _i, _vp, _vp]),
+    "mused_adj_fuse_table": (_i, [C.POINTER(_vp), _i, C.POINTER(C.c_uint64), _i, _i, _vp, _vp]),
+    "mused_adj_fuse_threshold": (_i, [C.POINTER(_vp), C.POINTER(_d), _i, _d, _i, _i, _vp, _vp]),
     "mused_adj_degrees": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mused_adj_csr_fill": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "mused_adj_transpose": (_i, [_vp, _i, _i, _vp, _vp]),

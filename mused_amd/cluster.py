@@ -246,7 +246,10 @@ class _DeviceOps:
 
         buf = self._lab.get((key, n))
         if buf is None:
-            buf = self._lab[(key, n)] = torch.empty(n, dtype=torch.int32, device=self.dev)
+            # allocated on the stream that writes it: taken from the calling thread's current stream, the block can be one
+            # that a tensor freed there (a window's sigma) still has a pending write to, which then lands on the labels
+            with _stream(self.st):
+                buf = self._lab[(key, n)] = torch.empty(n, dtype=torch.int32, device=self.dev)
         return buf
 
     def _args(self, X):

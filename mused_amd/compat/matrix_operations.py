@@ -3,6 +3,7 @@
 from mused_amd.matrix_operations import (  # noqa: F401
     create_adjacency_matrix,
     fuse_matrices,
+    fuse_matrices_threshold,
     fuse_matrices_weighted,
     match_clusters,
     perform_clustering,

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import fusion as _fusion
 from ._lib import F32, F64, I64, METRIC_COSINE, METRIC_L2, MusedError, call
 
 _DT = {torch.float32: F32, torch.float64: F64, torch.int64: I64}
@@ -149,6 +150,13 @@ def check_weights(weights, count=None):
         if not (np.isfinite(x) and x > 0.0):
             raise ValueError(f"modality weights must be finite and > 0, got {x!r}")
     return w
+
+
+def check_threshold(weights, tau):
+    """(weights, tau) of a fusion by agreement threshold as (list of floats, float), or the ValueError of the rule
+    (mused_amd/fusion.py): weights as `check_weights` takes them; tau finite, > 0 and at most the score of all modalities --
+    the fp64 sum of the weights from 0.0 in modality order."""
+    return _fusion.check_threshold(check_weights(weights), tau)
 
 
 class WeightedAdjacency:
@@ -698,6 +706,33 @@ class WindowEngine:
     def fuse_weighted(self, adjs, weights) -> WeightedAdjacency:
         """The weighted fusion sum_m w_m A_m of the modality adjacencies (at most 8; weights finite and > 0)."""
         return WeightedAdjacency(adjs, weights)
+
+    def fuse_threshold(self, adjs, threshold, weights=None) -> Adjacency:
+        """Fusion by agreement threshold: edge (i, j) iff the sum of w_m over the modalities that have it (in modality order,
+        from 0.0; every weight 1.0 without `weights`) is >= threshold.  The truth table of (weights, threshold) is built on
+        the host (mused_amd/fusion.py) and one launch evaluates it on the masks (csrc/adj_fuse_table.hip).  A 0/1 matrix
+        like `fuse`'s, a subset of its pattern; at most 8 modalities."""
+        adjs = list(adjs)
+        if not adjs or not all(isinstance(a, Adjacency) for a in adjs):
+            raise ValueError("a threshold fusion needs at least one Adjacency")
+        if weights is None:
+            if not 1 <= len(adjs) <= MAX_WEIGHTED_PARTS:
+                raise ValueError(f"a threshold fusion takes 1 .. {MAX_WEIGHTED_PARTS} modalities, got {len(adjs)}")
+            weights = [1.0] * len(adjs)
+        w, tau = check_threshold(check_weights(weights, len(adjs)), threshold)
+        return self.fuse_table(adjs, _fusion.threshold_table(w, tau))
+
+    def fuse_table(self, adjs, table) -> Adjacency:
+        """out = T(masks) for a 256-bit truth table over the modalities (4 uint64; mused_amd/fusion.py), in one launch."""
+        n, words = adjs[0].n, adjs[0].words
+        for a in adjs:
+            if a.n != n or a.words != words:
+                raise ValueError("adjacency shapes differ")
+        t = _fusion.check_table(table, len(adjs))
+        out = torch.empty((n, words), dtype=torch.int64, device=self.device)
+        arr = (C.c_void_p * len(adjs))(*[a.mask.data_ptr() for a in adjs])
+        call("mused_adj_fuse_table", arr, len(adjs), t.ctypes.data_as(C.POINTER(C.c_uint64)), n, words, ptr(out), stream_ptr())
+        return Adjacency(out, n, fused=True)
 
     @staticmethod
     def max_row_sq_norm(adj: Adjacency) -> float:

@@ -38,6 +38,7 @@ import threading
 import numpy as np
 
 from . import engine as _eng
+from . import fusion as _fusion
 
 _METADATA_TYPES = ("location", "time", "username", "tags")
 # "text": the dense TF-IDF (n x vocabulary fp64) goes to the device while it stays below this many bytes; beyond it (or
@@ -362,6 +363,22 @@ def fuse_matrices_weighted(matrices, weights):
             raise ValueError("adjacency shapes differ")
         out = np.where(a != 0, out + wm, out)
     return out
+
+
+def fuse_matrices_threshold(matrices, threshold, weights=None):
+    """Fusion by agreement threshold: entry (i, j) is 1 iff the sum of w_m over the matrices with a nonzero (i, j) -- fp64,
+    from 0.0, in modality order; every weight 1.0 without `weights` -- is >= threshold (mused_amd/fusion.py states the rule;
+    ValueError for more than 8 matrices, a weight that is not finite and > 0, a threshold that is not finite, not > 0 or above
+    the sum of all weights).  OR, AND and "at least t of M" are thresholds of equal weights.  A list of `Adjacency` objects
+    gives a device `Adjacency` (one launch, csrc/adj_fuse_table.hip); ndarrays give the int64 0/1 matrix."""
+    if len(matrices) == 0:
+        raise IndexError("list index out of range")
+    if all(isinstance(m, _eng.Adjacency) for m in matrices):
+        return _eng.default_engine(matrices[0].n).fuse_threshold(list(matrices), threshold, weights)
+    w, tau = _eng.check_threshold([1.0] * len(matrices) if weights is None else _eng.check_weights(weights, len(matrices)),
+                                  threshold)
+    mats = [np.asarray(m.to_numpy() if isinstance(m, _eng.Adjacency) else m) for m in matrices]
+    return _fusion.fuse_table_numpy(mats, _fusion.threshold_table(w, tau))
 
 
 def max_row_sq_norm(fused) -> float:

@@ -3,7 +3,9 @@ built on the device engine.
 
 Per full window (trigger rule of main.py:32):
     per-modality kNN adjacency (device bitmask)  ->  OR-fusion (or, with `modality_weights`, the weighted sum
-    sum_m w_m A_m: the eigenstep then multiplies by a value per edge; the sketch approaches take bit rows and refuse it)  ->
+    sum_m w_m A_m: the eigenstep then multiplies by a value per edge; the sketch approaches take bit rows and refuse it; or,
+    with `fusion_threshold`, the 0/1 mask of the edges whose weighted agreement reaches the threshold, which every approach
+    takes; `modality_ks`: a k per modality)  ->
         approach "sSVDMC"/"sSVDMC_hung"/"sSVDMC_pot"/"sSVDMC_mini": randomized-SVD embedding (main.py:79)
         approach "SWFDMC"             : SeqBasedSWFD over the rows of the fused matrix, R from the
                                         first window only, sketch transposed to (W, l)  (main.py:58-76)
@@ -36,21 +38,61 @@ from . import matrix_operations as mo
 from . import meta as _meta
 from . import text as _text
 from ._lib import MusedError
-from .engine import WindowEngine, check_weights
+from . import fusion as _fusion
+from .engine import MAX_WEIGHTED_PARTS, WindowEngine, check_threshold, check_weights
 from .swfd import SeqBasedSWFD
+
+
+def check_ks(modality_ks, count=None):
+    """`modality_ks` as a list of ints, one k per modality, every one >= 1 (ValueError otherwise); None stays None."""
+    if modality_ks is None:
+        return None
+    try:
+        ks = list(modality_ks)
+    except TypeError:
+        raise ValueError(f"modality_ks must be a sequence of integers, got {modality_ks!r}") from None
+    for x in ks:
+        if isinstance(x, (bool, float, str)) or not isinstance(x, (int, np.integer)) or x < 1:
+            raise ValueError(f"modality_ks must be integers >= 1, got {x!r}")
+    if count is not None and len(ks) != count:
+        raise ValueError(f"{len(ks)} modality ks for {count} modalities")
+    return [int(x) for x in ks]
+
+
+def check_vote(fusion_threshold, modality_weights, count=None):
+    """The arguments of a fusion by agreement threshold as (tau, vote weights or None); with the number of modalities known
+    also checked against it (more than 8 modalities, a threshold above the sum of all weights: ValueError)."""
+    w = None if modality_weights is None else check_weights(modality_weights, count)
+    if w is None and count is not None:
+        if not 1 <= count <= MAX_WEIGHTED_PARTS:
+            raise ValueError(f"a threshold fusion takes 1 .. {MAX_WEIGHTED_PARTS} modalities, got {count}")
+        w = [1.0] * count
+    if w is not None:
+        return check_threshold(w, fusion_threshold)[1], (None if modality_weights is None else w)
+    tau = float(fusion_threshold)
+    if not (np.isfinite(tau) and tau > 0.0):
+        raise ValueError(f"the fusion threshold must be finite and > 0, got {fusion_threshold!r}")
+    return tau, None
 
 
 class StreamPipeline:
     def __init__(self, window_size, reduced_dim, k_basis, seed, approach="sSVDMC", modality_types=None,
                  step_window_ratio=1, engine=None, async_labels=True, feature_sketch=False, stream=None,
                  assume_finite=False, window_slots=1, n_clusters_total=None, eps=0.5, min_samples=5,
-                 dbscan_max_rows=None, modality_weights=None):
+                 dbscan_max_rows=None, modality_weights=None, fusion_threshold=None, modality_ks=None):
         if approach not in ("sSVDMC", "sSVDMC_hung", "sSVDMC_pot", "sSVDMC_mini", "SWFDMC", "DBSCAN_incr"):
             raise ValueError(f"approach {approach!r} is not on the device hot path")
         # None: OR-fusion, today's path exactly.  M weights (finite, > 0): the modalities are fused by weighted sum and the
         # eigenstep runs valued.  The sketches ingest bit rows: weighted rows for them are not built
+        # `fusion_threshold` (tau): the fused matrix is the 0/1 mask of the edges whose weighted agreement
+        # sum_m w_m [A_m has the edge] reaches tau (mused_amd/fusion.py; weights 1.0 without `modality_weights`, which then only
+        # weight the vote).  A 0/1 matrix again: every approach takes it, the sketches included, on the binary eigenstep
         self.weights = None
-        if modality_weights is not None:
+        self.threshold = self.vote_weights = self._table = None
+        n_mods = len(modality_types) if modality_types else None
+        if fusion_threshold is not None:
+            self.threshold, self.vote_weights = check_vote(fusion_threshold, modality_weights, n_mods)
+        elif modality_weights is not None:
             if approach == "SWFDMC" or feature_sketch:
                 raise ValueError("modality_weights: the SWFD sketch ingests the bit rows of the OR-fused adjacency; weighted "
                                  "fusion covers the approaches that go through the eigenstep")
@@ -79,6 +121,8 @@ class StreamPipeline:
         self.n_clusters_total = None if n_clusters_total is None else int(n_clusters_total)
         self.clusterer = None
         self.W, self.ell, self.k, self.seed = int(window_size), int(reduced_dim), int(k_basis), int(seed)
+        # a k per modality: modality m uses ks[m] wherever the reference uses k_basis for it ("time" still takes 3 k + 1 ...)
+        self.ks = check_ks(modality_ks, n_mods)
         self.approach = approach
         self.types = modality_types
         # rows with a non-finite entry are dropped from the kNN (matrix_operations.py:114-115).  Finding out needs one
@@ -103,7 +147,7 @@ class StreamPipeline:
         # library serialises those resource calls with every capture of the process (csrc/internal.h: capture_mutex;
         # round 2 ran them beside another slot's capture and aborted, gpurun_out/r2_gputest23.log).  Such streams still
         # keep one slot: a re-creation stalls every slot behind that lock for tens of milliseconds.
-        if any(mo.edges_per_row(t, self.k) is None for t in (modality_types or [])):
+        if self._optimistic_nnz():
             self._nslots = 1
         # DEFERRED FLAGS: the candidate-list overflow of the fused kNN and the weak-pivot / edge-count flags of the
         # eigenstep are not read on the enqueueing thread; they travel to the host behind the window's event and a
@@ -196,8 +240,11 @@ class StreamPipeline:
         # hopping windows (step_window_ratio > 1): consecutive windows share rows -> the dense modalities reuse their
         # candidate lists across windows (engine.knn_adjacency_hop).  `lo` = stream row of the window's row 0.
         reuse = lo is not None and self._hop_reuse and eng is self.eng
-        adjs = [self._adjacency(m, t, eng, hop=((i, lo) if reuse else None)) for i, (m, t) in enumerate(zip(mods, types))]
-        if self.weights is not None:
+        ks = self._ks(len(mods))
+        adjs = [self._adjacency(m, t, eng, hop=((i, lo) if reuse else None), k=ks[i]) for i, (m, t) in enumerate(zip(mods, types))]
+        if self.threshold is not None:
+            fused = self._fuse_vote(adjs, eng)              # a subset of the OR mask: every edge bound below holds
+        elif self.weights is not None:
             if len(self.weights) != len(adjs):
                 raise ValueError(f"{len(self.weights)} modality weights for {len(adjs)} modalities")
             fused = eng.fuse_weighted(adjs, self.weights)   # the pattern is the OR mask: every edge bound below holds
@@ -229,7 +276,7 @@ class StreamPipeline:
             reduced = B.t().contiguous() if B.shape[0] != self.W else B  # main.py:73-76
             return reduced, sigma, None
         # edges per row: k selected (l2; the row itself is normally one of them) or k + 1 (cosine / text)
-        per_row = [mo.edges_per_row(t, self.k) for t in types]
+        per_row = [mo.edges_per_row(t, k) for t, k in zip(types, ks)]
         if all(b is not None for b in per_row):
             nnz_cap = fused.n * sum(per_row)
         elif defer:
@@ -244,15 +291,38 @@ class StreamPipeline:
             flags = eng.window_flags(flags)
         return emb, sigma, flags
 
-    def _adjacency(self, m, t, eng=None, hop=None):
-        """One modality of one window -> device adjacency, with the reference's row filtering."""
+    def _ks(self, n_mods):
+        """k of each of the window's modalities: `modality_ks`, or k_basis for all."""
+        if self.ks is None:
+            return [self.k] * n_mods
+        if len(self.ks) != n_mods:
+            raise ValueError(f"{len(self.ks)} modality ks for {n_mods} modalities")
+        return self.ks
+
+    def _fuse_vote(self, adjs, eng=None):
+        """The thresholded 0/1 mask of one window's modality adjacencies (the table is built at the first window)."""
+        if self._table is None:
+            tau, w = check_vote(self.threshold, self.vote_weights, len(adjs))
+            self._table = _fusion.threshold_table(w if w is not None else [1.0] * len(adjs), tau)
+        return (eng or self.eng).fuse_table(adjs, self._table)
+
+    def _fuse_binary(self, adjs, eng=None):
+        """The 0/1 matrix the sketches ingest: the thresholded mask, or the OR mask."""
+        if self.threshold is not None:
+            return self._fuse_vote(adjs, eng)
+        return (eng or self.eng).fuse(adjs) if len(adjs) > 1 else adjs[0]
+
+    def _adjacency(self, m, t, eng=None, hop=None, k=None):
+        """One modality of one window -> device adjacency, with the reference's row filtering.  k: this modality's k (k_basis
+        without it)."""
         eng = eng or self.eng
+        k = self.k if k is None else k
         if t == "text" or t in mo._METADATA_TYPES or not isinstance(m, torch.Tensor):
             # (text: thousands of documents tie at similarity 0 and overflow the candidate lists in most windows -- the
             # overflow word is read at once there instead of repeating the whole window, TF-IDF included, afterwards)
             was, eng.defer = eng.defer, eng.defer and t != "text"
             try:
-                return mo.adjacency_on_device(m, t, self.k, engine=eng)
+                return mo.adjacency_on_device(m, t, k, engine=eng)
             finally:
                 eng.defer = was
         metric = mo._metric_for(t)
@@ -271,10 +341,10 @@ class StreamPipeline:
             with torch.cuda.stream(self._chk):
                 ok = bool(torch.isfinite(m).all().item())
             if not ok:
-                return mo.adjacency_on_device(m, t, self.k, engine=eng)
+                return mo.adjacency_on_device(m, t, k, engine=eng)
         if hop is not None:
-            return eng.knn_adjacency_hop(m, self.k, metric, key=hop[0], lo=hop[1])
-        return eng.knn_adjacency(m, self.k, metric)
+            return eng.knn_adjacency_hop(m, k, metric, key=hop[0], lo=hop[1])
+        return eng.knn_adjacency(m, k, metric)
 
     # ---- host consumers -------------------------------------------------------------------------
     def _cluster(self, job):
@@ -375,7 +445,7 @@ class StreamPipeline:
         self._chain(self._cluster(job), job)
 
     def _optimistic_nnz(self):
-        return any(mo.edges_per_row(t, self.k) is None for t in (self.types or []))
+        return any(mo.edges_per_row(t, self.k) is None for t in (self.types or []))   # ("username": whatever its k)
 
     def _redo_window(self, mods):
         """One window on the fallback engine (score-matrix kNN, LU / Householder eigenstep, exact edge count), on the
@@ -674,9 +744,13 @@ class StreamPipeline:
 
 def process_streaming_data(results, data_modalities, modality_types, window_size, reduced_dim, k_basis, n_clusters_total,
                            seed, approach, complete_true_labels, step_window_ratio, noise_rate, label_mode, sorting,
-                           eps, min_samples, score=False, modality_weights=None):
+                           eps, min_samples, score=False, modality_weights=None, fusion_threshold=None, modality_ks=None):
     """Same positional parameters as main.py:13.  `modality_weights` (one weight per modality, finite and > 0): fusion by
-    weighted sum instead of OR for the approaches that go through the eigenstep ("SWFDMC": ValueError); None: OR.  Returns `results` with the label arrays ("all_clusters") and the wall
+    weighted sum instead of OR for the approaches that go through the eigenstep ("SWFDMC": ValueError); None: OR.
+    `fusion_threshold` (tau): every window's fused matrix is the 0/1 mask of the edges whose agreement sum_m w_m [modality m
+    has the edge] is >= tau -- for every approach, "SWFDMC" and "DBSCAN_incr" included; `modality_weights` then only weight
+    the vote (1.0 each without them).  `modality_ks`: one k >= 1 per modality, used wherever the reference uses k_basis for
+    that modality; k_basis is what the scored results report.  Returns `results` with the label arrays ("all_clusters") and the wall
     time ("processing_time").  `score=True`: `results` (get_initial_results()'s lists when none is given) also receives
     what the reference's compute_all_metrics appends (main.py:128: the concatenated window labels against the
     concatenated true labels of main.py:39-40, which repeat rows when step_window_ratio > 1; "processing_time" is then
@@ -690,7 +764,7 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
     with StreamPipeline(window_size, reduced_dim, k_basis, seed, approach, list(modality_types), step_window_ratio,
                         window_slots=int(os.environ.get("MUSED_WINDOW_SLOTS", "1")), n_clusters_total=n_clusters_total,
                         eps=eps, min_samples=min_samples, dbscan_max_rows=int(incr_rows) if incr_rows else None,
-                        modality_weights=modality_weights) as pipe:
+                        modality_weights=modality_weights, fusion_threshold=fusion_threshold, modality_ks=modality_ks) as pipe:
         clusters = pipe.run(data_modalities, np.asarray(complete_true_labels))
     t1 = time.time_ns()
     if score:
@@ -731,15 +805,23 @@ BATCH_APPROACHES = ("SVDMC_batch", "DBSCAN_batch", "HDBSCAN_batch")
 
 
 def batch_embedding(data_modalities, modality_types, reduced_dim, k_basis, seed, engine=None, timings=None,
-                    modality_weights=None):
+                    modality_weights=None, fusion_threshold=None, modality_ks=None):
     """Device part of process_batch_data (main.py:138-147): per-modality kNN adjacency of all rows, OR-fused into one
     bitmask as it arrives (one modality mask alive beside the fused one), then the randomized-SVD embedding at n = subset
     size.  Returns (embedding (n, m) fp64 CUDA tensor, sigma, number of fused edges).  `timings`: a dict that receives
     the seconds of every phase (synchronised) and, as "peak_bytes", the most device memory in use beyond what was in
     use on entry at the end of any phase.  `modality_weights`: fusion by weighted sum (every modality's mask then stays alive
-    until the eigenstep has read it, and the eigenstep holds 16 bytes of values per edge)."""
+    until the eigenstep has read it, and the eigenstep holds 16 bytes of values per edge).  `fusion_threshold`: fusion by
+    agreement threshold (process_streaming_data); the vote needs every modality's bit at once, so the masks cannot be ORed as
+    they arrive: every modality's mask stays alive until the one fusion launch, as on the weighted path (M + 1 masks at the
+    peak instead of 2); the eigenstep is the binary one.  `modality_ks`: one k per modality instead of k_basis."""
     n = len(data_modalities[0])
-    weights = None if modality_weights is None else check_weights(modality_weights, len(data_modalities))
+    threshold = None
+    if fusion_threshold is not None:
+        threshold, weights = check_vote(fusion_threshold, modality_weights, len(data_modalities))
+    else:
+        weights = None if modality_weights is None else check_weights(modality_weights, len(data_modalities))
+    ks = check_ks(modality_ks, len(data_modalities)) or [k_basis] * len(data_modalities)
     parts = []
     base = torch.cuda.mem_get_info()[1] - torch.cuda.mem_get_info()[0] if timings is not None else 0
     eng = engine or WindowEngine(max(n, 2))
@@ -761,15 +843,18 @@ def batch_embedding(data_modalities, modality_types, reduced_dim, k_basis, seed,
             if ty == "text" and mo.text_on_device() and not isinstance(m, (_text.TextCorpus, _text.TextWindow)):
                 m = _text.tokenise_for_device(m, eng.device)   # the whole subset is one window of this corpus
                 t = tick(f"tokenise[{i}]", t)
-            adj = mo.adjacency_on_device(m, ty, k_basis, engine=eng)
+            adj = mo.adjacency_on_device(m, ty, ks[i], engine=eng)
             t = tick(f"knn[{i}:{ty or 'l2'}]", t)
-            if weights is not None:
+            if weights is not None or threshold is not None:
                 parts.append(adj)
             else:
                 fused = adj if fused is None else eng.fuse_into(fused, adj)
             del adj
             t = tick("fusion", t)
-        if weights is not None:
+        if threshold is not None:
+            fused = eng.fuse_threshold(parts, threshold, weights)
+            parts.clear()
+        elif weights is not None:
             fused = eng.fuse_weighted(parts, weights)
         deg, _, _ = fused.degrees()
         nnz = int(deg.to(torch.int64).sum().item())
@@ -787,8 +872,9 @@ def batch_embedding(data_modalities, modality_types, reduced_dim, k_basis, seed,
 
 def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_basis, n_clusters, seed, approach,
                        complete_true_labels, noise_rate, label_mode, sorting, eps, min_samples, min_cluster_size,
-                       window_size, timings=None, score=False, modality_weights=None):
-    """`modality_weights`: as for process_streaming_data (every batch approach goes through the eigenstep).
+                       window_size, timings=None, score=False, modality_weights=None, fusion_threshold=None, modality_ks=None):
+    """`modality_weights`, `fusion_threshold`, `modality_ks`: as for process_streaming_data (every batch approach goes through
+    the eigenstep; see batch_embedding for what a threshold costs in memory).
     Same positional parameters as main.py:132: the whole subset as one window -- kNN adjacency per modality, fusion,
     randomized-SVD embedding on the device (`batch_embedding`), then "SVDMC_batch": k-means with n_clusters on the device
     (perform_clustering_on_device: scikit-learn's labels); "DBSCAN_batch": DBSCAN on the device embedding
@@ -807,7 +893,7 @@ def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_
         import hdbscan  # noqa: F401  (the reference imports it at module level: without it nothing runs)
     t0 = time.time_ns()
     emb, _, nnz = batch_embedding(data_modalities, list(modality_types), reduced_dim, k_basis, seed, timings=timings,
-                                  modality_weights=modality_weights)
+                                  modality_weights=modality_weights, fusion_threshold=fusion_threshold, modality_ks=modality_ks)
     t1 = time.perf_counter()
     if hd_mode == "device":
         clusters = mo.perform_hdbscan_clustering_on_device(emb, min_cluster_size=min_cluster_size, min_samples=min_samples)
@@ -846,28 +932,36 @@ class SwfdmcLanes:
         out = lanes.run(windows, labels)                     # windows[t] = list of modality tensors of stream window t
     """
 
-    def __init__(self, W, ell, k, seed, lanes, R, modality_types=None, stream=None, assume_finite=False, modality_weights=None):
+    def __init__(self, W, ell, k, seed, lanes, R, modality_types=None, stream=None, assume_finite=False, modality_weights=None,
+                 fusion_threshold=None, modality_ks=None):
         from .swfd import SeqBasedSWFD
 
-        if modality_weights is not None:
+        # `fusion_threshold`: the sketch ingests the bit rows of the thresholded mask (weights then only weight the vote);
+        # `modality_ks`: one k per modality -- both as for StreamPipeline, which fuses for the lanes
+        if modality_weights is not None and fusion_threshold is None:
             raise ValueError("modality_weights: the SWFD sketch ingests the bit rows of the OR-fused adjacency")
 
         self.W, self.ell, self.k, self.seed, self.lanes = int(W), int(ell), int(k), int(seed), int(lanes)
         self.types = list(modality_types) if modality_types else None
         self.pipe = StreamPipeline(W, ell, k, seed, "sSVDMC", modality_types=self.types, async_labels=True, stream=stream,
-                                   assume_finite=assume_finite)
+                                   assume_finite=assume_finite, modality_weights=modality_weights,
+                                   fusion_threshold=fusion_threshold, modality_ks=modality_ks)
         self.sk = SeqBasedSWFD(N=self.W, R=float(R), d=self.W, sketch_dim=self.ell, lanes=self.lanes)
         self.words = (self.W + 63) // 64
         self._masks = torch.zeros((self.lanes, self.W, self.words), dtype=torch.int64, device="cuda")
 
     @staticmethod
-    def r_of_first_window(mods, W, k, modality_types=None, seed=0):
-        """main.py:61 on the fused adjacency of stream window 0."""
-        with StreamPipeline(W, 2, k, seed, "sSVDMC", modality_types=modality_types, async_labels=False) as p:
-            types = p.types or [""] * len(mods)
-            adjs = [p._adjacency(_to_dev(m), t) for m, t in zip(mods, types)]
-            fused = p.eng.fuse(adjs) if len(adjs) > 1 else adjs[0]
-            return p.eng.max_row_sq_norm(fused)
+    def r_of_first_window(mods, W, k, modality_types=None, seed=0, modality_weights=None, fusion_threshold=None,
+                          modality_ks=None):
+        """main.py:61 on the fused adjacency of stream window 0 (fused as the lanes will fuse it: give the same
+        `fusion_threshold`, vote weights and `modality_ks`)."""
+        if modality_weights is not None and fusion_threshold is None:
+            raise ValueError("modality_weights: the SWFD sketch ingests the bit rows of the OR-fused adjacency")
+        with StreamPipeline(W, 2, k, seed, "sSVDMC", modality_types=modality_types, async_labels=False,
+                            modality_weights=modality_weights, fusion_threshold=fusion_threshold, modality_ks=modality_ks) as p:
+            types, ks = p.types or [""] * len(mods), p._ks(len(mods))
+            adjs = [p._adjacency(_to_dev(m), t, k=ks[i]) for i, (m, t) in enumerate(zip(mods, types))]
+            return p.eng.max_row_sq_norm(p._fuse_binary(adjs))
 
     def step(self, mods_per_lane, labels_per_lane, triggers, want):
         """One lock-step: lane p appends the fused adjacency of mods_per_lane[p] (None: a window of empty rows); lanes with
@@ -879,9 +973,9 @@ class SwfdmcLanes:
                 continue
             types = self.types or [""] * len(mods)
             eng.begin_window(False)
-            adjs = [self.pipe._adjacency(_to_dev(m), t) for m, t in zip(mods, types)]
-            fused = eng.fuse(adjs) if len(adjs) > 1 else adjs[0]
-            self._masks[p].copy_(fused.mask)
+            ks = self.pipe._ks(len(mods))
+            adjs = [self.pipe._adjacency(_to_dev(m), t, k=ks[i]) for i, (m, t) in enumerate(zip(mods, types))]
+            self._masks[p].copy_(self.pipe._fuse_binary(adjs, eng).mask)
         self.sk.fit_adjacency_lanes(self._masks)
         if not any(want):
             return
