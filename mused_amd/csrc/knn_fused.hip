@@ -85,6 +85,9 @@ __device__ __forceinline__ void cand_push(const CandArgs& c, int slot, int col, 
 // layout -- slot (delta_signed + a) * 128 + (column mod 128) for the 2 a + 1 column tiles within cyclic distance
 // a = n_delta - 1 -- and the scores are stored without atomics (columns beyond n as +inf); the host presets the
 // counts to (2 a + 1) * 128.  Requires tiles >= 2 a + 2 (no column tile reached from both sides).
+// A slot beyond n carries a column id of its own (0x7fffffff - slot, above every absolute id): columns are unique within a
+// list, which the tie handling of cand_select_kernel relies on when the k-th candidate of a short row is such a slot
+// (k > 512: a = 0, and a row of the ragged last tile holds fewer real candidates than k after the second launch).
 template <typename T, bool VEC, int METRIC, bool DIRECT>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void knn_band_kernel(GemmArgs g, CandArgs c, int tiles, int d_lo,
                                                                   int n_delta) {
@@ -137,7 +140,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void knn_band_kernel(GemmArgs g, C
               const long p = (long)srow * c.cap + (a + delta) * 128 + cl;
               const bool ok = col < n;
               c.cscore[p] = ok ? score_of<METRIC>(c.nrm, row, col, av) : inf;
-              c.ccol[p] = ok ? col + c.col_base : 0x7fffffff;
+              c.ccol[p] = ok ? col + c.col_base : 0x7fffffff - ((a + delta) * 128 + cl);
             } else if (col_new && col < n) {
               const double v = score_of<METRIC>(c.nrm, row, col, av);
               if (v < trow || (v == trow && col + c.col_base < crow)) cand_push(c, srow, col, v);
@@ -148,7 +151,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void knn_band_kernel(GemmArgs g, C
               const long p = (long)cand_slot(c, col) * c.cap + (a - delta) * 128 + rl;
               const bool ok = row < n;
               c.cscore[p] = ok ? score_of<METRIC>(c.nrm, col, row, av) : inf;
-              c.ccol[p] = ok ? row + c.col_base : 0x7fffffff;
+              c.ccol[p] = ok ? row + c.col_base : 0x7fffffff - ((a - delta) * 128 + rl);
             } else if (row_new && row < n) {
               const int sc_ = cand_slot(c, col);
               const double tc = c.tau[sc_];

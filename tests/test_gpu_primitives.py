@@ -539,7 +539,7 @@ def _fused_topk(L, X, k, metric, cap):
     (1024, 64, 50, 0, np.float32),    # 8 tiles: even tile count (antipodal pairs once)
     (1500, 48, 50, 1, np.float32),    # cosine, 12 tiles
     (2000, 24, 200, 0, np.float64),   # large k: the lists hold 4 k + 128 candidates
-    (2900, 40, 31, 1, np.float64),    # 23 tiles: four phases
+    (2900, 40, 31, 1, np.float64),    # 23 tiles (odd): DIRECT first phase 0..2, the other distances 3..11 in one launch
 ])
 def test_knn_fused_equals_classic(L, n, d, k, metric, dtype):
     """Fused similarity + selection (no score matrix) == mused_pairwise_scores + mused_select_k_smallest, bit for bit:
