@@ -364,6 +364,12 @@ int mused_spmm_binary_path(int n, int r, long ldq, long ldy, int q_align, int y_
 int mused_spmm_force_path(int path);
 /* ws_int: n + ceil(n/16) ints, ws_f64: 4 * (r + n) doubles */
 int mused_lu_permute_l(double* Y, int n, int r, long ld, int* ws_int, double* ws_f64, void* stream);
+/* Diagnostics, no device needed.  mused_lu_mode: the LU variant MUSED_LU_MODE / MUSED_LU_BLOCKED ask for, read once per
+ * process: 0 column-at-a-time, 1 blocked panels (the default), 2 one launch per column.  mused_lu_path: the variant
+ * mused_lu_permute_l runs for an n x r panel (the blocked panels hold at most 10,240 rows; above that the column-at-a-time
+ * kernels run); -1 for a shape it rejects.  All three variants give the same bits. */
+int mused_lu_mode(void);
+int mused_lu_path(int n, int r);
 /* ws_f64: r + ceil(n/512) * r + 2 n doubles; n >= r */
 int mused_qr_economic(double* Y, int n, int r, long ldy, double* Q, long ldq, double* ws_f64, void* stream);
 /* BLOCKING (creates/destroys its plan): eigen-decomposition of `batch` symmetric n x n matrices, n even */

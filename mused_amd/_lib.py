@@ -82,6 +82,8 @@ _PROTOS = {
     "mused_spmm_binary_path": (_i, [_i, _i, _l, _l, _i, _i]),
     "mused_spmm_force_path": (_i, [_i]),
     "mused_lu_permute_l": (_i, [_vp, _i, _i, _l, _vp, _vp, _vp]),
+    "mused_lu_mode": (_i, []),
+    "mused_lu_path": (_i, [_i, _i]),
     "mused_qr_economic": (_i, [_vp, _i, _i, _l, _vp, _l, _vp, _vp]),
     "mused_syevj_batched": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "mused_gemm_f64": (_i, [_i, _i, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _d, _vp]),

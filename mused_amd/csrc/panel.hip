@@ -359,6 +359,28 @@ __global__ __launch_bounds__(256) void luc_step_kernel(double* __restrict__ Y, i
   }
 }
 
+// MUSED_LU_MODE / MUSED_LU_BLOCKED, read once per process: 0 column-at-a-time (2 launches per column), 1 blocked panels,
+// 2 one launch per column
+static int lu_mode() {
+  static const int mode = [] {
+    const char* ub = getenv("MUSED_LU_BLOCKED");
+    const char* um = getenv("MUSED_LU_MODE");
+    if (um) return atoi(um);
+    return (ub && ub[0] == '0') ? 0 : 1;
+  }();
+  return mode;
+}
+
+// the variant lu_permute_l runs for this shape and workspace (numbered as lu_mode): the blocked panels hold at most 10,240
+// rows, and a variant whose buffers do not fit behind prow gives way to the column-at-a-time kernels
+static int lu_path(int n, int r, long ws_f64_len) {
+  const int npc = cdiv(n, LUC_ROWS);
+  // candidate buffers of the one-launch-per-column path: 2 x npc doubles and 2 x npc ints behind prow[r]
+  if (lu_mode() == 2 && ws_f64_len >= (long)r + 3l * npc + 2) return 2;
+  if (lu_mode() != 0 && n <= 10240 && ws_f64_len >= (long)LU_NB * ((long)r + n)) return 1;
+  return 0;
+}
+
 // ws_f64_len: doubles available behind prow (the blocked path needs LU_NB * (r + n))
 int lu_permute_l(double* Y, int n, int r, long ld, int* pivstep, double* prow, long ws_f64_len, hipStream_t st) {
   // workspace layout, column-at-a-time path: pivstep[n] ints, then npart ints of candidate rows; prow[r] doubles,
@@ -367,24 +389,16 @@ int lu_permute_l(double* Y, int n, int r, long ld, int* pivstep, double* prow, l
   const int npart = cdiv(n, LU_ROWS_PER_WG);
   int zrc = zero_ints(pivstep, n, st);
   if (zrc) return zrc;
-  static const int lu_mode = [] {  // 0 column-at-a-time (2 launches per column), 1 blocked panels, 2 one launch per column
-    const char* ub = getenv("MUSED_LU_BLOCKED");
-    const char* um = getenv("MUSED_LU_MODE");
-    if (um) return atoi(um);
-    return (ub && ub[0] == '0') ? 0 : 1;
-  }();
   const int npc = cdiv(n, LUC_ROWS);
-  // candidate buffers of the one-launch-per-column path: 2 x npc doubles and 2 x npc ints behind prow[r]
-  const bool percol = lu_mode == 2 && ws_f64_len >= (long)r + 3l * npc + 2;
-  const bool blocked = !percol && lu_mode != 0 && n <= 10240 && ws_f64_len >= (long)LU_NB * ((long)r + n);
-  if (percol) {
+  const int path = lu_path(n, r, ws_f64_len);
+  if (path == 2) {
     double* pval = prow + r;
     int* pidx = reinterpret_cast<int*>(pval + 2l * npc);
     hipLaunchKernelGGL(luc_first_kernel, dim3(npc), dim3(256), 0, st, Y, n, ld, pivstep, pval, pidx);
     for (int j = 0; j < k; ++j)
       hipLaunchKernelGGL(luc_step_kernel, dim3(npc), dim3(256), sizeof(double) * (r - j), st, Y, n, r, ld, j, k, npc, pivstep,
                          pval, pidx);
-  } else if (blocked) {
+  } else if (path == 1) {
     double* prowN = prow;
     double* pc = prow + (long)LU_NB * r;
     int nbp = 0;
@@ -575,6 +589,15 @@ extern "C" {
 int mused_lu_permute_l(double* Y, int n, int r, long ld, int* ws_int, double* ws_f64, void* stream) {
   MUSED_REQUIRE(Y && ws_int && ws_f64 && n > 0 && r > 0 && ld >= r, "mused_lu_permute_l: bad arguments");
   return lu_permute_l(Y, n, r, ld, ws_int, ws_f64, 4l * ((long)r + n), (hipStream_t)stream);
+}
+
+// diagnostics, no device needed: the variant the environment asks for (0 column-at-a-time, 1 blocked panels, 2 one launch
+// per column; read once per process) and the one mused_lu_permute_l runs for an n x r panel with its documented workspace
+int mused_lu_mode(void) { return lu_mode(); }
+
+int mused_lu_path(int n, int r) {
+  if (n <= 0 || r <= 0) return -1;
+  return lu_path(n, r, 4l * ((long)r + n));
 }
 
 // Q (n x r, ldq) <- economic Householder QR of Y (n x r, ldy; destroyed).  n >= r.
