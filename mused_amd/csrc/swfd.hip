@@ -12,7 +12,8 @@
 //     decide: sort lam, delta = lam[l-1], s2 = max(lam - delta, 0); rows with s2 >= theta_s are
 //             dumped to the snapshot ring, the rest kept; Wc_s = diag(sqrt(s2/lam)) U[:, top l]^T
 //     T_s   = Wc_s buf_s                       (l x d)     MFMA fp64 GEMM, K = 2l
-//     scatter T_s rows to buf_s (kept) / snapshot ring (dumped), zero the tail.
+//     settle: T_s rows to buf_s (kept) / snapshot ring (dumped), the call's next block behind the kept rows, zeros over
+//             the rows the rotation freed (swfd_settle_kernel; MUSED_SWFD_SETTLE=0: scatter, zero the tail, append apart).
 // Control flow is data independent (the rotation schedule depends only on the row counter),
 // all data-dependent decisions (dumps, expiry, level choice) stay on the device: no host sync
 // anywhere on the update or query path.
@@ -33,7 +34,17 @@ struct Swfd {
   bool twin;  // MAIN and AUX of every level still identical (both empty at the start of this epoch, no state imported)
   int sweeps;
   // persistent state
+  // THE ZERO TAIL.  A live sketch's buffer is [kept rows ; pending rows ; +0.0]: at every launch boundary its rows from
+  // nk + pend on are +0.0 (nk = meta[s][0]).  The Gram product, the reduced solver orders (offs) and the K bound of the
+  // rotate product (kact) rely on it, and the settle kernel relies on it to clear only the rows a rotation frees.  Writers:
+  // creation and begin_epoch (memset), swfd_restart_kernel (MAIN <- a whole AUX buffer, AUX <- 0), append (rows below
+  // nk + pend), settle / scatter (clear up to the rows in use before the rotation).  import_half and begin_epoch with a
+  // blob copy bytes nobody has checked: they set `tail_dirty`, and the next rotation clears up to row n2.  mused_fd_rotate
+  // declares all n2 rows in use.  A frozen MAIN level (rep < 0) is outside the invariant until AUX replaces it.
   double* buf;         // S x n2 x d
+  bool tail_dirty;     // rows beyond nk + pend may hold anything (an imported blob): the next rotation clears to row n2
+  bool settle;         // one settle kernel after the rotate product (scatter + the next block's append); MUSED_SWFD_SETTLE=0: off
+  int* used;           // S         rows in use before the rotation under way (old nk + pend), left by swfd_decide_kernel; null: settle off
   double* queue;       // S x cap x d
   long long* qt;       // S x cap   snapshot timestamps
   int* meta;           // S x 4     {nk, qhead, qcount, dumps the next level did not make, since the last clear}
@@ -82,6 +93,56 @@ __device__ __forceinline__ double row_elem<BitWord>(const BitWord* row, int c) {
   return (double)((row[c >> 6].w >> (c & 63)) & 1ull);
 }
 
+// Elements c and c + 1 (c even) of a row as one access: 16 bytes in for double / int64 rows, 8 for float rows, one word
+// for bit rows (c even: both bits sit in the same word).  The conversions are row_elem's.
+template <typename T>
+__device__ __forceinline__ double2 row_pair(const T* row, int c);
+template <>
+__device__ __forceinline__ double2 row_pair<double>(const double* row, int c) { return *(const double2*)(row + c); }
+template <>
+__device__ __forceinline__ double2 row_pair<long long>(const long long* row, int c) {
+  const longlong2 v = *(const longlong2*)(row + c);
+  return make_double2((double)v.x, (double)v.y);
+}
+template <>
+__device__ __forceinline__ double2 row_pair<float>(const float* row, int c) {
+  const float2 v = *(const float2*)(row + c);
+  return make_double2((double)v.x, (double)v.y);
+}
+template <>
+__device__ __forceinline__ double2 row_pair<BitWord>(const BitWord* row, int c) {
+  const unsigned long long w = row[c >> 6].w >> (c & 63);
+  return make_double2((double)(w & 1ull), (double)((w >> 1) & 1ull));
+}
+// bytes a source row has to be aligned to for row_pair (its base, pitch and lane stride all enter the row's address)
+template <typename T> struct RowPairAlign { static constexpr unsigned long long mask = 15; };
+template <> struct RowPairAlign<float> { static constexpr unsigned long long mask = 7; };
+template <> struct RowPairAlign<BitWord> { static constexpr unsigned long long mask = 7; };
+
+// The row movers of the sketch: one workgroup moves one row of d doubles, 16 bytes per lane and store when d is even and
+// both rows are aligned for it (8-byte accesses run at 0.54-0.70 of that rate), one element per lane otherwise.  Rows of
+// buf, queue and T (hipMalloc bases, pitch d doubles) are 16-byte aligned whenever d is even; a caller's rows need not be.
+template <typename T>
+__device__ __forceinline__ void row_copy(double* __restrict__ dst, const T* __restrict__ src, int d) {
+  const bool wide = (d & 1) == 0 && ((unsigned long long)dst & 15ull) == 0 &&
+                    ((unsigned long long)src & RowPairAlign<T>::mask) == 0;
+  if (wide) {
+    double2* dst2 = (double2*)dst;
+    for (int c = threadIdx.x; c < (d >> 1); c += blockDim.x) dst2[c] = row_pair<T>(src, 2 * c);
+  } else {
+    for (int c = threadIdx.x; c < d; c += blockDim.x) dst[c] = row_elem<T>(src, c);
+  }
+}
+
+__device__ __forceinline__ void row_zero(double* __restrict__ dst, int d) {
+  if ((d & 1) == 0 && ((unsigned long long)dst & 15ull) == 0) {
+    double2* dst2 = (double2*)dst;
+    for (int c = threadIdx.x; c < (d >> 1); c += blockDim.x) dst2[c] = make_double2(0.0, 0.0);
+  } else {
+    for (int c = threadIdx.x; c < d; c += blockDim.x) dst[c] = 0.0;
+  }
+}
+
 template <typename T>
 __global__ void swfd_append_kernel(const T* __restrict__ X, long ldx, long lane_stride, int per_lane, int m, int d,
                                    int n2, int pend, const int* __restrict__ meta, double* __restrict__ buf) {
@@ -89,9 +150,7 @@ __global__ void swfd_append_kernel(const T* __restrict__ X, long ldx, long lane_
   X += (long)(s / per_lane) * lane_stride;
   const int row = meta[s * 4 + 0] + pend + r;
   if (row >= n2) return;  // cannot happen by construction (nk <= l - 1, pend + m <= l)
-  double* dst = buf + ((long)s * n2 + row) * d;
-  const T* src = X + (long)r * ldx;
-  for (int c = threadIdx.x; c < d; c += blockDim.x) dst[c] = row_elem<T>(src, c);
+  row_copy<T>(buf + ((long)s * n2 + row) * d, X + (long)r * ldx, d);
 }
 
 // epoch start: MAIN <- AUX, AUX <- empty  (sketch index = kind * L + level)
@@ -218,7 +277,8 @@ __global__ __launch_bounds__(1024) void swfd_decide_kernel(const double* __restr
                                                           const double* __restrict__ theta, int* __restrict__ meta,
                                                           long long* __restrict__ qt, long long* __restrict__ dropped,
                                                           int* __restrict__ plan, int* __restrict__ keep_src,
-                                                          double* __restrict__ Wc, const int* __restrict__ rep) {
+                                                          double* __restrict__ Wc, const int* __restrict__ rep,
+                                                          int* __restrict__ used, int pend) {
   __shared__ double lam[1024];
   __shared__ int order[1024];
   __shared__ double scale[512];  // sqrt(s2 / lam) of the top-l rows (0 = discarded)
@@ -324,6 +384,8 @@ __global__ __launch_bounds__(1024) void swfd_decide_kernel(const double* __restr
     plan[(s * ell + t) * 2 + 1] = pos;
   }
   if (t == 0) {
+    // (the rows in use before this rotation: the settle kernel clears the buffer up to there and no further)
+    if (used) used[s] = min(n2, meta[s * 4 + 0] + pend);
     meta[s * 4 + 0] = nk;
     meta[s * 4 + 1] = (head1 + nevict) % cap;
     meta[s * 4 + 2] = cnt1 + nd - nevict;
@@ -363,7 +425,49 @@ __global__ void swfd_scatter_kernel(const double* __restrict__ T, const int* __r
   }
 }
 
-static int swfd_rotate_all(Swfd* h, hipStream_t st) {
+// The scatter and the append of the next block in one pass (round 8).  Workgroup (rho, s) settles row rho of sketch s:
+//   rho < l and direction rho dumped     T row rho -> its slot of the snapshot ring              (as the scatter)
+//   rho < nk                             the kept row of T[rep[s]]                               (as the scatter)
+//   nk <= rho < nk + nxt                 row rho - nk of the call's next block X, converted as row_elem does (as the append
+//                                        that would follow: pend = 0 behind a rotation)
+//   nk + nxt <= rho < used[s]            +0.0: the rows the rotation has freed.  Rows from used[s] on are +0.0 already (the
+//                                        zero tail of Swfd::buf) and are not touched; fill_all: up to n2 (tail_dirty)
+// A frozen MAIN sketch (rep < 0) gets what the pair gives it: the next rows at meta[s][0] + r, nothing else.
+// nxt = 0 (X may be null): the scatter with the shorter zero range.  nk <= l - 1 and nxt <= l: nk + nxt < n2 = the grid.
+template <typename Src>
+__global__ void swfd_settle_kernel(const double* __restrict__ T, const int* __restrict__ plan,
+                                   const int* __restrict__ keep_src, const int* __restrict__ meta,
+                                   const int* __restrict__ used, int fill_all, double* __restrict__ buf,
+                                   double* __restrict__ queue, int n2, int ell, int cap, int d, const int* __restrict__ rep,
+                                   const Src* __restrict__ X, long ldx, long lane_stride, int per_lane, int nxt) {
+  const int rho = blockIdx.x, s = blockIdx.y;
+  const int sr = rep ? rep[s] : s;
+  const int nk = meta[s * 4 + 0];
+  if (sr < 0) {  // dead MAIN sketch: frozen, but the raw rows still land behind its kept rows
+    if (rho < nxt && nk + rho < n2)
+      row_copy<Src>(buf + ((long)s * n2 + nk + rho) * d, X + (long)(s / per_lane) * lane_stride + (long)rho * ldx, d);
+    return;
+  }
+  const double* Ts = T + (long)sr * ell * d;
+  if (rho < ell && plan[(s * ell + rho) * 2] == 2) {
+    const int slot = plan[(s * ell + rho) * 2 + 1];
+    row_copy<double>(queue + ((long)s * cap + slot) * d, Ts + (long)rho * d, d);
+  }
+  double* dst = buf + ((long)s * n2 + rho) * d;
+  if (rho < nk) {
+    row_copy<double>(dst, Ts + (long)keep_src[s * ell + rho] * d, d);
+  } else if (rho < nk + nxt) {
+    row_copy<Src>(dst, X + (long)(s / per_lane) * lane_stride + (long)(rho - nk) * ldx, d);
+  } else if (rho < (fill_all ? n2 : used[s])) {
+    row_zero(dst, d);
+  }
+}
+
+// One rotation of all sketches.  (next, nxt): the first nxt rows of the block that follows in the same append call (row pitch
+// ldx, lanes lane_stride apart), which the settle kernel puts behind the kept rows; nxt = 0: none.  Leaves pend = 0: the
+// caller counts the nxt rows when its loop reaches them.
+template <typename Src>
+static int swfd_rotate_all(Swfd* h, hipStream_t st, const Src* next, long ldx, long lane_stride, int nxt) {
   const int S = h->S, n2 = h->n2, d = h->d, ell = h->ell;
   int rc;
   if (h->rep)
@@ -385,12 +489,20 @@ static int swfd_rotate_all(Swfd* h, hipStream_t st) {
   if ((rc = eig_plan_run_inplace(h->eig, nullptr, nullptr, st, true))) return rc;
   const EigColumns e = eig_plan_columns(h->eig);
   hipLaunchKernelGGL(swfd_decide_kernel, dim3(S), dim3(1024), 0, st, e.lam, e.cols, e.ld, n2, ell, h->cap, h->N, h->now_dev,
-                     h->theta, h->meta, h->qt, h->dropped, h->plan, h->keep_src, h->Wc, h->rep);
+                     h->theta, h->meta, h->qt, h->dropped, h->plan, h->keep_src, h->Wc, h->rep, h->settle ? h->used : nullptr,
+                     h->pend);
   if ((rc = gemm_f64(true, false, h->Wc, n2, (long)ell * n2, h->buf, d, (long)n2 * d, h->T, d, (long)ell * d, ell, d,
                      n2, S, 1.0, st, h->rep, h->list, h->kact)))
     return rc;
-  hipLaunchKernelGGL(swfd_scatter_kernel, dim3(n2, S), dim3(256), 0, st, h->T, h->plan, h->keep_src, h->meta, h->buf,
-                     h->queue, n2, ell, h->cap, d, h->rep);
+  if (h->settle) {
+    hipLaunchKernelGGL(swfd_settle_kernel<Src>, dim3(n2, S), dim3(256), 0, st, h->T, h->plan, h->keep_src, h->meta, h->used,
+                       h->tail_dirty ? 1 : 0, h->buf, h->queue, n2, ell, h->cap, d, h->rep, next, ldx, lane_stride, 2 * h->L,
+                       nxt);
+    h->tail_dirty = false;
+  } else {
+    hipLaunchKernelGGL(swfd_scatter_kernel, dim3(n2, S), dim3(256), 0, st, h->T, h->plan, h->keep_src, h->meta, h->buf,
+                       h->queue, n2, ell, h->cap, d, h->rep);
+  }
   MUSED_LAUNCH_CHECK();
   h->pend = 0;
   return MUSED_OK;
@@ -477,6 +589,7 @@ static int swfd_append_t(Swfd* h, const T* X, long ldx, long lane_stride, long m
   // blocks of this call already rotated into pre_out: [pre_first, pre_first + pre_n), in call-row coordinates
   PreBlocks pb;
   int pre_n = 0, pre_next = 0;
+  int placed = 0;  // rows of the block at r that the last rotation of this call has already put into the buffers
   while (r < m) {
     if (h->i > 0 && h->i % h->N == 0 && h->restart_mark != h->i) {
       // first row of a new epoch (pend == 0 here: the epoch-end rotation has run)
@@ -509,7 +622,14 @@ static int swfd_append_t(Swfd* h, const T* X, long ldx, long lane_stride, long m
       }
       from_pre = true;
     }
-    if (from_pre) {
+    if (placed > 0) {
+      // the rotation before this block has put these rows in place (swfd_settle_kernel): only the counters move
+      if (placed != take) {
+        set_error("mused_swfd_append: internal: %d rows placed ahead, the block takes %ld", placed, take);
+        return MUSED_ERR_STATE;
+      }
+      placed = 0;
+    } else if (from_pre) {
       const double* src = h->pre_out + (long)pre_next * h->lanes * h->ell * h->d;
       hipLaunchKernelGGL(swfd_append_kernel<double>, dim3((int)take, h->S), dim3(256), 0, st, src, (long)h->d,
                          (long)h->ell * h->d, 2 * h->L, (int)take, h->d, h->n2, h->pend, h->meta, h->buf);
@@ -523,7 +643,17 @@ static int swfd_append_t(Swfd* h, const T* X, long ldx, long lane_stride, long m
     h->i += take;
     r += take;
     if (take == until) {
-      if ((rc = swfd_rotate_all(h, st))) return rc;
+      // The block that follows in this call -- whole, or as far as the call goes -- is settled by the rotation itself,
+      // unless its first row starts an epoch (swfd_restart runs between the two) or the blocks are pre-rotated.
+      long nxt = 0;
+      if (h->settle && h->pre_chunk == 0 && r < m && h->i % h->N != 0) {
+        const long ie = h->i % h->N;
+        long u = h->ell - (ie % h->ell);
+        if (h->N - ie < u) u = h->N - ie;
+        nxt = (m - r) < u ? (m - r) : u;
+      }
+      if ((rc = swfd_rotate_all<T>(h, st, nxt ? X + r * ldx : nullptr, ldx, lane_stride, (int)nxt))) return rc;
+      placed = (int)nxt;
     }
   }
   return MUSED_OK;
@@ -764,6 +894,9 @@ static int swfd_create_impl(Swfd* h, long N, double R, int d, int ell, int sweep
     }
     const char* sd = getenv("MUSED_SWFD_SKIP_DEAD");
     h->skip_dead = (sd && sd[0] == '0') ? 0 : 1;
+    // MUSED_SWFD_SETTLE=0: every rotation ends with swfd_scatter_kernel and every block starts with swfd_append_kernel
+    h->settle = !off("MUSED_SWFD_SETTLE");
+    if (h->settle) ZALLOC(h->used, 4 * S);
   }
   ZALLOC(h->dropped, 8 * S);
   ZALLOC(h->status, 4);
@@ -834,7 +967,7 @@ int mused_swfd_destroy(void* handle) {
   if (h->eigp) eig_plan_destroy(h->eigp);
   void* bufs[] = {h->buf, h->queue, h->qt, h->meta, h->dropped, h->theta, h->T, h->Wc, h->plan,
                   h->keep_src, h->now_dev, h->stack, h->Wq, h->Bout, h->sig_out, h->qinfo, h->qsel,
-                  h->rep, h->pre_in, h->pre_out, h->pre_gram, h->status, h->gpart, h->list, h->offs, h->kact, h->ostat};
+                  h->rep, h->pre_in, h->pre_out, h->pre_gram, h->status, h->gpart, h->list, h->offs, h->kact, h->ostat, h->used};
   for (void* b : bufs) (void)hipFree(b);
   if (h->status_host) (void)hipHostFree(h->status_host);
   delete h;
@@ -910,6 +1043,17 @@ int mused_swfd_debug_state(void* handle, int* rep_out, int* meta_out) {
   if (h->rep && rep_out) MUSED_CHECK_HIP(hipMemcpy(rep_out, h->rep, 4 * (size_t)h->S, hipMemcpyDeviceToHost));
   if (meta_out) MUSED_CHECK_HIP(hipMemcpy(meta_out, h->meta, 16 * (size_t)h->S, hipMemcpyDeviceToHost));
   return h->rep ? 1 : 0;
+}
+
+// Diagnostic (not part of the declared ABI): used_out[S] = the rows every sketch had in use before its last rotation (what
+// the settle kernel cleared up to; tools/swfd_settle_bytes.py).  Returns 1 when the handle settles, else 0 (nothing copied).
+int mused_swfd_debug_used(void* handle, int* used_out) {
+  Swfd* h = (Swfd*)handle;
+  if (!h || !used_out) return MUSED_ERR_ARG;
+  if (!h->used) return 0;
+  MUSED_CHECK_HIP(hipDeviceSynchronize());
+  MUSED_CHECK_HIP(hipMemcpy(used_out, h->used, 4 * (size_t)h->S, hipMemcpyDeviceToHost));
+  return 1;
 }
 
 // Diagnostic (not part of the declared ABI): out[18] = {rotations, representatives, representatives by the order their Gram
@@ -990,6 +1134,7 @@ int mused_swfd_import_half(void* handle, int kind, const void* src, void* stream
   MUSED_REQUIRE(h && src && (kind == 0 || kind == 1), "mused_swfd_import_half: bad arguments");
   MUSED_REQUIRE(h->lanes == 1, "mused_swfd_import_half: single-lane handles only");
   h->twin = false;
+  h->tail_dirty = true;  // (the blob's rows behind nk + pend are the exporter's word, not this handle's)
   return half_copy(h, kind, (char*)src, false, (hipStream_t)stream);
 }
 
@@ -1016,6 +1161,7 @@ int mused_swfd_begin_epoch(void* handle, long rows_seen, const void* main_half, 
   h->pend = 0;
   h->restart_mark = rows_seen;  // the epoch-start swap is what this call just did
   h->twin = (main_half == nullptr);
+  h->tail_dirty = (main_half != nullptr);  // every buffer has just been cleared; a blob brings rows of its own
   return MUSED_OK;
 }
 
@@ -1037,7 +1183,7 @@ extern "C" int mused_fd_rotate(double* buf, int ell, int d, double* sigma_out, i
   hipError_t e = hipMemcpyAsync(h->buf, buf, bytes, hipMemcpyDeviceToDevice, st);
   h->i = 2 * ell;
   h->pend = 2 * ell;  // (no kept rows: the whole buffer counts as rows in use)
-  if (e == hipSuccess) rc = mused::swfd_rotate_all(h, st);
+  if (e == hipSuccess) rc = mused::swfd_rotate_all<double>(h, st, nullptr, 0, 0, 0);  // (used = 2 l: the whole buffer is settled)
   if (e == hipSuccess && !rc) e = hipMemcpyAsync(buf, h->buf, bytes, hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess && !rc) {
     hipLaunchKernelGGL(mused::swfd_finish_rows_kernel, dim3(ell), dim3(256), 0, st, buf, d, sigma_out);
