@@ -16,8 +16,17 @@
 // LDS buffers, next tile prefetched into registers under the MFMAs.
 // One f64 MFMA is 64 cycles per SIMD, 16 of them per 8 ds_read_b64: the loop is
 // matrix-pipe bound by construction.
+// Symmetric launches (GemmArgs::sym): tiles on or above the diagonal only.  An off-diagonal tile runs the loop above and
+// stores its result twice (the second time transposed through LDS); a diagonal tile stages ONE operand and computes the
+// 36 blocks with block-row <= block-column, 9 MFMAs per wave and K sub-step on 4 / 6 / 7 / 8 ds_read_b64 ("diagonal
+// tile" below; measured alone at order 256: 0.82 - 0.84 of the time of three ordinary tiles).
+// v_mfma_f64_16x16x4_f64 is an FMA chain over k whose products do not depend on which operand is A
+// and which is B (measured: the symmetric and the full product of one matrix agree in every bit), so the mirrored
+// entries carry the bits a direct computation gives.
 #pragma once
+#include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include "common.h"
 
 namespace mused {
@@ -48,7 +57,11 @@ struct GemmArgs {
   const int* kact;  // optional (plain batched launches): entry z multiplies over k < kact[z] only -- for operands that are
                     // exact zeros from there on: the skipped terms are fma(0, 0, acc), the result is bit-identical
   int sym;  // C = A A^T (A == B, M == N) with a symmetric epilogue: only tiles on or above the diagonal are computed,
-            // each off-diagonal tile is also written mirrored (epi(z, col, row, v)): half the MFMA work
+            // each off-diagonal tile is also written mirrored (epi.put(z, col, row, epi.value(col, row, v))), and a
+            // diagonal tile computes its 36 blocks of 16 x 16 on or above the diagonal from the one staged operand and
+            // mirrors the 28 above it: 36 + 64 + 36 of 4 x 64 block products for a 2 x 2 grid of tiles.  Callers set 0 / 1;
+            // the launcher turns 1 into 2 (diagonal tiles as described) unless MUSED_GEMM_SYM_DIAG=0 (1: diagonal tiles
+            // run the ordinary main loop).  Bit for bit the full product either way.
 };
 
 // ---- staging -------------------------------------------------------------
@@ -254,6 +267,169 @@ __device__ __forceinline__ void gemm_tile_mainloop(const GemmArgs& g, const TA* 
   }
 }
 
+// ---- diagonal tile of a symmetric launch -----------------------------------
+// A 128 x 128 tile on the diagonal of C = A A^T is symmetric itself: of its 8 x 8 blocks of 16 x 16 only the 36 with
+// block-row i <= block-column j are computed, 9 per wave, and the 28 below the diagonal are the mirrors of those above.
+// Both MFMA operands are fragments of the ONE staged panel: fragment b = As[k][b * 16 + (lane & 15)] is the row fragment
+// of block-row b and the column fragment of block-column b alike, so nothing is loaded or stored for B.
+// Block n of wave w is (DIAG_I[w][n], DIAG_J[w][n]); wave w reads fragments 0 .. DIAG_NF[w] - 1 (4 / 6 / 7 / 8 ds_read_b64
+// per 9 MFMAs).  A block of column j with i < j is mirrored in the group of its column: DIAG_GRP[w][.] = {j, first i, count}.
+constexpr int DIAG_I[4][9] = {{0, 0, 1, 0, 1, 2, 0, 1, 2}, {3, 0, 1, 2, 3, 4, 0, 1, 2}, {3, 4, 5, 0, 1, 2, 3, 4, 5}, {6, 0, 1, 2, 3, 4, 5, 6, 7}};
+constexpr int DIAG_J[4][9] = {{0, 1, 1, 2, 2, 2, 3, 3, 3}, {3, 4, 4, 4, 4, 4, 5, 5, 5}, {5, 5, 5, 6, 6, 6, 6, 6, 6}, {6, 7, 7, 7, 7, 7, 7, 7, 7}};
+constexpr int DIAG_NF[4] = {4, 6, 7, 8};
+constexpr int DIAG_NGRP[4] = {3, 2, 2, 1};
+constexpr int DIAG_GRP[4][3][3] = {{{1, 0, 1}, {2, 0, 2}, {3, 0, 3}}, {{4, 0, 4}, {5, 0, 3}, {0, 0, 0}}, {{5, 3, 2}, {6, 0, 6}, {0, 0, 0}}, {{7, 0, 7}, {0, 0, 0}, {0, 0, 0}}};
+constexpr int DIAG_PATCH_LD = 130;  // pitch of the wave's 16-row transposition patch: 2 (mod 32), writes (li, kq) -> li * 130 + kq hit 32 banks
+
+constexpr int diag_acc_index(int w, int i, int j) {
+  for (int n = 0; n < 9; ++n)
+    if (DIAG_I[w][n] == i && DIAG_J[w][n] == j) return n;
+  return -1;
+}
+
+// the 4 K sub-steps of one staged panel for wave W: 9 accumulators, every index a compile-time constant
+template <int W, int N = 0>
+__device__ __forceinline__ void diag_mfma9(const double (&f)[8], v4f64 (&acc)[9]) {
+  if constexpr (N < 9) {
+    constexpr int i = DIAG_I[W][N], j = DIAG_J[W][N];
+    acc[N] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[i], f[j], acc[N], 0, 0, 0);
+    diag_mfma9<W, N + 1>(f, acc);
+  }
+}
+template <int W>
+__device__ __forceinline__ void diag_kstep(const double* __restrict__ a, v4f64 (&acc)[9]) {
+#pragma unroll
+  for (int kk = 0; kk < GEMM_BK / 4; ++kk) {
+    double f[8];
+#pragma unroll
+    for (int b = 0; b < 8; ++b) f[b] = (b < DIAG_NF[W]) ? a[kk * 4 * GEMM_LD + b * 16] : 0.0;
+    diag_mfma9<W>(f, acc);
+  }
+}
+
+// K loop of a diagonal tile: as gemm_tile_mainloop with one operand.  Every computed element is the same chain as there
+// (K steps of 16 ascending, four MFMAs per step in kk order, from +0.0).
+template <typename TA, bool A_KC, bool VEC>
+__device__ __forceinline__ void gemm_tile_mainloop_diag(const GemmArgs& g, const TA* __restrict__ A, int m0, int k_lo, int k_hi,
+                                                        double* As, int wave, v4f64 (&acc)[9]) {
+  const int lane = threadIdx.x & 63;
+  const int kq = lane >> 4, li = lane & 15;
+#pragma unroll
+  for (int n = 0; n < 9; ++n) acc[n] = (v4f64){0.0, 0.0, 0.0, 0.0};
+
+  TA ra[8];
+  const int nkt = (k_hi - k_lo + GEMM_BK - 1) / GEMM_BK;
+  const bool full_m = VEC && m0 + GEMM_BM <= g.M;  // (uniform over the workgroup)
+  auto load_tile = [&](int kt) {
+    const int k0 = k_lo + kt * GEMM_BK;
+    if (full_m && k0 + GEMM_BK <= k_hi) {
+      if (A_KC) stage_load_kc_full<TA>(A, g.lda, m0, k0, ra); else stage_load_mc_full<TA>(A, g.lda, m0, k0, ra);
+      return;
+    }
+    if (A_KC) stage_load_kc<TA, VEC>(A, g.lda, m0, g.M, k0, k_hi, ra);
+    else      stage_load_mc<TA, VEC>(A, g.lda, m0, g.M, k0, k_hi, ra);
+  };
+  auto store_tile = [&](int buf) {
+    double* a = As + buf * GEMM_BK * GEMM_LD;
+    if (A_KC) stage_store_kc(a, ra); else stage_store_mc(a, ra);
+  };
+
+  if (nkt > 0) {
+    load_tile(0);
+    store_tile(0);
+  }
+  __syncthreads();
+
+  int cur = 0;
+  for (int kt = 0; kt < nkt; ++kt) {
+    const bool more = (kt + 1 < nkt);
+    if (more) load_tile(kt + 1);
+    const double* a = As + cur * GEMM_BK * GEMM_LD + kq * GEMM_LD + li;
+    switch (wave) {  // wave-uniform
+      case 0: diag_kstep<0>(a, acc); break;
+      case 1: diag_kstep<1>(a, acc); break;
+      case 2: diag_kstep<2>(a, acc); break;
+      default: diag_kstep<3>(a, acc); break;
+    }
+    if (more) store_tile(cur ^ 1);
+    __syncthreads();
+    cur ^= 1;
+  }
+}
+
+// Stores of wave W's 9 blocks, and of the mirrors of those above the diagonal.  The mirrors of the blocks of one column j
+// (block-rows i0 .. i0 + cnt - 1) are rows j * 16 .. + 15, columns i0 * 16 .. of the tile: transposed through a wave-private
+// LDS patch of 16 rows, so that a store instruction writes runs of at least 128 contiguous bytes (512 from cnt = 4 on).
+template <int W, int GI, int II, typename Epi>
+__device__ __forceinline__ void diag_mirror_fill(const GemmArgs& g, const Epi& epi, int m0, double* patch, const v4f64 (&acc)[9]) {
+  constexpr int j = DIAG_GRP[W][GI][0], i0 = DIAG_GRP[W][GI][1], cnt = DIAG_GRP[W][GI][2];
+  if constexpr (II < cnt) {
+    constexpr int n = diag_acc_index(W, i0 + II, j);
+    static_assert(n >= 0, "block not held by this wave");
+    const int lane = threadIdx.x & 63;
+    const int kq = lane >> 4, li = lane & 15;
+    const int col = m0 + j * 16 + li;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rl = II * 16 + kq + 4 * r;
+      const int rg = m0 + i0 * 16 + rl;
+      // entry (col, row) of the result: evaluated in ITS orientation (the epilogue need not be commutative)
+      patch[li * DIAG_PATCH_LD + rl] = (rg < g.M && col < g.N) ? epi.value(col, rg, acc[n][r]) : 0.0;
+    }
+    diag_mirror_fill<W, GI, II + 1>(g, epi, m0, patch, acc);
+  }
+}
+
+template <int W, int GI, typename Epi>
+__device__ __forceinline__ void diag_mirror_groups(const GemmArgs& g, const Epi& epi, int z, int m0, double* patch,
+                                                   const v4f64 (&acc)[9]) {
+  if constexpr (GI < DIAG_NGRP[W]) {
+    constexpr int j = DIAG_GRP[W][GI][0], i0 = DIAG_GRP[W][GI][1], cnt = DIAG_GRP[W][GI][2];
+    constexpr int width = cnt * 16;
+    const int lane = threadIdx.x & 63;
+    diag_mirror_fill<W, GI, 0>(g, epi, m0, patch, acc);
+    // wave-private patch: LDS operations of one wave complete in order, no barrier
+#pragma unroll
+    for (int t = 0; t < width / 4; ++t) {
+      const int idx = t * 64 + lane;
+      const int c = idx / width, off = idx % width;
+      const int rowm = m0 + j * 16 + c, colm = m0 + i0 * 16 + off;
+      if (rowm < g.N && colm < g.M) epi.put(z, rowm, colm, patch[c * DIAG_PATCH_LD + off]);
+    }
+    diag_mirror_groups<W, GI + 1>(g, epi, z, m0, patch, acc);
+  }
+}
+
+template <int W, int N, typename Epi>
+__device__ __forceinline__ void diag_store_blocks(const GemmArgs& g, const Epi& epi, int z, int m0, const v4f64 (&acc)[9]) {
+  if constexpr (N < 9) {
+    const int lane = threadIdx.x & 63;
+    const int col = m0 + DIAG_J[W][N] * 16 + (lane & 15);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = m0 + DIAG_I[W][N] * 16 + (lane >> 4) + 4 * r;
+      if (row < g.M && col < g.N) epi(z, row, col, acc[N][r]);
+    }
+    diag_store_blocks<W, N + 1>(g, epi, z, m0, acc);
+  }
+}
+
+template <int W, typename Epi>
+__device__ __forceinline__ void diag_epilogue(const GemmArgs& g, const Epi& epi, int z, int m0, double* smem,
+                                              const v4f64 (&acc)[9]) {
+  diag_store_blocks<W, 0>(g, epi, z, m0, acc);
+  diag_mirror_groups<W, 0>(g, epi, z, m0, smem + W * (16 * DIAG_PATCH_LD), acc);
+}
+
+// MUSED_GEMM_SYM_DIAG=0: the diagonal tiles of symmetric launches run the ordinary main loop (all 64 blocks, two operands).
+inline int gemm_sym_diag_enabled() {
+  static const int on = [] {
+    const char* s = getenv("MUSED_GEMM_SYM_DIAG");
+    return (s && s[0] == '0') ? 0 : 1;
+  }();
+  return on;
+}
+
 // Epilogue concept:  void operator()(int batch, int row, int col, double v) const
 template <typename TA, typename TB, bool A_KC, bool B_KC, bool VEC, typename Epi>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_f64_kernel(GemmArgs g, Epi epi) {
@@ -312,6 +488,22 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_f64_kernel(GemmArgs g, E
       k_hi = min(g.K, k_lo + g.kchunk);
     } else if (g.kact) {
       k_hi = min(g.K, g.kact[zb]);
+    }
+  }
+
+  if constexpr (std::is_same<TA, TB>::value && A_KC == B_KC) {
+    if (g.sym == 2 && tm == tn) {  // (uniform over the workgroup)
+      const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+      v4f64 acc9[9];
+      gemm_tile_mainloop_diag<TA, A_KC, VEC>(g, A, m0, k_lo, k_hi, smem, w, acc9);
+      // behind the main loop's last barrier every wave is done with the operand buffers: the patches may overwrite them
+      switch (w) {
+        case 0: diag_epilogue<0>(g, epi, z, m0, smem, acc9); break;
+        case 1: diag_epilogue<1>(g, epi, z, m0, smem, acc9); break;
+        case 2: diag_epilogue<2>(g, epi, z, m0, smem, acc9); break;
+        default: diag_epilogue<3>(g, epi, z, m0, smem, acc9); break;
+      }
+      return;
     }
   }
 
@@ -403,6 +595,7 @@ template <typename TA, typename TB, bool A_KC, bool B_KC, typename Epi>
 int gemm_f64_launch_t(GemmArgs g, int batch, Epi epi, bool vec, hipStream_t stream) {
   g.tiles_m = cdiv(g.M, GEMM_BM);
   g.tiles_n = cdiv(g.N, GEMM_BN);
+  if (g.sym) g.sym = gemm_sym_diag_enabled() ? 2 : 1;
   if (g.M <= 0 || g.N <= 0 || batch <= 0) return MUSED_OK;
   dim3 grid(g.sym ? g.tiles_n * (g.tiles_n + 1) / 2 : g.tiles_m * g.tiles_n, 1, batch);
   int rc;
