@@ -656,6 +656,41 @@ long mused_score_ws_bytes(long n_seg, long cells_cap);
 int mused_score_labels(const int* truth, const int* pred, long n_seg, long seg_len, long cells_cap, double* out, int* info,
                        void* ws, long ws_bytes, void* stream);
 
+/* ---- scoring clusters WITHOUT ground truth, csrc/silhouette.hip: sklearn.metrics.silhouette_samples(X, labels,
+ * metric="euclidean") with the sum of the samples, and davies_bouldin_score / calinski_harabasz_score (specification:
+ * mused_amd/silhouette.py, pinned to scikit-learn 1.7).  Any int32 value is a cluster id, -1 included (a cluster like any
+ * other).  The rows are ordered by label (stable radix sort, one gathered copy with an even pitch); the silhouette then walks
+ * the fp64 MFMA distance tiles row tile by row tile, the columns arriving cluster by cluster, and keeps a running sum, a(i)
+ * and the running minimum b(i) per row: O(n + clusters) workspace beside the gathered rows, no n x n and no n x clusters
+ * array.  d(i, j) = sqrt(max(0, |x_i|^2 + |x_j|^2 - 2 x_i.x_j)), exactly 0 for i == j; a(i) = own-cluster sum / (size - 1),
+ * b(i) = smallest mean over the other clusters, s(i) = (b - a) / max(a, b), 0 for a row alone in its cluster and for 0 / 0.
+ * Every sum has one fixed order (no floating-point atomic): two calls on the same inputs give the same bits.  Enqueue-only.
+ * X: n x d fp64 (pitch ld), n <= 2^19, d < 2^20.  labels: n int32 (DEVICE).
+ * samples_out: n fp64 (DEVICE), the caller's row order.
+ * info_out (DEVICE, 16 bytes) = {int32 flags, int32 clusters, fp64 sum of the samples in a fixed order (the score is sum / n)}.
+ *   Flags: 2 a row is not finite (or its squared norm overflows); 4 the number of distinct labels is outside [2, n - 1].
+ *   With a flag samples_out is NOT written and the sum is NaN: raise what scikit-learn raises.
+ * ws: mused_silhouette_ws_bytes(n, d) bytes (32 n + 1024 ceil(n / 1024) + 8 n (d rounded up to even) and alignment; -1 for n
+ *   outside [1, 2^19] or d outside [1, 2^20)), plus 32 S n where the column tiles are cut into S = mused_silhouette_slices(n)
+ *   > 1 slices (n <= 32,640: S <= 16 runs of whole column tiles, so that about 512 workgroups run; the cut clusters are
+ *   closed by a merge kernel in slice order; S depends on n alone).  Scratch only.  Outside these limits, or with a short
+ *   workspace, the call returns an error and launches nothing.  MUSED_SIL_SLICES=1 (read per call): one slice. */
+long mused_silhouette_ws_bytes(long n, int d);
+int mused_silhouette_slices(long n);
+int mused_silhouette(const double* X, long n, int d, long ld, const int* labels, double* samples_out, void* info_out, void* ws,
+                     long ws_bytes, void* stream);
+/* The two cheaper indices from the same sorted order: centroids by a segmented fixed-order reduction, the mean distance of a
+ * cluster's rows to its centroid and the sum of their squares (from the differences x - c), the centroid distances, the two
+ * dispersions.  O(n d + clusters^2 d) work.
+ * out (DEVICE, 2 fp64) = {Davies-Bouldin, Calinski-Harabasz}.  Davies-Bouldin is 0.0 when every mean distance or every
+ *   centroid distance is <= 1e-8 (scikit-learn's allclose), a zero centroid distance counts as infinite; Calinski-Harabasz
+ *   is 1.0 when the within-cluster dispersion is exactly 0.
+ * info_out (DEVICE, 4 int32) = {flags, clusters, 0, 0}, flags as above; with a flag `out` is NOT written.
+ * ws: mused_cluster_indices_ws_bytes(n, d) bytes (what mused_silhouette takes + 8 n d + 8 d + 40 n and alignment). */
+long mused_cluster_indices_ws_bytes(long n, int d);
+int mused_cluster_indices(const double* X, long n, int d, long ld, const int* labels, double* out, int* info_out, void* ws,
+                          long ws_bytes, void* stream);
+
 /* ---- a5-a7: SeqBasedSWFD (swfd submodule; call sites main.py:62,65-67,70) ---------------------- */
 
 /* SeqBasedSWFD(N=, R=, d=, sketch_dim=) */

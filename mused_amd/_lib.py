@@ -125,6 +125,11 @@ _PROTOS = {
     "mused_emst": (_i, [_vp, _l, _i, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "mused_score_ws_bytes": (_l, [_l, _l]),
     "mused_score_labels": (_i, [_vp, _vp, _l, _l, _l, _vp, _vp, _vp, _l, _vp]),
+    "mused_silhouette_ws_bytes": (_l, [_l, _i]),
+    "mused_silhouette_slices": (_i, [_l]),
+    "mused_silhouette": (_i, [_vp, _l, _i, _l, _vp, _vp, _vp, _vp, _l, _vp]),
+    "mused_cluster_indices_ws_bytes": (_l, [_l, _i]),
+    "mused_cluster_indices": (_i, [_vp, _l, _i, _l, _vp, _vp, _vp, _vp, _l, _vp]),
     "mused_swfd_create": (_i, [_l, _d, _i, _i, _i, C.POINTER(_vp)]),
     "mused_swfd_create_lanes": (_i, [_l, _d, _i, _i, _i, _i, C.POINTER(_vp)]),
     "mused_swfd_lanes": (_i, [_vp]),

@@ -579,6 +579,51 @@ def perform_clustering_on_device(emb_dev, n_clusters, seed, emb_host=None, strea
     return out
 
 
+def check_k_candidates(candidates, n):
+    """`candidates` as a list of distinct ints in ascending order; ValueError unless it is a non-empty iterable of ints with
+    2 <= k <= n - 1."""
+    import numbers
+
+    try:
+        ks = list(candidates)
+    except TypeError:
+        raise ValueError(f"candidates must be an iterable of ints, got {candidates!r}") from None
+    if not ks:
+        raise ValueError("candidates is empty")
+    for k in ks:
+        if not isinstance(k, numbers.Integral) or isinstance(k, bool) or not 2 <= int(k) <= n - 1:
+            raise ValueError(f"candidate k = {k!r}: every k must be an int with 2 <= k <= n - 1 = {n - 1}")
+    return sorted({int(k) for k in ks})
+
+
+def select_n_clusters_on_device(embedding, candidates, seed, stream=None, emb_host=None):
+    """k chosen without ground truth: for every k in `candidates`, `perform_clustering_on_device(embedding, k, seed)` and the
+    silhouette score of its labels from csrc/silhouette.hip (metrics_evaluation.internal_metrics_raw).  Returns (best_k,
+    the labels of best_k, {k: score}); the highest score wins, ties go to the smaller k.  A k whose labels hold a single
+    value has no silhouette: its score is NaN and it never wins (all NaN: the smallest k).
+    embedding: (n, d) fp64 CUDA tensor; candidates: a non-empty iterable of ints with 2 <= k <= n - 1 (ValueError otherwise);
+    emb_host: the embedding's host copy if the caller has one (read only by a k-means fallback); stream: both kernels run on
+    it, for which the embedding must be complete (as for perform_clustering_on_device)."""
+    import torch
+
+    from . import metrics_evaluation as me
+
+    if not isinstance(embedding, torch.Tensor) or not embedding.is_cuda or embedding.dim() != 2 \
+            or embedding.dtype != torch.float64:
+        raise ValueError("embedding must be an (n, d) float64 CUDA tensor")
+    ks = check_k_candidates(candidates, embedding.shape[0])
+    scores, best_k, best_labels = {}, None, None
+    for k in ks:   # ascending: a later k replaces the best one only with a strictly higher score
+        labels = perform_clustering_on_device(embedding, k, seed, emb_host=emb_host, stream=stream)
+        flags, clusters, s, _, _, Xd = me.internal_metrics_raw(embedding, labels, stream, indices=False, wait_current=False)
+        if flags & 2:
+            me._raise_flags(flags, clusters, Xd)
+        scores[k] = s
+        if best_k is None or (s == s and not (scores[best_k] >= s)):
+            best_k, best_labels = k, labels
+    return best_k, best_labels, scores
+
+
 def _overlap_costs(prev_clusters, new_clusters, min_overlap):
     up, un = np.unique(prev_clusters), np.unique(new_clusters)
     cost = np.full((len(up), len(un)), np.inf)

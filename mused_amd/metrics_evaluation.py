@@ -220,3 +220,174 @@ def compute_all_metrics(results, subset_size, noise_rate, label_mode, sorting, r
         parts.append(f"processing_time={processing_time:.2f}")
     print("".join(parts))
     return results
+
+
+# ---- scores without ground truth: silhouette, Davies-Bouldin, Calinski-Harabasz (csrc/silhouette.hip) -------------------
+INTERNAL_KEYS = ("silhouette", "davies_bouldin", "calinski_harabasz")
+INTERNAL_MAX_ROWS = 1 << 19   # csrc/silhouette.hip: what the tile grid of dbscan.hip holds, the limit of every tile kernel
+_INTERNAL_WS = {}
+
+
+def _internal_stream(X, stream, wait_current=True):
+    """The stream the kernels and every conversion of their inputs run on: the caller's, behind whatever the current stream
+    holds (tensor arguments) unless `wait_current` is off, or the current one."""
+    import torch
+
+    dev = X.device if isinstance(X, torch.Tensor) and X.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    cur = torch.cuda.current_stream(dev)
+    if stream is None:
+        return cur
+    if wait_current:
+        stream.wait_stream(cur)
+    return stream
+
+
+def _internal_inputs(X, labels):
+    """(X as an (n, d) fp64 CUDA tensor with unit column stride, labels as n int32 CUDA) for the kernels; uploads and
+    conversions run on the current stream (the caller has entered the kernels' stream)."""
+    import torch
+
+    if isinstance(X, torch.Tensor):
+        Xd = X if X.is_cuda else X.cuda()
+    else:
+        a = np.asarray(X)
+        if a.dtype.kind not in "fiub":
+            raise ValueError("X must be numeric")
+        Xd = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
+    if Xd.dim() != 2 or Xd.shape[0] < 1 or Xd.shape[1] < 1:
+        raise ValueError("X must be (n, d) with n, d >= 1")
+    if Xd.dtype != torch.float64:
+        Xd = Xd.to(torch.float64)
+    if Xd.stride(1) != 1 or Xd.stride(0) < Xd.shape[1]:
+        Xd = Xd.contiguous()
+    if isinstance(labels, torch.Tensor):
+        if labels.dtype not in (torch.int32, torch.int64):
+            raise ValueError("labels must be integers")
+        ld = labels.to(Xd.device)
+    else:
+        a = np.asarray(labels)
+        if a.dtype.kind not in "iu" or (a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31)):
+            raise ValueError("labels must be int32 values")
+        ld = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(Xd.device)
+    if tuple(ld.shape) != (Xd.shape[0],):
+        raise ValueError(f"labels must be {Xd.shape[0]} integers, got shape {tuple(ld.shape)}")
+    if Xd.shape[0] > INTERNAL_MAX_ROWS or Xd.shape[1] >= 1 << 20:
+        raise ValueError(f"{Xd.shape[0]} x {Xd.shape[1]} rows: the device indices take at most 2^19 rows "
+                         "(MUSED_SCORE=host scores any size with scikit-learn)")
+    return Xd, ld.to(torch.int32).contiguous()
+
+
+def _internal_ws(kind, need, dev, st):
+    import torch
+
+    key = (kind, dev, st.cuda_stream)
+    ws = _INTERNAL_WS.get(key)
+    if ws is None or ws.numel() < need:
+        if len(_INTERNAL_WS) > 16:
+            _INTERNAL_WS.clear()
+        ws = _INTERNAL_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def silhouette_launch(Xd, labels_d, st, samples=None, info=None):
+    """mused_silhouette enqueued on stream `st` (entered by the caller): (samples n fp64 CUDA, info 16 bytes CUDA = {int32
+    flags, int32 clusters, fp64 sum of the samples}).  Nothing is read."""
+    import torch
+
+    from . import _lib
+    from . import engine as _eng
+
+    n, d = Xd.shape
+    ws = _internal_ws("sil", int(_lib.lib().mused_silhouette_ws_bytes(n, d)), Xd.device, st)
+    if samples is None:
+        samples = torch.empty(n, dtype=torch.float64, device=Xd.device)
+    if info is None:
+        info = torch.empty(16, dtype=torch.uint8, device=Xd.device)
+    _lib.call("mused_silhouette", _eng.ptr(Xd), n, d, Xd.stride(0), _eng.ptr(labels_d), _eng.ptr(samples), _eng.ptr(info),
+              _eng.ptr(ws), ws.numel(), C.c_void_p(st.cuda_stream))
+    return samples, info
+
+
+def _raise_flags(flags, clusters, Xd):
+    """A flag of csrc/silhouette.hip as scikit-learn's ValueError (the non-finite check comes first there too)."""
+    import torch
+
+    from . import silhouette as _sil
+
+    if flags & _sil.FLAG_NONFINITE:
+        raise _sil.nonfinite_error(bool(torch.isnan(Xd).any().item()))
+    if flags & _sil.FLAG_LABELS:
+        raise _sil.labels_error(int(clusters))
+
+
+def _host_internal(X, labels):
+    from sklearn import metrics as skm
+
+    X, labels = np.asarray(_to_host(X)), np.asarray(_to_host(labels))
+    return {"silhouette": float(skm.silhouette_score(X, labels, metric="euclidean")),
+            "davies_bouldin": float(skm.davies_bouldin_score(X, labels)),
+            "calinski_harabasz": float(skm.calinski_harabasz_score(X, labels))}
+
+
+def silhouette_samples_on_device(X, labels, stream=None):
+    """sklearn.metrics.silhouette_samples(X, labels, metric="euclidean") as an n fp64 CUDA tensor (csrc/silhouette.hip; the
+    rule: mused_amd/silhouette.py).  X: (n, d) NumPy array or tensor (taken as fp64), labels: n integers, NumPy or tensor;
+    any int32 value is a cluster id and -1 is a cluster like any other -- mask noise rows yourself.  Raises scikit-learn's
+    ValueError for a non-finite row and for fewer than 2 or more than n - 1 distinct labels (the call reads the flags, so
+    it returns after the stream has finished).  MUSED_SCORE=host: scikit-learn on host copies, uploaded."""
+    import torch
+
+    if _want_host():
+        from sklearn import metrics as skm
+
+        s = skm.silhouette_samples(np.asarray(_to_host(X)), np.asarray(_to_host(labels)), metric="euclidean")
+        return torch.from_numpy(np.ascontiguousarray(s, dtype=np.float64)).cuda()
+    st = _internal_stream(X, stream)
+    with torch.cuda.stream(st):
+        Xd, ld = _internal_inputs(X, labels)
+        samples, info = silhouette_launch(Xd, ld, st)
+        head = info.cpu().numpy()[:8].view(np.int32)
+    _raise_flags(int(head[0]), int(head[1]), Xd)
+    return samples
+
+
+def internal_metrics_raw(X, labels, stream=None, indices=True, wait_current=True):
+    """Both kernels of csrc/silhouette.hip and ONE read: (flags, clusters, silhouette score, Davies-Bouldin,
+    Calinski-Harabasz, the device X).  With a flag the three numbers are NaN; `indices=False` runs the silhouette alone.
+    `wait_current=False`: `stream` does not wait for the current stream -- for callers whose tensors are already complete
+    for it (the pipeline's label workers, like perform_clustering_on_device)."""
+    import torch
+
+    from . import _lib
+    from . import engine as _eng
+
+    st = _internal_stream(X, stream, wait_current)
+    with torch.cuda.stream(st):
+        Xd, ld = _internal_inputs(X, labels)
+        n, d = Xd.shape
+        res = torch.zeros(48, dtype=torch.uint8, device=Xd.device)   # silhouette info | {DB, CH} | indices info
+        silhouette_launch(Xd, ld, st, info=res[:16])
+        if indices:
+            ws = _internal_ws("idx", int(_lib.lib().mused_cluster_indices_ws_bytes(n, d)), Xd.device, st)
+            _lib.call("mused_cluster_indices", _eng.ptr(Xd), n, d, Xd.stride(0), _eng.ptr(ld), _eng.ptr(res[16:32]),
+                      _eng.ptr(res[32:]), _eng.ptr(ws), ws.numel(), C.c_void_p(st.cuda_stream))
+        h = res.cpu().numpy()
+    flags, clusters = (int(v) for v in h[:8].view(np.int32))
+    if flags:
+        return flags, clusters, float("nan"), float("nan"), float("nan"), Xd
+    db, ch = (float(v) for v in h[16:32].view(np.float64)) if indices else (float("nan"), float("nan"))
+    return flags, clusters, float(h[8:16].view(np.float64)[0]) / n, db, ch, Xd
+
+
+def compute_internal_metrics(X, labels, stream=None):
+    """{"silhouette", "davies_bouldin", "calinski_harabasz"} of a clustering as Python floats, without ground truth:
+    scikit-learn's silhouette_score(metric="euclidean"), davies_bouldin_score and calinski_harabasz_score from
+    csrc/silhouette.hip (the rules and conventions: mused_amd/silhouette.py; the error bound: DESIGN section 20).
+    X: (n, d) NumPy array or tensor, n <= 2^19 on the device; labels: n integers.  Any int32 value is a cluster id, -1
+    included: callers that treat -1 as noise mask those rows themselves.  A non-finite row and a label count outside
+    [2, n - 1] raise scikit-learn's ValueError.  MUSED_SCORE=host: scikit-learn's three calls on host copies."""
+    if _want_host():
+        return _host_internal(X, labels)
+    flags, clusters, s, db, ch, Xd = internal_metrics_raw(X, labels, stream)
+    _raise_flags(flags, clusters, Xd)
+    return {"silhouette": s, "davies_bouldin": db, "calinski_harabasz": ch}

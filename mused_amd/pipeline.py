@@ -59,6 +59,30 @@ def check_ks(modality_ks, count=None):
     return [int(x) for x in ks]
 
 
+def check_k_range(n_clusters_range, approach, n):
+    """`n_clusters_range` as (lo, hi) with 2 <= lo <= hi <= n - 1, or None.  ValueError for anything else, for the approaches
+    that take no k per window ("sSVDMC_mini": one clusterer for the stream; "DBSCAN_incr", "DBSCAN_batch", "HDBSCAN_batch":
+    no k at all) and under MUSED_KMEANS=host (the selector has no host form)."""
+    import numbers
+
+    if n_clusters_range is None:
+        return None
+    if approach in ("sSVDMC_mini", "DBSCAN_incr", "DBSCAN_batch", "HDBSCAN_batch"):
+        raise ValueError(f"n_clusters_range: approach {approach!r} takes no k per window")
+    if os.environ.get("MUSED_KMEANS", "device") == "host":
+        raise ValueError("n_clusters_range: the selector runs on the device only (MUSED_KMEANS=host is set)")
+    try:
+        lo, hi = n_clusters_range
+    except (TypeError, ValueError):
+        raise ValueError(f"n_clusters_range must be (lo, hi), got {n_clusters_range!r}") from None
+    for v in (lo, hi):
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool):
+            raise ValueError(f"n_clusters_range must hold two ints, got {n_clusters_range!r}")
+    if not 2 <= lo <= hi <= n - 1:
+        raise ValueError(f"n_clusters_range = {n_clusters_range!r}: need 2 <= lo <= hi <= rows - 1 = {n - 1}")
+    return int(lo), int(hi)
+
+
 def check_vote(fusion_threshold, modality_weights, count=None):
     """The arguments of a fusion by agreement threshold as (tau, vote weights or None); with the number of modalities known
     also checked against it (more than 8 modalities, a threshold above the sum of all weights: ValueError)."""
@@ -79,9 +103,19 @@ class StreamPipeline:
     def __init__(self, window_size, reduced_dim, k_basis, seed, approach="sSVDMC", modality_types=None,
                  step_window_ratio=1, engine=None, async_labels=True, feature_sketch=False, stream=None,
                  assume_finite=False, window_slots=1, n_clusters_total=None, eps=0.5, min_samples=5,
-                 dbscan_max_rows=None, modality_weights=None, fusion_threshold=None, modality_ks=None):
+                 dbscan_max_rows=None, modality_weights=None, fusion_threshold=None, modality_ks=None,
+                 n_clusters_range=None, internal_scores=False):
         if approach not in ("sSVDMC", "sSVDMC_hung", "sSVDMC_pot", "sSVDMC_mini", "SWFDMC", "DBSCAN_incr"):
             raise ValueError(f"approach {approach!r} is not on the device hot path")
+        # WITHOUT GROUND TRUTH (both off by default: nothing below runs then).  `n_clusters_range` = (lo, hi): every k-means
+        # window chooses its own k among lo .. hi by the device silhouette (matrix_operations.select_n_clusters_on_device)
+        # instead of taking the number of distinct true labels, which may then be None; the k of every window: `chosen_k`.
+        # `internal_scores`: silhouette, Davies-Bouldin and Calinski-Harabasz of every window's (embedding, raw labels), on
+        # the label worker's stream before the matching: `internal_scores`, a list of dicts in window order (NaNs for a
+        # window whose labels hold a single value).
+        self._k_range = check_k_range(n_clusters_range, approach, int(window_size))
+        self._internal = bool(internal_scores)
+        self.chosen_k, self.internal_scores = [], []
         # None: OR-fusion, today's path exactly.  M weights (finite, > 0): the modalities are fused by weighted sum and the
         # eigenstep runs valued.  The sketches ingest bit rows: weighted rows for them are not built
         # `fusion_threshold` (tau): the fused matrix is the 0/1 mask of the edges whose weighted agreement
@@ -384,12 +418,36 @@ class StreamPipeline:
             if st is None:
                 st = self._km_local.stream = torch.cuda.Stream(priority=-1)
             reduced_dev.record_stream(st)  # produced on the pipeline's stream, complete (ev), consumed on the worker's
-            clusters = mo.perform_clustering_on_device(reduced_dev, n_clusters, self.seed, emb_host=reduced_host, stream=st)
+            if self._k_range is not None:
+                n_clusters, clusters, _ = mo.select_n_clusters_on_device(
+                    reduced_dev, range(self._k_range[0], self._k_range[1] + 1), self.seed, stream=st, emb_host=reduced_host)
+            else:
+                clusters = mo.perform_clustering_on_device(reduced_dev, n_clusters, self.seed, emb_host=reduced_host, stream=st)
             self.km_device_windows += 1
+        elif self._k_range is not None:
+            raise ValueError("n_clusters_range: the window's embedding is not an fp64 device tensor; the selector has no host form")
         else:
             clusters = mo.perform_clustering(reduced_host, n_clusters, self.seed)
         self.host_ms["kmeans"].append(1e3 * (time.perf_counter() - t0))
+        if self._k_range is not None or self._internal:
+            return clusters, sigma_host, n_clusters, self._internal_scores(reduced_dev, clusters) if self._internal else None
         return clusters, sigma_host
+
+    def _internal_scores(self, reduced_dev, clusters):
+        """The three truth-free indices of (embedding, raw labels) on this label worker's stream; the embedding is read where
+        it lies on the device.  Labels with a single value have no such score: NaNs."""
+        from . import metrics_evaluation as me
+
+        if reduced_dev is None:
+            raise ValueError("internal_scores: the window's embedding is not on the device")
+        st = getattr(self._km_local, "stream", None)
+        if st is None:
+            st = self._km_local.stream = torch.cuda.Stream(priority=-1)
+        reduced_dev.record_stream(st)  # produced on the pipeline's stream, complete (ev), consumed on the worker's
+        flags, n_labels, s, db, ch, Xd = me.internal_metrics_raw(reduced_dev, np.asarray(clusters), st, wait_current=False)
+        if flags & 2:
+            me._raise_flags(flags, n_labels, Xd)
+        return {"silhouette": s, "davies_bouldin": db, "calinski_harabasz": ch}
 
     def _rows_stay_on_device(self, reduced):
         """A k-means window with device seeding: nothing on the host reads the embedding (the labels, sigma and the flag
@@ -476,7 +534,13 @@ class StreamPipeline:
     def _chain(self, fut, job):
         """Sequential over windows: matching against the previous window (main.py:105-119), Hungarian or, for
         "sSVDMC_pot", by the Sinkhorn plan."""
-        clusters, sigma_host = fut.result() if hasattr(fut, "result") else fut
+        res = fut.result() if hasattr(fut, "result") else fut
+        clusters, sigma_host = res[0], res[1]
+        if len(res) > 2:   # n_clusters_range / internal_scores: kept in window order, like everything this worker appends
+            if self._k_range is not None:
+                self.chosen_k.append(int(res[2]))
+            if self._internal:
+                self.internal_scores.append(res[3])
         trigger, t_start = job[4], job[5]
         t0 = time.perf_counter()
         method = "pot" if self._pot else "hungarian"
@@ -560,7 +624,8 @@ class StreamPipeline:
         """One full window.  `lo`: stream row of its first row -- given for hopping windows it lets the dense modalities
         reuse the previous window's similarity work (only with one engine and windows handed in in order)."""
         t_start = time.perf_counter()
-        n_clusters = len(np.unique(true_labels_window))  # main.py:41
+        # main.py:41 (with n_clusters_range the window chooses its k itself and the true labels may be None)
+        n_clusters = len(np.unique(true_labels_window)) if self._k_range is None else None
         caller = torch.cuda.current_stream()
         if self._slots is None:
             first = self._stream if self._stream is not None else caller
@@ -615,7 +680,7 @@ class StreamPipeline:
         (main.py:97) and the trace entry {trigger, sigma, raw, matched}.  For drivers that produce the embedding themselves
         (`SwfdmcLanes`); the matching of `out` follows the order of the calls, `trace[i]["raw"]` is order independent."""
         t_start = time.perf_counter()
-        n_clusters = len(np.unique(true_labels_window))
+        n_clusters = len(np.unique(true_labels_window)) if self._k_range is None else None
         red_pin, sig_pin = self._get_pins(reduced, sigma)
         if not self._rows_stay_on_device(reduced):
             red_pin.copy_(reduced, non_blocking=True)
@@ -679,7 +744,7 @@ class StreamPipeline:
         for i in range(n):
             if i + 1 >= self.W and (i + 1) * self.ratio % self.W == 0:  # main.py:32
                 lo = i + 1 - self.W
-                self.process_window([m[lo : i + 1] for m in dev], true_labels[lo : i + 1], trigger=i,
+                self.process_window([m[lo : i + 1] for m in dev], None if true_labels is None else true_labels[lo : i + 1], trigger=i,
                                     lo=lo if self.ratio > 1 else None)
         self.flush()
         return np.array(self.out)
@@ -744,7 +809,8 @@ class StreamPipeline:
 
 def process_streaming_data(results, data_modalities, modality_types, window_size, reduced_dim, k_basis, n_clusters_total,
                            seed, approach, complete_true_labels, step_window_ratio, noise_rate, label_mode, sorting,
-                           eps, min_samples, score=False, modality_weights=None, fusion_threshold=None, modality_ks=None):
+                           eps, min_samples, score=False, modality_weights=None, fusion_threshold=None, modality_ks=None,
+                           n_clusters_range=None, internal_scores=False):
     """Same positional parameters as main.py:13.  `modality_weights` (one weight per modality, finite and > 0): fusion by
     weighted sum instead of OR for the approaches that go through the eigenstep ("SWFDMC": ValueError); None: OR.
     `fusion_threshold` (tau): every window's fused matrix is the 0/1 mask of the edges whose agreement sum_m w_m [modality m
@@ -755,7 +821,14 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
     what the reference's compute_all_metrics appends (main.py:128: the concatenated window labels against the
     concatenated true labels of main.py:39-40, which repeat rows when step_window_ratio > 1; "processing_time" is then
     the reference's list), and "window_scores", the (K, 7) scores of the K windows from one launch
-    (metrics_evaluation.score_windows)."""
+    (metrics_evaluation.score_windows).
+    `n_clusters_range` = (lo, hi): every window chooses its k among lo .. hi by the device silhouette instead of taking it from
+    the true labels (`results["chosen_k"]`, one per window; `complete_true_labels` may then be None unless `score`); ValueError
+    for "sSVDMC_mini" and "DBSCAN_incr" and under MUSED_KMEANS=host.  `internal_scores=True`: `results["internal_scores"]`, per
+    window the dict of metrics_evaluation.compute_internal_metrics on (embedding, raw labels), NaNs where the labels hold a
+    single value."""
+    if score and complete_true_labels is None:
+        raise ValueError("score=True compares against complete_true_labels, which is None")
     # MUSED_DBSCAN_INCR_ROWS (read at every call; DBSCAN_incr only): the rows the stream's IncrementalDBSCAN holds at most
     incr_rows = os.environ.get("MUSED_DBSCAN_INCR_ROWS") if approach == "DBSCAN_incr" else None
     t0 = time.time_ns()
@@ -764,17 +837,23 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
     with StreamPipeline(window_size, reduced_dim, k_basis, seed, approach, list(modality_types), step_window_ratio,
                         window_slots=int(os.environ.get("MUSED_WINDOW_SLOTS", "1")), n_clusters_total=n_clusters_total,
                         eps=eps, min_samples=min_samples, dbscan_max_rows=int(incr_rows) if incr_rows else None,
-                        modality_weights=modality_weights, fusion_threshold=fusion_threshold, modality_ks=modality_ks) as pipe:
-        clusters = pipe.run(data_modalities, np.asarray(complete_true_labels))
+                        modality_weights=modality_weights, fusion_threshold=fusion_threshold, modality_ks=modality_ks,
+                        n_clusters_range=n_clusters_range, internal_scores=internal_scores) as pipe:
+        clusters = pipe.run(data_modalities, None if complete_true_labels is None else np.asarray(complete_true_labels))
     t1 = time.time_ns()
     if score:
-        return _scored(results, clusters, _window_true_labels(complete_true_labels, len(data_modalities[0]), window_size,
-                                                              step_window_ratio),
-                       (len(data_modalities[0]), noise_rate, label_mode, sorting, reduced_dim, k_basis, window_size), t1, t0,
-                       window_size)
-    results = dict(results or {})
-    results["all_clusters"] = clusters
-    results["processing_time"] = (t1 - t0) / 1e9
+        results = _scored(results, clusters, _window_true_labels(complete_true_labels, len(data_modalities[0]), window_size,
+                                                                 step_window_ratio),
+                          (len(data_modalities[0]), noise_rate, label_mode, sorting, reduced_dim, k_basis, window_size), t1, t0,
+                          window_size)
+    else:
+        results = dict(results or {})
+        results["all_clusters"] = clusters
+        results["processing_time"] = (t1 - t0) / 1e9
+    if n_clusters_range is not None:
+        results["chosen_k"] = list(pipe.chosen_k)
+    if internal_scores:
+        results["internal_scores"] = list(pipe.internal_scores)
     return results
 
 
@@ -872,9 +951,11 @@ def batch_embedding(data_modalities, modality_types, reduced_dim, k_basis, seed,
 
 def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_basis, n_clusters, seed, approach,
                        complete_true_labels, noise_rate, label_mode, sorting, eps, min_samples, min_cluster_size,
-                       window_size, timings=None, score=False, modality_weights=None, fusion_threshold=None, modality_ks=None):
+                       window_size, timings=None, score=False, modality_weights=None, fusion_threshold=None, modality_ks=None,
+                       n_clusters_range=None, internal_scores=False):
     """`modality_weights`, `fusion_threshold`, `modality_ks`: as for process_streaming_data (every batch approach goes through
-    the eigenstep; see batch_embedding for what a threshold costs in memory).
+    the eigenstep; see batch_embedding for what a threshold costs in memory).  `n_clusters_range`, `internal_scores`: as for
+    process_streaming_data with the subset as the one window ("SVDMC_batch" chooses its k; the density approaches raise).
     Same positional parameters as main.py:132: the whole subset as one window -- kNN adjacency per modality, fusion,
     randomized-SVD embedding on the device (`batch_embedding`), then "SVDMC_batch": k-means with n_clusters on the device
     (perform_clustering_on_device: scikit-learn's labels); "DBSCAN_batch": DBSCAN on the device embedding
@@ -891,6 +972,9 @@ def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_
         raise ValueError(f"MUSED_HDBSCAN={hd_mode!r}: expected package, device or sklearn")
     if hd_mode == "package":
         import hdbscan  # noqa: F401  (the reference imports it at module level: without it nothing runs)
+    k_range = check_k_range(n_clusters_range, approach, len(data_modalities[0]))
+    if score and complete_true_labels is None:
+        raise ValueError("score=True compares against complete_true_labels, which is None")
     t0 = time.time_ns()
     emb, _, nnz = batch_embedding(data_modalities, list(modality_types), reduced_dim, k_basis, seed, timings=timings,
                                   modality_weights=modality_weights, fusion_threshold=fusion_threshold, modality_ks=modality_ks)
@@ -905,18 +989,33 @@ def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_
                                                  min_samples=min_samples)
     elif approach == "DBSCAN_batch":
         clusters = mo.perform_dbscan_clustering_on_device(emb, eps=eps, min_samples=min_samples)
+    elif k_range is not None:
+        n_clusters, clusters, _ = mo.select_n_clusters_on_device(emb, range(k_range[0], k_range[1] + 1), seed)
     else:
         clusters = mo.perform_clustering_on_device(emb, n_clusters, seed)
+    scores = None
+    if internal_scores:
+        from . import metrics_evaluation as me
+
+        flags, n_labels, s, db, ch, Xd = me.internal_metrics_raw(emb, np.asarray(clusters))
+        if flags & 2:
+            me._raise_flags(flags, n_labels, Xd)
+        scores = {"silhouette": s, "davies_bouldin": db, "calinski_harabasz": ch}   # NaNs: the labels hold a single value
     if timings is not None:
         timings["clustering"] = time.perf_counter() - t1
         timings["edges"] = nnz
     t_end = time.time_ns()
     if score:
-        return _scored(results, clusters, np.array(complete_true_labels),
-                       (len(data_modalities[0]), noise_rate, label_mode, sorting, reduced_dim, k_basis, window_size), t_end, t0)
-    results = dict(results or {})
-    results["all_clusters"] = np.asarray(clusters)
-    results["processing_time"] = (t_end - t0) / 1e9
+        results = _scored(results, clusters, np.array(complete_true_labels),
+                          (len(data_modalities[0]), noise_rate, label_mode, sorting, reduced_dim, k_basis, window_size), t_end, t0)
+    else:
+        results = dict(results or {})
+        results["all_clusters"] = np.asarray(clusters)
+        results["processing_time"] = (t_end - t0) / 1e9
+    if k_range is not None:
+        results["chosen_k"] = [int(n_clusters)]
+    if scores is not None:
+        results["internal_scores"] = [scores]
     return results
 
 
