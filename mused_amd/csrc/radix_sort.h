@@ -2,6 +2,9 @@
 // (entries by term) and csrc/rows_find.hip (elements by group).  A histogram per tile of 1024 entries (one wave a tile), one
 // exclusive scan of the digit-major table (block_scan.h), then the scatter in tile order with the ranks inside a chunk of 64
 // from ballots: entries of one digit keep their order.  The callers loop over the passes; their pass counts follow their keys.
+// Key range: p passes order the pairs by the low 8 p bits of the keys, as unsigned numbers.  So with fewer than four passes
+// the keys are non-negative and below 2^(8 p) (tokenise.hip's term ids, rows_find.hip's slots); four passes order all 32 bits
+// as one unsigned word, which is why silhouette.hip flips the sign bit of its labels first.
 #pragma once
 #include "block_scan.h"
 

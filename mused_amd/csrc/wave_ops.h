@@ -23,6 +23,7 @@ __device__ __forceinline__ double swap32_add(double a, double b) {
   auto rh = __builtin_amdgcn_permlane32_swap((unsigned)(ua >> 32), (unsigned)(ub >> 32), false, false);
   return f64_from_parts(rl[0], rh[0]) + f64_from_parts(rl[1], rh[1]);
 }
+// a(l) + a(l ^ 16) on the lanes with bit 4 clear (0-15, 32-47), b(l) + b(l ^ 16) on those with bit 4 set (16-31, 48-63)
 __device__ __forceinline__ double swap16_add(double a, double b) {
   const unsigned long long ua = (unsigned long long)__double_as_longlong(a), ub = (unsigned long long)__double_as_longlong(b);
   auto rl = __builtin_amdgcn_permlane16_swap((unsigned)(ua & 0xffffffffull), (unsigned)(ub & 0xffffffffull), false, false);
