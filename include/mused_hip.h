@@ -656,6 +656,28 @@ long mused_score_ws_bytes(long n_seg, long cells_cap);
 int mused_score_labels(const int* truth, const int* pred, long n_seg, long seg_len, long cells_cap, double* out, int* info,
                        void* ws, long ws_bytes, void* stream);
 
+/* ---- scoring a partition against the truth whatever the clusters are called, csrc/score_partitions.hip: what ARI, AMI,
+ * homogeneity / completeness / V-measure, Fowlkes-Mallows, purity and the matched accuracy are finished from on the host
+ * (specification: mused_amd/partition_scores.py, pinned to scikit-learn 1.7.2 and SciPy).  Labels, segments, cells_cap and
+ * the flags 4 and 8 as for mused_score_labels.  Up to four launches, enqueue-only: no host read or wait inside the call.
+ * want_emi: nonzero asks for the expected mutual information (AMI's correction), about min(T, P) * seg_len terms.
+ * out (DEVICE, n_seg x 8 fp64) = {MI, H(truth), H(pred), EMI, 0, 0, 0, 0}, natural logarithms, MI clipped at 0, an entropy
+ *   exactly 0 for a side with one value.  Two calls on the same labels give the same bits.
+ * ints (DEVICE, n_seg x 8 int64) = {sum n_ij^2, sum a_i^2, sum b_j^2, sum over columns of the column maximum, sum over rows
+ *   of the row maximum, number of EMI terms, seg_len, 0}: exact.
+ * info (DEVICE, n_seg x 8 int32) = {T, P, flags, 0, 0, 0, 0, 0}.  Flags 4 and 8: out and ints (but seg_len) are 0, score the
+ *   segment on the host.  Flag 64: the EMI slot is NaN -- want_emi was 0, seg_len > 2^24 or the segment has more than 2^34
+ *   EMI terms (limits that keep one call short); every other output is valid.
+ * table_out (DEVICE, may be NULL): n_seg x cells_cap int32; segment s's T x P table, row-major, values in ascending order
+ *   on both sides, at s * cells_cap (the cells behind T * P are not written).
+ * ws: mused_score_partitions_ws_bytes(n_seg, seg_len, cells_cap) bytes, 8-byte aligned: the log-gamma table (8 (seg_len + 1)
+ *   bytes up to seg_len = 2^22; longer segments evaluate lgamma where it is used, the same values), per segment 64 min(seg_len, 4096)
+ *   bytes of row partials, a and b (32 KiB) and the table (4 cells_cap), each array rounded up to 256 bytes.
+ * MUSED_PARTITION_LGAMMA=direct (read per call): no log-gamma table at any length. */
+long mused_score_partitions_ws_bytes(long n_seg, long seg_len, long cells_cap);
+int mused_score_partitions(const int* truth, const int* pred, long n_seg, long seg_len, long cells_cap, int want_emi, double* out,
+                           long* ints, int* info, int* table_out, void* ws, long ws_bytes, void* stream);
+
 /* ---- scoring clusters WITHOUT ground truth, csrc/silhouette.hip: sklearn.metrics.silhouette_samples(X, labels,
  * metric="euclidean") with the sum of the samples, and davies_bouldin_score / calinski_harabasz_score (specification:
  * mused_amd/silhouette.py, pinned to scikit-learn 1.7).  Any int32 value is a cluster id, -1 included (a cluster like any

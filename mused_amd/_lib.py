@@ -125,6 +125,8 @@ _PROTOS = {
     "mused_emst": (_i, [_vp, _l, _i, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "mused_score_ws_bytes": (_l, [_l, _l]),
     "mused_score_labels": (_i, [_vp, _vp, _l, _l, _l, _vp, _vp, _vp, _l, _vp]),
+    "mused_score_partitions_ws_bytes": (_l, [_l, _l, _l]),
+    "mused_score_partitions": (_i, [_vp, _vp, _l, _l, _l, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "mused_silhouette_ws_bytes": (_l, [_l, _i]),
     "mused_silhouette_slices": (_i, [_l]),
     "mused_silhouette": (_i, [_vp, _l, _i, _l, _vp, _vp, _vp, _vp, _l, _vp]),

@@ -7,6 +7,10 @@ scikit-learn within 1e-12 (the rounding of `log` and of the sums). 
 reference's own scikit-learn calls.  It runs, and `score_fallbacks` counts it, when MUSED_SCORE=host, when the labels
 are not integers, when the lengths differ or the input is empty (scikit-learn raises, and so does this), and when the
 kernel raised a flag (a label outside [-1, 65534], more than 4096 distinct values on a side, a table above the cap).
+
+Beside the reference's seven: `compute_partition_metrics` and `partition_windows`, nine scores that do not depend on how the
+clusters are numbered (csrc/score_partitions.hip; the rule: mused_amd/partition_scores.py), and the three truth-free indices
+of csrc/silhouette.hip.
 """
 from __future__ import annotations
 
@@ -30,10 +34,13 @@ _LOGGED = (("nmi_score", "nmi"), ("nmi_e_score", "nmi_e"), ("f1_score", "f1"), (
            ("recall", "recall"), ("accuracy", "accuracy"), ("mae", "mae"))
 
 
-def get_initial_results():
+def get_initial_results(partition=False):
     """(results, independent_variables): empty lists for the seven metrics, the processing time and the seven
-    independent variables of an experiment."""
+    independent variables of an experiment.  `partition=True` adds the nine lists of PARTITION_KEYS, which
+    compute_all_metrics then fills as well."""
     results = {k: [] for k in KEYS + ("processing_time",) + _VARIABLES}
+    if partition:
+        results.update({k: [] for k in PARTITION_KEYS})
     return results, list(_VARIABLES)
 
 
@@ -213,6 +220,12 @@ def compute_all_metrics(results, subset_size, noise_rate, label_mode, sorting, r
         if key in results:
             results[key].append(values[key])
             parts.append(f"{short}={values[key]:.2f}, ")
+    if any(k in results for k in PARTITION_KEYS):   # the nine partition scores, after the seven
+        values = compute_partition_metrics(true_labels, clusters)
+        for key, short in _PARTITION_LOGGED:
+            if key in results:
+                results[key].append(values[key])
+                parts.append(f"{short}={values[key]:.2f}, ")
     if "processing_time" in results:
         processing_time = (end_time - start_time) / 1e9
         results["processing_time"].append(processing_time)
@@ -391,3 +404,205 @@ def compute_internal_metrics(X, labels, stream=None):
     flags, clusters, s, db, ch, Xd = internal_metrics_raw(X, labels, stream)
     _raise_flags(flags, clusters, Xd)
     return {"silhouette": s, "davies_bouldin": db, "calinski_harabasz": ch}
+
+
+# ---- scores against the truth that ignore how clusters are numbered (csrc/score_partitions.hip) ---------------------------
+# ARI, AMI, homogeneity / completeness / V-measure, Fowlkes-Mallows, purity, inverse purity and the accuracy under the best
+# one-to-one matching of clusters to classes.  The rule: mused_amd/partition_scores.py; the bounds: DESIGN section 21.
+from . import partition_scores as _ps  # noqa: E402
+from .partition_scores import KEYS as PARTITION_KEYS  # noqa: E402
+
+partition_fallbacks = 0
+PARTITION_FLAG_NO_EMI = 64           # the kernel left the EMI out (csrc/score_partitions.hip): only AMI goes to the host
+PARTITION_MATCH_MAX_LEN = 1 << 20    # the wide solver's window length (matrix_operations.MATCH_WIDE_MAX_W)
+_PARTITION_WS = {}
+_PARTITION_LOGGED = (("ari_score", "ari"), ("ami_score", "ami"), ("homogeneity", "homogeneity"), ("completeness", "completeness"),
+                     ("v_measure", "v_measure"), ("fowlkes_mallows", "fowlkes_mallows"), ("purity", "purity"),
+                     ("inverse_purity", "inverse_purity"), ("matched_accuracy", "matched_accuracy"))
+
+
+def _count_partition_fallback():
+    global partition_fallbacks
+    with _fallback_lock:
+        partition_fallbacks += 1
+
+
+def host_partition_scores(true_labels, clusters, keys=PARTITION_KEYS):
+    """The nine values from scikit-learn's and SciPy's calls on host copies, for the values named in `keys`."""
+    from scipy.optimize import linear_sum_assignment
+    from sklearn import metrics as skm
+    from sklearn.metrics.cluster import contingency_matrix
+
+    true_labels, clusters = np.asarray(_to_host(true_labels)), np.asarray(_to_host(clusters))
+    out = {}
+    if "ari_score" in keys:
+        out["ari_score"] = float(skm.adjusted_rand_score(true_labels, clusters))
+    if "ami_score" in keys:
+        out["ami_score"] = float(skm.adjusted_mutual_info_score(true_labels, clusters))
+    if any(k in keys for k in ("homogeneity", "completeness", "v_measure")):
+        h, c, v = skm.homogeneity_completeness_v_measure(true_labels, clusters)
+        out.update({k: x for k, x in (("homogeneity", h), ("completeness", c), ("v_measure", v)) if k in keys})
+    if "fowlkes_mallows" in keys:
+        out["fowlkes_mallows"] = float(skm.fowlkes_mallows_score(true_labels, clusters))
+    if any(k in keys for k in ("purity", "inverse_purity", "matched_accuracy")):
+        table = contingency_matrix(true_labels, clusters).astype(np.int64)
+        n = int(table.sum())
+        if n == 0:
+            raise ValueError("no samples")
+        rows, cols = linear_sum_assignment(table, maximize=True)
+        own = {"purity": int(table.max(axis=0).sum()) / n, "inverse_purity": int(table.max(axis=1).sum()) / n,
+               "matched_accuracy": int(table[rows, cols].sum()) / n}
+        out.update({k: x for k, x in own.items() if k in keys})
+    return {k: out[k] for k in PARTITION_KEYS if k in out}
+
+
+def partition_scores_on_device(truth_dev, pred_dev, cells_cap, want_emi=True, want_table=True, stream=None):
+    """mused_score_partitions on int32 CUDA tensors of shape (n,) or (K, W): (out (K, 8) float64, ints (K, 8) int64, info
+    (K, 8) int32 as NumPy arrays after ONE read, the tables as a (K, cells) int32 CUDA tensor or None).  `cells` is cells_cap,
+    or seg_len^2 where that is smaller (no table is larger).  Synchronises the stream."""
+    import torch
+
+    from . import _lib
+    from . import engine as _eng
+
+    if truth_dev.shape != pred_dev.shape or truth_dev.dtype != torch.int32 or pred_dev.dtype != torch.int32:
+        raise ValueError("partition_scores_on_device: int32 tensors of equal shape")
+    n_seg, seg_len = (1, truth_dev.shape[0]) if truth_dev.dim() == 1 else tuple(truth_dev.shape)
+    cells = int(min(cells_cap, seg_len * seg_len))
+    dev = truth_dev.device
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    need = int(_lib.lib().mused_score_partitions_ws_bytes(n_seg, seg_len, cells))
+    with torch.cuda.stream(st):
+        key = (dev, st.cuda_stream)
+        ws = _PARTITION_WS.get(key)
+        if ws is None or ws.numel() < need:
+            if len(_PARTITION_WS) > 16:
+                _PARTITION_WS.clear()
+            ws = _PARTITION_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+        res = torch.empty(n_seg * 160, dtype=torch.uint8, device=dev)   # 8 doubles, 8 int64, 8 int32 per segment
+        out, ints, info = res[: n_seg * 64], res[n_seg * 64 : n_seg * 128], res[n_seg * 128 :]
+        tables = torch.empty((n_seg, cells), dtype=torch.int32, device=dev) if want_table else None
+        truth_dev, pred_dev = truth_dev.contiguous(), pred_dev.contiguous()
+        _lib.call("mused_score_partitions", _eng.ptr(truth_dev), _eng.ptr(pred_dev), n_seg, seg_len, cells, 1 if want_emi else 0,
+                  _eng.ptr(out), _eng.ptr(ints), _eng.ptr(info), _eng.ptr(tables) if want_table else None, _eng.ptr(ws),
+                  ws.numel(), C.c_void_p(st.cuda_stream))
+        res_h = res.cpu().numpy()
+    return (res_h[: n_seg * 64].view(np.float64).reshape(n_seg, 8).copy(),
+            res_h[n_seg * 64 : n_seg * 128].view(np.int64).reshape(n_seg, 8).copy(),
+            res_h[n_seg * 128 :].view(np.int32).reshape(n_seg, 8).copy(), tables)
+
+
+def _matched_total(truth_seg, pred_seg, table_seg, T, P, stream):
+    """The optimum of the assignment problem on one segment's T x P table (`table_seg`: its cells on the device): the wide
+    Hungarian solver with the truth as the previous window and min_overlap 0 (every count is a finite cost), the table summed
+    over the assigned cells.  A solve the solver flags, and a segment longer than its window limit, take SciPy on a host copy
+    of the table (counted)."""
+    import torch
+
+    from . import matrix_operations as mo
+
+    tab = table_seg[: T * P].view(T, P)
+    if truth_seg.shape[0] <= PARTITION_MATCH_MAX_LEN:
+        _, info_h, assign = mo.match_wide_launch(pred_seg.view(1, -1), truth_seg, 0, stream=stream, want_assign=True)
+        if info_h[0, 4] == 0 and info_h[0, 3] == 1 and info_h[0, 0] == T and info_h[0, 1] == P:
+            with torch.cuda.stream(stream):
+                col = assign[0, :T].to(torch.int64)
+                picked = tab.gather(1, col.clamp(min=0).unsqueeze(1)).squeeze(1).to(torch.int64)
+                return int((picked * (col >= 0)).sum().item())
+    _count_partition_fallback()
+    return _ps.matched_total(tab.cpu().numpy())
+
+
+def _finish_partition(out, ints, info):
+    """The values of one unflagged segment but the matched accuracy, finished with the rule's own expressions: Python ints and
+    np.int64 for the integer-derived ones (scikit-learn's bits), scikit-learn's order of operations for the rest.  `ami_score`
+    is None where the kernel left the EMI out (flag 64)."""
+    mi, ht, hp, e = (float(v) for v in out[:4])
+    sq, sa, sb, cmax, rmax, _, n = (int(v) for v in ints[:7])
+    T, P, flags = (int(v) for v in info[:3])
+    h, c, v = _ps.hcv_from(mi, ht, hp)
+    no_emi = bool(flags & PARTITION_FLAG_NO_EMI) and T > 1 and P > 1
+    return {"ari_score": _ps.ari_from_sums(sq, sa, sb, n), "ami_score": None if no_emi else _ps.ami_from(mi, ht, hp, e, T, P),
+            "homogeneity": h, "completeness": c, "v_measure": v, "fowlkes_mallows": _ps.fowlkes_mallows_from_sums(sq, sa, sb, n),
+            "purity": cmax / n, "inverse_purity": rmax / n}
+
+
+def _partition_segment(k, labels, out, ints, info, tables, stream, host_labels):
+    """The nine values of segment k of a device result as a dict in the order of PARTITION_KEYS; `host_labels()` gives the
+    (truth, clusters) of the segment on the host for what the device left out."""
+    if info[k, 2] & (SCORE_FLAG_RANGE | SCORE_FLAG_SIZE):
+        _count_partition_fallback()
+        return host_partition_scores(*host_labels())
+    vals = _finish_partition(out[k], ints[k], info[k])
+    if vals["ami_score"] is None:
+        _count_partition_fallback()
+        vals["ami_score"] = host_partition_scores(*host_labels(), keys=("ami_score",))["ami_score"]
+    t2, p2 = (x.view(len(info), -1) for x in labels)
+    total = _matched_total(t2[k], p2[k], tables[k], int(info[k, 0]), int(info[k, 1]), stream)
+    vals["matched_accuracy"] = total / int(ints[k, 6])
+    return {key: vals[key] for key in PARTITION_KEYS}
+
+
+def compute_partition_metrics(true_labels, clusters, stream=None):
+    """{key: value} for the nine PARTITION_KEYS as Python floats: adjusted Rand index, adjusted mutual information
+    (arithmetic mean), homogeneity, completeness, V-measure, Fowlkes-Mallows, purity, inverse purity and the accuracy under
+    the best one-to-one matching of clusters to classes.  None depends on how either side numbers its groups.
+    true_labels, clusters: lists, NumPy arrays or int32 / int64 CUDA tensors of equal length.  One launch group of
+    csrc/score_partitions.hip and one read; the integer-derived values (ARI, Fowlkes-Mallows, the purities, the matched
+    accuracy) are scikit-learn's and SciPy's bits, the others agree within the bounds of DESIGN section 21.  The matching is
+    the wide Hungarian solver's (csrc/match_wide.hip).  The host path (scikit-learn and SciPy, counted in
+    `partition_fallbacks`) runs when MUSED_SCORE=host, when the labels are not integers, when the lengths differ or the
+    input is empty (scikit-learn raises, and so does this) and when the kernel raised flag 4 or 8; with flag 64 only
+    `ami_score` comes from scikit-learn."""
+    if not _want_host():
+        import torch
+
+        labels = None
+        dev = next((x.device for x in (true_labels, clusters) if _is_cuda(x)), None)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        if stream is not None:
+            stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(st):
+            labels = _device_labels(true_labels, clusters)
+        if labels is not None and labels[0].dim() == 1:
+            out, ints, info, tables = partition_scores_on_device(labels[0], labels[1], RUN_CELLS_CAP, stream=st)
+            return _partition_segment(0, labels, out, ints, info, tables, st, lambda: (true_labels, clusters))
+    _count_partition_fallback()
+    return host_partition_scores(true_labels, clusters)
+
+
+def partition_windows(true_kw, pred_kw):
+    """K x W label arrays (lists, NumPy, int32 / int64 CUDA tensors) scored as K segments of one launch group: a (K, 9) float64
+    array in the order of PARTITION_KEYS.  The matched accuracy takes one solver call per window.  A flagged window is scored
+    on the host (and counted)."""
+    labels = None
+    if not _want_host():
+        t2, p2 = (x if _is_cuda(x) else np.asarray(_to_host(x)) for x in (true_kw, pred_kw))
+        if t2.ndim != 2 or tuple(t2.shape) != tuple(p2.shape):
+            raise ValueError("partition_windows: two K x W label arrays of equal shape")
+        labels = _device_labels(t2, p2)
+    th, ph = None, None
+
+    def host_pair(k):
+        nonlocal th, ph
+        if th is None:
+            th, ph = np.asarray(_to_host(true_kw)), np.asarray(_to_host(pred_kw))
+        return th[k], ph[k]
+
+    if labels is None:
+        K = len(np.asarray(_to_host(true_kw)))
+        res = np.empty((K, len(PARTITION_KEYS)))
+        for k in range(K):
+            _count_partition_fallback()
+            h = host_partition_scores(*host_pair(k))
+            res[k] = [h[key] for key in PARTITION_KEYS]
+        return res
+    import torch
+
+    st = torch.cuda.current_stream(labels[0].device)
+    out, ints, info, tables = partition_scores_on_device(labels[0], labels[1], WINDOW_CELLS_CAP, stream=st)
+    res = np.empty((len(info), len(PARTITION_KEYS)))
+    for k in range(len(info)):
+        vals = _partition_segment(k, labels, out, ints, info, tables, st, lambda k=k: host_pair(k))
+        res[k] = [vals[key] for key in PARTITION_KEYS]
+    return res

@@ -810,7 +810,7 @@ class StreamPipeline:
 def process_streaming_data(results, data_modalities, modality_types, window_size, reduced_dim, k_basis, n_clusters_total,
                            seed, approach, complete_true_labels, step_window_ratio, noise_rate, label_mode, sorting,
                            eps, min_samples, score=False, modality_weights=None, fusion_threshold=None, modality_ks=None,
-                           n_clusters_range=None, internal_scores=False):
+                           n_clusters_range=None, internal_scores=False, partition_scores=False):
     """Same positional parameters as main.py:13.  `modality_weights` (one weight per modality, finite and > 0): fusion by
     weighted sum instead of OR for the approaches that go through the eigenstep ("SWFDMC": ValueError); None: OR.
     `fusion_threshold` (tau): every window's fused matrix is the 0/1 mask of the edges whose agreement sum_m w_m [modality m
@@ -826,9 +826,14 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
     the true labels (`results["chosen_k"]`, one per window; `complete_true_labels` may then be None unless `score`); ValueError
     for "sSVDMC_mini" and "DBSCAN_incr" and under MUSED_KMEANS=host.  `internal_scores=True`: `results["internal_scores"]`, per
     window the dict of metrics_evaluation.compute_internal_metrics on (embedding, raw labels), NaNs where the labels hold a
-    single value."""
+    single value.  `partition_scores=True`: `results["partition_scores"]`, the dict of
+    metrics_evaluation.compute_partition_metrics (ARI, AMI, V-measure, ..., matched accuracy: scores that ignore how clusters
+    are numbered) on the same concatenated labels, and `results["window_partition_scores"]`, the (K, 9) array of
+    metrics_evaluation.partition_windows; ValueError when `complete_true_labels` is None."""
     if score and complete_true_labels is None:
         raise ValueError("score=True compares against complete_true_labels, which is None")
+    if partition_scores and complete_true_labels is None:
+        raise ValueError("partition_scores=True compares against complete_true_labels, which is None")
     # MUSED_DBSCAN_INCR_ROWS (read at every call; DBSCAN_incr only): the rows the stream's IncrementalDBSCAN holds at most
     incr_rows = os.environ.get("MUSED_DBSCAN_INCR_ROWS") if approach == "DBSCAN_incr" else None
     t0 = time.time_ns()
@@ -854,6 +859,9 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
         results["chosen_k"] = list(pipe.chosen_k)
     if internal_scores:
         results["internal_scores"] = list(pipe.internal_scores)
+    if partition_scores:
+        _partition_scored(results, clusters, _window_true_labels(complete_true_labels, len(data_modalities[0]), window_size,
+                                                                 step_window_ratio), window_size)
     return results
 
 
@@ -878,6 +886,18 @@ def _scored(results, clusters, true_labels, variables, t1, t0, window_size=None)
         results["window_scores"] = (me.score_windows(true_labels.reshape(-1, window_size), clusters.reshape(-1, window_size))
                                     if len(clusters) else np.empty((0, 7)))
     return results
+
+
+def _partition_scored(results, clusters, true_labels, window_size=None):
+    """Adds "partition_scores" (and, for a stream, "window_partition_scores") to `results`."""
+    from . import metrics_evaluation as me
+
+    clusters, true_labels = np.asarray(clusters), np.asarray(true_labels)
+    results["partition_scores"] = me.compute_partition_metrics(true_labels, clusters)
+    if window_size is not None:
+        results["window_partition_scores"] = (me.partition_windows(true_labels.reshape(-1, window_size),
+                                                                   clusters.reshape(-1, window_size))
+                                              if len(clusters) else np.empty((0, len(me.PARTITION_KEYS))))
 
 
 BATCH_APPROACHES = ("SVDMC_batch", "DBSCAN_batch", "HDBSCAN_batch")
@@ -952,7 +972,7 @@ def batch_embedding(data_modalities, modality_types, reduced_dim, k_basis, seed,
 def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_basis, n_clusters, seed, approach,
                        complete_true_labels, noise_rate, label_mode, sorting, eps, min_samples, min_cluster_size,
                        window_size, timings=None, score=False, modality_weights=None, fusion_threshold=None, modality_ks=None,
-                       n_clusters_range=None, internal_scores=False):
+                       n_clusters_range=None, internal_scores=False, partition_scores=False):
     """`modality_weights`, `fusion_threshold`, `modality_ks`: as for process_streaming_data (every batch approach goes through
     the eigenstep; see batch_embedding for what a threshold costs in memory).  `n_clusters_range`, `internal_scores`: as for
     process_streaming_data with the subset as the one window ("SVDMC_batch" chooses its k; the density approaches raise).
@@ -964,7 +984,8 @@ def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_
     perform_hdbscan_clustering_on_device on the device embedding (scikit-learn's HDBSCAN labels, csrc/emst.hip; pinned to
     scikit-learn, NOT to the package, hence opt-in); `sklearn`: scikit-learn's estimator on a host copy.  Returns `results` with the labels ("all_clusters") and the wall time
     ("processing_time"), like process_streaming_data.  `timings`: see batch_embedding (plus "clustering" and "edges").
-    `score=True`: `results` also receives what the reference's compute_all_metrics appends (main.py:165)."""
+    `score=True`: `results` also receives what the reference's compute_all_metrics appends (main.py:165).
+    `partition_scores=True`: `results["partition_scores"]`, as for process_streaming_data."""
     if approach not in BATCH_APPROACHES:
         raise ValueError(f"approach {approach!r} is not a batch approach {BATCH_APPROACHES}")
     hd_mode = os.environ.get("MUSED_HDBSCAN", "package") if approach == "HDBSCAN_batch" else None
@@ -975,6 +996,8 @@ def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_
     k_range = check_k_range(n_clusters_range, approach, len(data_modalities[0]))
     if score and complete_true_labels is None:
         raise ValueError("score=True compares against complete_true_labels, which is None")
+    if partition_scores and complete_true_labels is None:
+        raise ValueError("partition_scores=True compares against complete_true_labels, which is None")
     t0 = time.time_ns()
     emb, _, nnz = batch_embedding(data_modalities, list(modality_types), reduced_dim, k_basis, seed, timings=timings,
                                   modality_weights=modality_weights, fusion_threshold=fusion_threshold, modality_ks=modality_ks)
@@ -1016,6 +1039,8 @@ def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_
         results["chosen_k"] = [int(n_clusters)]
     if scores is not None:
         results["internal_scores"] = [scores]
+    if partition_scores:
+        _partition_scored(results, clusters, np.array(complete_true_labels))
     return results
 
 
