@@ -1536,8 +1536,46 @@ int mused_debug_eig_time(const double* G, int n, int batch, int sweeps, int reps
   return rc;
 }
 
-// Unit-testable primitive: eigen-decomposition of `batch` symmetric n x n fp64 matrices
-// (n even).  evals: batch x n (unsorted), V: batch x n x n with V[:, j] the eigenvector of
+// Diagnostic (not part of the declared ABI): a plan that outlives one solve, as the pipeline's plans do -- what a second solve
+// inherits (convergence flags, the queue's counters and unit ring, the blocked direct solver's reject list) is only visible
+// this way.  Thin wrappers: eig_plan_create with the caller's flags / need / rep (device ints or null) / own_graph ...
+int mused_debug_eig_plan_create(int n, int batch, int sweeps, int flags, int need, const int* rep, int own_graph, void** handle) {
+  MUSED_REQUIRE(handle, "mused_debug_eig_plan_create: null handle");
+  EigPlan* p = nullptr;
+  const int rc = eig_plan_create(n, batch, sweeps, own_graph != 0, &p, rep, flags, nullptr, need);
+  if (rc) return rc;
+  *handle = p;
+  return MUSED_OK;
+}
+
+// ... G (batch x n x n, device) copied into the plan's input, eig_plan_run_inplace (evals / V may be null), the working copy
+// (batch x ldn x ldn, column-major: columns lam_j u_j) copied to Gc_out when that is not null, and the stream synchronised.
+int mused_debug_eig_plan_run(void* handle, const double* G, double* evals, double* V, double* Gc_out, int allow_graph,
+                             void* stream) {
+  MUSED_REQUIRE(handle && G, "mused_debug_eig_plan_run: null pointer");
+  EigPlan* p = (EigPlan*)handle;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t batch = (size_t)p->batch;
+  MUSED_CHECK_HIP(hipMemcpyAsync(eig_plan_input(p), G, sizeof(double) * batch * p->n * p->n, hipMemcpyDeviceToDevice, st));
+  int rc = eig_plan_run_inplace(p, evals, V, st, allow_graph != 0);
+  if (!rc && Gc_out) {
+    const hipError_t ce = hipMemcpyAsync(Gc_out, p->Gc, sizeof(double) * batch * p->c.ldn * p->c.ldn, hipMemcpyDeviceToDevice, st);
+    if (ce != hipSuccess) rc = MUSED_ERR_HIP;
+  }
+  const hipError_t e = hipStreamSynchronize(st);
+  if (rc) return rc;
+  MUSED_CHECK_HIP(e);
+  return MUSED_OK;
+}
+
+int mused_debug_eig_plan_destroy(void* handle) {
+  eig_plan_destroy((EigPlan*)handle);
+  return MUSED_OK;
+}
+
+// Unit-testable primitive: eigen-decomposition of `batch` symmetric POSITIVE SEMIDEFINITE n x n fp64 matrices
+// (n even; the one-sided Jacobi returns column norms: an indefinite matrix would come back as |lam_j|).
+// evals: batch x n (unsorted), V: batch x n x n with V[:, j] the eigenvector of
 // evals[j].  Creates and destroys a plan per call (test/diagnostic use only).
 int mused_syevj_batched(const double* G, int n, int batch, int sweeps, double* evals, double* V, void* stream) {
   MUSED_REQUIRE(G && evals && V, "mused_syevj_batched: null pointer");
