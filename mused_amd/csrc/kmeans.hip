@@ -19,23 +19,16 @@
 // scikit-learn for that window.
 //
 // Two entries: mused_kmeans_lloyd keeps all k centres and the k x d sums of a chunk in LDS (k * d <= 8192);
-// mused_kmeans_lloyd_wide (second half of this file) works in tiles for any k <= 1024, d <= 512 and returns the same bits.
+// mused_kmeans_lloyd_wide works in tiles for any k <= 1024, d <= 512 and returns the same bits.  Both run km_lloyd_run,
+// the one host driver (workspace from km_carve), with their own E-step and M-step launches, and both take from
+// kmeans_common.h what decides a label or a stop: the first-minimum rule (km_take, km_lane_min), the centre norms
+// (km_csq_kernel, km_norm2), the shift tree with the stop rule (km_finish) and the tile choice of the streamed E step
+// (km_stream_tiles), which csrc/minibatch.hip uses too.
 #include <stdlib.h>
 
-#include <mutex>
-
-#include "internal.h"
+#include "kmeans_common.h"
 
 namespace mused {
-
-constexpr int KM_CHUNK = 256;
-
-struct KmInfo {
-  int iters;      // Lloyd iterations run
-  int done;       // 0 running, 1 strict convergence (labels repeated), 2 centre shift <= tol
-  int empty;      // a cluster lost all its rows
-  int changed;    // scratch: some label differs from the previous iteration
-};
 
 __global__ void km_center_kernel(const double* __restrict__ X, long ldx, const double* __restrict__ mean, int n, int d,
                                  double* __restrict__ Xc) {
@@ -45,12 +38,13 @@ __global__ void km_center_kernel(const double* __restrict__ X, long ldx, const d
   Xc[gid] = X[(long)r * ldx + c] - mean[c];
 }
 
-__global__ void km_csq_kernel(const double* __restrict__ C, int k, int d, double* __restrict__ csq) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= k) return;
-  double s = 0.0;
-  for (int c = 0; c < d; ++c) s += C[(long)j * d + c] * C[(long)j * d + c];
-  csq[j] = s;
+// pcnt[j] <- rows of a chunk (labels sL[0 .. rows) in LDS) with label j; k may exceed the 256 threads
+__device__ __forceinline__ void km_chunk_counts(const int* sL, int rows, int k, int* __restrict__ pcnt) {
+  for (int j = threadIdx.x; j < k; j += KM_CHUNK) {
+    int cnt = 0;
+    for (int r = 0; r < rows; ++r) cnt += (sL[r] == j);
+    pcnt[j] = cnt;
+  }
 }
 
 // E step for one chunk of 256 rows + the chunk's partial sums of the M step.  LDS: centres [k][d], sums [k][d], labels.
@@ -71,18 +65,14 @@ __global__ __launch_bounds__(KM_CHUNK) void km_assign_kernel(const double* __res
   }
   __syncthreads();
   const int row = r0 + t;
-  int lab = -1;
+  double best = KM_NO_DIST;
+  int lab = KM_NO_LABEL;  // stays so for a thread past the last row: sL[t] is not read there
   if (row < n) {
     const double* x = Xc + (long)row * d;
-    double best = 0.0;
     for (int j = 0; j < k; ++j) {
       double dot = 0.0;
       for (int c = 0; c < d; ++c) dot = fma(x[c], sC[(long)j * d + c], dot);
-      const double dist = csq[j] - 2.0 * dot;
-      if (j == 0 || dist < best) {  // strict <: the first minimum wins, as in sklearn
-        best = dist;
-        lab = j;
-      }
+      km_take(best, lab, csq[j] - 2.0 * dot, j);
     }
     labels[row] = lab;
     if (labels_old && labels_old[row] != lab) info->changed = 1;  // benign race: everybody writes 1
@@ -98,23 +88,17 @@ __global__ __launch_bounds__(KM_CHUNK) void km_assign_kernel(const double* __res
       sS[(long)j * d + c] += Xc[(long)(r0 + r) * d + c];
     }
   }
-  for (int j = t; j < k; j += KM_CHUNK) {  // k may exceed the chunk (k <= 1024, k * d <= 8192)
-    int cnt = 0;
-    for (int r = 0; r < rows; ++r) cnt += (sL[r] == j);
-    pcnt[(long)blockIdx.x * k + j] = cnt;
-  }
+  km_chunk_counts(sL, rows, k, pcnt + (long)blockIdx.x * k);
   __syncthreads();
   for (int e = t; e < k * d; e += KM_CHUNK) psum[(long)blockIdx.x * k * d + e] = sS[e];
 }
 
-// The same E step + M-step partials with the chunk's rows staged through LDS (round 4).  The kernel above gives every thread a
-// row and lets it read that row from global memory once per centre: 64 different cache lines per load instruction, the row
-// fetched k times -- 223 us per call at n = 10,000, d = 128, k = 8, ~50 calls per window, 4 % of the benchmark's kernel time
-// for 10 MFLOP.  Here a 256-row chunk travels as 256 / TR sub-tiles of TR rows, loaded coalesced into LDS (pitch d + 1);
-// PT = 256 / TR threads share a row (centres j = part, part + PT, ...: every dot product still runs over c = 0 .. d - 1 in
-// sequence, so the distances have the same bits) and agree on the first minimum by a lexicographic (distance, j) exchange;
-// the M-step partials add the rows of the chunk in the same order as before, from LDS.  Results are bit-identical to the
-// kernel above (same sums in the same order).
+// The same E step + M-step partials with the chunk's rows staged through LDS.  The kernel above gives every thread a row
+// and reads it from global memory once per centre (64 cache lines per load instruction, the row fetched k times: DESIGN.md).
+// Here a 256-row chunk travels as 256 / TR sub-tiles of TR rows, loaded coalesced into LDS (pitch d + 1); PT = 256 / TR
+// threads share a row (centres j = part, part + PT, ...: every dot product still runs over c = 0 .. d - 1 in sequence)
+// and agree on the first minimum by km_lane_min; the M-step partials add the rows of the chunk in the same order as
+// before, from LDS.  Results are bit-identical to the kernel above (same sums in the same order).
 template <int TR>
 __global__ __launch_bounds__(KM_CHUNK) void km_assign_tiled_kernel(const double* __restrict__ Xc, int n, int d, int k,
                                                                   const double* __restrict__ C, const double* __restrict__ csq,
@@ -145,30 +129,18 @@ __global__ __launch_bounds__(KM_CHUNK) void km_assign_tiled_kernel(const double*
       xs[(long)r * dp + c] = Xc[(long)(rb + r) * d + c];
     }
     __syncthreads();
-    double best = 1.7976931348623157e308;
-    int lab = 0x7fffffff;
+    double best = KM_NO_DIST;
+    int lab = KM_NO_LABEL;
     if (row < nr) {
       const double* x = xs + (long)row * dp;
       for (int j = part; j < k; j += PT) {
         const double* cj = sC + (long)j * dp;
         double dot = 0.0;
         for (int c = 0; c < d; ++c) dot = fma(x[c], cj[c], dot);
-        const double dist = csq[j] - 2.0 * dot;
-        if (lab == 0x7fffffff || dist < best) {  // strict <: the first minimum wins, as in sklearn
-          best = dist;
-          lab = j;
-        }
+        km_take(best, lab, csq[j] - 2.0 * dot, j);
       }
     }
-#pragma unroll
-    for (int o = 1; o < PT; o <<= 1) {  // the PT threads of a row are adjacent lanes
-      const double ob = __shfl_xor(best, o);
-      const int ol = __shfl_xor(lab, o);
-      if (ol != 0x7fffffff && (lab == 0x7fffffff || ob < best || (ob == best && ol < lab))) {
-        best = ob;
-        lab = ol;
-      }
-    }
+    km_lane_min(best, lab, PT);  // the PT threads of a row are adjacent lanes
     if (part == 0 && row < nr) {
       labels[rb + row] = lab;
       if (labels_old && labels_old[rb + row] != lab) info->changed = 1;  // benign race: everybody writes 1
@@ -182,11 +154,7 @@ __global__ __launch_bounds__(KM_CHUNK) void km_assign_tiled_kernel(const double*
   }
   if (!want_sums) return;
   __syncthreads();
-  for (int j = t; j < k; j += KM_CHUNK) {  // k may exceed the chunk (k <= 1024, k * d <= 8192)
-    int cnt = 0;
-    for (int r = 0; r < rows; ++r) cnt += (sL[r] == j);
-    pcnt[(long)blockIdx.x * k + j] = cnt;
-  }
+  km_chunk_counts(sL, rows, k, pcnt + (long)blockIdx.x * k);
   for (int e = t; e < k * d; e += KM_CHUNK) psum[(long)blockIdx.x * k * d + e] = sS[e];
 }
 
@@ -195,7 +163,6 @@ __global__ __launch_bounds__(1024) void km_update_kernel(const double* __restric
                                                         int nchunk, int k, int d, double* __restrict__ C,
                                                         double* __restrict__ csq, double tol, int first_iter,
                                                         KmInfo* __restrict__ info) {
-  __shared__ double red[1024];
   __shared__ int s_cnt[1024];
   if (info->done) return;
   const int t = threadIdx.x;
@@ -214,26 +181,10 @@ __global__ __launch_bounds__(1024) void km_update_kernel(const double* __restric
     // sklearn averages by multiplying with the reciprocal (_k_means_common.pyx _average_centers: alpha = 1.0 / weight)
     const double nw = s_cnt[j] > 0 ? s * (1.0 / (double)s_cnt[j]) : C[e];
     const double df = nw - C[e];
-    acc += df * df;
+    acc = fma(df, df, acc);
     C[e] = nw;
   }
-  red[t] = acc;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
-  for (int j = t; j < k; j += 1024) {
-    double s = 0.0;
-    for (int c = 0; c < d; ++c) s += C[(long)j * d + c] * C[(long)j * d + c];
-    csq[j] = s;
-  }
-  if (t == 0) {
-    info->iters += 1;
-    if (!first_iter && info->changed == 0) info->done = 1;       // labels repeated: strict convergence
-    else if (red[0] <= tol) info->done = 2;                       // centres stopped moving
-    info->changed = 0;
-  }
+  km_finish(acc, C, k, d, csq, tol, first_iter, info);
 }
 
 // LDS bytes of km_assign_tiled_kernel<tr>: centres [k][d + 1], sums [k][d], rows [tr][d + 1], labels
@@ -257,17 +208,19 @@ static int km_assign_rows(int d, int k) {
 
 // ---- any k x d (k <= 1024, d <= 512): mused_kmeans_lloyd_wide ---------------------------------------------------------
 // The kernels above keep all k centres and a k x d block of sums in LDS, hence k * d <= 8192.  Here the iteration is three
-// steps that each hold a tile: the E step streams the centres through LDS (mbkm_assign_kernel's scheme, csrc/minibatch.hip),
-// the M-step partials take a column tile of the sums per workgroup, and the centre sums are spread over workgroups.  Every
-// sum keeps the order of the kernels above -- a dot product runs over c = 0 .. d - 1, the rows of a 256-row chunk are added
-// in row order from 0.0, the chunks in chunk order, the shift as the per-thread sums e = t, t + 1024, ... and the same tree
+// steps that each hold a tile: the E step streams the centres through LDS (kmw_assign_kernel), the M-step
+// partials take a column tile of the sums per workgroup, and the centre sums are spread over workgroups.  Every sum keeps
+// the order of the kernels above -- a dot product runs over c = 0 .. d - 1, the rows of a 256-row chunk are added in row
+// order from 0.0, the chunks in chunk order, the shift as the per-thread sums e = t, t + 1024, ... into km_finish's tree
 // -- so labels, info and the centres' bits equal mused_kmeans_lloyd's wherever both accept the shape.
 constexpr size_t KMW_ASSIGN_LDS_DOUBLES = 19456;  // 152 KiB: row tile + centre tile of the E step
 
 // E step.  A workgroup owns TR rows (LDS, pitch d + 1) and walks the centres in tiles of KT (LDS, pitch d + 1); PT = 256 / TR
 // adjacent lanes share a row and take centres part, part + PT, ... of every tile, two at a time (two independent chains: each
 // dot product is still sequential over c).  Candidates of one thread come in ascending j, so strict < keeps the first
-// minimum; the PT lanes then agree on the lexicographic (distance, j) minimum.
+// minimum; the PT lanes then agree on the lexicographic (distance, j) minimum.  The two rules are km_take and km_lane_min
+// (kmeans_common.h) written out, and mbkm_assign_kernel (csrc/minibatch.hip) is this kernel without the Lloyd flags on
+// pitched rows: one template for both, and calls of the helpers here, measured 3 to 9 % slower.
 __global__ __launch_bounds__(KM_CHUNK) void kmw_assign_kernel(const double* __restrict__ Xc, int n, int d, int k,
                                                              const double* __restrict__ C, const double* __restrict__ csq,
                                                              int* __restrict__ labels, const int* __restrict__ labels_old,
@@ -286,8 +239,8 @@ __global__ __launch_bounds__(KM_CHUNK) void kmw_assign_kernel(const double* __re
   }
   const int row = t / PT, part = t % PT;
   const double* x = xs + (long)row * dp;
-  double best = 1.7976931348623157e308;
-  int lab = 0x7fffffff;
+  double best = KM_NO_DIST;
+  int lab = KM_NO_LABEL;
   for (int j0 = 0; j0 < k; j0 += KT) {
     const int kt = min(KT, k - j0);
     __syncthreads();  // the row tile is staged / the previous centre tile is consumed
@@ -307,7 +260,7 @@ __global__ __launch_bounds__(KM_CHUNK) void kmw_assign_kernel(const double* __re
         db = fma(x[c], cb[c], db);
       }
       const double dista = csq[j0 + jj] - 2.0 * da;
-      if (lab == 0x7fffffff || dista < best) {  // strict <: the first minimum wins, as in sklearn
+      if (lab == KM_NO_LABEL || dista < best) {  // strict <: the first minimum wins, as in sklearn
         best = dista;
         lab = j0 + jj;
       }
@@ -322,7 +275,7 @@ __global__ __launch_bounds__(KM_CHUNK) void kmw_assign_kernel(const double* __re
       double da = 0.0;
       for (int c = 0; c < d; ++c) da = fma(x[c], ca[c], da);
       const double dista = csq[j0 + jj] - 2.0 * da;
-      if (lab == 0x7fffffff || dista < best) {
+      if (lab == KM_NO_LABEL || dista < best) {
         best = dista;
         lab = j0 + jj;
       }
@@ -331,7 +284,7 @@ __global__ __launch_bounds__(KM_CHUNK) void kmw_assign_kernel(const double* __re
   for (int o = 1; o < PT; o <<= 1) {  // the PT threads of a row are adjacent lanes of one wave (PT <= 16)
     const double ob = __shfl_xor(best, o);
     const int ol = __shfl_xor(lab, o);
-    if (ol != 0x7fffffff && (lab == 0x7fffffff || ob < best || (ob == best && ol < lab))) {
+    if (ol != KM_NO_LABEL && (lab == KM_NO_LABEL || ob < best || (ob == best && ol < lab))) {
       best = ob;
       lab = ol;
     }
@@ -366,13 +319,7 @@ __global__ __launch_bounds__(KM_CHUNK) void kmw_partial_kernel(const double* __r
       if ((j & gmask) == g && (unsigned)j < (unsigned)k) sS[(long)j * DT + c] += x[(long)r * d];
     }
   }
-  if (blockIdx.y == 0) {
-    for (int j = t; j < k; j += KM_CHUNK) {
-      int cnt = 0;
-      for (int r = 0; r < rows; ++r) cnt += (sL[r] == j);
-      pcnt[(long)blockIdx.x * k + j] = cnt;
-    }
-  }
+  if (blockIdx.y == 0) km_chunk_counts(sL, rows, k, pcnt + (long)blockIdx.x * k);
   __syncthreads();
   for (int e = t; e < k * DT; e += KM_CHUNK) {
     const int j = e / DT, cc = e - j * DT;
@@ -399,58 +346,23 @@ __global__ __launch_bounds__(256) void kmw_centres_kernel(const double* __restri
   C[e] = nw;
 }
 
-// M step, second half: the total squared shift in km_update_kernel's order, the centre norms and the stopping rule.
+// M step, second half: the total squared shift in km_update_kernel's order, then km_finish as there.
 __global__ __launch_bounds__(1024) void kmw_finish_kernel(const double* __restrict__ shift, int k, int d,
                                                          const double* __restrict__ C, double* __restrict__ csq, double tol,
                                                          int first_iter, KmInfo* __restrict__ info) {
-  __shared__ double red[1024];
   if (info->done) return;
-  const int t = threadIdx.x;
   double acc = 0.0;  // this thread's share of the squared shift, elements in a fixed order
-  for (int e = t; e < k * d; e += 1024) {
-    const double df = shift[e];
-    acc += df * df;
-  }
-  red[t] = acc;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
-  for (int j = t; j < k; j += 1024) {
-    double s = 0.0;
-    for (int c = 0; c < d; ++c) s += C[(long)j * d + c] * C[(long)j * d + c];
-    csq[j] = s;
-  }
-  if (t == 0) {
-    info->iters += 1;
-    if (!first_iter && info->changed == 0) info->done = 1;       // labels repeated: strict convergence
-    else if (red[0] <= tol) info->done = 2;                       // centres stopped moving
-    info->changed = 0;
-  }
+  for (int e = threadIdx.x; e < k * d; e += 1024) acc = fma(shift[e], shift[e], acc);
+  km_finish(acc, C, k, d, csq, tol, first_iter, info);
 }
 
-// Tiles of the wide kernels: TR rows (32, else 16) and KT centres (a multiple of PT = 256 / TR, or all k) of the E step
-// within its budget; DT columns (64 / 32 / 16) of the M-step partials: the widest whose k x DT sums stay within 64 KiB
-// (several workgroups per CU), 16 beyond that (128 KiB at k = 1024), and no wider than d needs.
+// Tiles of the wide kernels: TR rows and KT centres of the E step within its budget (km_stream_tiles); DT columns
+// (64 / 32 / 16) of the M-step partials: the widest whose k x DT sums stay within 64 KiB (several workgroups per CU), 16
+// beyond that (128 KiB at k = 1024), and no wider than d needs.
 static size_t kmw_partial_lds(int dt, int k) { return 8 * (size_t)k * dt + 4 * KM_CHUNK + 16; }
 static bool kmw_tiles(int d, int k, int* TR, int* KT, int* DT) {
   if (d <= 0 || k <= 0 || d > 512 || k > 1024) return false;
-  const int cap = (int)(KMW_ASSIGN_LDS_DOUBLES / (d + 1));
-  bool ok = false;
-  for (int tr : {32, 16}) {
-    const int pt = KM_CHUNK / tr;
-    int kt = cap - tr;
-    if (kt >= k) kt = k;
-    else kt = (kt / pt) * pt;
-    if (kt >= 1 && (kt >= pt || kt == k)) {
-      *TR = tr;
-      *KT = kt;
-      ok = true;
-      break;
-    }
-  }
-  if (!ok) return false;
+  if (!km_stream_tiles(KMW_ASSIGN_LDS_DOUBLES, d, k, TR, KT)) return false;
   int dt = 16;
   for (int w : {64, 32})
     if (8 * (size_t)k * w <= 64 * 1024) {
@@ -462,6 +374,72 @@ static bool kmw_tiles(int d, int k, int* TR, int* KT, int* DT) {
   return kmw_partial_lds(dt, k) <= KM_LDS_MAX;
 }
 
+// The workspace of both entries; `shift` (k x d) only in the wide one.  The bytes count 8 n for the n labels of lab2 and
+// 4096 on top, which covers the carver's rounding (seven arrays).
+struct KmWs {
+  double *Xc, *psum, *shift, *csq;
+  int *pcnt, *lab2;
+  KmInfo* info;
+};
+static long km_ws_bytes(int n, int d, int k, bool wide) {
+  const long nchunk = cdiv(n, KM_CHUNK);
+  return 8l * n * d + 8l * nchunk * k * d + (wide ? 8l * k * d : 0) + 4l * nchunk * k + 8l * k + 8l * n + 4096;
+}
+static KmWs km_carve(void* ws, int n, int d, int k, bool wide) {
+  const size_t nchunk = cdiv(n, KM_CHUNK), kd = (size_t)k * d;
+  WsCarver c{(char*)ws};
+  KmWs w;
+  w.Xc = c.take<double>((size_t)n * d);
+  w.psum = c.take<double>(nchunk * kd);
+  w.shift = wide ? c.take<double>(kd) : nullptr;
+  w.csq = c.take<double>(k);
+  w.pcnt = c.take<int>(nchunk * k);
+  w.lab2 = c.take<int>(n);
+  w.info = c.take<KmInfo>(1);
+  return w;
+}
+
+// The Lloyd iterations of both entries, after their argument checks.  estep(labels, labels_old or null, want_sums) queues
+// the E step of an iteration and, with want_sums, the M-step partials; mstep(first_iter) queues the rest of the M step,
+// which ends in km_finish.  BLOCKING: reads KmInfo every four iterations.
+template <typename EStep, typename MStep>
+static int km_lloyd_run(const double* X, long ld, int n, int d, int k, const double* mean, double* centers, int max_iter,
+                        int* labels_out, int* info_out, const KmWs& w, hipStream_t st, EStep estep, MStep mstep) {
+  MUSED_CHECK_HIP(hipMemsetAsync(w.info, 0, sizeof(KmInfo), st));
+  hipLaunchKernelGGL(km_center_kernel, dim3(cdiv((long)n * d, 256)), dim3(256), 0, st, X, ld, mean, n, d, w.Xc);
+  hipLaunchKernelGGL(km_csq_kernel, dim3(cdiv(k, 64)), dim3(64), 0, st, centers, k, d, w.csq);
+  KmInfo h = {};
+  int* cur = labels_out;
+  int* old = w.lab2;
+  int it = 0;
+  while (it < max_iter && !h.done) {
+    const int batch = (max_iter - it) < 4 ? (max_iter - it) : 4;  // iterations between two reads of the stopping flag
+    for (int b = 0; b < batch; ++b, ++it) {
+      estep(cur, it > 0 ? old : (const int*)nullptr, 1);
+      mstep(it == 0 ? 1 : 0);
+      int* tmp = cur; cur = old; old = tmp;  // `old` now holds the labels of the iteration just queued
+    }
+    MUSED_LAUNCH_CHECK();
+    MUSED_CHECK_HIP(hipMemcpyAsync(&h, w.info, sizeof(h), hipMemcpyDeviceToHost, st));
+    MUSED_CHECK_HIP(hipStreamSynchronize(st));
+    if (h.empty) break;
+  }
+  // labels of the last iteration that RAN are in one of the two buffers: iterations queued after convergence returned at
+  // once, so parity of h.iters tells which.  Iteration i (0-based) wrote labels_out when i is even.
+  int* last = ((h.iters - 1) % 2 == 0) ? labels_out : w.lab2;
+  if (h.done != 1 && !h.empty) {
+    // not strictly converged: labels must match the final centres (one more E step, no update)
+    MUSED_CHECK_HIP(hipMemsetAsync(&w.info->done, 0, sizeof(int), st));
+    estep(labels_out, (const int*)nullptr, 0);
+    MUSED_LAUNCH_CHECK();
+  } else if (last != labels_out) {
+    MUSED_CHECK_HIP(hipMemcpyAsync(labels_out, last, 4l * n, hipMemcpyDeviceToDevice, st));
+  }
+  MUSED_CHECK_HIP(hipStreamSynchronize(st));
+  info_out[0] = h.iters; info_out[1] = h.done; info_out[2] = h.empty; info_out[3] = 0;
+  return MUSED_OK;
+}
+
 }  // namespace mused
 
 using namespace mused;
@@ -470,9 +448,7 @@ extern "C" {
 
 // workspace bytes for mused_kmeans_lloyd_wide; -1 for a shape it rejects
 long mused_kmeans_wide_ws_bytes(int n, int d, int k) {
-  if (n <= 0 || d <= 0 || k <= 0 || k > 1024 || d > 512 || k > n) return -1;
-  const long nchunk = (n + KM_CHUNK - 1) / KM_CHUNK;
-  return 8l * n * d + 8l * nchunk * k * d + 8l * k * d + 4l * nchunk * k + 8l * k + 8l * n + 4096;
+  return n <= 0 || d <= 0 || k <= 0 || k > 1024 || d > 512 || k > n ? -1 : km_ws_bytes(n, d, k, true);
 }
 
 // diagnostic: out[0..2] = {rows per tile, centres per tile of the E step, columns per tile of the M-step partials} that
@@ -495,76 +471,35 @@ int mused_kmeans_lloyd_wide(const double* X, long ld, int n, int d, int k, const
   MUSED_REQUIRE(kmw_tiles(d, k, &TR, &KT, &DT), "mused_kmeans_lloyd_wide: no tile fits d = %d, k = %d", d, k);
   hipStream_t st = (hipStream_t)stream;
   const int nchunk = cdiv(n, KM_CHUNK);
-  char* w = (char*)ws;
-  double* Xc = (double*)w; w += 8l * n * d;
-  double* psum = (double*)w; w += 8l * nchunk * k * d;
-  double* shift = (double*)w; w += 8l * k * d;
-  double* csq = (double*)w; w += 8l * k;
-  int* pcnt = (int*)w; w += 4l * nchunk * k;
-  w = (char*)(((uintptr_t)w + 15) & ~(uintptr_t)15);
-  int* lab2 = (int*)w; w += 4l * n;
-  w = (char*)(((uintptr_t)w + 15) & ~(uintptr_t)15);
-  KmInfo* info = (KmInfo*)w;
+  const KmWs w = km_carve(ws, n, d, k, true);
   static std::once_flag once;
   static hipError_t aerr = hipSuccess;
   std::call_once(once, [] {
-    aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(kmw_assign_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(8 * KMW_ASSIGN_LDS_DOUBLES));
-    if (aerr == hipSuccess)
-      aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(kmw_partial_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KM_LDS_MAX);
+    aerr = km_allow_lds(reinterpret_cast<const void*>(kmw_assign_kernel), 8 * KMW_ASSIGN_LDS_DOUBLES);
+    if (aerr == hipSuccess) aerr = km_allow_lds(reinterpret_cast<const void*>(kmw_partial_kernel), KM_LDS_MAX);
   });
   MUSED_CHECK_HIP(aerr);
   const size_t lds_e = 8 * (size_t)(TR + KT) * (d + 1), lds_m = kmw_partial_lds(DT, k);
-  auto assign = [&](int* cur_, const int* old_, int want) {
-    hipLaunchKernelGGL(kmw_assign_kernel, dim3(cdiv(n, TR)), dim3(KM_CHUNK), lds_e, st, Xc, n, d, k, centers, csq, cur_, old_,
-                       info, TR, KT);
-    if (want)
-      hipLaunchKernelGGL(kmw_partial_kernel, dim3(nchunk, cdiv(d, DT)), dim3(KM_CHUNK), lds_m, st, Xc, n, d, k, cur_, psum,
-                         pcnt, info, DT);
-  };
-  MUSED_CHECK_HIP(hipMemsetAsync(info, 0, sizeof(KmInfo), st));
-  hipLaunchKernelGGL(km_center_kernel, dim3(cdiv((long)n * d, 256)), dim3(256), 0, st, X, ld, mean, n, d, Xc);
-  hipLaunchKernelGGL(km_csq_kernel, dim3(cdiv(k, 64)), dim3(64), 0, st, centers, k, d, csq);
-  KmInfo h;
-  memset(&h, 0, sizeof(h));
-  int* cur = labels_out;
-  int* old = lab2;
-  int it = 0;
-  while (it < max_iter && !h.done) {
-    const int batch = (max_iter - it) < 4 ? (max_iter - it) : 4;  // iterations between two reads of the stopping flag
-    for (int b = 0; b < batch; ++b, ++it) {
-      assign(cur, it > 0 ? old : (const int*)nullptr, 1);
-      hipLaunchKernelGGL(kmw_centres_kernel, dim3(cdiv(k * d, 256)), dim3(256), 0, st, psum, pcnt, nchunk, k, d, centers,
-                         shift, info);
-      hipLaunchKernelGGL(kmw_finish_kernel, dim3(1), dim3(1024), 0, st, shift, k, d, centers, csq, tol, it == 0 ? 1 : 0,
-                         info);
-      int* tmp = cur; cur = old; old = tmp;  // `old` now holds the labels of the iteration just queued
-    }
-    MUSED_LAUNCH_CHECK();
-    MUSED_CHECK_HIP(hipMemcpyAsync(&h, info, sizeof(h), hipMemcpyDeviceToHost, st));
-    MUSED_CHECK_HIP(hipStreamSynchronize(st));
-    if (h.empty) break;
-  }
-  // as in mused_kmeans_lloyd: iteration i (0-based) wrote labels_out when i is even
-  int* last = ((h.iters - 1) % 2 == 0) ? labels_out : lab2;
-  if (h.done != 1 && !h.empty) {
-    // not strictly converged: labels must match the final centres (one more E step, no update)
-    MUSED_CHECK_HIP(hipMemsetAsync(&info->done, 0, sizeof(int), st));
-    assign(labels_out, (const int*)nullptr, 0);
-    MUSED_LAUNCH_CHECK();
-  } else if (last != labels_out) {
-    MUSED_CHECK_HIP(hipMemcpyAsync(labels_out, last, 4l * n, hipMemcpyDeviceToDevice, st));
-  }
-  MUSED_CHECK_HIP(hipStreamSynchronize(st));
-  info_out[0] = h.iters; info_out[1] = h.done; info_out[2] = h.empty; info_out[3] = 0;
-  return MUSED_OK;
+  return km_lloyd_run(
+      X, ld, n, d, k, mean, centers, max_iter, labels_out, info_out, w, st,
+      [&](int* cur, const int* old, int want) {
+        hipLaunchKernelGGL(kmw_assign_kernel, dim3(cdiv(n, TR)), dim3(KM_CHUNK), lds_e, st, w.Xc, n, d, k, centers, w.csq, cur,
+                           old, w.info, TR, KT);
+        if (want)
+          hipLaunchKernelGGL(kmw_partial_kernel, dim3(nchunk, cdiv(d, DT)), dim3(KM_CHUNK), lds_m, st, w.Xc, n, d, k, cur,
+                             w.psum, w.pcnt, w.info, DT);
+      },
+      [&](int first_iter) {
+        hipLaunchKernelGGL(kmw_centres_kernel, dim3(cdiv(k * d, 256)), dim3(256), 0, st, w.psum, w.pcnt, nchunk, k, d, centers,
+                           w.shift, w.info);
+        hipLaunchKernelGGL(kmw_finish_kernel, dim3(1), dim3(1024), 0, st, w.shift, k, d, centers, w.csq, tol, first_iter,
+                           w.info);
+      });
 }
 
 // workspace bytes for mused_kmeans_lloyd
 long mused_kmeans_ws_bytes(int n, int d, int k) {
-  if (n <= 0 || d <= 0 || k <= 0) return -1;
-  const long nchunk = (n + KM_CHUNK - 1) / KM_CHUNK;
-  return 8l * n * d + 8l * nchunk * k * d + 4l * nchunk * k + 8l * k + 8l * n + 4096;
+  return n <= 0 || d <= 0 || k <= 0 ? -1 : km_ws_bytes(n, d, k, false);
 }
 
 // diagnostic: the sub-tile rows mused_kmeans_lloyd launches its E/M step with for (d, k): 64 / 32 / 16, 0 = row per thread
@@ -574,12 +509,8 @@ int mused_kmeans_assign_rows(int d, int k) {
 }
 
 // Replaces the Lloyd iterations of KMeans(n_clusters = k, random_state = seed).fit_predict(X)
-// (matrix_operations.py:149-153) for the embedding X (n x d fp64, pitch ld, DEVICE), given -- from mused_kmeans_moments
-// and mused_kmeans_seed, or computed on the host by NumPy and scikit-learn -- the column means `mean` (d), the k-means++
-// centres of the CENTRED rows `centers` (k x d, in: seeds, out: final centres of the centred data) and
-// tol = mean(var(X, axis = 0)) * 1e-4 (by value: a caller that computed it on the device reads it first).
-// labels_out: n int32 (DEVICE).  info_out (4 ints, HOST): {iterations, 1 strict / 2 tol / 0 max_iter, empty-cluster
-// flag, 0}.  BLOCKING (reads its stopping flag every few iterations).  k * d <= 8192.
+// (matrix_operations.py:149-153); arguments and contract: include/mused_hip.h.  tol comes by value: a caller that
+// computed it on the device reads it first.  BLOCKING (reads its stopping flag every few iterations).  k * d <= 8192.
 int mused_kmeans_lloyd(const double* X, long ld, int n, int d, int k, const double* mean, double* centers, double tol,
                        int max_iter, int* labels_out, int* info_out, void* ws, long ws_bytes, void* stream) {
   MUSED_REQUIRE(X && mean && centers && labels_out && info_out && ws && n > 0 && d > 0 && k > 0 && k <= n && ld >= d,
@@ -588,73 +519,34 @@ int mused_kmeans_lloyd(const double* X, long ld, int n, int d, int k, const doub
   MUSED_REQUIRE(ws_bytes >= mused_kmeans_ws_bytes(n, d, k), "mused_kmeans_lloyd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int nchunk = cdiv(n, KM_CHUNK);
-  char* w = (char*)ws;
-  double* Xc = (double*)w; w += 8l * n * d;
-  double* psum = (double*)w; w += 8l * nchunk * k * d;
-  double* csq = (double*)w; w += 8l * k;
-  int* pcnt = (int*)w; w += 4l * nchunk * k;
-  w = (char*)(((uintptr_t)w + 15) & ~(uintptr_t)15);
-  int* lab2 = (int*)w; w += 4l * n;
-  w = (char*)(((uintptr_t)w + 15) & ~(uintptr_t)15);
-  KmInfo* info = (KmInfo*)w;
+  const KmWs w = km_carve(ws, n, d, k, false);
   const int tr = km_assign_rows(d, k);
   const size_t lds = tr ? km_tiled_lds(tr, d, k) : 8 * 2 * (size_t)k * d + 4 * (KM_CHUNK + (size_t)k) + 16;
   static std::once_flag once;
   static hipError_t aerr = hipSuccess;
   std::call_once(once, [] {
-    aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               8 * 2 * 8192 + 4 * (KM_CHUNK + 1024) + 16);
-    if (aerr == hipSuccess)
-      aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_tiled_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KM_LDS_MAX);
-    if (aerr == hipSuccess)
-      aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_tiled_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KM_LDS_MAX);
-    if (aerr == hipSuccess)
-      aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_tiled_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KM_LDS_MAX);
+    aerr = km_allow_lds(reinterpret_cast<const void*>(km_assign_kernel), 8 * 2 * 8192 + 4 * (KM_CHUNK + 1024) + 16);
+    for (const void* tiled : {reinterpret_cast<const void*>(km_assign_tiled_kernel<64>),
+                              reinterpret_cast<const void*>(km_assign_tiled_kernel<32>),
+                              reinterpret_cast<const void*>(km_assign_tiled_kernel<16>)})
+      if (aerr == hipSuccess) aerr = km_allow_lds(tiled, KM_LDS_MAX);
   });
   MUSED_CHECK_HIP(aerr);
-  auto assign = [&](int* cur_, const int* old_, int want) {
-    switch (tr) {
-      case 64: hipLaunchKernelGGL(km_assign_tiled_kernel<64>, dim3(nchunk), dim3(KM_CHUNK), lds, st, Xc, n, d, k, centers, csq, cur_, old_, psum, pcnt, info, want); break;
-      case 32: hipLaunchKernelGGL(km_assign_tiled_kernel<32>, dim3(nchunk), dim3(KM_CHUNK), lds, st, Xc, n, d, k, centers, csq, cur_, old_, psum, pcnt, info, want); break;
-      case 16: hipLaunchKernelGGL(km_assign_tiled_kernel<16>, dim3(nchunk), dim3(KM_CHUNK), lds, st, Xc, n, d, k, centers, csq, cur_, old_, psum, pcnt, info, want); break;
-      default: hipLaunchKernelGGL(km_assign_kernel, dim3(nchunk), dim3(KM_CHUNK), lds, st, Xc, n, d, k, centers, csq, cur_, old_, psum, pcnt, info, want);
-    }
-  };
-  MUSED_CHECK_HIP(hipMemsetAsync(info, 0, sizeof(KmInfo), st));
-  hipLaunchKernelGGL(km_center_kernel, dim3(cdiv((long)n * d, 256)), dim3(256), 0, st, X, ld, mean, n, d, Xc);
-  hipLaunchKernelGGL(km_csq_kernel, dim3(cdiv(k, 64)), dim3(64), 0, st, centers, k, d, csq);
-  KmInfo h;
-  memset(&h, 0, sizeof(h));
-  int* cur = labels_out;
-  int* old = lab2;
-  int it = 0;
-  while (it < max_iter && !h.done) {
-    const int batch = (max_iter - it) < 4 ? (max_iter - it) : 4;  // iterations between two reads of the stopping flag
-    for (int b = 0; b < batch; ++b, ++it) {
-      assign(cur, it > 0 ? old : (const int*)nullptr, 1);
-      hipLaunchKernelGGL(km_update_kernel, dim3(1), dim3(1024), 0, st, psum, pcnt, nchunk, k, d, centers, csq, tol,
-                         it == 0 ? 1 : 0, info);
-      int* tmp = cur; cur = old; old = tmp;  // `old` now holds the labels of the iteration just queued
-    }
-    MUSED_LAUNCH_CHECK();
-    MUSED_CHECK_HIP(hipMemcpyAsync(&h, info, sizeof(h), hipMemcpyDeviceToHost, st));
-    MUSED_CHECK_HIP(hipStreamSynchronize(st));
-    if (h.empty) break;
-  }
-  // labels of the last iteration that RAN are in one of the two buffers: iterations queued after convergence returned at
-  // once, so parity of h.iters tells which.  Iteration i (0-based) wrote labels_out when i is even.
-  int* last = ((h.iters - 1) % 2 == 0) ? labels_out : lab2;
-  if (h.done != 1 && !h.empty) {
-    // not strictly converged: labels must match the final centres (one more E step, no update)
-    MUSED_CHECK_HIP(hipMemsetAsync(&info->done, 0, sizeof(int), st));
-    assign(labels_out, (const int*)nullptr, 0);
-    MUSED_LAUNCH_CHECK();
-  } else if (last != labels_out) {
-    MUSED_CHECK_HIP(hipMemcpyAsync(labels_out, last, 4l * n, hipMemcpyDeviceToDevice, st));
-  }
-  MUSED_CHECK_HIP(hipStreamSynchronize(st));
-  info_out[0] = h.iters; info_out[1] = h.done; info_out[2] = h.empty; info_out[3] = 0;
-  return MUSED_OK;
+  // the fused E step + M-step partials of this (d, k): all four kernels take the same arguments
+  const auto assign = tr == 64   ? km_assign_tiled_kernel<64>
+                      : tr == 32 ? km_assign_tiled_kernel<32>
+                      : tr == 16 ? km_assign_tiled_kernel<16>
+                                 : km_assign_kernel;
+  return km_lloyd_run(
+      X, ld, n, d, k, mean, centers, max_iter, labels_out, info_out, w, st,
+      [&](int* cur, const int* old, int want) {
+        hipLaunchKernelGGL(assign, dim3(nchunk), dim3(KM_CHUNK), lds, st, w.Xc, n, d, k, centers, w.csq, cur, old, w.psum,
+                           w.pcnt, w.info, want);
+      },
+      [&](int first_iter) {
+        hipLaunchKernelGGL(km_update_kernel, dim3(1), dim3(1024), 0, st, w.psum, w.pcnt, nchunk, k, d, centers, w.csq, tol,
+                           first_iter, w.info);
+      });
 }
 
 }  // extern "C"

@@ -9,10 +9,11 @@
 //   reassign    centres[dst] <- X[src], counts <- host vector                               (_kmeans.py _mini_batch_step :1643-1673)
 //
 // The update is deterministic per cluster (no atomics, no order that depends on the schedule), so the centres and counts
-// equal scikit-learn's bit for bit whenever the labels agree.  The distance arithmetic is km_assign_tiled_kernel's
-// (csrc/kmeans.hip): a sequential fma chain over c = 0 .. d - 1, then csq - 2 dot, strict <.  fp64 throughout; k <= 1024,
+// equal scikit-learn's bit for bit whenever the labels agree.  The E step takes the centre norms (km_csq_kernel)
+// and its tiles (km_stream_tiles, within this file's budget) from kmeans_common.h; mbkm_assign_kernel is the wide Lloyd
+// entry's kmw_assign_kernel (csrc/kmeans.hip) without the stop flags, on X with its pitch ld.  fp64 throughout; k <= 1024,
 // d <= 512, no k * d bound: the centres travel through LDS in tiles.
-#include "internal.h"
+#include "kmeans_common.h"
 
 namespace mused {
 
@@ -21,19 +22,11 @@ constexpr int MB_ASSIGN_LDS_DOUBLES = 17920;  // 140 KiB: row tile + centre tile
 constexpr int MB_UPDATE_LDS_DOUBLES = 7168;   // 56 KiB: rows staged by the update kernel (stays under the 64 KiB default)
 constexpr int MB_LIST = 1024;                 // labels scanned per pass of the update kernel
 
-// |c_j|^2 as a sequential fma chain (the bits km_csq_kernel produces)
-__global__ void mbkm_csq_kernel(const double* __restrict__ C, int k, int d, double* __restrict__ csq) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= k) return;
-  double s = 0.0;
-  for (int c = 0; c < d; ++c) s = fma(C[(long)j * d + c], C[(long)j * d + c], s);
-  csq[j] = s;
-}
-
 // E step.  A workgroup owns TR rows (staged in LDS, pitch d + 1) and walks the centres in tiles of KT (LDS, pitch d + 1);
 // PT = 256 / TR adjacent lanes share a row and take centres part, part + PT, ... of every tile, two at a time (two
 // independent chains: the sum of each dot product is still sequential over c).  Candidates of one thread come in
-// ascending j, so strict < keeps the first minimum; the PT threads then agree on the lexicographic (distance, j) minimum.
+// ascending j, so strict < keeps the first minimum; the PT threads then agree on the lexicographic (distance, j) minimum:
+// km_take and km_lane_min (kmeans_common.h) written out, as in kmw_assign_kernel (csrc/kmeans.hip), whose copy this is.
 __global__ __launch_bounds__(MB_THREADS) void mbkm_assign_kernel(const double* __restrict__ X, long ld, int n, int d, int k,
                                                                  const double* __restrict__ C, const double* __restrict__ csq,
                                                                  int* __restrict__ labels, int TR, int KT) {
@@ -49,8 +42,8 @@ __global__ __launch_bounds__(MB_THREADS) void mbkm_assign_kernel(const double* _
   }
   const int row = t / PT, part = t % PT;
   const double* x = xs + (long)row * dp;
-  double best = 1.7976931348623157e308;
-  int lab = 0x7fffffff;
+  double best = KM_NO_DIST;
+  int lab = KM_NO_LABEL;
   for (int j0 = 0; j0 < k; j0 += KT) {
     const int kt = min(KT, k - j0);
     __syncthreads();  // the row tile is staged / the previous centre tile is consumed
@@ -70,7 +63,7 @@ __global__ __launch_bounds__(MB_THREADS) void mbkm_assign_kernel(const double* _
         db = fma(x[c], cb[c], db);
       }
       const double dista = csq[j0 + jj] - 2.0 * da;
-      if (lab == 0x7fffffff || dista < best) {  // strict <: the first minimum wins, as in sklearn
+      if (lab == KM_NO_LABEL || dista < best) {  // strict <: the first minimum wins, as in sklearn
         best = dista;
         lab = j0 + jj;
       }
@@ -85,7 +78,7 @@ __global__ __launch_bounds__(MB_THREADS) void mbkm_assign_kernel(const double* _
       double da = 0.0;
       for (int c = 0; c < d; ++c) da = fma(x[c], ca[c], da);
       const double dista = csq[j0 + jj] - 2.0 * da;
-      if (lab == 0x7fffffff || dista < best) {
+      if (lab == KM_NO_LABEL || dista < best) {
         best = dista;
         lab = j0 + jj;
       }
@@ -94,7 +87,7 @@ __global__ __launch_bounds__(MB_THREADS) void mbkm_assign_kernel(const double* _
   for (int o = 1; o < PT; o <<= 1) {  // the PT threads of a row are adjacent lanes of one wave (PT <= 16)
     const double ob = __shfl_xor(best, o);
     const int ol = __shfl_xor(lab, o);
-    if (ol != 0x7fffffff && (lab == 0x7fffffff || ob < best || (ob == best && ol < lab))) {
+    if (ol != KM_NO_LABEL && (lab == KM_NO_LABEL || ob < best || (ob == best && ol < lab))) {
       best = ob;
       lab = ol;
     }
@@ -179,36 +172,18 @@ __global__ __launch_bounds__(MB_THREADS) void mbkm_reassign_kernel(const double*
   }
 }
 
-// Tile sizes of the assign kernel: TR rows (32, else 16) and KT centres (a multiple of PT, or all k) within the budget.
-static bool assign_tiles(int d, int k, int* TR, int* KT) {
-  const int cap = MB_ASSIGN_LDS_DOUBLES / (d + 1);
-  for (int tr : {32, 16}) {
-    const int pt = MB_THREADS / tr;
-    int kt = cap - tr;
-    if (kt >= k) kt = k;
-    else kt = (kt / pt) * pt;
-    if (kt >= 1 && (kt >= pt || kt == k)) {
-      *TR = tr;
-      *KT = kt;
-      return true;
-    }
-  }
-  return false;
-}
-
+// centre norms into csq, then the E step
 static int assign_launch(const double* X, long ld, int n, int d, int k, const double* C, double* csq, int* labels,
                          hipStream_t st) {
   int TR = 0, KT = 0;
-  MUSED_REQUIRE(assign_tiles(d, k, &TR, &KT), "minibatch assign: no tile fits d = %d", d);
+  MUSED_REQUIRE(km_stream_tiles(MB_ASSIGN_LDS_DOUBLES, d, k, &TR, &KT), "minibatch assign: no tile fits d = %d", d);
   static std::once_flag once;
   static hipError_t aerr = hipSuccess;
   std::call_once(once, [] {
-    CaptureLock lk(capture_mutex());
-    aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(mbkm_assign_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               8 * MB_ASSIGN_LDS_DOUBLES);
+    aerr = km_allow_lds(reinterpret_cast<const void*>(mbkm_assign_kernel), 8 * MB_ASSIGN_LDS_DOUBLES);
   });
   MUSED_CHECK_HIP(aerr);
-  hipLaunchKernelGGL(mbkm_csq_kernel, dim3(cdiv(k, 64)), dim3(64), 0, st, C, k, d, csq);
+  hipLaunchKernelGGL(km_csq_kernel, dim3(cdiv(k, 64)), dim3(64), 0, st, C, k, d, csq);
   const size_t lds = 8 * (size_t)(TR + KT) * (d + 1);
   hipLaunchKernelGGL(mbkm_assign_kernel, dim3(cdiv(n, TR)), dim3(MB_THREADS), lds, st, X, ld, n, d, k, C, csq, labels, TR, KT);
   MUSED_LAUNCH_CHECK();

@@ -1,7 +1,7 @@
 """On the GPU: mused_kmeans_lloyd_wide (csrc/kmeans.hip), the Lloyd iterations for any k <= 1024, d <= 512 -- against the
 high-precision reference on the cases of tests/lloyd_wide_cases.py (k * d > 8192), bit for bit against mused_kmeans_lloyd
 on every case both accept, run to run, the empty-cluster flag, the wrapper with and without MUSED_KMEANS_WIDE=host, a
-two-window pipeline run, and the argument checks."""
+two-window pipeline run, the argument checks, and the E step it shares with mused_kmeans_lloyd and mused_kmeans_assign."""
 import ctypes as C
 import functools
 
@@ -15,8 +15,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-from test_gpu_lloyd import (INFO_SENT, LAB_SENT, MUSED_ERR_ARG, Buffers, assert_matches_reference,  # noqa: E402
-                            bits)
+from test_gpu_lloyd import (INFO_SENT, LAB_SENT, MUSED_ERR_ARG, Buffers, P, S, assert_matches_reference,  # noqa: E402
+                            bits, dev)
 from test_gpu_lloyd import first_run as narrow_first_run  # noqa: E402
 
 WIDE = "mused_kmeans_lloyd_wide"
@@ -260,3 +260,35 @@ def test_bad_arguments_rejected_without_launch():
         lab, cen, info = b.read()
         assert (lab == LAB_SENT).all() and info == [INFO_SENT] * 4
         assert np.array_equal(bits(cen), bits(C0))
+
+
+# ---- 8. one E step behind the three entries -----------------------------------------------------------------------
+SHARED_E_STEP = [(WIDE, 300, 482, 17),                   # k d = 8194, the last chunk holds 44 rows
+                 (WIDE, 1100, 16, 1024),                 # mused_kmeans_assign walks two centre tiles (1016 + 8), Lloyd one
+                 ("mused_kmeans_lloyd", 300, 16, 40)]    # the staged kernel, 64 rows per sub-tile
+
+
+@pytest.mark.parametrize("entry,n,d,k", SHARED_E_STEP, ids=[f"{e}-{n}x{d}x{k}" for e, n, d, k in SHARED_E_STEP])
+def test_assign_gives_the_lloyd_entrys_final_labels(entry, n, d, k):
+    """The three entries promise one E step (first-minimum rule, centre norms and tiles: csrc/kmeans_common.h; the streamed
+    kernels of csrc/kmeans.hip and csrc/minibatch.hip are copies of each other).  With mean = 0 the centring is exact
+    (Xc == X) and with max_iter = 1 a Lloyd entry ends with an E step on the centres it returns, so mused_kmeans_assign on
+    those centres gives its labels element for element.  Gaussian rows of tests/lloyd_cases.py (continuous: no two
+    distances tie), seeded with their first k rows (each seed keeps at least itself: no empty cluster)."""
+    from mused_amd import _lib
+
+    lib = _lib.lib()
+    if entry != WIDE:
+        assert lib.mused_kmeans_assign_rows(d, k) == 64
+    X = lc.inputs(lc.Case("shared_e_step", n, d, k, 0, 0))[0]
+    b = (WideBuffers if entry == WIDE else Buffers)(X, np.zeros(d), X[:k])
+    _lib.call(entry, *b.args(lc.sklearn_tolerance(X), 1))
+    lab, cen, info = b.read()
+    assert info[1] != 1, "max_iter = 1 converged strictly on this case, so no final E step ran: pick another seed"
+    assert info[0] == 1 and info[2] == 0, info
+    Xd, Cd = dev(X), dev(cen)
+    got = torch.full((n,), LAB_SENT, dtype=torch.int32, device="cuda")
+    ws = torch.empty(int(lib.mused_mbkm_ws_bytes(n, d, k)), dtype=torch.uint8, device="cuda")
+    _lib.call("mused_kmeans_assign", P(Xd), d, n, d, k, P(Cd), P(got), P(ws), ws.numel(), S())
+    torch.cuda.synchronize()
+    assert np.array_equal(got.cpu().numpy(), lab), f"{np.count_nonzero(got.cpu().numpy() != lab)} labels differ"

@@ -67,7 +67,8 @@ def assign(L, Xd, ld, n, d, k, Cd):
 
 
 def assign_tiles(d, k):
-    """Python copy of assign_tiles (csrc/minibatch.hip): (TR rows, PT = 256 / TR lanes per row, KT centres per tile)."""
+    """Python copy of km_stream_tiles (csrc/kmeans_common.h) with the budget of csrc/minibatch.hip: (TR rows,
+    PT = 256 / TR lanes per row, KT centres per tile)."""
     cap = 17920 // (d + 1)
     for tr in (32, 16):
         pt = 256 // tr
