@@ -37,12 +37,9 @@
 // of one another.  tau(i, j) = 2 (d + 8) 2^-52 (|x_i|^2 + |x_j|^2) + 4 ulp(eps^2): where no pair is within tau of eps^2
 // every comparison, and with it every label, equals scikit-learn's.  Otherwise flag 1 is raised and the caller runs
 // scikit-learn itself: exact labels or a flag, never labels that hang on the last bits.
-#include "gemm_f64.h"
-#include "internal.h"
+#include "pair_tile.h"
 #include "dbscan_common.h"
 #include "union_find.h"
-
-extern "C" int mused_row_sq_norms(const void* X, int dtype, long n, int d, long ld, double* out, void* stream);
 
 namespace mused {
 
@@ -59,21 +56,13 @@ struct DbArgs {
   int min_samples;
 };
 
-// tile (I, (I + delta) mod tiles), delta in [0, tiles / 2]: every unordered pair of row tiles once; 64 consecutive workgroups
-// (one XCD's share) touch 8 A row-panels and 15 B row-panels.  Grid: ceil(tiles / 8) * 8 * (tiles / 2 + 1).
+// tile (I, (I + delta) mod tiles), delta in [0, tiles / 2]: every unordered pair of row tiles once (pair_tile.h)
 template <int PASS, bool VEC>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_tile_kernel(GemmArgs g, DbArgs a, int tiles) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int n_delta = tiles / 2 + 1;
-  const int e = xcd_remap(blockIdx.x, gridDim.x);
-  const int per_group = 8 * n_delta;
-  const int ig = e / per_group, rem = e - ig * per_group;
-  const int delta = rem >> 3;
-  const int I = ig * 8 + (rem & 7);
-  if (I >= tiles) return;
-  if (2 * delta == tiles && I >= tiles / 2) return;  // even tile count: the antipodal pairs once
-  int J = I + delta;
-  if (J >= tiles) J -= tiles;
+  int I, delta, J;
+  pair_slot(tiles / 2 + 1, I, delta);
+  if (!pair_tile(I, delta, tiles, J)) return;
   const bool both = (delta != 0);  // a diagonal tile holds both orientations of its pairs itself
   if (PASS == DB_UNION) {
     if (!(a.tflag[I] & DB_HAS_CORE) || !(a.tflag[J] & DB_HAS_CORE)) return;
@@ -87,8 +76,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_tile_kernel(GemmArgs g
   v4f64 acc[4][4];
   gemm_tile_mainloop<double, double, true, true, VEC>(g, X, X, m0, n0, 0, g.K, smem, acc);
 
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wr = wave >> 1, wc = wave & 1, kq = lane >> 4, li = lane & 15;
+  int lane, wr, wc, kq, li;
+  patch_lanes(lane, wr, wc, kq, li);
   const int n = g.M;
 
   // Rows and columns beyond n read entry n - 1 (no branch around a load: with branches inside the row loop the compiler sinks
@@ -98,7 +87,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_tile_kernel(GemmArgs g
   bool cok[4], corec[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int col = n0 + wc * 64 + j * 16 + li;
+    const int col = patch_col(n0, wc, li) + j * 16;
     const int cc = min(col, n - 1);
     cok[j] = col < n;
     ncol[j] = a.nrm[cc];
@@ -114,7 +103,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_tile_kernel(GemmArgs g
   for (int i = 0; i < 4; ++i) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int row = m0 + wr * 64 + i * 16 + kq + 4 * r;
+      const int row = patch_row(m0, wr, kq) + i * 16 + 4 * r;
       const int rc = min(row, n - 1);
       const bool rok = row < n;
       const double nrow = a.nrm[rc];
@@ -123,7 +112,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_tile_kernel(GemmArgs g
       const int rroot = (PASS == DB_BORDER && corer) ? a.root[rc] : DB_NONE;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int col = n0 + wc * 64 + j * 16 + li;
+        const int col = patch_col(n0, wc, li) + j * 16;
         const bool ok = rok && cok[j];
         const double s = nrow + ncol[j];
         const double dd = s - 2.0 * acc[i][j][r];
@@ -163,7 +152,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_tile_kernel(GemmArgs g
   if (PASS == DB_COUNT || PASS == DB_BORDER) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int row = m0 + wr * 64 + (q >> 2) * 16 + kq + 4 * (q & 3);
+      const int row = patch_row(m0, wr, kq) + (q >> 2) * 16 + 4 * (q & 3);
       if (li == 0 && row < n) {
         if (PASS == DB_COUNT && rsum[q]) atomicAdd(a.count + row, rsum[q]);
         if (PASS == DB_BORDER && rsum[q] != DB_NONE) atomicMin(a.root + row, rsum[q]);
@@ -180,7 +169,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_tile_kernel(GemmArgs g
         const int x = __shfl_xor(v, o);
         v = (PASS == DB_COUNT) ? v + x : min(v, x);
       }
-      const int col = n0 + wc * 64 + j * 16 + li;
+      const int col = patch_col(n0, wc, li) + j * 16;
       if (both && kq == 0 && col < n) {
         if (PASS == DB_COUNT && v) atomicAdd(a.count + col, v);
         if (PASS == DB_BORDER && v != DB_NONE) atomicMin(a.root + col, v);
@@ -199,14 +188,6 @@ __global__ void dbscan_init_kernel(DbArgs a, int n) {
   a.parent[i] = i;
   a.count[i] = 0;
   a.root[i] = DB_NONE;
-}
-
-// (after init: a separate launch, so that the flag is not cleared behind it)
-__global__ void dbscan_finite_kernel(DbArgs a, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const double v = i < n ? a.nrm[i] : 0.0;
-  const bool bad = !(fabs(v) <= 1.7976931348623157e308);  // NaN or inf (an overflowing norm of finite values included)
-  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(a.info, 2);
 }
 
 __global__ void dbscan_core_kernel(DbArgs a, int n, int tiles) {
@@ -260,20 +241,9 @@ static size_t db_layout(long n, char* base, DbWs* ws) {
 }
 
 template <int PASS>
-static int db_tile_launch(const GemmArgs& g, const DbArgs& a, bool vec, int tiles, hipStream_t st) {
-  static std::once_flag once[2];
-  static hipError_t err[2];
-  const int v = vec ? 1 : 0;
-  std::call_once(once[v], [&] {
-    const void* fn = vec ? (const void*)dbscan_tile_kernel<PASS, true> : (const void*)dbscan_tile_kernel<PASS, false>;
-    err[v] = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
-  });
-  MUSED_CHECK_HIP(err[v]);
-  const dim3 grid(cdiv(tiles, 8) * 8 * (tiles / 2 + 1)), blk(GEMM_THREADS);
-  if (vec) hipLaunchKernelGGL((dbscan_tile_kernel<PASS, true>), grid, blk, GEMM_LDS_BYTES, st, g, a, tiles);
-  else hipLaunchKernelGGL((dbscan_tile_kernel<PASS, false>), grid, blk, GEMM_LDS_BYTES, st, g, a, tiles);
-  MUSED_LAUNCH_CHECK();
-  return MUSED_OK;
+static int db_pass(const GemmArgs& g, const DbArgs& a, bool vec, int tiles, hipStream_t st) {
+  return pair_launch<dbscan_tile_kernel<PASS, true>, dbscan_tile_kernel<PASS, false>>(vec, pair_grid(tiles), GEMM_LDS_BYTES, st, g,
+                                                                                          a, tiles);
 }
 
 }  // namespace mused
@@ -303,24 +273,20 @@ int mused_dbscan(const double* X, long n, int d, long ld, double eps, int min_sa
   db_layout(n, (char*)ws, &w);
   const int tiles = cdiv(n, GEMM_BM);
   const double eps2 = eps * eps;
-  // 4 ulp of eps^2 (an ulp is at most eps2 * 2^-52; subnormal squares: the smallest subnormal)
-  const double ulp = eps2 * 2.220446049250313e-16 > 4.9406564584124654e-324 ? eps2 * 2.220446049250313e-16 : 4.9406564584124654e-324;
-  DbArgs a{w.nrm, w.count, w.parent, w.root, w.tflag, w.info, eps2, 2.0 * (d + 8) * 2.220446049250313e-16, 4.0 * ulp, min_samples};
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A = X; g.B = X; g.lda = ld; g.ldb = ld; g.M = (int)n; g.N = (int)n; g.K = d;
+  DbArgs a{w.nrm, w.count, w.parent, w.root, w.tflag, w.info, eps2, pair_tau_coeff(d), ulp4(eps2), min_samples};
+  const GemmArgs g = self_product_args(X, ld, n, d);
   const bool vec = vec_ok<double>(X, ld, 0);
   const dim3 rows(cdiv(n, 256)), blk(256);
   int rc;
   if ((rc = mused_row_sq_norms(X, MUSED_F64, n, d, ld, w.nrm, stream))) return rc;
   hipLaunchKernelGGL(dbscan_init_kernel, rows, blk, 0, st, a, (int)n);
-  hipLaunchKernelGGL(dbscan_finite_kernel, rows, blk, 0, st, a, (int)n);
-  if ((rc = db_tile_launch<DB_COUNT>(g, a, vec, tiles, st))) return rc;
+  hipLaunchKernelGGL(norms_finite_kernel, rows, blk, 0, st, w.nrm, (int)n, w.info, 2);  // (behind init, which clears the flag)
+  if ((rc = db_pass<DB_COUNT>(g, a, vec, tiles, st))) return rc;
   hipLaunchKernelGGL(dbscan_core_kernel, rows, blk, 0, st, a, (int)n, tiles);
-  if ((rc = db_tile_launch<DB_UNION>(g, a, vec, tiles, st))) return rc;
+  if ((rc = db_pass<DB_UNION>(g, a, vec, tiles, st))) return rc;
   hipLaunchKernelGGL(dbscan_flatten_kernel, rows, blk, 0, st, a, (int)n);
   hipLaunchKernelGGL(dbscan_rank_kernel, dim3(1), dim3(DB_RANK_THREADS), 0, st, w.root, w.rank, w.info, (int)n);
-  if ((rc = db_tile_launch<DB_BORDER>(g, a, vec, tiles, st))) return rc;
+  if ((rc = db_pass<DB_BORDER>(g, a, vec, tiles, st))) return rc;
   hipLaunchKernelGGL(dbscan_labels_kernel, rows, blk, 0, st, a, w.rank, labels_out, (int)n);
   MUSED_LAUNCH_CHECK();
   MUSED_CHECK_HIP(hipMemcpyAsync(info_out, w.info, 16, hipMemcpyDeviceToDevice, st));

@@ -68,13 +68,10 @@
 //                     surv[pos[i]] = i
 //   dbi_gather        (mask) the surviving rows, packed, into X_out (the rows do have to move here; the prefix leaves them)
 //   dbscan_rank, dbi_labels   over the n - m survivors
-#include "gemm_f64.h"
-#include "internal.h"
+#include "pair_tile.h"
 #include "dbscan_common.h"
 #include "union_find.h"
 #include "block_scan.h"
-
-extern "C" int mused_row_sq_norms(const void* X, int dtype, long n, int d, long ld, double* out, void* stream);
 
 namespace mused {
 
@@ -118,8 +115,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_incr_tile_kernel(GemmA
   gemm_tile_mainloop<double, double, true, true, VEC>(g, reinterpret_cast<const double*>(g.A), reinterpret_cast<const double*>(g.B),
                                                       m0, n0, 0, g.K, smem, acc);
 
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wr = wave >> 1, wc = wave & 1, kq = lane >> 4, li = lane & 15;
+  int lane, wr, wc, kq, li;
+  patch_lanes(lane, wr, wc, kq, li);
   const int ma = g.M, n = g.N;
 
   // Rows and columns beyond the end read the last entry and are masked (no branch around a load: csrc/dbscan.hip)
@@ -128,7 +125,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_incr_tile_kernel(GemmA
   bool cok[4], corec[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int col = n0 + wc * 64 + j * 16 + li;
+    const int col = patch_col(n0, wc, li) + j * 16;
     const int cc = min(col, n - 1);
     cok[j] = col < n && (!DEL || col >= a.n0);
     ncol[j] = a.nrm[cc];
@@ -145,7 +142,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_incr_tile_kernel(GemmA
   for (int i = 0; i < 4; ++i) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int lrow = m0 + wr * 64 + i * 16 + kq + 4 * r;
+      const int lrow = patch_row(m0, wr, kq) + i * 16 + 4 * r;
       const bool rok = lrow < ma;
       const int lr = min(lrow, ma - 1);
       const int rid = a.ids ? a.ids[lr] : a.a_base + lr;  // (a valid row also where rok is false)
@@ -157,7 +154,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_incr_tile_kernel(GemmA
       int racc = CNT ? 0 : (UNI ? -1 : DB_NONE);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int col = n0 + wc * 64 + j * 16 + li;
+        const int col = patch_col(n0, wc, li) + j * 16;
         const bool ok = rtake && cok[j];
         const double s = nrow + ncol[j];
         const double dd = s - 2.0 * acc[i][j][r];
@@ -196,7 +193,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_incr_tile_kernel(GemmA
   if (PASS == DBI_COUNT || BRW) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int lrow = m0 + wr * 64 + (q >> 2) * 16 + kq + 4 * (q & 3);
+      const int lrow = patch_row(m0, wr, kq) + (q >> 2) * 16 + 4 * (q & 3);
       if (li == 0 && lrow < ma) {
         if (PASS == DBI_COUNT && rsum[q]) atomicAdd(a.count + rids[q], rsum[q]);
         if (BRW && rsum[q] != DB_NONE) atomicMin(a.best + rids[q], rsum[q]);
@@ -213,7 +210,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dbscan_incr_tile_kernel(GemmA
         const int x = __shfl_xor(v, o);
         v = CNT ? v + x : min(v, x);
       }
-      const int col = n0 + wc * 64 + j * 16 + li;
+      const int col = patch_col(n0, wc, li) + j * 16;
       if (kq == 0 && col < n) {
         if (PASS == DBI_COUNT && v && col < a.n0) atomicAdd(a.count + col, v);  // (new columns: counted from their row side)
         if (PASS == DBI_UNCOUNT && v) atomicSub(a.count + col, v);  // (v counts columns of S only)
@@ -237,7 +234,7 @@ __global__ void dbi_begin_kernel(DbiArgs a, int* __restrict__ rootb, int n0, int
     a.count[i] = 0;
     a.best[i] = DB_NONE;
     rootb[i] = -1;
-    bad = !(fabs(a.nrm[i]) <= 1.7976931348623157e308);  // NaN or inf (an overflowing norm of finite values included)
+    bad = norm_not_finite(a.nrm[i]);
   }
   if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(a.info, 2);
 }
@@ -522,23 +519,6 @@ static bool dbi_shape_ok(long n, int d, long chunk) {
   return n >= 1 && n <= DB_MAX_ROWS && d >= 1 && d < (1 << 20) && chunk >= GEMM_BM && chunk <= DBI_MAX_CHUNK && chunk % GEMM_BM == 0;
 }
 
-template <int PASS>
-static int dbi_tile_launch(const GemmArgs& g, const DbiArgs& a, bool vec, hipStream_t st) {
-  static std::once_flag once[2];
-  static hipError_t err[2];
-  const int v = vec ? 1 : 0;
-  std::call_once(once[v], [&] {
-    const void* fn = vec ? (const void*)dbscan_incr_tile_kernel<PASS, true> : (const void*)dbscan_incr_tile_kernel<PASS, false>;
-    err[v] = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
-  });
-  MUSED_CHECK_HIP(err[v]);
-  const dim3 grid(cdiv(g.M, GEMM_BM) * cdiv(g.N, GEMM_BN)), blk(GEMM_THREADS);
-  if (vec) hipLaunchKernelGGL((dbscan_incr_tile_kernel<PASS, true>), grid, blk, GEMM_LDS_BYTES, st, g, a);
-  else hipLaunchKernelGGL((dbscan_incr_tile_kernel<PASS, false>), grid, blk, GEMM_LDS_BYTES, st, g, a);
-  MUSED_LAUNCH_CHECK();
-  return MUSED_OK;
-}
-
 // one pass over the new slice (list == nullptr) or over list[0 .. count) through the staging panel, in chunks
 template <int PASS>
 static int dbi_pass(const double* X, long ld, int d, long n, long n0, long count, const int* list, long chunk, const DbiWs& w,
@@ -560,8 +540,9 @@ static int dbi_pass(const double* X, long ld, int d, long n, long n0, long count
       a.a_base = (int)(n0 + c0);
       a.aflag = w.aflag + c0 / GEMM_BM;
     }
-    int rc;
-    if ((rc = dbi_tile_launch<PASS>(g, a, vec, st))) return rc;
+    const int rc = pair_launch<dbscan_incr_tile_kernel<PASS, true>, dbscan_incr_tile_kernel<PASS, false>>(
+        vec, cdiv(g.M, GEMM_BM) * cdiv(g.N, GEMM_BN), GEMM_LDS_BYTES, st, g, a);
+    if (rc) return rc;
   }
   return MUSED_OK;
 }
@@ -639,9 +620,8 @@ int mused_dbscan_incr_insert(const double* X, long ld, int d, double* nrm, int* 
   DbiWs k;
   dbi_layout(n, d, chunk, (char*)ws, &k);
   const double eps2 = eps * eps;
-  const double ulp = eps2 * 2.220446049250313e-16 > 4.9406564584124654e-324 ? eps2 * 2.220446049250313e-16 : 4.9406564584124654e-324;
-  DbiArgs a{nrm, count, parent, best, k.root, nullptr, k.tflag, k.aflag, k.info, eps2, 2.0 * (d + 8) * 2.220446049250313e-16,
-            4.0 * ulp, min_samples, (int)n0, (int)n0};
+  DbiArgs a{nrm, count, parent, best, k.root, nullptr, k.tflag, k.aflag, k.info, eps2, pair_tau_coeff(d), ulp4(eps2),
+            min_samples, (int)n0, (int)n0};
   const bool vec = vec_ok<double>(X, ld, 0);
   const dim3 rows(cdiv(n, 256)), blk(256);
   int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};

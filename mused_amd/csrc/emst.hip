@@ -47,11 +47,8 @@
 // raised when some row's candidate does not.  Without it in any round every pick is the strict minimum of its component's
 // cut under scikit-learn's evaluation too, hence an MST edge there (cut property), and the components of every round and the
 // final edge set coincide.  Exact or a flag; never a tree that hangs on the last bits.
-#include "gemm_f64.h"
-#include "internal.h"
+#include "pair_tile.h"
 #include "union_find.h"
-
-extern "C" int mused_row_sq_norms(const void* X, int dtype, long n, int d, long ld, double* out, void* stream);
 
 namespace mused {
 
@@ -88,23 +85,15 @@ __device__ __forceinline__ void em_min64(em_u64* p, em_u64 v) {
 }
 __device__ __forceinline__ double em_dmin(double a, double b) { return b < a ? b : a; }  // keeps a when b is NaN
 __device__ __forceinline__ em_u64 em_key(int i, int j) { return ((em_u64)(unsigned)min(i, j) << 32) | (em_u64)(unsigned)max(i, j); }
-__device__ __forceinline__ double em_ulp4(double v) { return 4.0 * fmax(v * 2.220446049250313e-16, 4.9406564584124654e-324); }
 
 // tile (I, (I + delta) mod tiles), delta in [0, tiles / 2]: the grid of dbscan_tile_kernel
 template <int PASS, bool VEC>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void emst_tile_kernel(GemmArgs g, EmArgs a, int tiles) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   if (db_load(a.ctl)) return;  // done
-  const int n_delta = tiles / 2 + 1;
-  const int e = xcd_remap(blockIdx.x, gridDim.x);
-  const int per_group = 8 * n_delta;
-  const int ig = e / per_group, rem = e - ig * per_group;
-  const int delta = rem >> 3;
-  const int I = ig * 8 + (rem & 7);
-  if (I >= tiles) return;
-  if (2 * delta == tiles && I >= tiles / 2) return;  // even tile count: the antipodal pairs once
-  int J = I + delta;
-  if (J >= tiles) J -= tiles;
+  int I, delta, J;
+  pair_slot(tiles / 2 + 1, I, delta);
+  if (!pair_tile(I, delta, tiles, J)) return;
   const bool both = (delta != 0);  // a diagonal tile: the entries with row < col, for both sides
   {
     const int ti = a.tcomp[I], tj = a.tcomp[J];
@@ -115,8 +104,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void emst_tile_kernel(GemmArgs g, 
   v4f64 acc[4][4];
   gemm_tile_mainloop<double, double, true, true, VEC>(g, X, X, m0, n0, 0, g.K, smem, acc);
 
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wr = wave >> 1, wc = wave & 1, kq = lane >> 4, li = lane & 15;
+  int lane, wr, wc, kq, li;
+  patch_lanes(lane, wr, wc, kq, li);
   const int n = g.M;
   const double inf = __longlong_as_double((long long)EM_INF);
 
@@ -127,7 +116,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void emst_tile_kernel(GemmArgs g, 
   bool cok[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int col = n0 + wc * 64 + j * 16 + li;
+    const int col = patch_col(n0, wc, li) + j * 16;
     const int cc = min(col, n - 1);
     cok[j] = col < n;
     ncol[j] = a.nrm[cc];
@@ -141,7 +130,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void emst_tile_kernel(GemmArgs g, 
   for (int i = 0; i < 4; ++i) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int row = m0 + wr * 64 + i * 16 + kq + 4 * r;
+      const int row = patch_row(m0, wr, kq) + i * 16 + 4 * r;
       const int rc = min(row, n - 1);
       const bool rok = row < n;
       const double nrow = a.nrm[rc];
@@ -151,7 +140,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void emst_tile_kernel(GemmArgs g, 
       int rmin = EM_NOCOL, rmax = -1;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int col = n0 + wc * 64 + j * 16 + li;
+        const int col = patch_col(n0, wc, li) + j * 16;
         const double s = nrow + ncol[j];
         double dd = s - 2.0 * acc[i][j][r];
         dd = dd < 0.0 ? 0.0 : dd;  // (NaN stays NaN and passes no comparison below)
@@ -211,7 +200,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void emst_tile_kernel(GemmArgs g, 
         hi = max(hi, __shfl_xor(hi, o));
       }
     }
-    const int col = n0 + wc * 64 + j * 16 + li;
+    const int col = patch_col(n0, wc, li) + j * 16;
     if (kq == 0 && col < n) {
       em_min64((PASS == EM_BEST ? a.best : a.second) + col, (em_u64)__double_as_longlong(v));
       if (PASS == EM_SECOND && lo != EM_NOCOL) {
@@ -228,14 +217,6 @@ __global__ void emst_init_kernel(EmArgs a, int n, int tiles) {
   if (i < 2) a.ctl[i] = 0;
   if (i < tiles) a.tcomp[i] = -1;
   if (i < n) a.parent[i] = i;
-}
-
-// (after init: a separate launch, so that the flag is not cleared behind it)
-__global__ void emst_finite_kernel(EmArgs a, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const double v = i < n ? a.nrm[i] : 0.0;
-  const bool bad = !(fabs(v) <= 1.7976931348623157e308);  // NaN or inf (an overflowing norm of finite values included)
-  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(a.info, 2);
 }
 
 // one thread, alone on the stream: the only writer of `done`.  first: before round 0 (nothing to do for one row or rows
@@ -328,8 +309,8 @@ __global__ void emst_pick_kernel(EmArgs a, int n) {
   if (v != EM_INF) {
     const double vd = __longlong_as_double((long long)v);
     const int pa = (int)(k >> 32), pb = (int)(k & 0xffffffffull);
-    const double tau_pick = a.ctau * (a.nrm[pa] + a.nrm[pb]) + em_ulp4(pd);
-    const double tau_cand = a.ctau * (3.0 * a.nrm[i] + 2.0 * vd) + em_ulp4(vd);  // bound of tau(i, its column): head of this file
+    const double tau_pick = a.ctau * (a.nrm[pa] + a.nrm[pb]) + ulp4(pd);
+    const double tau_cand = a.ctau * (3.0 * a.nrm[i] + 2.0 * vd) + ulp4(vd);  // bound of tau(i, its column): head of this file
     if (!(vd - pd > tau_pick + tau_cand)) atomicOr(a.info, 1);
   }
   if (mine) {
@@ -372,20 +353,9 @@ static size_t em_layout(long n, char* base, EmWs* ws) {
 }
 
 template <int PASS>
-static int em_tile_launch(const GemmArgs& g, const EmArgs& a, bool vec, int tiles, hipStream_t st) {
-  static std::once_flag once[2];
-  static hipError_t err[2];
-  const int v = vec ? 1 : 0;
-  std::call_once(once[v], [&] {
-    const void* fn = vec ? (const void*)emst_tile_kernel<PASS, true> : (const void*)emst_tile_kernel<PASS, false>;
-    err[v] = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
-  });
-  MUSED_CHECK_HIP(err[v]);
-  const dim3 grid(cdiv(tiles, 8) * 8 * (tiles / 2 + 1)), blk(GEMM_THREADS);
-  if (vec) hipLaunchKernelGGL((emst_tile_kernel<PASS, true>), grid, blk, GEMM_LDS_BYTES, st, g, a, tiles);
-  else hipLaunchKernelGGL((emst_tile_kernel<PASS, false>), grid, blk, GEMM_LDS_BYTES, st, g, a, tiles);
-  MUSED_LAUNCH_CHECK();
-  return MUSED_OK;
+static int em_pass(const GemmArgs& g, const EmArgs& a, bool vec, int tiles, hipStream_t st) {
+  return pair_launch<emst_tile_kernel<PASS, true>, emst_tile_kernel<PASS, false>>(vec, pair_grid(tiles), GEMM_LDS_BYTES, st, g, a,
+                                                                                      tiles);
 }
 
 }  // namespace mused
@@ -416,10 +386,8 @@ int mused_emst(const double* X, long n, int d, long ld, int* edge_a, int* edge_b
   em_layout(n, (char*)ws, &w);
   const int tiles = cdiv(n, GEMM_BM);
   EmArgs a{w.nrm, w.best, w.second, w.bcol, w.bcol2, w.comp, w.parent, w.cbest, w.ckey, w.tcomp, w.info, w.ctl,
-           edge_a, edge_b, edge_d2, 2.0 * (d + 8) * 2.220446049250313e-16};
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A = X; g.B = X; g.lda = ld; g.ldb = ld; g.M = (int)n; g.N = (int)n; g.K = d;
+           edge_a, edge_b, edge_d2, pair_tau_coeff(d)};
+  const GemmArgs g = self_product_args(X, ld, n, d);
   const bool vec = vec_ok<double>(X, ld, 0);
   const dim3 rows(cdiv(n, 256)), blk(256), one(1);
   int rounds = 0;  // ceil(log2 n): every round at least halves the number of components
@@ -427,12 +395,12 @@ int mused_emst(const double* X, long n, int d, long ld, int* edge_a, int* edge_b
   int rc;
   if ((rc = mused_row_sq_norms(X, MUSED_F64, n, d, ld, w.nrm, stream))) return rc;
   hipLaunchKernelGGL(emst_init_kernel, rows, blk, 0, st, a, (int)n, tiles);
-  hipLaunchKernelGGL(emst_finite_kernel, rows, blk, 0, st, a, (int)n);
+  hipLaunchKernelGGL(norms_finite_kernel, rows, blk, 0, st, w.nrm, (int)n, w.info, 2);  // (behind init, which clears the flag)
   hipLaunchKernelGGL(emst_round_end_kernel, one, dim3(64), 0, st, a, (int)n, 1);
   hipLaunchKernelGGL(emst_flatten_kernel, dim3(tiles), dim3(EM_FLAT_THREADS), 0, st, a, (int)n);
   for (int r = 0; r < rounds; ++r) {
-    if ((rc = em_tile_launch<EM_BEST>(g, a, vec, tiles, st))) return rc;
-    if ((rc = em_tile_launch<EM_SECOND>(g, a, vec, tiles, st))) return rc;
+    if ((rc = em_pass<EM_BEST>(g, a, vec, tiles, st))) return rc;
+    if ((rc = em_pass<EM_SECOND>(g, a, vec, tiles, st))) return rc;
     hipLaunchKernelGGL(emst_comp_best_kernel, rows, blk, 0, st, a, (int)n);
     hipLaunchKernelGGL(emst_comp_key_kernel, rows, blk, 0, st, a, (int)n);
     hipLaunchKernelGGL(emst_pick_kernel, rows, blk, 0, st, a, (int)n);

@@ -27,7 +27,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <type_traits>
-#include "common.h"
+#include "internal.h"
 
 namespace mused {
 
@@ -580,13 +580,9 @@ template <typename TA, typename TB, bool A_KC, bool B_KC, bool VEC, typename Epi
 int gemm_f64_prepare_t() {
   // > 64 KiB of dynamic LDS needs the attribute once per kernel; done outside stream capture.  Several host
   // threads drive the library (sketch groups + the main path): one-time, thread-safe.
-  static std::once_flag once;
-  static hipError_t err = hipSuccess;
-  std::call_once(once, [] {
-    auto k = gemm_f64_kernel<TA, TB, A_KC, B_KC, VEC, Epi>;
-    err = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              GEMM_LDS_BYTES);
-  });
+  static LdsOptIn opt;
+  auto k = gemm_f64_kernel<TA, TB, A_KC, B_KC, VEC, Epi>;
+  const hipError_t err = allow_dynamic_lds(opt, reinterpret_cast<const void*>(k), GEMM_LDS_BYTES);
   MUSED_CHECK_HIP(err);
   return MUSED_OK;
 }

@@ -2,7 +2,11 @@
 #pragma once
 #include "common.h"
 
+#include <atomic>
 #include <mutex>
+
+// knn.hip (a C entry, include/mused_hip.h): out[i] = |x_i|^2, for the kernels that turn a tile of dot products into distances
+extern "C" int mused_row_sq_norms(const void* X, int dtype, long n, int d, long ld, double* out, void* stream);
 
 namespace mused {
 
@@ -20,11 +24,37 @@ int select_window_tag_sets(const int* rowptr, const int* tags, const int* postpt
 
 // One process-wide lock around every stream capture of this library AND around the calls that create or release HIP
 // resources next to one (handle / plan creation and destruction: hipMalloc, hipFree, hipGraph(Exec)Destroy,
-// hipStreamCreate / Destroy, hipFuncSetAttribute).  Round 2 locked only Begin..EndCapture; a handle re-created on one host
+// hipStreamCreate / Destroy, allow_dynamic_lds below).  Round 2 locked only Begin..EndCapture; a handle re-created on one host
 // thread then ran those calls beside another thread's capture (gpurun_out/r2_gputest23.log; tools/repro_capture_threads.hip
 // asks the runtime which of them a ThreadLocal capture survives).  Recursive: creation paths nest (rsvd -> eig plan).
 std::recursive_mutex& capture_mutex();
 using CaptureLock = std::lock_guard<std::recursive_mutex>;
+
+// The dynamic-LDS opt-in of one kernel instance (more than 64 KiB needs it once per kernel): the library's only call of
+// hipFuncSetAttribute.  One LdsOptIn, static, per kernel instance.  A launch that finds `done` set takes no lock: it never
+// waits behind another thread's capture.  The first caller takes capture_mutex() -- the ONLY lock involved -- checks again,
+// sets the attribute, keeps the error (sticky) and publishes `done`.  No std::call_once around or inside: the prepare
+// functions are reached both from plan creation, capture_mutex() held, and lazily from a solve, without it; with the mutex
+// taken inside a once, thread B would sit in the once waiting for the mutex while thread A, holding the mutex, waits at the
+// same once.  Here a caller that holds the mutex nests (recursive), one that does not waits for it and nothing else.
+struct LdsOptIn {
+  std::atomic<bool> done{false};
+  hipError_t err = hipSuccess;
+};
+inline hipError_t allow_dynamic_lds(LdsOptIn& s, const void* kernel, size_t bytes) {
+  if (!s.done.load(std::memory_order_acquire)) {
+    CaptureLock lock(capture_mutex());
+    if (!s.done.load(std::memory_order_relaxed)) {
+      s.err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+      s.done.store(true, std::memory_order_release);
+    }
+  }
+  return s.err;
+}
+// several kernels behind one entry: the first failure wins, the kernels behind it are left alone
+inline hipError_t allow_dynamic_lds(hipError_t before, LdsOptIn& s, const void* kernel, size_t bytes) {
+  return before != hipSuccess ? before : allow_dynamic_lds(s, kernel, bytes);
+}
 
 
 // C[z] = alpha * opA(A[z]) * opB(B[z]); fp64 in / fp64 out, MFMA f64 16x16x4.

@@ -472,12 +472,9 @@ int mused_kmeans_lloyd_wide(const double* X, long ld, int n, int d, int k, const
   hipStream_t st = (hipStream_t)stream;
   const int nchunk = cdiv(n, KM_CHUNK);
   const KmWs w = km_carve(ws, n, d, k, true);
-  static std::once_flag once;
-  static hipError_t aerr = hipSuccess;
-  std::call_once(once, [] {
-    aerr = km_allow_lds(reinterpret_cast<const void*>(kmw_assign_kernel), 8 * KMW_ASSIGN_LDS_DOUBLES);
-    if (aerr == hipSuccess) aerr = km_allow_lds(reinterpret_cast<const void*>(kmw_partial_kernel), KM_LDS_MAX);
-  });
+  static LdsOptIn opt[2];
+  hipError_t aerr = allow_dynamic_lds(opt[0], reinterpret_cast<const void*>(kmw_assign_kernel), 8 * KMW_ASSIGN_LDS_DOUBLES);
+  aerr = allow_dynamic_lds(aerr, opt[1], reinterpret_cast<const void*>(kmw_partial_kernel), KM_LDS_MAX);
   MUSED_CHECK_HIP(aerr);
   const size_t lds_e = 8 * (size_t)(TR + KT) * (d + 1), lds_m = kmw_partial_lds(DT, k);
   return km_lloyd_run(
@@ -522,15 +519,11 @@ int mused_kmeans_lloyd(const double* X, long ld, int n, int d, int k, const doub
   const KmWs w = km_carve(ws, n, d, k, false);
   const int tr = km_assign_rows(d, k);
   const size_t lds = tr ? km_tiled_lds(tr, d, k) : 8 * 2 * (size_t)k * d + 4 * (KM_CHUNK + (size_t)k) + 16;
-  static std::once_flag once;
-  static hipError_t aerr = hipSuccess;
-  std::call_once(once, [] {
-    aerr = km_allow_lds(reinterpret_cast<const void*>(km_assign_kernel), 8 * 2 * 8192 + 4 * (KM_CHUNK + 1024) + 16);
-    for (const void* tiled : {reinterpret_cast<const void*>(km_assign_tiled_kernel<64>),
-                              reinterpret_cast<const void*>(km_assign_tiled_kernel<32>),
-                              reinterpret_cast<const void*>(km_assign_tiled_kernel<16>)})
-      if (aerr == hipSuccess) aerr = km_allow_lds(tiled, KM_LDS_MAX);
-  });
+  static LdsOptIn opt[4];
+  hipError_t aerr = allow_dynamic_lds(opt[0], reinterpret_cast<const void*>(km_assign_kernel), 8 * 2 * 8192 + 4 * (KM_CHUNK + 1024) + 16);
+  aerr = allow_dynamic_lds(aerr, opt[1], reinterpret_cast<const void*>(km_assign_tiled_kernel<64>), KM_LDS_MAX);
+  aerr = allow_dynamic_lds(aerr, opt[2], reinterpret_cast<const void*>(km_assign_tiled_kernel<32>), KM_LDS_MAX);
+  aerr = allow_dynamic_lds(aerr, opt[3], reinterpret_cast<const void*>(km_assign_tiled_kernel<16>), KM_LDS_MAX);
   MUSED_CHECK_HIP(aerr);
   // the fused E step + M-step partials of this (d, k): all four kernels take the same arguments
   const auto assign = tr == 64   ? km_assign_tiled_kernel<64>

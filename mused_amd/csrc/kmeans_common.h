@@ -2,7 +2,7 @@
 // mused_kmeans_lloyd_wide (csrc/kmeans.hip) and mused_mbkm_step / mused_kmeans_assign (csrc/minibatch.hip):
 //   km_take / km_lane_min    first minimum of csq_j - 2 x . c_j: strict < per thread, lexicographic (distance, j) across lanes
 //   km_stream_tiles          tile sizes of the streamed E-step kernels (kmw_assign_kernel, mbkm_assign_kernel) within an
-//                            LDS budget; km_allow_lds raises a kernel's limit to one
+//                            LDS budget; allow_dynamic_lds (internal.h) raises a kernel's limit to one
 //   km_norm2 / km_csq_kernel |c_j|^2 as one fma chain over c = 0 .. d - 1
 //   km_finish                tail of a Lloyd M step: total squared shift (fixed tree), centre norms, stop rule
 #pragma once
@@ -70,12 +70,6 @@ static inline bool km_stream_tiles(size_t budget, int d, int k, int* TR, int* KT
     }
   }
   return false;
-}
-
-// Raises a kernel's dynamic LDS limit, under the capture lock: another thread's stream capture does not survive the call.
-static inline hipError_t km_allow_lds(const void* kernel, size_t bytes) {
-  CaptureLock lk(capture_mutex());
-  return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
 // Tail of a Lloyd M step in one workgroup of 1024 threads, after the centres C are written.  `acc` is this thread's share

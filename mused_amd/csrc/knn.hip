@@ -318,13 +318,9 @@ static int select_launch_src(const double* S, long ld, int n, int k, int* out_id
                              int mask_words, const SelSource& src, hipStream_t stream) {
   // keys of the row (cached case) + the 16-bit intersection counters of SRC_JACCARD behind them
   const size_t lds = ((SRC != SRC_MATRIX || n <= SEL_MAX_LDS_KEYS) ? (size_t)n * 8 : 0) + (src_tag_sets(SRC) ? (size_t)n * 2 + 8 : 0);
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(select_k_kernel<SRC>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  src_tag_sets(SRC) ? SEL_MAX_JACCARD_ROWS * 10 + 64 : SEL_MAX_LDS_KEYS * 8);
-  });
+  static LdsOptIn opt;
+  const hipError_t attr_rc = allow_dynamic_lds(opt, reinterpret_cast<const void*>(select_k_kernel<SRC>),
+                                               src_tag_sets(SRC) ? SEL_MAX_JACCARD_ROWS * 10 + 64 : SEL_MAX_LDS_KEYS * 8);
   MUSED_CHECK_HIP(attr_rc);
   hipLaunchKernelGGL(select_k_kernel<SRC>, dim3(n), dim3(SEL_THREADS), lds, stream, S, ld, n, k, out_idx, out_mask,
                      mask_words, src);

@@ -27,10 +27,8 @@
 // falls back to the classic path -- never a wrong result.
 #include <vector>
 
-#include "gemm_f64.h"
-#include "internal.h"
+#include "pair_tile.h"
 
-extern "C" int mused_row_sq_norms(const void* X, int dtype, long n, int d, long ld, double* out, void* stream);
 
 namespace mused {
 
@@ -112,8 +110,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void knn_band_kernel(GemmArgs g, C
   v4f64 acc[4][4];
   gemm_tile_mainloop<T, T, true, true, VEC>(g, X, X, m0, n0, 0, g.K, smem, acc);
 
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wr = wave >> 1, wc = wave & 1, kq = lane >> 4, li = lane & 15;
+  int lane, wr, wc, kq, li;
+  patch_lanes(lane, wr, wc, kq, li);
   const int n = g.M;
   const bool both = (delta != 0);  // a diagonal tile holds both orientations of its pairs itself
   if constexpr (DIRECT) {
@@ -124,7 +122,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void knn_band_kernel(GemmArgs g, C
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int rl = wr * 64 + i * 16 + kq + 4 * r, row = m0 + rl;
+        const int rl = patch_row(0, wr, kq) + i * 16 + 4 * r, row = m0 + rl;
         const bool row_new = row >= c.n_ret;
         const int srow = row < n ? cand_slot(c, row) : 0;
         double trow = 0.0;
@@ -132,7 +130,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void knn_band_kernel(GemmArgs g, C
         if (hopm && !row_new && row < n) { trow = c.tau[srow]; crow = c.taucol[srow]; }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const int cl = wc * 64 + j * 16 + li, col = n0 + cl;
+          const int cl = patch_col(0, wc, li) + j * 16, col = n0 + cl;
           const double av = acc[i][j][r];
           const bool col_new = col >= c.n_ret;
           if (row < n) {  // row side: columns of tile J at signed distance +delta
@@ -170,7 +168,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void knn_band_kernel(GemmArgs g, C
   int tccol[4], scol[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int col = n0 + wc * 64 + j * 16 + li;
+    const int col = patch_col(n0, wc, li) + j * 16;
     const bool ok = both && col < n;
     scol[j] = ok ? cand_slot(c, col) : 0;
     tcol[j] = ok ? c.tau[scol[j]] : __longlong_as_double(0xfff0000000000000ll);  // -inf admits nothing
@@ -180,14 +178,14 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void knn_band_kernel(GemmArgs g, C
   for (int i = 0; i < 4; ++i) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int row = m0 + wr * 64 + i * 16 + kq + 4 * r;
+      const int row = patch_row(m0, wr, kq) + i * 16 + 4 * r;
       if (row >= n) continue;
       const int srow = cand_slot(c, row);
       const double trow = c.tau[srow];
       const int crow = c.taucol[srow];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int col = n0 + wc * 64 + j * 16 + li;
+        const int col = patch_col(n0, wc, li) + j * 16;
         if (col >= n) continue;
         if (row < c.n_ret && col < c.n_ret) continue;  // hop mode: this pair is in both rows' kept lists (or was never admitted)
         const double a = acc[i][j][r];
@@ -464,21 +462,10 @@ int inv_norms_launch(double* norms, long n, hipStream_t st);  // knn.hip: sq nor
 
 template <typename T, int METRIC, bool DIRECT>
 static int band_launch(const GemmArgs& g, const CandArgs& c, bool vec, int tiles, int d_lo, int nd, hipStream_t st) {
-  static std::once_flag once[2];
-  static hipError_t err[2];
-  const int v = vec ? 1 : 0;
-  std::call_once(once[v], [&] {
-    const void* fn = vec ? (const void*)knn_band_kernel<T, true, METRIC, DIRECT> : (const void*)knn_band_kernel<T, false, METRIC, DIRECT>;
-    err[v] = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
-  });
-  MUSED_CHECK_HIP(err[v]);
   const int t_new = c.n_ret / GEMM_BM, d_hi_ = d_lo + nd - 1;
   const int ibase_min = t_new > d_hi_ ? t_new - d_hi_ : 0;
-  const dim3 grid(cdiv(tiles - ibase_min, 8) * 8 * nd), blk(GEMM_THREADS);
-  if (vec) hipLaunchKernelGGL((knn_band_kernel<T, true, METRIC, DIRECT>), grid, blk, GEMM_LDS_BYTES, st, g, c, tiles, d_lo, nd);
-  else hipLaunchKernelGGL((knn_band_kernel<T, false, METRIC, DIRECT>), grid, blk, GEMM_LDS_BYTES, st, g, c, tiles, d_lo, nd);
-  MUSED_LAUNCH_CHECK();
-  return MUSED_OK;
+  return pair_launch<knn_band_kernel<T, true, METRIC, DIRECT>, knn_band_kernel<T, false, METRIC, DIRECT>>(
+      vec, pair_grid(tiles - ibase_min, nd), GEMM_LDS_BYTES, st, g, c, tiles, d_lo, nd);
 }
 
 // lo_abs: stream position of window row 0 (0 for tumbling use); n_new: 0 = compute the window from scratch, else the number
@@ -489,9 +476,7 @@ static int knn_fused_t(const T* X, long n, int d, long ld, int k, int metric, co
                        bool ring = false) {
   const int tiles = cdiv(n, GEMM_BM);
   const int hmax = tiles / 2;
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A = X; g.B = X; g.lda = ld; g.ldb = ld; g.M = (int)n; g.N = (int)n; g.K = d;
+  const GemmArgs g = self_product_args(X, ld, n, d);
   const bool hop = ring && n_new > 0 && n_new < n;
   CandArgs c{ws.tau, ws.taucol, ws.count, ws.cscore, ws.ccol, cap, ws.overflow, ws.norms,
              ring ? (int)(lo_abs % n) : 0, ring ? (int)(lo_abs & 0x3fffffff) : 0, hop ? (int)(n - n_new) : 0, (int)n};

@@ -333,13 +333,8 @@ int mused_match_pot_chain(const int* raw, int K_windows, int W, const int* prev0
   MUSED_REQUIRE(raw && matched_out && info_out && ws && K_windows > 0 && W > 0, "mused_match_pot_chain: bad arguments");
   MUSED_REQUIRE((long)K_windows * W < (1l << 31) && K_windows < (1 << 24), "mused_match_pot_chain: K_windows * W must stay below 2^31");
   MUSED_REQUIRE(ws_bytes >= mused_match_pot_ws_bytes(), "mused_match_pot_chain: workspace too small");
-  static std::once_flag once;
-  static hipError_t aerr = hipSuccess;
-  std::call_once(once, [] {
-    CaptureLock lk(capture_mutex());
-    aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(match_pot_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)sizeof(MatchLds));
-  });
+  static LdsOptIn opt;
+  const hipError_t aerr = allow_dynamic_lds(opt, reinterpret_cast<const void*>(match_pot_chain_kernel), sizeof(MatchLds));
   MUSED_CHECK_HIP(aerr);
   int* ov = (int*)ws;
   double* kx = (double*)((char*)ws + MT_WS_OV_BYTES);

@@ -275,13 +275,8 @@ int mused_match_hung_chain(const int* raw, int K_windows, int W, const int* prev
   MUSED_REQUIRE(raw && matched_out && info_out && ws && K_windows > 0 && W > 0, "mused_match_hung_chain: bad arguments");
   MUSED_REQUIRE((long)K_windows * W < (1l << 31) && K_windows < (1 << 24), "mused_match_hung_chain: K_windows * W must stay below 2^31");
   MUSED_REQUIRE(ws_bytes >= mused_match_hung_ws_bytes(), "mused_match_hung_chain: workspace too small");
-  static std::once_flag once;
-  static hipError_t aerr = hipSuccess;
-  std::call_once(once, [] {
-    CaptureLock lk(capture_mutex());
-    aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(match_hung_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)sizeof(HungLds));
-  });
+  static LdsOptIn opt;
+  const hipError_t aerr = allow_dynamic_lds(opt, reinterpret_cast<const void*>(match_hung_chain_kernel), sizeof(HungLds));
   MUSED_CHECK_HIP(aerr);
   hipLaunchKernelGGL(match_hung_chain_kernel, dim3(1), dim3(MT_THREADS), sizeof(HungLds), (hipStream_t)stream, raw, K_windows, W,
                      prev0, min_overlap, matched_out, info_out, assign_out, (int*)ws);

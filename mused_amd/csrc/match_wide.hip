@@ -451,13 +451,8 @@ int mused_match_hung_wide_chain(const int* raw, int K_windows, int W, const int*
                 "mused_match_hung_wide_chain: K_windows * W must stay below 2^31, K_windows below 2^18, max_steps >= 0");
   MUSED_REQUIRE(ws_bytes >= mw_ws_bytes(W) && ((size_t)ws & 255) == 0,
                 "mused_match_hung_wide_chain: workspace too small or not 256-byte aligned");
-  static std::once_flag once;
-  static hipError_t aerr = hipSuccess;
-  std::call_once(once, [] {
-    CaptureLock lk(capture_mutex());
-    aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(mw_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)sizeof(WideLds));
-  });
+  static LdsOptIn opt;
+  const hipError_t aerr = allow_dynamic_lds(opt, reinterpret_cast<const void*>(mw_solve_kernel), sizeof(WideLds));
   MUSED_CHECK_HIP(aerr);
   hipStream_t st = (hipStream_t)stream;
   const WideWs w = mw_carve(ws, W);

@@ -120,12 +120,8 @@ int mused_jaccard_scores(const int* rowptr, const int* tags, const int* postptr,
   // a set has < 65536 tags (16-bit intersection counters) and the counters of one row fit the 160 KB of LDS
   MUSED_REQUIRE(n <= 65536, "mused_jaccard_scores: at most 65536 rows per window (n=%d)", n);
   const size_t lds = (size_t)n * sizeof(unsigned short);
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute((const void*)jaccard_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  128 * 1024);
-  });
+  static LdsOptIn opt;
+  const hipError_t attr_rc = allow_dynamic_lds(opt, (const void*)jaccard_scores_kernel, 128 * 1024);
   MUSED_CHECK_HIP(attr_rc);
   jaccard_scores_kernel<<<n, 256, lds, (hipStream_t)stream>>>(rowptr, tags, postptr, postrow, n, S);
   MUSED_LAUNCH_CHECK();

@@ -206,13 +206,8 @@ int chunk_for(int k, int chunk) {
 template <int SRC>
 static int chunk_select_launch(int n, int k, int chunk, const ChunkSource& src, int* out_idx, unsigned long long* out_mask,
                                int mask_words, hipStream_t st) {
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [] {
-    CaptureLock lock(capture_mutex());
-    attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(chunk_select_kernel<SRC>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, CS_LDS_DYN);
-  });
+  static LdsOptIn opt;
+  const hipError_t attr_rc = allow_dynamic_lds(opt, reinterpret_cast<const void*>(chunk_select_kernel<SRC>), CS_LDS_DYN);
   MUSED_CHECK_HIP(attr_rc);
   const int c = chunk_for(k, chunk);
   hipLaunchKernelGGL(chunk_select_kernel<SRC>, dim3(n), dim3(CS_THREADS), (size_t)chunk_lds_bytes(k, c), st, n, k, c, src,

@@ -177,11 +177,8 @@ static int assign_launch(const double* X, long ld, int n, int d, int k, const do
                          hipStream_t st) {
   int TR = 0, KT = 0;
   MUSED_REQUIRE(km_stream_tiles(MB_ASSIGN_LDS_DOUBLES, d, k, &TR, &KT), "minibatch assign: no tile fits d = %d", d);
-  static std::once_flag once;
-  static hipError_t aerr = hipSuccess;
-  std::call_once(once, [] {
-    aerr = km_allow_lds(reinterpret_cast<const void*>(mbkm_assign_kernel), 8 * MB_ASSIGN_LDS_DOUBLES);
-  });
+  static LdsOptIn opt;
+  const hipError_t aerr = allow_dynamic_lds(opt, reinterpret_cast<const void*>(mbkm_assign_kernel), 8 * MB_ASSIGN_LDS_DOUBLES);
   MUSED_CHECK_HIP(aerr);
   hipLaunchKernelGGL(km_csq_kernel, dim3(cdiv(k, 64)), dim3(64), 0, st, C, k, d, csq);
   const size_t lds = 8 * (size_t)(TR + KT) * (d + 1);

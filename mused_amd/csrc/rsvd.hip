@@ -348,13 +348,9 @@ __global__ void col_scale_kernel(double* __restrict__ V, long total, int ncol, c
 
 // trsm_rows_kernel asks for more dynamic LDS than a kernel gets by default: set once per process, before its first launch
 static int trsm_rows_prepare() {
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [] {
-    const int tri = (int)(sizeof(double) * CHOLQR_MAX_R * (CHOLQR_MAX_R + 1) / 2);
-    attr_rc = hipFuncSetAttribute((const void*)trsm_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  tri + (int)(sizeof(double) * 64 * (CHOLQR_MAX_R | 1)));
-  });
+  static LdsOptIn opt;
+  const int tri = (int)(sizeof(double) * CHOLQR_MAX_R * (CHOLQR_MAX_R + 1) / 2);
+  const hipError_t attr_rc = allow_dynamic_lds(opt, (const void*)trsm_rows_kernel, tri + (int)(sizeof(double) * 64 * (CHOLQR_MAX_R | 1)));
   MUSED_CHECK_HIP(attr_rc);
   return MUSED_OK;
 }

@@ -199,13 +199,8 @@ int mused_score_labels(const int* truth, const int* pred, long n_seg, long seg_l
   MUSED_REQUIRE(seg_len < (1l << 31) && n_seg < (1l << 31) && cells_cap <= (long)SC_MAXC * SC_MAXC,
                 "mused_score_labels: seg_len and n_seg must stay below 2^31, cells_cap at or below 4096^2");
   MUSED_REQUIRE(ws_bytes >= mused_score_ws_bytes(n_seg, cells_cap), "mused_score_labels: workspace too small");
-  static std::once_flag once;
-  static hipError_t aerr = hipSuccess;
-  std::call_once(once, [] {
-    CaptureLock lk(capture_mutex());
-    aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(score_labels_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)sizeof(ScoreLds));
-  });
+  static LdsOptIn opt;
+  const hipError_t aerr = allow_dynamic_lds(opt, reinterpret_cast<const void*>(score_labels_kernel), sizeof(ScoreLds));
   MUSED_CHECK_HIP(aerr);
   // 16-byte loads need every segment to start on a 16-byte boundary
   const bool vec = ((uintptr_t)truth % 16 == 0) && ((uintptr_t)pred % 16 == 0) && (n_seg == 1 || seg_len % 4 == 0);

@@ -317,13 +317,8 @@ int mused_score_partitions(const int* truth, const int* pred, long n_seg, long s
                 "mused_score_partitions: seg_len and n_seg must stay below 2^31, cells_cap at or below 4096^2");
   MUSED_REQUIRE((uintptr_t)ws % 8 == 0 && ws_bytes >= mused_score_partitions_ws_bytes(n_seg, seg_len, cells_cap),
                 "mused_score_partitions: workspace too small or not 8-byte aligned");
-  static std::once_flag once;
-  static hipError_t aerr = hipSuccess;
-  std::call_once(once, [] {
-    CaptureLock lk(capture_mutex());
-    aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(partition_table_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)sizeof(PartLds));
-  });
+  static LdsOptIn opt;
+  const hipError_t aerr = allow_dynamic_lds(opt, reinterpret_cast<const void*>(partition_table_kernel), sizeof(PartLds));
   MUSED_CHECK_HIP(aerr);
   const hipStream_t st = (hipStream_t)stream;
   const PartWs w = part_carve(ws, n_seg, seg_len, cells_cap);

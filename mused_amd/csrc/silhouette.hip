@@ -37,12 +37,9 @@
 // then the distance of every row to the centroid from the differences (sum (x - c)^2, a wave per row); a wave per cluster
 // takes the centroid distances to all other clusters; one workgroup adds the per-cluster numbers in a fixed tree.
 // O(n d + C^2 d) work.
-#include "gemm_f64.h"
-#include "internal.h"
+#include "pair_tile.h"
 #include "dbscan_common.h"
 #include "radix_sort.h"
-
-extern "C" int mused_row_sq_norms(const void* X, int dtype, long n, int d, long ld, double* out, void* stream);
 
 namespace mused {
 
@@ -134,13 +131,6 @@ __global__ __launch_bounds__(256) void sil_gather_kernel(const double* __restric
     const int j = (int)(e - p * lds);
     Xs[e] = j < d ? X[(long)perm[p] * ld + j] : 0.0;
   }
-}
-
-__global__ __launch_bounds__(256) void sil_finite_kernel(const double* __restrict__ nrm, int* __restrict__ info, int n) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const double v = i < n ? nrm[i] : 0.0;
-  const bool bad = !(fabs(v) <= 1.7976931348623157e308);  // NaN or inf (an overflowing norm of finite values included)
-  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(info, SIL_FLAG_NONFINITE);
 }
 
 // ---- silhouette --------------------------------------------------------------------------------------------------------
@@ -492,24 +482,15 @@ static int sil_prepare(const double* X, long n, int d, long ld, const int* label
   MUSED_LAUNCH_CHECK();
   const int rc = mused_row_sq_norms(w.Xs, MUSED_F64, n, d, lds, w.nrm, (void*)st);
   if (rc) return rc;
-  hipLaunchKernelGGL(sil_finite_kernel, rows, blk, 0, st, w.nrm, w.info, (int)n);
+  hipLaunchKernelGGL(norms_finite_kernel, rows, blk, 0, st, w.nrm, (int)n, w.info, SIL_FLAG_NONFINITE);
   MUSED_LAUNCH_CHECK();
   return MUSED_OK;
 }
 
-static int sil_tile_launch(const GemmArgs& g, const SilArgs& a, bool vec, int tiles, int slices, hipStream_t st) {
-  static std::once_flag once[2];
-  static hipError_t err[2];
-  const int v = vec ? 1 : 0;
-  std::call_once(once[v], [&] {
-    const void* fn = vec ? (const void*)sil_tile_kernel<true> : (const void*)sil_tile_kernel<false>;
-    err[v] = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SIL_LDS_BYTES);
-  });
-  MUSED_CHECK_HIP(err[v]);
-  const dim3 grid(tiles * slices), blk(GEMM_THREADS);
-  if (vec) hipLaunchKernelGGL((sil_tile_kernel<true>), grid, blk, SIL_LDS_BYTES, st, g, a, tiles, slices);
-  else hipLaunchKernelGGL((sil_tile_kernel<false>), grid, blk, SIL_LDS_BYTES, st, g, a, tiles, slices);
-  MUSED_LAUNCH_CHECK();
+// the tile kernel over (row tile, slice) and, with several slices, their merge
+static int sil_launch(const GemmArgs& g, const SilArgs& a, bool vec, int tiles, int slices, hipStream_t st) {
+  const int rc = pair_launch<sil_tile_kernel<true>, sil_tile_kernel<false>>(vec, tiles * slices, SIL_LDS_BYTES, st, g, a, tiles, slices);
+  if (rc) return rc;
   if (slices > 1) {
     hipLaunchKernelGGL(sil_merge_kernel, dim3(cdiv(g.M, 256)), dim3(256), 0, st, a, g.M, tiles, slices);
     MUSED_LAUNCH_CHECK();
@@ -551,14 +532,12 @@ int mused_silhouette(const double* X, long n, int d, long ld, const int* labels,
   int rc;
   if ((rc = sil_prepare(X, n, d, ld, labels, w, st))) return rc;
   const long lds = sil_pitch(d);
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A = w.Xs; g.B = w.Xs; g.lda = lds; g.ldb = lds; g.M = (int)n; g.N = (int)n; g.K = d;
+  const GemmArgs g = self_product_args(w.Xs, lds, n, d);
   SilArgs a{w.nrm, w.cid, w.seg, w.val[0], w.info, samples_out, w.part};
   const int tiles = cdiv(n, GEMM_BM);
   const char* one = getenv("MUSED_SIL_SLICES");  // "1": no column slices (diagnostic; the workspace is sized for the default)
   const int slices = (one && one[0] == '1' && one[1] == 0) ? 1 : sil_slices(tiles);
-  if ((rc = sil_tile_launch(g, a, vec_ok<double>(w.Xs, lds, 0), tiles, slices, st))) return rc;
+  if ((rc = sil_launch(g, a, vec_ok<double>(w.Xs, lds, 0), tiles, slices, st))) return rc;
   hipLaunchKernelGGL(sil_finish_kernel, dim3(1), dim3(SIL_REDUCE_THREADS), 0, st, samples_out, w.info, (SilInfoOut*)info_out, (int)n);
   MUSED_LAUNCH_CHECK();
   return MUSED_OK;

@@ -500,15 +500,10 @@ static int tk_build_launch(const TkWs& l, long n_docs, long slots, int n_tokens,
   int n = 1;
   while (n < doc_tokens) n <<= 1;
   const size_t lds = tk_rows_lds(n);
-  static std::once_flag once;
-  static hipError_t aerr = hipSuccess;
-  std::call_once(once, [&] {
-    CaptureLock lock(capture_mutex());
-    const int most = (int)tk_rows_lds(TK_MAX_DOC_TOKENS);
-    aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(tk_rows_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    if (aerr == hipSuccess)
-      aerr = hipFuncSetAttribute(reinterpret_cast<const void*>(tk_rows_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
-  });
+  static LdsOptIn opt[2];
+  const size_t most = tk_rows_lds(TK_MAX_DOC_TOKENS);
+  hipError_t aerr = allow_dynamic_lds(opt[0], reinterpret_cast<const void*>(tk_rows_kernel<false>), most);
+  aerr = allow_dynamic_lds(aerr, opt[1], reinterpret_cast<const void*>(tk_rows_kernel<true>), most);
   MUSED_CHECK_HIP(aerr);
   TkRows a{l.docptr, l.tok_start, l.tok_slot, l.table, rank, vrow, (int)n_docs, n_tokens, n_terms, (int)slots, n};
   const int threads = n / 2 < 64 ? 64 : (n / 2 > 256 ? 256 : n / 2);

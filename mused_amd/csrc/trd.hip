@@ -619,13 +619,9 @@ constexpr int L_DM_TOTAL = L_S + 2 * DM_TOTAL;     // kernel D
 constexpr int C_LDS = trd_c_lds_doubles<L256, 32>();        // kernel C: T, exchange, the pivot sequences of 32 vectors
 
 int trd_prepare() {
-  static std::once_flag once;
-  static hipError_t rc = hipSuccess;
-  std::call_once(once, [] {
-    rc = hipFuncSetAttribute((const void*)trd_d_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * L_DM_TOTAL));
-    if (rc == hipSuccess)
-      rc = hipFuncSetAttribute((const void*)trd_c_kernel<L256, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * C_LDS));
-  });
+  static LdsOptIn opt[2];
+  hipError_t rc = allow_dynamic_lds(opt[0], (const void*)trd_d_kernel, sizeof(double) * L_DM_TOTAL);
+  rc = allow_dynamic_lds(rc, opt[1], (const void*)trd_c_kernel<L256, 32>, sizeof(double) * C_LDS);
   MUSED_CHECK_HIP(rc);
   return MUSED_OK;
 }

@@ -849,21 +849,11 @@ __global__ void trdx_export_kernel(const double* __restrict__ ws, double* __rest
 template <int NX>
 static int trdx_prepare_t() {
   using LY = LX<NX>;
-  static std::once_flag once;
-  static hipError_t rc = hipSuccess;
-  std::call_once(once, [] {
-    rc = hipFuncSetAttribute((const void*)trdx_a_kernel<NX>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)(sizeof(double) * trdx_a_lds_doubles<NX>()));
-    if (rc == hipSuccess)
-      rc = hipFuncSetAttribute((const void*)trd_c_kernel<LY, XA<NX>::VPW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(sizeof(double) * trd_c_lds_doubles<LY, XA<NX>::VPW>()));
-    if (rc == hipSuccess)
-      rc = hipFuncSetAttribute((const void*)trdx_tfac_kernel<NX>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(sizeof(double) * TF_LDS_DOUBLES));
-    if (rc == hipSuccess)
-      rc = hipFuncSetAttribute((const void*)trdx_back_kernel<NX>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(sizeof(double) * XZ<NX>::LDS_DOUBLES));
-  });
+  static LdsOptIn opt[4];
+  hipError_t rc = allow_dynamic_lds(opt[0], (const void*)trdx_a_kernel<NX>, sizeof(double) * trdx_a_lds_doubles<NX>());
+  rc = allow_dynamic_lds(rc, opt[1], (const void*)trd_c_kernel<LY, XA<NX>::VPW>, sizeof(double) * trd_c_lds_doubles<LY, XA<NX>::VPW>());
+  rc = allow_dynamic_lds(rc, opt[2], (const void*)trdx_tfac_kernel<NX>, sizeof(double) * TF_LDS_DOUBLES);
+  rc = allow_dynamic_lds(rc, opt[3], (const void*)trdx_back_kernel<NX>, sizeof(double) * XZ<NX>::LDS_DOUBLES);
   MUSED_CHECK_HIP(rc);
   return trd_prepare();
 }

@@ -34,6 +34,13 @@ def _duplicates():
     return np.concatenate([X, X[:50]])
 
 
+def _pairs(n, h):
+    """Row i and row i + h are 0.5 apart, every other pair at least 9.5: with h a multiple of 128 each neighbour pair lies in
+    a pair of row tiles h / 128 apart -- antipodal at n = 512 (4 tiles), across the wrap-around at n = 640 (5 tiles)."""
+    i = np.arange(n)
+    return np.stack([10.0 * (i % h) + 0.5 * (i // h), np.zeros(n)], axis=1)
+
+
 def small_cases():
     out = []
     for n in (1, 2, 127, 128, 129):
@@ -46,6 +53,11 @@ def small_cases():
     out.append(("bridge_ba", _bridge(True), 0.85, 5, 0))
     out.append(("duplicates", _duplicates(), 2.0, 4, 0))
     out.append(("min_samples_1", _normal(300, 8), 1.0, 1, 0))
+    # a tile pair served twice makes the m3 cases core (scikit-learn: all noise), one never served makes the m2 cases noise
+    # (scikit-learn: label[i] == i % h)
+    for n in (512, 640):
+        for ms in (2, 3):
+            out.append((f"pairs_n{n}_m{ms}", _pairs(n, n // 2), 1.0, ms, 0))
     return out
 
 
