@@ -713,6 +713,38 @@ long mused_cluster_indices_ws_bytes(long n, int d);
 int mused_cluster_indices(const double* X, long n, int d, long ld, const int* labels, double* out, int* info_out, void* ws,
                           long ws_bytes, void* stream);
 
+/* ---- DBSCAN's eps from the data, csrc/kdist.hip (specification: mused_amd/kdist.py): the squared distance of every row to
+ * its k-th nearest row, THE ROW ITSELF COUNTED (scikit-learn's convention for min_samples and for
+ * NearestNeighbors(n_neighbors=k).kneighbors(X)): kd2[i] = the k-th smallest of d2(i, j) over all j,
+ * d2 = max(0, |x_i|^2 + |x_j|^2 - 2 x_i.x_j), exactly 0 for j == i.  The full-square schedule of mused_silhouette: a workgroup
+ * owns a 128-row tile, walks column tiles of fp64 MFMA products and keeps every row's k smallest values in LDS; only entries
+ * below a row's current k-th value leave the accumulators, and none is dropped (rows with more passing entries than staging
+ * slots are served in further rounds).  Below 256 row tiles the column tiles are cut into the S <= 16 slices of
+ * mused_silhouette_slices(n) and a merge kernel takes the k-th smallest of a row's S lists.  The k-th smallest of a multiset
+ * does not depend on the order of arrival: two calls give the same bits; no floating-point atomic.  Two instances, lists of 8
+ * (k <= 8) and of 64.  Enqueue-only.
+ * X: n x d fp64 (pitch ld >= d), 1 <= n <= 2^19, d < 2^20, 1 <= k <= min(n, 64).
+ * kd2_out: n fp64 (DEVICE), SQUARED distances.
+ * info_out (DEVICE, 4 int32) = {flags, slices, list length of the instance (8 or 64), 0}.  Flags: 2 a row is not finite (or its
+ *   squared norm overflows); kd2_out is NOT written then.
+ * ws: mused_kth_distance_ws_bytes(n, k) bytes (16 + 8 n, plus 8 S k n with S > 1 slices, and alignment; -1 outside the limits
+ *   above).  Scratch only.  Outside the limits, or with a short workspace, the call returns an error and launches nothing. */
+long mused_kth_distance_ws_bytes(long n, int k);
+int mused_kth_distance(const double* X, long n, int d, long ld, int k, double* kd2_out, int* info_out, void* ws, long ws_bytes,
+                       void* stream);
+/* The knee of the sorted k-distance curve and the eps between its knee and the next larger value (mused_amd/kdist.py: knee,
+ * eps_from_curve).  v = sqrt(kd2) sorted ascending by bit pattern (eight stable radix passes: low word, then high word);
+ * g_i = i / (n - 1) - (v_i - v_0) / (v_{n-1} - v_0); i* = the FIRST maximum of g (a fixed-order reduction, ties to the smaller
+ * index); nxt = the first index > i* with v[nxt] > v[i*]; eps = 0.5 (v[i*] + v[nxt]) -- the bits of the NumPy rule.
+ * kd2: n fp64 (DEVICE), n <= 2^19, every value finite and >= 0.
+ * out (DEVICE, 48 bytes) = {int64 i*, int64 nxt, fp64 v[i*], fp64 v[nxt], fp64 eps, int64 flags}.  Flags: 2 a value of kd2 is
+ *   negative or not finite; 4 the curve is flat (v[n-1] == v[0]: always for k = 1 and for n = 1).  With a flag the indices
+ *   are -1 and the three numbers NaN.
+ * ws: mused_eps_knee_ws_bytes(n) bytes (40 n + 1024 ceil(n / 1024) + 16 and alignment; -1 for n outside [1, 2^19]).  Its
+ *   FIRST n doubles hold the sorted curve v after the call, for callers that plot it; the rest is scratch. */
+long mused_eps_knee_ws_bytes(long n);
+int mused_eps_knee(const double* kd2, long n, void* out, void* ws, long ws_bytes, void* stream);
+
 /* ---- a5-a7: SeqBasedSWFD (swfd submodule; call sites main.py:62,65-67,70) ---------------------- */
 
 /* SeqBasedSWFD(N=, R=, d=, sketch_dim=) */

@@ -132,6 +132,10 @@ _PROTOS = {
     "mused_silhouette": (_i, [_vp, _l, _i, _l, _vp, _vp, _vp, _vp, _l, _vp]),
     "mused_cluster_indices_ws_bytes": (_l, [_l, _i]),
     "mused_cluster_indices": (_i, [_vp, _l, _i, _l, _vp, _vp, _vp, _vp, _l, _vp]),
+    "mused_kth_distance_ws_bytes": (_l, [_l, _i]),
+    "mused_kth_distance": (_i, [_vp, _l, _i, _l, _i, _vp, _vp, _vp, _l, _vp]),
+    "mused_eps_knee_ws_bytes": (_l, [_l]),
+    "mused_eps_knee": (_i, [_vp, _l, _vp, _vp, _l, _vp]),
     "mused_swfd_create": (_i, [_l, _d, _i, _i, _i, C.POINTER(_vp)]),
     "mused_swfd_create_lanes": (_i, [_l, _d, _i, _i, _i, _i, C.POINTER(_vp)]),
     "mused_swfd_lanes": (_i, [_vp]),

@@ -1,10 +1,11 @@
 // What the kernels that decide something per pair of rows share (dbscan_tile_kernel, dbscan_incr_tile_kernel,
-// emst_tile_kernel, sil_tile_kernel, knn_band_kernel): each leaves a 128 x 128 tile of x_i . x_j in the accumulators of
+// emst_tile_kernel, sil_tile_kernel, kd_tile_kernel, knn_band_kernel): each leaves a 128 x 128 tile of x_i . x_j in the accumulators of
 // gemm_tile_mainloop (gemm_f64.h) and then looks at every entry.  The deciding part is each file's own; here are
 //   pair_slot / pair_tile / pair_grid   which tile a workgroup takes when every unordered pair of row tiles is visited once
 //   patch_lanes / patch_row / patch_col where the entries of a thread's accumulators lie in the tile, and which lanes share a
 //                                       row or a column of it
 //   pair_launch                    the launch of a kernel's VEC or plain instance, behind its dynamic-LDS opt-in
+//   col_slices                          how a full-square schedule cuts its column tiles below 256 row tiles
 //   self_product_args                   GemmArgs of X X^T
 //   norm_not_finite / norms_finite_kernel, pair_tau_coeff / ulp4   the guards around a comparison of squared distances
 // A wrong formula here gives no error: it gives results that are wrong for the pairs of particular tiles only.
@@ -55,6 +56,16 @@ __device__ __forceinline__ int patch_row(int m0, int wr, int kq) { return m0 + w
 __device__ __forceinline__ int patch_col(int n0, int wc, int li) { return n0 + wc * 64 + li; }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
+// Full-square schedules (sil_tile_kernel, kd_tile_kernel: a workgroup owns a row tile and walks column tiles): column slices
+// for `tiles` row tiles.  1 from 256 tiles on (the row tiles alone fill the GPU), else as many runs of whole column tiles as
+// bring the grid to about 512 workgroups, at most 16
+constexpr int MAX_COL_SLICES = 16;
+static inline int col_slices(int tiles) {
+  if (tiles >= 256) return 1;
+  const int s = 512 / tiles < tiles ? 512 / tiles : tiles;
+  return s < MAX_COL_SLICES ? s : MAX_COL_SLICES;
+}
+
 // X X^T for n rows of length d
 static inline GemmArgs self_product_args(const void* X, long ld, long n, int d) {
   GemmArgs g;

@@ -22,7 +22,7 @@
 // floating-point value anywhere in this file; the flags are integer atomicOr.
 //
 // Column slices.  Below 256 row tiles (n <= 32,640) n / 128 workgroups leave most of the GPU idle, so the column tiles are cut
-// into S = sil_slices(tiles) <= 16 runs of whole tiles and workgroup (row tile, slice) walks one run: about 512 workgroups.
+// into S = col_slices(tiles) <= 16 runs of whole tiles and workgroup (row tile, slice) walks one run: about 512 workgroups.
 // A cluster that lies inside a slice is settled there; of the clusters a slice cuts it leaves, per row, the sum of the one
 // that began before the slice and ended in it (head) and of the one still open at its end (tail), with its a and b so far:
 // 4 S n doubles.  sil_merge_kernel then walks a row's slices in ascending order and closes the cut clusters: carry + head.
@@ -57,15 +57,6 @@ struct SilWs {
 
 static long sil_pitch(int d) { return ((long)d + 1) & ~1l; }
 
-// column slices for `tiles` row tiles: 1 from 256 tiles on (the row tiles alone fill the GPU), else as many runs of whole
-// column tiles as bring the grid to about 512 workgroups, at most 16
-constexpr int SIL_MAX_SLICES = 16;
-static int sil_slices(int tiles) {
-  if (tiles >= 256) return 1;
-  const int s = 512 / tiles < tiles ? 512 / tiles : tiles;
-  return s < SIL_MAX_SLICES ? s : SIL_MAX_SLICES;
-}
-
 static size_t sil_layout(long n, int d, bool indices, char* base, SilWs* ws) {
   SilWs sizing;
   SilWs& w = ws ? *ws : sizing;
@@ -80,7 +71,7 @@ static size_t sil_layout(long n, int d, bool indices, char* base, SilWs* ws) {
   w.info = c.take<int>(4);
   w.nrm = c.take<double>(n);
   w.Xs = c.take<double>((size_t)n * sil_pitch(d));
-  const int slices = sil_slices(cdiv(n, GEMM_BM));
+  const int slices = col_slices(cdiv(n, GEMM_BM));
   w.part = (!indices && slices > 1) ? c.take<double>((size_t)slices * 4 * n) : nullptr;
   if (indices) {
     w.cen = c.take<double>((size_t)n * d);
@@ -513,7 +504,7 @@ long mused_silhouette_ws_bytes(long n, int d) {
 // column slices mused_silhouette cuts n rows into (csrc/silhouette.hip, head of the file); -1 outside [1, 2^19]
 int mused_silhouette_slices(long n) {
   if (n < 1 || n > DB_MAX_ROWS) return -1;
-  return sil_slices(cdiv(n, GEMM_BM));
+  return col_slices(cdiv(n, GEMM_BM));
 }
 
 long mused_cluster_indices_ws_bytes(long n, int d) {
@@ -536,7 +527,7 @@ int mused_silhouette(const double* X, long n, int d, long ld, const int* labels,
   SilArgs a{w.nrm, w.cid, w.seg, w.val[0], w.info, samples_out, w.part};
   const int tiles = cdiv(n, GEMM_BM);
   const char* one = getenv("MUSED_SIL_SLICES");  // "1": no column slices (diagnostic; the workspace is sized for the default)
-  const int slices = (one && one[0] == '1' && one[1] == 0) ? 1 : sil_slices(tiles);
+  const int slices = (one && one[0] == '1' && one[1] == 0) ? 1 : col_slices(tiles);
   if ((rc = sil_launch(g, a, vec_ok<double>(w.Xs, lds, 0), tiles, slices, st))) return rc;
   hipLaunchKernelGGL(sil_finish_kernel, dim3(1), dim3(SIL_REDUCE_THREADS), 0, st, samples_out, w.info, (SilInfoOut*)info_out, (int)n);
   MUSED_LAUNCH_CHECK();

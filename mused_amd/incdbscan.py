@@ -37,7 +37,9 @@ _FIRST_CAPACITY = 4096
 
 
 class IncrementalDBSCAN:
-    """eps, min_pts: as DBSCAN's eps, min_samples.  chunk: rows per staging panel of the kernels (a multiple of 128).
+    """eps, min_pts: as DBSCAN's eps, min_samples.  eps="auto": eps is chosen by `matrix_operations.select_eps_on_device` from
+    the rows of the first insert (k = min_pts; the knee of their sorted k-distance curve) and then fixed for the object's life,
+    in sliding and by_value modes alike; `.eps_` is the eps in use (None until chosen).  chunk: rows per staging panel of the kernels (a multiple of 128).
     stream: the kernels run on it (default: the current stream at each insert); an insert returns after they have finished.
 
     max_rows: None (the default: the state only grows, as the reference's use of the class has it), or the most rows to hold: an
@@ -63,7 +65,13 @@ class IncrementalDBSCAN:
     copied to the front whenever the tail runs out."""
 
     def __init__(self, eps=1.0, min_pts=5, chunk=4096, stream=None, max_rows=None, by_value=False):
-        if not (float(eps) > 0.0) or int(min_pts) < 1:
+        self._auto = isinstance(eps, str)
+        if self._auto:
+            if eps != "auto":
+                raise ValueError(f'eps must be a number or "auto", got {eps!r}')
+            if int(min_pts) < 1:
+                raise ValueError("eps must be > 0 and min_pts >= 1")
+        elif not (float(eps) > 0.0) or int(min_pts) < 1:
             raise ValueError("eps must be > 0 and min_pts >= 1")
         if max_rows is not None and int(max_rows) < 1:
             raise ValueError("max_rows must be >= 1")
@@ -74,10 +82,11 @@ class IncrementalDBSCAN:
         self._two = False          # such a delete has happened
         self._find_ws = None
         self.last_delete_info = None   # device mode: {0, clusters, core rows, lost core status, |R|, |B|} of the last delete
-        self.eps, self.min_pts, self.chunk = float(eps), int(min_pts), int(chunk)
+        self.eps, self.min_pts, self.chunk = (None if self._auto else float(eps)), int(min_pts), int(chunk)
+        self.eps_ = self.eps       # the eps in use: the number given, or the one chosen at the first insert (None before it)
         self._stream = stream
         self.n, self.d = 0, None
-        self._host_mode = os.environ.get("MUSED_DBSCAN", "device") == "host" or not self.eps < 1e150
+        self._host_mode = os.environ.get("MUSED_DBSCAN", "device") == "host" or not (self._auto or self.eps < 1e150)
         self._counted = False      # host mode entered through the flag: inserts are counted
         self._host_rows = None
         self._dead = False
@@ -162,6 +171,10 @@ class IncrementalDBSCAN:
                 raise ValueError(f"a window of {rows.shape[0]} rows is larger than max_rows = {self.max_rows}")
             if self.n + rows.shape[0] > self.max_rows:
                 self._delete(self.n + int(rows.shape[0]) - self.max_rows, refit=False)   # (host mode: the insert below refits)
+        if self.eps is None:
+            # eps="auto": chosen from the rows of the FIRST insert, then fixed (a ValueError -- a flat curve, min_pts = 1 or more
+            # than 64 or than the rows, a non-finite row -- leaves the object without an eps and the insert undone)
+            self.eps = self.eps_ = mo.select_eps_on_device(rows, self.min_pts, self._stream)[0]
         n0, n = self.n, self.n + int(rows.shape[0])
         if not self._host_mode and n > MAX_ROWS:
             self._to_host_mode(False)

@@ -992,6 +992,144 @@ def dbscan_launch(X_dev, eps, min_samples, stream=None):
     return labels, info_h
 
 
+# ---- DBSCAN's eps from the data (csrc/kdist.hip; the rule: mused_amd/kdist.py) --------------------------------------------
+# the eps that the last eps="auto" call of perform_dbscan_clustering_on_device chose (None before the first)
+last_chosen_eps = None
+
+
+def _kdist_rows(X, k):
+    """X as an (n, d) fp64 CUDA tensor with unit column stride (uploads and conversions on the current stream), k checked."""
+    import numbers
+
+    import torch
+
+    from . import kdist as _kd
+
+    if isinstance(X, torch.Tensor):
+        Xd = X if X.is_cuda else X.cuda()
+    else:
+        a = np.asarray(X)
+        if a.dtype.kind not in "fiub":
+            raise ValueError("X must be numeric")
+        Xd = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
+    if Xd.dim() != 2 or Xd.shape[0] < 1 or Xd.shape[1] < 1:
+        raise ValueError("X must be (n, d) with n, d >= 1")
+    if Xd.dtype != torch.float64:
+        Xd = Xd.to(torch.float64)
+    if Xd.stride(1) != 1 or Xd.stride(0) < Xd.shape[1]:
+        Xd = Xd.contiguous()
+    n = Xd.shape[0]
+    if not isinstance(k, numbers.Integral) or isinstance(k, bool) or not 1 <= k <= min(n, _kd.MAX_K):
+        raise ValueError(f"k must be an integer in [1, min(n, {_kd.MAX_K})] (n = {n}), got {k!r}")
+    if n > _kd.MAX_ROWS or Xd.shape[1] >= 1 << 20:
+        raise ValueError(f"{n} x {Xd.shape[1]} rows: the device k-distances take at most 2^19 rows "
+                         "(MUSED_KDIST=host runs the NumPy rule at any size)")
+    return Xd, int(k)
+
+
+def _kdist_host() -> bool:
+    """MUSED_KDIST (read at every call): "device" (default) or "host" = the NumPy rule of mused_amd/kdist.py."""
+    return os.environ.get("MUSED_KDIST", "device") == "host"
+
+
+def _kdist_to_host(X):
+    return X.detach().cpu().numpy() if hasattr(X, "detach") else np.asarray(X)
+
+
+def kth_distance_launch(Xd, k, st):
+    """mused_kth_distance enqueued on stream `st` (entered by the caller): (kd2 n fp64 CUDA, SQUARED; info 4 int32 CUDA).
+    Nothing is read."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+
+    n, d = Xd.shape
+    ws = _km_workspace(("kth_distance", n, k, Xd.device, st.cuda_stream), _lib.lib().mused_kth_distance_ws_bytes(n, k), Xd.device)
+    kd2 = torch.empty(n, dtype=torch.float64, device=Xd.device)
+    info = torch.empty(4, dtype=torch.int32, device=Xd.device)
+    _lib.call("mused_kth_distance", _eng.ptr(Xd), n, d, Xd.stride(0), k, _eng.ptr(kd2), _eng.ptr(info), _eng.ptr(ws), ws.numel(),
+              C.c_void_p(st.cuda_stream))
+    return kd2, info
+
+
+def _kdist_raise_nonfinite():
+    raise ValueError("Input contains NaN or infinity.")   # (scikit-learn's check_array text, as mused_amd.dbscan)
+
+
+def kth_neighbor_distances_on_device(X, k, stream=None):
+    """The distance of every row to its k-th nearest row, the row itself counted -- column k - 1 of
+    `NearestNeighbors(n_neighbors=k).fit(X).kneighbors(X)[0]` -- as an n fp64 CUDA tensor (csrc/kdist.hip; the rule and its
+    bound: mused_amd/kdist.py).  X: (n, d) NumPy array or tensor (taken as fp64), n <= 2^19; 1 <= k <= min(n, 64).
+    Raises scikit-learn's ValueError for a non-finite row (the call reads the flag, so it returns after the stream has
+    finished) and ValueError for k outside its range.  MUSED_KDIST=host: the NumPy rule on a host copy, uploaded."""
+    import torch
+
+    from . import kdist as _kd
+
+    if _kdist_host():
+        v = np.sqrt(_kd.kth_sq_distances(_kdist_to_host(X), k))
+        return torch.from_numpy(np.ascontiguousarray(v)).cuda()
+    st = _match_stream(stream)
+    with torch.cuda.stream(st):
+        Xd, k = _kdist_rows(X, k)
+        kd2, info = kth_distance_launch(Xd, k, st)
+        out = torch.sqrt(kd2)
+        flags = int(info.cpu().numpy()[0])
+    if flags & _kd.FLAG_NONFINITE:
+        _kdist_raise_nonfinite()
+    return out
+
+
+def select_eps_on_device(embedding, min_samples, stream=None):
+    """DBSCAN's eps from the sorted k-distance curve of `embedding` (k = min_samples, the row itself counted): the midpoint
+    between the curve's value at its knee and the next larger value, so that no k-th neighbour pair lies on the threshold
+    and the device DBSCAN can use it (mused_amd/kdist.py; csrc/kdist.hip: the pair pass, the sort and the knee all run on
+    the device, one 48-byte read).  Returns (eps, info) with info = {"knee": i*, "next": nxt, "v_knee": v[i*],
+    "v_next": v[nxt], "curve": the sorted curve as an n fp64 CUDA tensor}.
+    embedding: (n, d) NumPy array or tensor, n <= 2^19; 2 <= min_samples <= min(n, 64) in effect: min_samples = 1 gives
+    the flat curve of zeros.  Raises scikit-learn's ValueError for a non-finite row and ValueError for min_samples
+    outside [1, min(n, 64)] and for a flat curve (all k-distances equal).  MUSED_KDIST=host: the NumPy rule."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    from . import kdist as _kd
+
+    if _kdist_host():
+        Xh = _kdist_to_host(embedding)
+        v = np.sort(np.sqrt(_kd.kth_sq_distances(Xh, min_samples)))
+        i, nxt = _kd.knee(v)
+        return float(0.5 * (v[i] + v[nxt])), {"knee": i, "next": nxt, "v_knee": float(v[i]), "v_next": float(v[nxt]),
+                                             "curve": torch.from_numpy(v).cuda()}
+    st = _match_stream(stream)
+    with torch.cuda.stream(st):
+        Xd, k = _kdist_rows(embedding, min_samples)
+        n = Xd.shape[0]
+        kd2, info_k = kth_distance_launch(Xd, k, st)
+        nb = int(_lib.lib().mused_eps_knee_ws_bytes(n))
+        ws = torch.empty(nb, dtype=torch.uint8, device=Xd.device)   # (its head is returned as the curve: not shared)
+        res = torch.empty(64, dtype=torch.uint8, device=Xd.device)  # the knee's 48 bytes | the k-distances' info
+        # (a flagged mused_kth_distance leaves kd2 as allocated; its flag is looked at first, below)
+        _lib.call("mused_eps_knee", _eng.ptr(kd2), n, _eng.ptr(res), _eng.ptr(ws), nb, C.c_void_p(st.cuda_stream))
+        res[48:].copy_(info_k.view(torch.uint8))
+        h = res.cpu().numpy()                                        # ONE read
+        flags_k = int(h[48:52].view(np.int32)[0])
+        h = h[:48]
+    if flags_k & _kd.FLAG_NONFINITE:
+        _kdist_raise_nonfinite()
+    idx, num = h.view(np.int64), h.view(np.float64)
+    flags = int(idx[5])
+    if flags & _kd.FLAG_NONFINITE:
+        _kdist_raise_nonfinite()
+    if flags & _kd.FLAG_FLAT:
+        raise ValueError(_kd.FLAT_TEXT)
+    return float(num[4]), {"knee": int(idx[0]), "next": int(idx[1]), "v_knee": float(num[2]), "v_next": float(num[3]),
+                           "curve": ws[: 8 * n].view(torch.float64)}
+
+
 def perform_dbscan_clustering_on_device(emb, eps=0.5, min_samples=5, stream=None):
     """`perform_dbscan_clustering(emb, eps, min_samples)` with the pair work on the device (csrc/dbscan.hip; the rule and
     its rounding margin: mused_amd/dbscan.py): scikit-learn's labels as int64 NumPy, O(n) device memory beside the rows.
@@ -1001,13 +1139,22 @@ def perform_dbscan_clustering_on_device(emb, eps=0.5, min_samples=5, stream=None
     call uncounted: MUSED_DBSCAN=host (the former path as a whole), rows that are not fp64 (scikit-learn's arithmetic
     follows the dtype), arguments scikit-learn rejects, more than 2^19 rows.
     stream: the kernels run on it behind whatever the current stream holds; the call returns after they have finished (it
-    reads the flags), so `emb` need only stay alive until then."""
+    reads the flags), so `emb` need only stay alive until then.
+    eps="auto": eps is chosen first, by `select_eps_on_device(emb, min_samples)` (the knee of the sorted k-distance curve;
+    it raises for min_samples = 1, a flat curve and non-finite rows), kept in `last_chosen_eps`, and the call goes on with
+    that number."""
     import numbers
     import os
 
     import torch
 
     on_dev = isinstance(emb, torch.Tensor)
+    if isinstance(eps, str):
+        if eps != "auto":
+            raise ValueError(f'eps must be a number or "auto", got {eps!r}')
+        global last_chosen_eps
+        eps, _ = select_eps_on_device(emb, min_samples, stream)
+        last_chosen_eps = eps
 
     def host():
         return perform_dbscan_clustering(emb.cpu().numpy() if on_dev else emb, eps=eps, min_samples=min_samples)
@@ -1155,6 +1302,8 @@ def perform_dbscan_incr_clustering(data, previous_centroids, previous_labels, ep
     from scipy.spatial.distance import cdist
     from sklearn.cluster import DBSCAN
 
+    if isinstance(eps, str):
+        raise ValueError('eps="auto" is chosen on the device (select_eps_on_device); this host helper takes a number')
     if not isinstance(data, np.ndarray):
         data = np.array(data, dtype=np.float32)
     if data.ndim != 2:

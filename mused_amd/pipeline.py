@@ -142,6 +142,10 @@ class StreamPipeline:
         # every window's embedding in window order -- a chain like the one above, on the chain worker, with one window slot
         self._incr = approach == "DBSCAN_incr"
         self._chained = self._mini or self._incr
+        # eps="auto" ("DBSCAN_incr"): the stream's IncrementalDBSCAN chooses eps from the first window's embedding
+        # (matrix_operations.select_eps_on_device) and keeps it: `chosen_eps` once that window has been clustered
+        if isinstance(eps, str) and eps != "auto":
+            raise ValueError(f'eps must be a number or "auto", got {eps!r}')
         self.eps, self.min_samples = eps, min_samples
         # None: the state only grows (main.py:87-91).  A number: IncrementalDBSCAN(max_rows=...), at least one window
         self.dbscan_max_rows = None if dbscan_max_rows is None else int(dbscan_max_rows)
@@ -480,6 +484,12 @@ class StreamPipeline:
             X = np.ascontiguousarray(reduced_host, dtype=np.float64)
         self.km_device_windows += 1
         return self.clusterer.partial_fit(X).labels_
+
+    @property
+    def chosen_eps(self):
+        """The eps the stream's IncrementalDBSCAN runs with ("DBSCAN_incr"; None before its first window and for the other
+        approaches): the number given, or the one eps="auto" chose."""
+        return getattr(self.clusterer, "eps_", None) if self._incr else None
 
     def _dbscan_incr(self, reduced_dev, reduced_host):
         """main.py:87-91: clusterer.insert(reduced).get_cluster_labels(reduced) on the stream's one IncrementalDBSCAN.  Called
@@ -822,6 +832,9 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
     concatenated true labels of main.py:39-40, which repeat rows when step_window_ratio > 1; "processing_time" is then
     the reference's list), and "window_scores", the (K, 7) scores of the K windows from one launch
     (metrics_evaluation.score_windows).
+    `eps="auto"` ("DBSCAN_incr"; the other approaches ignore eps as before): the stream's IncrementalDBSCAN chooses eps from
+    the first window's embedding (matrix_operations.select_eps_on_device, k = min_samples) and keeps it:
+    `results["chosen_eps"]`.
     `n_clusters_range` = (lo, hi): every window chooses its k among lo .. hi by the device silhouette instead of taking it from
     the true labels (`results["chosen_k"]`, one per window; `complete_true_labels` may then be None unless `score`); ValueError
     for "sSVDMC_mini" and "DBSCAN_incr" and under MUSED_KMEANS=host.  `internal_scores=True`: `results["internal_scores"]`, per
@@ -855,6 +868,8 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
         results = dict(results or {})
         results["all_clusters"] = clusters
         results["processing_time"] = (t1 - t0) / 1e9
+    if approach == "DBSCAN_incr" and isinstance(eps, str):
+        results["chosen_eps"] = pipe.chosen_eps
     if n_clusters_range is not None:
         results["chosen_k"] = list(pipe.chosen_k)
     if internal_scores:
@@ -985,6 +1000,8 @@ def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_
     scikit-learn, NOT to the package, hence opt-in); `sklearn`: scikit-learn's estimator on a host copy.  Returns `results` with the labels ("all_clusters") and the wall time
     ("processing_time"), like process_streaming_data.  `timings`: see batch_embedding (plus "clustering" and "edges").
     `score=True`: `results` also receives what the reference's compute_all_metrics appends (main.py:165).
+    `eps="auto"` ("DBSCAN_batch"): eps is chosen from the embedding by matrix_operations.select_eps_on_device (k = min_samples)
+    and stored as `results["chosen_eps"]`.
     `partition_scores=True`: `results["partition_scores"]`, as for process_streaming_data."""
     if approach not in BATCH_APPROACHES:
         raise ValueError(f"approach {approach!r} is not a batch approach {BATCH_APPROACHES}")
@@ -1011,6 +1028,11 @@ def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_
         clusters = mo.perform_hdbscan_clustering(emb.cpu().numpy(), min_cluster_size=min_cluster_size,
                                                  min_samples=min_samples)
     elif approach == "DBSCAN_batch":
+        chosen_eps = None
+        if isinstance(eps, str):   # "auto": chosen from the embedding (matrix_operations.select_eps_on_device)
+            if eps != "auto":
+                raise ValueError(f'eps must be a number or "auto", got {eps!r}')
+            eps = chosen_eps = mo.select_eps_on_device(emb, min_samples)[0]
         clusters = mo.perform_dbscan_clustering_on_device(emb, eps=eps, min_samples=min_samples)
     elif k_range is not None:
         n_clusters, clusters, _ = mo.select_n_clusters_on_device(emb, range(k_range[0], k_range[1] + 1), seed)
@@ -1035,6 +1057,8 @@ def process_batch_data(results, data_modalities, modality_types, reduced_dim, k_
         results = dict(results or {})
         results["all_clusters"] = np.asarray(clusters)
         results["processing_time"] = (t_end - t0) / 1e9
+    if approach == "DBSCAN_batch" and chosen_eps is not None:
+        results["chosen_eps"] = chosen_eps
     if k_range is not None:
         results["chosen_k"] = [int(n_clusters)]
     if scores is not None:
