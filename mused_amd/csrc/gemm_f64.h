@@ -62,7 +62,37 @@ struct GemmArgs {
             // mirrors the 28 above it: 36 + 64 + 36 of 4 x 64 block products for a 2 x 2 grid of tiles.  Callers set 0 / 1;
             // the launcher turns 1 into 2 (diagonal tiles as described) unless MUSED_GEMM_SYM_DIAG=0 (1: diagonal tiles
             // run the ordinary main loop).  Bit for bit the full product either way.
+  // Optional second row segment of an operand built from sketch buffers (TAIL instantiations of the kernel only: launches
+  // with tail == null run the kernels they always ran).  Row r of entry z of such an operand, nk = tail_split[z * tail_split_stride]:
+  //   r < nk                    the operand's own row r, as ever
+  //   nk <= r < nk + tail_pend  row r - nk of the lane's tail: tail + (z / tail_per) * tail_stride, the operand's row pitch
+  //   r >= nk + tail_pend       +0.0, whatever the operand holds there: read from tail_zero, a row of the operand's length that
+  //                             holds +0.0 (a select behind the loads would make every K step wait for them)
+  // Which operands: both of a launch with two K-contiguous operands (the Gram: their M / N rows split), the K-rows operand B
+  // ([K][N]: its k rows split) of a launch with A K-contiguous.  The launchers refuse a tail on anything else.
+  // Tile order, K order and MFMA sequence are the plain kernel's: the staged doubles are those of the materialised operand.
+  const double* tail;
+  long tail_stride;
+  int tail_per;
+  const int* tail_split;
+  int tail_split_stride;
+  int tail_pend;
+  const double* tail_zero;
 };
+
+// the split of one batch entry (TAIL kernels): rows [nk, nend) come from `tail`, rows from nend on are zero
+struct GemmSplit {
+  const double* tail;
+  const double* zero;
+  int nk, nend;
+};
+// Row r of a split operand: where it starts, and whether it is a zero row (r >= nend or r >= nrows: the address is then
+// that of the row of zeros).
+__device__ __forceinline__ const double* split_row(const double* __restrict__ base, long ld, const GemmSplit& sp, int r, int nrows,
+                                                   bool& zero) {
+  zero = r >= sp.nend || r >= nrows;
+  return zero ? sp.zero : (r < sp.nk ? base + (long)r * ld : sp.tail + (long)(r - sp.nk) * ld);
+}
 
 // ---- staging -------------------------------------------------------------
 // K-contiguous operand: tile rows [r0, r0+128), k in [k0, k0+16).  Thread t owns
@@ -185,6 +215,40 @@ __device__ __forceinline__ void stage_load_mc_full(const TIn* __restrict__ src, 
   stage_load8(src + (long)(k0 + (threadIdx.x >> 4)) * ld + c0 + (threadIdx.x & 15) * 8, r);
 }
 
+// Split operands (GemmSplit): the row a thread stages is given by its address (null: a zero row).
+template <bool VEC>
+__device__ __forceinline__ void stage_load_kc_row(const double* __restrict__ prow, int k0, int kend, double (&r)[8]) {
+  const int k = k0 + (threadIdx.x >> 7) * 8;
+  if (prow) {
+    const double* p = prow + k;
+    if (VEC && k + 8 <= kend) {
+      stage_load8(p, r);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) r[j] = (k + j < kend) ? p[j] : 0.0;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = 0.0;
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void stage_load_mc_row(const double* __restrict__ prow, int c0, int ncols, double (&r)[8]) {
+  const int c = c0 + (threadIdx.x & 15) * 8;
+  if (prow) {
+    const double* p = prow + c;
+    if (VEC && c + 8 <= ncols) {
+      stage_load8(p, r);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) r[j] = (c + j < ncols) ? p[j] : 0.0;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = 0.0;
+  }
+}
+
 // XCD-aware workgroup id: blocks b and b+8 share an XCD (observed round-robin
 // dispatch; speed only).  Give every XCD a contiguous run of tiles so that
 // neighbouring tiles (same A rows) hit the same L2.  Bijective for any nwg.
@@ -197,10 +261,11 @@ __device__ __forceinline__ int xcd_remap(int pid, int nwg) {
 // One 128 x 128 output tile: K loop of the workgroup (staging through LDS, MFMA), result left in the accumulators.
 // C/D map of v_mfma_f64_16x16x4_f64 inside the wave's 64 x 64 block: acc[i][j][r] is the element
 //   row = wr * 64 + i * 16 + (lane >> 4) + 4 * r,   col = wc * 64 + j * 16 + (lane & 15)      (wr = wave >> 1, wc = wave & 1).
-template <typename TA, typename TB, bool A_KC, bool B_KC, bool VEC>
+// TAIL: operands with a second row segment (GemmArgs::tail, doubles only); `sp` is the entry's split.
+template <typename TA, typename TB, bool A_KC, bool B_KC, bool VEC, bool TAIL = false>
 __device__ __forceinline__ void gemm_tile_mainloop(const GemmArgs& g, const TA* __restrict__ A, const TB* __restrict__ B,
                                                    int m0, int n0, int k_lo, int k_hi, double* smem,
-                                                   v4f64 (&acc)[4][4]) {
+                                                   v4f64 (&acc)[4][4], const GemmSplit& sp = GemmSplit{}) {
   double* As = smem;                                 // [2][BK][LD]
   double* Bs = smem + 2 * GEMM_BK * GEMM_LD;         // [2][BK][LD]
   const int lane = threadIdx.x & 63;
@@ -217,8 +282,45 @@ __device__ __forceinline__ void gemm_tile_mainloop(const GemmArgs& g, const TA* 
   const int nkt = (k_hi - k_lo + GEMM_BK - 1) / GEMM_BK;
 
   const bool full_mn = VEC && m0 + GEMM_BM <= g.M && n0 + GEMM_BN <= g.N;  // (uniform over the workgroup)
+  // TAIL: a K-contiguous split operand gives every thread one row for the whole K loop (pa / pb; za / zb: it is a zero row,
+  // which the steps that are not full stage without loading); a K-rows split operand gives it another row every K step
+  const double *pa = nullptr, *pb = nullptr;
+  bool za = false, zb = false;
+  constexpr bool split_a = TAIL && A_KC && B_KC;  // (B always splits; which operands split is fixed by the layouts: GemmArgs::tail)
+  if constexpr (TAIL) {
+    static_assert(!TAIL || (std::is_same<TA, double>::value && std::is_same<TB, double>::value), "split operands are doubles");
+    if (split_a) pa = split_row((const double*)A, g.lda, sp, m0 + (threadIdx.x & 127), g.M, za);
+    if (B_KC) pb = split_row((const double*)B, g.ldb, sp, n0 + (threadIdx.x & 127), g.N, zb);
+  }
   auto load_tile = [&](int kt) {
     const int k0 = k_lo + kt * GEMM_BK;
+    if constexpr (TAIL) {
+      double(&da)[8] = (double(&)[8])ra;
+      double(&db)[8] = (double(&)[8])rb;
+      // one uniform branch, as below: no conditional region between the loads of a full step
+      if (VEC && k0 + GEMM_BK <= k_hi && (split_a || m0 + GEMM_BM <= g.M) && (B_KC || n0 + GEMM_BN <= g.N)) {
+        if constexpr (split_a) stage_load8(pa + k0 + (threadIdx.x >> 7) * 8, da);
+        else if constexpr (A_KC) stage_load_kc_full<TA>(A, g.lda, m0, k0, ra);
+        else stage_load_mc_full<TA>(A, g.lda, m0, k0, ra);
+        if constexpr (B_KC) {
+          stage_load8(pb + k0 + (threadIdx.x >> 7) * 8, db);
+        } else {
+          const double* p = split_row((const double*)B, g.ldb, sp, k0 + (threadIdx.x >> 4), k_hi, zb);
+          stage_load8(p + n0 + (threadIdx.x & 15) * 8, db);
+        }
+        return;
+      }
+      if constexpr (split_a) stage_load_kc_row<VEC>(za ? nullptr : pa, k0, k_hi, da);
+      else if constexpr (A_KC) stage_load_kc<TA, VEC>(A, g.lda, m0, g.M, k0, k_hi, ra);
+      else stage_load_mc<TA, VEC>(A, g.lda, m0, g.M, k0, k_hi, ra);
+      if constexpr (B_KC) {
+        stage_load_kc_row<VEC>(zb ? nullptr : pb, k0, k_hi, db);
+      } else {
+        const double* p = split_row((const double*)B, g.ldb, sp, k0 + (threadIdx.x >> 4), k_hi, zb);
+        stage_load_mc_row<VEC>(zb ? nullptr : p, n0, g.N, db);
+      }
+      return;
+    }
     if (full_mn && k0 + GEMM_BK <= k_hi) {
       if (A_KC) stage_load_kc_full<TA>(A, g.lda, m0, k0, ra); else stage_load_mc_full<TA>(A, g.lda, m0, k0, ra);
       if (B_KC) stage_load_kc_full<TB>(B, g.ldb, n0, k0, rb); else stage_load_mc_full<TB>(B, g.ldb, n0, k0, rb);
@@ -309,9 +411,9 @@ __device__ __forceinline__ void diag_kstep(const double* __restrict__ a, v4f64 (
 
 // K loop of a diagonal tile: as gemm_tile_mainloop with one operand.  Every computed element is the same chain as there
 // (K steps of 16 ascending, four MFMAs per step in kk order, from +0.0).
-template <typename TA, bool A_KC, bool VEC>
+template <typename TA, bool A_KC, bool VEC, bool TAIL = false>
 __device__ __forceinline__ void gemm_tile_mainloop_diag(const GemmArgs& g, const TA* __restrict__ A, int m0, int k_lo, int k_hi,
-                                                        double* As, int wave, v4f64 (&acc)[9]) {
+                                                        double* As, int wave, v4f64 (&acc)[9], const GemmSplit& sp = GemmSplit{}) {
   const int lane = threadIdx.x & 63;
   const int kq = lane >> 4, li = lane & 15;
 #pragma unroll
@@ -320,8 +422,23 @@ __device__ __forceinline__ void gemm_tile_mainloop_diag(const GemmArgs& g, const
   TA ra[8];
   const int nkt = (k_hi - k_lo + GEMM_BK - 1) / GEMM_BK;
   const bool full_m = VEC && m0 + GEMM_BM <= g.M;  // (uniform over the workgroup)
+  // TAIL: the thread's row of the split operand, as in gemm_tile_mainloop
+  const double* pa = nullptr;
+  bool za = false;
+  constexpr bool split_a = TAIL && A_KC;
+  if constexpr (TAIL) {
+    if (split_a) pa = split_row((const double*)A, g.lda, sp, m0 + (threadIdx.x & 127), g.M, za);
+  }
   auto load_tile = [&](int kt) {
     const int k0 = k_lo + kt * GEMM_BK;
+    if constexpr (TAIL) {
+      if constexpr (split_a) {
+        double(&da)[8] = (double(&)[8])ra;
+        if (VEC && k0 + GEMM_BK <= k_hi) stage_load8(pa + k0 + (threadIdx.x >> 7) * 8, da);
+        else stage_load_kc_row<VEC>(za ? nullptr : pa, k0, k_hi, da);
+        return;
+      }
+    }
     if (full_m && k0 + GEMM_BK <= k_hi) {
       if (A_KC) stage_load_kc_full<TA>(A, g.lda, m0, k0, ra); else stage_load_mc_full<TA>(A, g.lda, m0, k0, ra);
       return;
@@ -431,7 +548,7 @@ inline int gemm_sym_diag_enabled() {
 }
 
 // Epilogue concept:  void operator()(int batch, int row, int col, double v) const
-template <typename TA, typename TB, bool A_KC, bool B_KC, bool VEC, typename Epi>
+template <typename TA, typename TB, bool A_KC, bool B_KC, bool VEC, typename Epi, bool TAIL = false>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_f64_kernel(GemmArgs g, Epi epi) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
 
@@ -491,11 +608,19 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_f64_kernel(GemmArgs g, E
     }
   }
 
+  GemmSplit sp{};
+  if constexpr (TAIL) {
+    sp.nk = g.tail_split[(long)zb * g.tail_split_stride];
+    sp.nend = sp.nk + g.tail_pend;
+    sp.tail = g.tail + (long)(zb / g.tail_per) * g.tail_stride;
+    sp.zero = g.tail_zero;
+  }
+
   if constexpr (std::is_same<TA, TB>::value && A_KC == B_KC) {
     if (g.sym == 2 && tm == tn) {  // (uniform over the workgroup)
       const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
       v4f64 acc9[9];
-      gemm_tile_mainloop_diag<TA, A_KC, VEC>(g, A, m0, k_lo, k_hi, smem, w, acc9);
+      gemm_tile_mainloop_diag<TA, A_KC, VEC, TAIL>(g, A, m0, k_lo, k_hi, smem, w, acc9, sp);
       // behind the main loop's last barrier every wave is done with the operand buffers: the patches may overwrite them
       switch (w) {
         case 0: diag_epilogue<0>(g, epi, z, m0, smem, acc9); break;
@@ -513,7 +638,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_f64_kernel(GemmArgs g, E
   const int kq = lane >> 4, li = lane & 15;
 
   v4f64 acc[4][4];
-  gemm_tile_mainloop<TA, TB, A_KC, B_KC, VEC>(g, A, B, m0, n0, k_lo, k_hi, smem, acc);
+  gemm_tile_mainloop<TA, TB, A_KC, B_KC, VEC, TAIL>(g, A, B, m0, n0, k_lo, k_hi, smem, acc, sp);
 
   // C/D map of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 * reg
 #pragma unroll
@@ -576,32 +701,32 @@ struct EpiStore {
   }
 };
 
-template <typename TA, typename TB, bool A_KC, bool B_KC, bool VEC, typename Epi>
+template <typename TA, typename TB, bool A_KC, bool B_KC, bool VEC, typename Epi, bool TAIL = false>
 int gemm_f64_prepare_t() {
   // > 64 KiB of dynamic LDS needs the attribute once per kernel; done outside stream capture.  Several host
   // threads drive the library (sketch groups + the main path): one-time, thread-safe.
   static LdsOptIn opt;
-  auto k = gemm_f64_kernel<TA, TB, A_KC, B_KC, VEC, Epi>;
+  auto k = gemm_f64_kernel<TA, TB, A_KC, B_KC, VEC, Epi, TAIL>;
   const hipError_t err = allow_dynamic_lds(opt, reinterpret_cast<const void*>(k), GEMM_LDS_BYTES);
   MUSED_CHECK_HIP(err);
   return MUSED_OK;
 }
 
-template <typename TA, typename TB, bool A_KC, bool B_KC, typename Epi>
+template <typename TA, typename TB, bool A_KC, bool B_KC, typename Epi, bool TAIL = false>
 int gemm_f64_launch_t(GemmArgs g, int batch, Epi epi, bool vec, hipStream_t stream) {
   g.tiles_m = cdiv(g.M, GEMM_BM);
   g.tiles_n = cdiv(g.N, GEMM_BN);
-  if (g.sym) g.sym = gemm_sym_diag_enabled() ? 2 : 1;
+  if (g.sym) g.sym = (g.sym != 3 && gemm_sym_diag_enabled()) ? 2 : 1;  // (3: the caller asks for ordinary diagonal tiles)
   if (g.M <= 0 || g.N <= 0 || batch <= 0) return MUSED_OK;
   dim3 grid(g.sym ? g.tiles_n * (g.tiles_n + 1) / 2 : g.tiles_m * g.tiles_n, 1, batch);
   int rc;
   if (vec) {
-    if ((rc = gemm_f64_prepare_t<TA, TB, A_KC, B_KC, true, Epi>())) return rc;
-    hipLaunchKernelGGL((gemm_f64_kernel<TA, TB, A_KC, B_KC, true, Epi>), grid, dim3(GEMM_THREADS), GEMM_LDS_BYTES,
+    if ((rc = gemm_f64_prepare_t<TA, TB, A_KC, B_KC, true, Epi, TAIL>())) return rc;
+    hipLaunchKernelGGL((gemm_f64_kernel<TA, TB, A_KC, B_KC, true, Epi, TAIL>), grid, dim3(GEMM_THREADS), GEMM_LDS_BYTES,
                        stream, g, epi);
   } else {
-    if ((rc = gemm_f64_prepare_t<TA, TB, A_KC, B_KC, false, Epi>())) return rc;
-    hipLaunchKernelGGL((gemm_f64_kernel<TA, TB, A_KC, B_KC, false, Epi>), grid, dim3(GEMM_THREADS), GEMM_LDS_BYTES,
+    if ((rc = gemm_f64_prepare_t<TA, TB, A_KC, B_KC, false, Epi, TAIL>())) return rc;
+    hipLaunchKernelGGL((gemm_f64_kernel<TA, TB, A_KC, B_KC, false, Epi, TAIL>), grid, dim3(GEMM_THREADS), GEMM_LDS_BYTES,
                        stream, g, epi);
   }
   MUSED_LAUNCH_CHECK();

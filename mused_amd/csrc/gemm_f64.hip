@@ -23,12 +23,26 @@ int gemm_f64_prepare_all() {
   PREP(true, true, true); PREP(true, true, false); PREP(true, false, true); PREP(true, false, false);
   PREP(false, true, true); PREP(false, true, false); PREP(false, false, true); PREP(false, false, false);
 #undef PREP
+#define PREP(a, b, v) rc |= gemm_f64_prepare_t<double, double, a, b, v, EpiStore, true>()
+  PREP(true, true, true); PREP(true, true, false); PREP(true, false, true); PREP(true, false, false);
+#undef PREP
   return rc ? MUSED_ERR_HIP : MUSED_OK;
+}
+
+// The operands a tail applies to (see GemmTail), checked; vec: whether the tail rows keep the 16-byte loads.
+static int gemm_set_tail(GemmArgs& g, const GemmTail& t, bool a_kc, bool b_kc, long ld, bool& vec) {
+  MUSED_REQUIRE(t.rows && t.split && t.zero_row && t.per_lane >= 1 && t.pend >= 0, "gemm_f64: bad tail");
+  MUSED_REQUIRE(a_kc && (!b_kc || g.sym), "gemm_f64: a tail needs a Gram launch or a K-rows operand B");
+  g.tail = t.rows; g.tail_stride = t.lane_stride; g.tail_per = t.per_lane;
+  g.tail_split = t.split; g.tail_split_stride = t.split_stride; g.tail_pend = t.pend; g.tail_zero = t.zero_row;
+  if (g.sym && t.plain_diag) g.sym = 3;
+  vec = vec && vec_ok<double>(t.rows, ld, t.lane_stride) && vec_ok<double>(t.zero_row, ld, 0);
+  return MUSED_OK;
 }
 
 int gemm_f64(bool a_kc, bool b_kc, const double* A, long lda, long strideA, const double* B, long ldb,
              long strideB, double* C, long ldc, long strideC, int M, int N, int K, int batch, double alpha,
-             hipStream_t stream, const int* rep, const int* list, const int* kact) {
+             hipStream_t stream, const int* rep, const int* list, const int* kact, const GemmTail* tail) {
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   g.A = A; g.B = B; g.lda = lda; g.ldb = ldb; g.strideA = strideA; g.strideB = strideB;
@@ -37,7 +51,13 @@ int gemm_f64(bool a_kc, bool b_kc, const double* A, long lda, long strideA, cons
   // Gram products (A A^T: same operand, same layout, square result): tiles on or above the diagonal + mirrored stores
   g.sym = (A == B && a_kc == b_kc && lda == ldb && strideA == strideB && M == N) ? 1 : 0;
   EpiStore epi{C, ldc, strideC, alpha};
-  const bool vec = vec_ok<double>(A, lda, strideA) && vec_ok<double>(B, ldb, strideB);
+  bool vec = vec_ok<double>(A, lda, strideA) && vec_ok<double>(B, ldb, strideB);
+  if (tail) {
+    int rc;
+    if ((rc = gemm_set_tail(g, *tail, a_kc, b_kc, ldb, vec))) return rc;
+    if (b_kc) return gemm_f64_launch_t<double, double, true, true, EpiStore, true>(g, batch, epi, vec, stream);
+    return gemm_f64_launch_t<double, double, true, false, EpiStore, true>(g, batch, epi, vec, stream);
+  }
   if (a_kc && b_kc) return gemm_f64_launch_t<double, double, true, true>(g, batch, epi, vec, stream);
   if (a_kc && !b_kc) return gemm_f64_launch_t<double, double, true, false>(g, batch, epi, vec, stream);
   if (!a_kc && b_kc) return gemm_f64_launch_t<double, double, false, true>(g, batch, epi, vec, stream);
@@ -74,7 +94,7 @@ __global__ void splitk_reduce_kernel(const double* __restrict__ partial, int nsp
 // batch).  For products whose K loop is long and whose tiles do not fill the GPU (sketch Gram matrices at d = 10,000).
 int gemm_f64_batched_splitk(bool a_kc, bool b_kc, const double* A, long lda, long strideA, const double* B, long ldb, long strideB,
                             double* partial, int M, int N, int K, int batch, int kchunk, int nsplit, hipStream_t stream,
-                            const int* rep, const int* list) {
+                            const int* rep, const int* list, const GemmTail* tail) {
   MUSED_REQUIRE(kchunk > 0 && kchunk % GEMM_BK == 0 && nsplit >= 1 && (long)kchunk * nsplit >= K,
                 "gemm_f64_batched_splitk: bad kchunk %d x %d for K=%d", kchunk, nsplit, K);
   GemmArgs g;
@@ -84,7 +104,13 @@ int gemm_f64_batched_splitk(bool a_kc, bool b_kc, const double* A, long lda, lon
   g.rep = rep; g.list = list;
   g.sym = (A == B && a_kc == b_kc && lda == ldb && strideA == strideB && M == N) ? 1 : 0;
   EpiStore epi{partial, (long)N, (long)M * N, 1.0};
-  const bool vec = vec_ok<double>(A, lda, strideA) && vec_ok<double>(B, ldb, strideB);
+  bool vec = vec_ok<double>(A, lda, strideA) && vec_ok<double>(B, ldb, strideB);
+  if (tail) {
+    int rc;
+    if ((rc = gemm_set_tail(g, *tail, a_kc, b_kc, ldb, vec))) return rc;
+    if (b_kc) return gemm_f64_launch_t<double, double, true, true, EpiStore, true>(g, batch * nsplit, epi, vec, stream);
+    return gemm_f64_launch_t<double, double, true, false, EpiStore, true>(g, batch * nsplit, epi, vec, stream);
+  }
   if (a_kc && b_kc) return gemm_f64_launch_t<double, double, true, true>(g, batch * nsplit, epi, vec, stream);
   if (a_kc && !b_kc) return gemm_f64_launch_t<double, double, true, false>(g, batch * nsplit, epi, vec, stream);
   if (!a_kc && b_kc) return gemm_f64_launch_t<double, double, false, true>(g, batch * nsplit, epi, vec, stream);
@@ -164,6 +190,26 @@ int mused_debug_gemm_f64_batched_active(int a_kc, int b_kc, const double* A, lon
                                         double alpha, const int* list, const int* kact, void* stream) {
   return mused::gemm_f64(a_kc != 0, b_kc != 0, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, M, N, K, batch,
                          alpha, (hipStream_t)stream, nullptr, list, kact);
+}
+
+// The same with a second row segment (GemmTail in internal.h) for the operands built from sketch buffers; nsplit > 1: the
+// batched split-K launch and its reduction (partial: batch x nsplit x M x N doubles), kact then unused.
+int mused_debug_gemm_f64_batched_tail(int a_kc, int b_kc, const double* A, long lda, long strideA, const double* B, long ldb,
+                                      long strideB, double* C, long ldc, long strideC, int M, int N, int K, int batch,
+                                      const int* list, const int* kact, const double* tail, long tail_stride, int per_lane,
+                                      const int* split, int split_stride, int pend, const double* zero_row, int plain_diag, double* partial,
+                                      int kchunk,
+                                      int nsplit, void* stream) {
+  MUSED_REQUIRE(A && B && C && tail && split && batch >= 1, "mused_debug_gemm_f64_batched_tail: bad arguments");
+  const mused::GemmTail t{tail, tail_stride, per_lane, split, split_stride, pend, zero_row, plain_diag};
+  if (nsplit <= 1)
+    return mused::gemm_f64(a_kc != 0, b_kc != 0, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, M, N, K, batch, 1.0,
+                           (hipStream_t)stream, nullptr, list, kact, &t);
+  MUSED_REQUIRE(partial && ldc == N && strideC == (long)M * N, "mused_debug_gemm_f64_batched_tail: split-K writes a dense C");
+  int rc = mused::gemm_f64_batched_splitk(a_kc != 0, b_kc != 0, A, lda, strideA, B, ldb, strideB, partial, M, N, K, batch, kchunk,
+                                          nsplit, (hipStream_t)stream, nullptr, list, &t);
+  if (rc != MUSED_OK) return rc;
+  return mused::gemm_batched_splitk_reduce(partial, nsplit, (long)M * N, C, batch, nullptr, (hipStream_t)stream, list);
 }
 
 int mused_gemm_f64_splitk(int a_kc, int b_kc, const double* A, long lda, const double* B, long ldb, double* partial,

@@ -59,9 +59,24 @@ inline hipError_t allow_dynamic_lds(hipError_t before, LdsOptIn& s, const void* 
 
 // C[z] = alpha * opA(A[z]) * opB(B[z]); fp64 in / fp64 out, MFMA f64 16x16x4.
 //   a_kc: A stored [M][K] (true) or [K][M] (false);  b_kc: B stored [N][K] (true) or [K][N] (false).
+// A second row segment for operands built from sketch buffers (GemmArgs::tail in gemm_f64.h): with nk = split[z * split_stride],
+// row r of entry z is the operand's row r below nk, row r - nk of rows + (z / per_lane) * lane_stride (the operand's pitch) below
+// nk + pend, and +0.0 from there on (read from zero_row: as many doubles of +0.0 as an operand row is long).  It applies to both operands of a Gram launch (A == B, both K-contiguous) and to the
+// K-rows operand B of an (a_kc, !b_kc) launch; other launches refuse it.
+struct GemmTail {
+  const double* rows;
+  long lane_stride;
+  int per_lane;
+  const int* split;
+  int split_stride;
+  int pend;
+  const double* zero_row;
+  int plain_diag;  // 1: the diagonal tiles of this (Gram) launch run the ordinary main loop, as under MUSED_GEMM_SYM_DIAG=0 (tests)
+};
 int gemm_f64(bool a_kc, bool b_kc, const double* A, long lda, long strideA, const double* B, long ldb,
              long strideB, double* C, long ldc, long strideC, int M, int N, int K, int batch, double alpha,
-             hipStream_t stream, const int* rep = nullptr, const int* list = nullptr, const int* kact = nullptr);
+             hipStream_t stream, const int* rep = nullptr, const int* list = nullptr, const int* kact = nullptr,
+             const GemmTail* tail = nullptr);
 // rep (device, batch ints, optional): entry z is computed only when rep[z] == z (duplicates are skipped)
 // list (device, 1 + batch ints, optional, instead of rep): the entries to compute, compacted -- list[0] of them, list[1 ..];
 //   workgroup z of the batch takes entry list[1 + z], so the workgroups with nothing to do are dispatched last
@@ -71,7 +86,7 @@ int gemm_f64(bool a_kc, bool b_kc, const double* A, long lda, long strideA, cons
 // batched split-K (see gemm_f64.hip): partial results per (entry, split), then the fixed-order sum
 int gemm_f64_batched_splitk(bool a_kc, bool b_kc, const double* A, long lda, long strideA, const double* B, long ldb, long strideB,
                             double* partial, int M, int N, int K, int batch, int kchunk, int nsplit, hipStream_t stream,
-                            const int* rep = nullptr, const int* list = nullptr);
+                            const int* rep = nullptr, const int* list = nullptr, const GemmTail* tail = nullptr);
 int gemm_batched_splitk_reduce(const double* partial, int nsplit, long count, double* out, int batch, const int* rep,
                                hipStream_t stream, const int* list = nullptr);
 // Sets the dynamic-LDS attribute of every plain GEMM instantiation (call before stream capture).

@@ -41,7 +41,18 @@ struct Swfd {
   // nk + pend), settle / scatter (clear up to the rows in use before the rotation).  import_half and begin_epoch with a
   // blob copy bytes nobody has checked: they set `tail_dirty`, and the next rotation clears up to row n2.  mused_fd_rotate
   // declares all n2 rows in use.  A frozen MAIN level (rep < 0) is outside the invariant until AUX replaces it.
+  // SHARED PENDING ROWS (round 10; `shared`).  All 2L sketches of a lane see the same pending rows: they are kept once per lane
+  // in `pendbuf` and in no sketch buffer.  A live sketch's buffer then holds its kept rows in [0, nk); its rows from nk on are
+  // UNSPECIFIED and no kernel reads them: every reader takes row r of a sketch as buf row r below nk, pendbuf row r - nk below
+  // nk + pend and +0.0 from there on (the GEMM operands: GemmTail; swfd_stack_kernel; swfd_export_rows_kernel).  A frozen MAIN
+  // level still receives the raw rows in its own buffer, and when it freezes the rotation writes its pending rows and its
+  // zero tail out once (swfd_settle_shared_kernel), so its buffer is byte for byte the one of the other mode.
   double* buf;         // S x n2 x d
+  double* pendbuf;     // lanes x l x d   row j of a lane: the j-th pending row of its current block, converted as row_copy does;
+                       //                 one row of +0.0 behind them (the zero row of the GEMM operands)
+  bool shared;         // pending rows live in pendbuf only (settle on, no pre-rotation, MUSED_SWFD_SHARED != 0)
+  int* froze;          // S         shared: 1 = the rotation under way is the one that freezes this MAIN level (swfd_rep_kernel)
+  int* nk0;            // S         shared: kept rows before the rotation under way (swfd_decide_kernel): the split of the rotate product
   bool tail_dirty;     // rows beyond nk + pend may hold anything (an imported blob): the next rotation clears to row n2
   bool settle;         // one settle kernel after the rotate product (scatter + the next block's append); MUSED_SWFD_SETTLE=0: off
   int* used;           // S         rows in use before the rotation under way (old nk + pend), left by swfd_decide_kernel; null: settle off
@@ -153,10 +164,26 @@ __global__ void swfd_append_kernel(const T* __restrict__ X, long ldx, long lane_
   row_copy<T>(buf + ((long)s * n2 + row) * d, X + (long)r * ldx, d);
 }
 
+// Shared mode: the rows go to [pend, pend + m) of the lane's pendbuf once (the workgroups of the lane's first sketch), and into
+// the buffer of every frozen MAIN level as swfd_append_kernel puts them.
+template <typename T>
+__global__ void swfd_append_shared_kernel(const T* __restrict__ X, long ldx, long lane_stride, int per_lane, int m, int d,
+                                          int n2, int ell, int pend, const int* __restrict__ meta, const int* __restrict__ rep,
+                                          double* __restrict__ buf, double* __restrict__ pendbuf) {
+  const int r = blockIdx.x, s = blockIdx.y;
+  const int lane = s / per_lane;
+  const T* src = X + (long)lane * lane_stride + (long)r * ldx;
+  if (s == lane * per_lane && pend + r < ell) row_copy<T>(pendbuf + ((long)lane * ell + pend + r) * d, src, d);
+  if (rep && rep[s] < 0) {
+    const int row = meta[s * 4 + 0] + pend + r;
+    if (row < n2) row_copy<T>(buf + ((long)s * n2 + row) * d, src, d);
+  }
+}
+
 // epoch start: MAIN <- AUX, AUX <- empty  (sketch index = kind * L + level)
 __global__ void swfd_restart_kernel(double* __restrict__ buf, double* __restrict__ queue, long long* __restrict__ qt,
                                     int* __restrict__ meta, long long* __restrict__ dropped, int L, long buf_elems,
-                                    long queue_elems, int cap) {
+                                    long queue_elems, int cap, int* __restrict__ live) {
   const int lane = blockIdx.y / L, j = blockIdx.y - lane * L;
   const int sm = lane * 2 * L + j, sa = sm + L;
   const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -173,6 +200,7 @@ __global__ void swfd_restart_kernel(double* __restrict__ buf, double* __restrict
     }
     dropped[sm] = dropped[sa];
     dropped[sa] = 0;
+    if (live) live[sm] = sm;  // (shared mode: MAIN is no longer frozen -- rep is read between rotations there)
   }
 }
 
@@ -211,13 +239,15 @@ __global__ __launch_bounds__(1024) void swfd_rep_kernel(const int* __restrict__ 
                                                         int twin, const long long* __restrict__ dropped, long long epoch_start,
                                                         int skip_dead, long long* __restrict__ now_dev, long long now, int pend,
                                                         int ell, int n2, int* __restrict__ list, int* __restrict__ offs,
-                                                        int* __restrict__ kact, long long* __restrict__ ostat, int oround) {
+                                                        int* __restrict__ kact, long long* __restrict__ ostat, int oround,
+                                                        int* __restrict__ froze) {
   extern __shared__ int s_key[];  // [S] rows in use of a representative, -1 for every other sketch
   __shared__ int s_hist[17];
   const int t = threadIdx.x, S = nchains * L;
   if (t == 0) *now_dev = now;  // (the rotation's time stamp: one launch less than a kernel of its own)
   if (t < 17) s_hist[t] = 0;
   auto put = [&](int s, int r) {
+    if (froze) froze[s] = (r < 0 && rep[s] >= 0) ? 1 : 0;  // (frozen by this rotation: was live at the last one)
     rep[s] = r;
     const int na = meta[s * 4 + 0] + pend;
     s_key[s] = (r == s) ? (na < n2 ? na : n2) : -1;
@@ -278,7 +308,7 @@ __global__ __launch_bounds__(1024) void swfd_decide_kernel(const double* __restr
                                                           long long* __restrict__ qt, long long* __restrict__ dropped,
                                                           int* __restrict__ plan, int* __restrict__ keep_src,
                                                           double* __restrict__ Wc, const int* __restrict__ rep,
-                                                          int* __restrict__ used, int pend) {
+                                                          int* __restrict__ used, int pend, int* __restrict__ nk0) {
   __shared__ double lam[1024];
   __shared__ int order[1024];
   __shared__ double scale[512];  // sqrt(s2 / lam) of the top-l rows (0 = discarded)
@@ -386,6 +416,7 @@ __global__ __launch_bounds__(1024) void swfd_decide_kernel(const double* __restr
   if (t == 0) {
     // (the rows in use before this rotation: the settle kernel clears the buffer up to there and no further)
     if (used) used[s] = min(n2, meta[s * 4 + 0] + pend);
+    if (nk0) nk0[s] = meta[s * 4 + 0];
     meta[s * 4 + 0] = nk;
     meta[s * 4 + 1] = (head1 + nevict) % cap;
     meta[s * 4 + 2] = cnt1 + nd - nevict;
@@ -463,6 +494,44 @@ __global__ void swfd_settle_kernel(const double* __restrict__ T, const int* __re
   }
 }
 
+// The settle kernel of the shared mode: kept rows and dumped rows as above; the call's next nxt rows once per lane into
+// pendbuf[0, nxt) (the workgroups of the lane's first sketch); no raw row and no zero into a live sketch's buffer.
+// A frozen MAIN level gets the next rows behind its kept rows as above.  The rotation that freezes it (froze[s]) also writes
+// out what the buffer of the other mode holds at that moment: the pend0 pending rows of this rotation (rows >= nxt of them: the
+// first nxt are overwritten by the next block in either mode; pendbuf rows >= nxt are not written by this launch) and +0.0
+// behind them up to row n2 -- unless the tail is an imported blob's (fill_all), which the other mode leaves alone as well.
+template <typename Src>
+__global__ void swfd_settle_shared_kernel(const double* __restrict__ T, const int* __restrict__ plan,
+                                          const int* __restrict__ keep_src, const int* __restrict__ meta,
+                                          const int* __restrict__ froze, int fill_all, double* __restrict__ buf,
+                                          double* __restrict__ queue, double* __restrict__ pendbuf, int n2, int ell, int cap, int d,
+                                          const int* __restrict__ rep, const Src* __restrict__ X, long ldx, long lane_stride,
+                                          int per_lane, int nxt, int pend0) {
+  const int rho = blockIdx.x, s = blockIdx.y;
+  const int lane = s / per_lane;
+  const int sr = rep ? rep[s] : s;
+  const int nk = meta[s * 4 + 0];
+  if (s == lane * per_lane && rho < nxt)
+    row_copy<Src>(pendbuf + ((long)lane * ell + rho) * d, X + (long)lane * lane_stride + (long)rho * ldx, d);
+  if (sr < 0) {
+    if (nk + rho >= n2) return;
+    double* dst = buf + ((long)s * n2 + nk + rho) * d;
+    if (rho < nxt) {
+      row_copy<Src>(dst, X + (long)lane * lane_stride + (long)rho * ldx, d);
+    } else if (froze[s]) {
+      if (rho < pend0) row_copy<double>(dst, pendbuf + ((long)lane * ell + rho) * d, d);
+      else if (!fill_all) row_zero(dst, d);
+    }
+    return;
+  }
+  const double* Ts = T + (long)sr * ell * d;
+  if (rho < ell && plan[(s * ell + rho) * 2] == 2) {
+    const int slot = plan[(s * ell + rho) * 2 + 1];
+    row_copy<double>(queue + ((long)s * cap + slot) * d, Ts + (long)rho * d, d);
+  }
+  if (rho < nk) row_copy<double>(buf + ((long)s * n2 + rho) * d, Ts + (long)keep_src[s * ell + rho] * d, d);
+}
+
 // One rotation of all sketches.  (next, nxt): the first nxt rows of the block that follows in the same append call (row pitch
 // ldx, lanes lane_stride apart), which the settle kernel puts behind the kept rows; nxt = 0: none.  Leaves pend = 0: the
 // caller counts the nxt rows when its loop reaches them.
@@ -473,28 +542,36 @@ static int swfd_rotate_all(Swfd* h, hipStream_t st, const Src* next, long ldx, l
   if (h->rep)
     hipLaunchKernelGGL(swfd_rep_kernel, dim3(1), dim3(1024), sizeof(int) * (size_t)S, st, h->meta, h->L, 2 * h->lanes, h->rep,
                        h->twin ? 1 : 0, h->dropped, (long long)(((h->i - 1) / h->N) * h->N), h->skip_dead, h->now_dev,
-                       (long long)h->i, h->pend, ell, n2, h->list, h->offs, h->kact, h->ostat, h->oround);
+                       (long long)h->i, h->pend, ell, n2, h->list, h->offs, h->kact, h->ostat, h->oround, h->froze);
   else
     hipLaunchKernelGGL(swfd_set_now_kernel, dim3(1), dim3(1), 0, st, h->now_dev, (long long)h->i);
+  // shared mode: rows [nk, nk + pend) of every operand built from a sketch buffer are the lane's pendbuf rows
+  const GemmTail gram_tail{h->pendbuf, (long)ell * d, 2 * h->L, h->meta, 4, h->pend, h->pendbuf + (long)h->lanes * ell * d, 0};
+  const GemmTail rot_tail{h->pendbuf, (long)ell * d, 2 * h->L, h->nk0, 1, h->pend, h->pendbuf + (long)h->lanes * ell * d, 0};
   if (h->gram_split > 1) {
     const int kchunk = ((d + h->gram_split - 1) / h->gram_split + 15) / 16 * 16;
     if ((rc = gemm_f64_batched_splitk(true, true, h->buf, d, (long)n2 * d, h->buf, d, (long)n2 * d, h->gpart, n2, n2, d, S, kchunk,
-                                      h->gram_split, st, h->rep, h->list)))
+                                      h->gram_split, st, h->rep, h->list, h->shared ? &gram_tail : nullptr)))
       return rc;
     if ((rc = gemm_batched_splitk_reduce(h->gpart, h->gram_split, (long)n2 * n2, eig_plan_input(h->eig), S, h->rep, st, h->list)))
       return rc;
   } else if ((rc = gemm_f64(true, true, h->buf, d, (long)n2 * d, h->buf, d, (long)n2 * d, eig_plan_input(h->eig), n2,
-                            (long)n2 * n2, n2, n2, d, S, 1.0, st, h->rep, h->list)))
+                            (long)n2 * n2, n2, n2, d, S, 1.0, st, h->rep, h->list, nullptr, h->shared ? &gram_tail : nullptr)))
     return rc;
   if ((rc = eig_plan_run_inplace(h->eig, nullptr, nullptr, st, true))) return rc;
   const EigColumns e = eig_plan_columns(h->eig);
   hipLaunchKernelGGL(swfd_decide_kernel, dim3(S), dim3(1024), 0, st, e.lam, e.cols, e.ld, n2, ell, h->cap, h->N, h->now_dev,
                      h->theta, h->meta, h->qt, h->dropped, h->plan, h->keep_src, h->Wc, h->rep, h->settle ? h->used : nullptr,
-                     h->pend);
+                     h->pend, h->nk0);
   if ((rc = gemm_f64(true, false, h->Wc, n2, (long)ell * n2, h->buf, d, (long)n2 * d, h->T, d, (long)ell * d, ell, d,
-                     n2, S, 1.0, st, h->rep, h->list, h->kact)))
+                     n2, S, 1.0, st, h->rep, h->list, h->kact, h->shared ? &rot_tail : nullptr)))
     return rc;
-  if (h->settle) {
+  if (h->shared) {
+    hipLaunchKernelGGL(swfd_settle_shared_kernel<Src>, dim3(n2, S), dim3(256), 0, st, h->T, h->plan, h->keep_src, h->meta,
+                       h->froze, h->tail_dirty ? 1 : 0, h->buf, h->queue, h->pendbuf, n2, ell, h->cap, d, h->rep, next, ldx,
+                       lane_stride, 2 * h->L, nxt, h->pend);
+    h->tail_dirty = false;
+  } else if (h->settle) {
     hipLaunchKernelGGL(swfd_settle_kernel<Src>, dim3(n2, S), dim3(256), 0, st, h->T, h->plan, h->keep_src, h->meta, h->used,
                        h->tail_dirty ? 1 : 0, h->buf, h->queue, n2, ell, h->cap, d, h->rep, next, ldx, lane_stride, 2 * h->L,
                        nxt);
@@ -512,7 +589,7 @@ static int swfd_restart(Swfd* h, hipStream_t st) {
   const long be = (long)h->n2 * h->d, qe = (long)h->cap * h->d;
   const long m = be > qe ? be : qe;
   hipLaunchKernelGGL(swfd_restart_kernel, dim3(cdiv(m, 256), h->L * h->lanes), dim3(256), 0, st, h->buf, h->queue, h->qt,
-                     h->meta, h->dropped, h->L, be, qe, h->cap);
+                     h->meta, h->dropped, h->L, be, qe, h->cap, h->shared ? h->rep : nullptr);
   MUSED_LAUNCH_CHECK();
   return MUSED_OK;
 }
@@ -634,6 +711,9 @@ static int swfd_append_t(Swfd* h, const T* X, long ldx, long lane_stride, long m
       hipLaunchKernelGGL(swfd_append_kernel<double>, dim3((int)take, h->S), dim3(256), 0, st, src, (long)h->d,
                          (long)h->ell * h->d, 2 * h->L, (int)take, h->d, h->n2, h->pend, h->meta, h->buf);
       ++pre_next;
+    } else if (h->shared) {
+      hipLaunchKernelGGL(swfd_append_shared_kernel<T>, dim3((int)take, h->S), dim3(256), 0, st, X + r * ldx, ldx, lane_stride,
+                         2 * h->L, (int)take, h->d, h->n2, h->ell, h->pend, h->meta, h->rep, h->buf, h->pendbuf);
     } else {
       hipLaunchKernelGGL(swfd_append_kernel<T>, dim3((int)take, h->S), dim3(256), 0, st, X + r * ldx, ldx, lane_stride,
                          2 * h->L, (int)take, h->d, h->n2, h->pend, h->meta, h->buf);
@@ -687,12 +767,13 @@ __global__ void swfd_select_kernel(const int* __restrict__ meta, const long long
 
 __global__ void swfd_stack_kernel(const int* __restrict__ qsel_all, const double* __restrict__ buf,
                                   const double* __restrict__ queue, int n2, int n4, int cap, int d, int pend,
-                                  double* __restrict__ stack) {
+                                  double* __restrict__ stack, const double* __restrict__ pendbuf, int ell) {
   const int rho = blockIdx.x, lane = blockIdx.y;
   const int* qsel = qsel_all + (long)lane * (4 + cap);
   const int ns = qsel[1], nk = qsel[2], sk = qsel[3];
   const double* src = nullptr;
   if (rho < ns) src = queue + ((long)sk * cap + qsel[4 + rho]) * d;
+  else if (pendbuf && rho >= ns + nk && rho < ns + nk + pend) src = pendbuf + ((long)lane * ell + (rho - ns - nk)) * d;  // shared mode
   else if (rho < ns + nk + pend) src = buf + ((long)sk * n2 + (rho - ns)) * d;
   double* dst = stack + ((long)lane * n4 + rho) * d;
   for (int c = threadIdx.x; c < d; c += blockDim.x) dst[c] = src ? src[c] : 0.0;
@@ -791,7 +872,7 @@ static int swfd_query(Swfd* h, double* outB, double* outSigma, double* outInfo, 
   hipLaunchKernelGGL(swfd_select_kernel, dim3(B), dim3(64), 0, st, h->meta, h->qt, h->dropped, h->L, h->cap, h->N,
                      (long long)h->i, h->qsel);
   hipLaunchKernelGGL(swfd_stack_kernel, dim3(n4, B), dim3(256), 0, st, h->qsel, h->buf, h->queue, h->n2, n4, h->cap, d,
-                     h->pend, h->stack);
+                     h->pend, h->stack, h->shared ? h->pendbuf : nullptr, ell);
   if ((rc = gemm_f64(true, true, h->stack, d, (long)n4 * d, h->stack, d, (long)n4 * d, eig_plan_input(eq), n4,
                      (long)n4 * n4, n4, n4, d, B, 1.0, st)))
     return rc;
@@ -809,6 +890,25 @@ static int swfd_query(Swfd* h, double* outB, double* outSigma, double* outInfo, 
     MUSED_CHECK_HIP(hipMemcpyAsync(outSigma, h->sig_out, sizeof(double) * (size_t)B * ell, hipMemcpyDeviceToDevice, st));
   if (outInfo) MUSED_CHECK_HIP(hipMemcpyAsync(outInfo, h->qinfo, sizeof(double) * 2 * B, hipMemcpyDeviceToDevice, st));
   return MUSED_OK;
+}
+
+// Shared mode, state blobs (single-lane handles).  Export: the buffers were copied as they are; rows from nk on of every level
+// that is not frozen are replaced by what the other mode's buffer holds -- the pending rows, then +0.0 (keep_tail: the rows
+// behind them are an imported blob's and stay).  One workgroup per (row, level of the half).
+__global__ void swfd_export_rows_kernel(double* __restrict__ out, const double* __restrict__ pendbuf, const int* __restrict__ meta,
+                                        const int* __restrict__ rep, int s0, int n2, int d, int pend, int keep_tail) {
+  const int r = blockIdx.x, j = blockIdx.y, s = s0 + j;
+  const int nk = meta[s * 4 + 0];
+  if (r < nk || (rep && rep[s] < 0)) return;
+  double* dst = out + ((long)j * n2 + r) * d;
+  if (r < nk + pend) row_copy<double>(dst, pendbuf + (long)(r - nk) * d, d);
+  else if (!keep_tail) row_zero(dst, d);
+}
+// Import: the pending rows of the imported half (those of its top level, which is never frozen) become the lane's.
+__global__ void swfd_import_pending_kernel(const double* __restrict__ buf, const int* __restrict__ meta, int s_top, int n2, int d,
+                                           double* __restrict__ pendbuf) {
+  const int j = blockIdx.x, row = meta[s_top * 4 + 0] + j;
+  if (row < n2) row_copy<double>(pendbuf + (long)j * d, buf + ((long)s_top * n2 + row) * d, d);
 }
 
 static size_t swfd_half_bytes(const Swfd* h) {
@@ -879,7 +979,7 @@ static int swfd_create_impl(Swfd* h, long N, double R, int d, int ell, int sweep
   ZALLOC(h->meta, 4 * S * 4);
   {
     const char* dd = getenv("MUSED_SWFD_DEDUPE");
-    if (!(dd && dd[0] == '0')) ALLOC(h->rep, 4 * S);
+    if (!(dd && dd[0] == '0')) ZALLOC(h->rep, 4 * S);  // (zero: no level frozen -- the shared mode reads it before the first rotation)
     // MUSED_SWFD_LIST=0: the rotation's workgroups test rep per sketch instead of going through the compacted list;
     // MUSED_SWFD_ORDERS=0: every Gram matrix is solved at order 2 l; MUSED_SWFD_KACT=0: the rotate product runs over all 2 l rows
     auto off = [](const char* name) { const char* v = getenv(name); return v && v[0] == '0'; };
@@ -924,6 +1024,15 @@ static int swfd_create_impl(Swfd* h, long N, double R, int d, int ell, int sweep
     for (int kind = 0; kind < 2; ++kind)
       for (int j = 0; j < h->L; ++j) th[sk_index(h, lane, j, kind)] = ldexp((double)h->N / ell, j);
   MUSED_CHECK_HIP(hipMemcpy(h->theta, th.data(), 8 * S, hipMemcpyHostToDevice));
+  // (allocated whatever the mode turns out to be: `shared` is decided below, once the pre-rotation is)
+  MUSED_CHECK_HIP(hipMalloc((void**)&h->pendbuf, 8 * ((size_t)lanes * l + 1) * dd));
+  MUSED_CHECK_HIP(hipMemset(h->pendbuf, 0, 8 * ((size_t)lanes * l + 1) * dd));
+  MUSED_CHECK_HIP(hipMalloc((void**)&h->nk0, 4 * S));
+  MUSED_CHECK_HIP(hipMemset(h->nk0, 0, 4 * S));
+  if (h->rep) {
+    MUSED_CHECK_HIP(hipMalloc((void**)&h->froze, 4 * S));
+    MUSED_CHECK_HIP(hipMemset(h->froze, 0, 4 * S));
+  }
   int rc;
   if ((rc = gemm_f64_prepare_all())) return rc;
   if ((rc = eig_plan_create(h->n2, h->S, h->sweeps, true, &h->eig, h->rep, EIG_PLAN_TOP_HALF, h->status, 0, h->list, h->offs)))
@@ -954,6 +1063,16 @@ static int swfd_create_impl(Swfd* h, long N, double R, int d, int ell, int sweep
         return rc;
     }
   }
+  {
+    // MUSED_SWFD_SHARED=0: every sketch keeps its own copy of the pending rows.  Also off without the settle kernel
+    // (MUSED_SWFD_SETTLE=0) and with the pre-rotation (MUSED_SWFD_PREROT=1): those paths are the code they were.
+    const char* sh = getenv("MUSED_SWFD_SHARED");
+    h->shared = h->settle && h->pre_chunk == 0 && !(sh && sh[0] == '0');
+    if (!h->shared) {  // (the kernels test these pointers)
+      (void)hipFree(h->froze); h->froze = nullptr;
+      (void)hipFree(h->nk0); h->nk0 = nullptr;
+    }
+  }
   return MUSED_OK;
 }
 
@@ -967,7 +1086,8 @@ int mused_swfd_destroy(void* handle) {
   if (h->eigp) eig_plan_destroy(h->eigp);
   void* bufs[] = {h->buf, h->queue, h->qt, h->meta, h->dropped, h->theta, h->T, h->Wc, h->plan,
                   h->keep_src, h->now_dev, h->stack, h->Wq, h->Bout, h->sig_out, h->qinfo, h->qsel,
-                  h->rep, h->pre_in, h->pre_out, h->pre_gram, h->status, h->gpart, h->list, h->offs, h->kact, h->ostat, h->used};
+                  h->rep, h->pre_in, h->pre_out, h->pre_gram, h->status, h->gpart, h->list, h->offs, h->kact, h->ostat, h->used,
+                  h->pendbuf, h->froze, h->nk0};
   for (void* b : bufs) (void)hipFree(b);
   if (h->status_host) (void)hipHostFree(h->status_host);
   delete h;
@@ -1056,6 +1176,9 @@ int mused_swfd_debug_used(void* handle, int* used_out) {
   return 1;
 }
 
+// Diagnostic (not part of the declared ABI): 1 when the handle keeps its pending rows once per lane (Swfd::shared), else 0.
+int mused_swfd_debug_shared(void* handle) { return handle ? (((Swfd*)handle)->shared ? 1 : 0) : MUSED_ERR_ARG; }
+
 // Diagnostic (not part of the declared ABI): out[18] = {rotations, representatives, representatives by the order their Gram
 // matrix was solved at: bucket b = orders in (16 b, 16 b + 16]}, counted on the device since the handle was created.
 // Returns 1 when the handle keeps the list (and so the counts), else 0.
@@ -1126,7 +1249,12 @@ int mused_swfd_export_half(void* handle, int kind, void* dst, void* stream) {
   Swfd* h = (Swfd*)handle;
   MUSED_REQUIRE(h && dst && (kind == 0 || kind == 1), "mused_swfd_export_half: bad arguments");
   MUSED_REQUIRE(h->lanes == 1, "mused_swfd_export_half: single-lane handles only");
-  return half_copy(h, kind, (char*)dst, true, (hipStream_t)stream);
+  int rc = half_copy(h, kind, (char*)dst, true, (hipStream_t)stream);
+  if (rc || !h->shared) return rc;
+  hipLaunchKernelGGL(swfd_export_rows_kernel, dim3(h->n2, h->L), dim3(256), 0, (hipStream_t)stream, (double*)dst, h->pendbuf,
+                     h->meta, h->rep, kind * h->L, h->n2, h->d, h->pend, h->tail_dirty ? 1 : 0);
+  MUSED_LAUNCH_CHECK();
+  return MUSED_OK;
 }
 
 int mused_swfd_import_half(void* handle, int kind, const void* src, void* stream) {
@@ -1135,7 +1263,12 @@ int mused_swfd_import_half(void* handle, int kind, const void* src, void* stream
   MUSED_REQUIRE(h->lanes == 1, "mused_swfd_import_half: single-lane handles only");
   h->twin = false;
   h->tail_dirty = true;  // (the blob's rows behind nk + pend are the exporter's word, not this handle's)
-  return half_copy(h, kind, (char*)src, false, (hipStream_t)stream);
+  int rc = half_copy(h, kind, (char*)src, false, (hipStream_t)stream);
+  if (rc || !h->shared || h->pend == 0) return rc;
+  hipLaunchKernelGGL(swfd_import_pending_kernel, dim3(h->pend), dim3(256), 0, (hipStream_t)stream, h->buf, h->meta,
+                     kind * h->L + h->L - 1, h->n2, h->d, h->pendbuf);
+  MUSED_LAUNCH_CHECK();
+  return MUSED_OK;
 }
 
 // Start epoch e = rows_seen / N on this rank with the row counter set to `rows_seen` (a multiple
@@ -1150,6 +1283,7 @@ int mused_swfd_begin_epoch(void* handle, long rows_seen, const void* main_half, 
   const size_t S = h->S, L = h->L;
   MUSED_CHECK_HIP(hipMemsetAsync(h->buf, 0, 8 * S * (size_t)h->n2 * h->d, st));
   MUSED_CHECK_HIP(hipMemsetAsync(h->meta, 0, 4 * S * 4, st));
+  if (h->shared && h->rep) MUSED_CHECK_HIP(hipMemsetAsync(h->rep, 0, 4 * S, st));  // (no level frozen)
   MUSED_CHECK_HIP(hipMemsetAsync(h->dropped, 0, 8 * S, st));
   MUSED_CHECK_HIP(hipMemsetAsync(h->qt, 0, 8 * S * h->cap, st));
   (void)L;
@@ -1178,6 +1312,7 @@ extern "C" int mused_fd_rotate(double* buf, int ell, int d, double* sigma_out, i
   int rc = mused_swfd_create(1l << 30, 1.0, d, ell, sweeps, &hv);  // one level, theta = 2^30 / l: never dumps
   if (rc) return rc;
   mused::Swfd* h = (mused::Swfd*)hv;
+  h->shared = false;  // (the whole buffer counts as pending rows: they stay where they are)
   hipStream_t st = (hipStream_t)stream;
   const size_t bytes = sizeof(double) * (size_t)2 * ell * d;
   hipError_t e = hipMemcpyAsync(h->buf, buf, bytes, hipMemcpyDeviceToDevice, st);

@@ -5,7 +5,9 @@ read back, and the rows each kernel writes follow from them:
 
     scatter + append (MUSED_SWFD_SETTLE=0)   live sketch: 2 l rows (kept rows, zeros to row 2 l) + l appended rows
     settle kernel                            live sketch: nk kept + l next rows + max(used - nk - l, 0) zero rows
-    either                                   frozen sketch: the l raw rows; dumped directions: one ring row each (not counted)
+    settle kernel, shared pending rows       live sketch: nk kept rows; every lane: the l next rows, once (the default)
+    all of them                              frozen sketch: the l raw rows; dumped directions: one ring row each (not counted)
+                                             (a level that freezes is written out once in the shared mode: not counted)
 
 argv: lanes [rotations of the second window].  Prints one JSON line."""
 import ctypes as C
@@ -35,7 +37,7 @@ for name in ("mused_swfd_debug_state", "mused_swfd_debug_used"):
 sk.fit_lanes(X[:, :W])
 rep, meta, used = (C.c_int * S)(), (C.c_int * (4 * S))(), (C.c_int * S)()
 row = 8 * d
-per = {"pair": [], "settle": [], "live": [], "frozen": [], "nk": [], "used": []}
+per = {"pair": [], "settle": [], "shared": [], "live": [], "frozen": [], "nk": [], "used": []}
 for k in range(rots):
     sk.fit_lanes(X[:, W + k * ell:W + (k + 1) * ell])      # one block a call: the counters after every rotation
     assert L.mused_swfd_debug_state(sk._h, rep, meta) == 1 and L.mused_swfd_debug_used(sk._h, used) == 1
@@ -44,6 +46,7 @@ for k in range(rots):
     zero = np.maximum(us - nk - ell, 0)
     per["pair"].append(int(live.sum()) * 3 * ell * row + int((~live).sum()) * ell * row)
     per["settle"].append(int((nk + ell + zero)[live].sum()) * row + int((~live).sum()) * ell * row)
+    per["shared"].append(int(nk[live].sum()) * row + B * ell * row + int((~live).sum()) * ell * row)
     per["live"].append(int(live.sum()))
     per["frozen"].append(int((~live).sum()))
     per["nk"].append(float(nk[live].mean()))
@@ -54,4 +57,5 @@ print(json.dumps({"lanes": B, "sketches": S, "rotations": rots, "live_mean": flo
                   "frozen_mean": float(np.mean(per["frozen"])), "kept_rows_mean": round(float(np.mean(per["nk"])), 1),
                   "rows_in_use_before_mean": round(float(np.mean(per["used"])), 1),
                   "MB_stored_per_rotation_scatter_plus_append": mb(per["pair"]), "MB_stored_per_rotation_settle": mb(per["settle"]),
+                  "MB_stored_per_rotation_settle_shared": mb(per["shared"]),
                   "MB_first_last_rotation_settle": [mb(per["settle"][:1]), mb(per["settle"][-1:])]}))
