@@ -745,6 +745,38 @@ int mused_kth_distance(const double* X, long n, int d, long ld, int k, double* k
 long mused_eps_knee_ws_bytes(long n);
 int mused_eps_knee(const double* kd2, long n, void* out, void* ws, long ws_bytes, void* stream);
 
+/* ---- Orthogonal Procrustes, csrc/procrustes.hip (specification: mused_amd/procrustes.py): the orthogonal R (r x r) that
+ * minimises |A R - B|_F, the polar factor of M = A^T B -- scipy.linalg.orthogonal_procrustes(A, B), reflections allowed.
+ * M by the split-K GEMM (256 rows a split, partials summed in split order), then ONE workgroup: one-sided Jacobi on the columns
+ * of M in LDS (round-robin pairs dealt to 16 waves, a pair rotated when (w_p.w_q)^2 > 2^-100 (w_p.w_p)(w_q.w_q), the sweep that
+ * rotates nothing is the last, at most 30), sigma_j = |w_j|, U = W / sigma, R0 = U (U^T M / sigma), one Newton-Schulz step
+ * R = 1/2 R0 (3 I - R0^T R0).  Fixed summation orders: two calls give the same bits.  Enqueue-only.
+ * A, B: m x r fp64 (DEVICE; pitches lda, ldb >= r; A == B allowed), 1 <= m < 2^30, 1 <= r <= 128.  r > 128 returns
+ *   MUSED_ERR_UNSUPPORTED (-4) before anything is launched.
+ * R_out (DEVICE): r x r fp64, row-major, pitch r.
+ * out_f64 (DEVICE, 4 fp64): [0] scale = the sum of the singular values of M, [1] sigma_max, [2] sigma_min, [3] 0.
+ * info_out (DEVICE, 4 int32): [0] flags, [1] sweeps run (the last, clean one counted), [2] 0, [3] 0.  Flags: 2 an entry of M is
+ *   not finite (an entry of A or B is not, or a product overflowed): R_out is NOT written, out_f64[0 .. 2] are NaN, sweeps 0;
+ *   4 sigma_max == 0 or sigma_min <= 2^-14 sigma_max (the data do not determine R: m < r, a zero column, ...); 8 the sweep
+ *   cap was hit.  With 4 or 8 R_out holds what the steps gave and is not to be relied on.
+ * ws: mused_procrustes_ws_bytes(m, r) bytes (24,576 + 8 r^2 (4 + ceil(m / 256)) and alignment; -1 outside the limits above).
+ *   Scratch only. */
+long mused_procrustes_ws_bytes(long m, int r);
+int mused_procrustes(const double* A, long lda, const double* B, long ldb, long m, int r, double* R_out, double* out_f64,
+                     int* info_out, void* ws, long ws_bytes, void* stream);
+/* out = E R for the n rows of a window (R: r x r row-major, pitch r, staged in LDS), and, with Bref, the three sums over
+ * the first m rows: sums_out[0] = |E[:m] R - Bref|_F^2, [1] = |Bref|_F^2, [2] = |E[:m] - Bref|_F^2 -- per-workgroup partials
+ * added in index order by a second launch, no floating-point atomic: two calls give the same bits.  Enqueue-only.
+ * E: n x r fp64 (pitch lde), out: n x r fp64 (pitch ldo), MUST NOT overlap E (checked: MUSED_ERR_ARG); 1 <= n < 2^30,
+ * r <= 128 (beyond: MUSED_ERR_UNSUPPORTED).  Bref: m x r fp64 (pitch ldb), 1 <= m <= n, or NULL (no sums; sums_out and m ignored).
+ * sums_out: 3 fp64 (DEVICE).  ws: at least 24,576 bytes of scratch (a workspace of mused_procrustes serves). */
+int mused_procrustes_apply(const double* E, long lde, long n, int r, const double* R, double* out, long ldo, const double* Bref,
+                           long ldb, long m, double* sums_out, void* ws, void* stream);
+/* The SVD kernel of mused_procrustes alone, for direct tests: W_out (r x r, row-major, pitch r) = M V, the columns of M after
+ * the Jacobi sweeps (mutually orthogonal to the rotation threshold), sigma_out[j] = |column j of W_out| (r fp64, NOT sorted),
+ * info_out as above.  M: r x r fp64 row-major (DEVICE, pitch ldm >= r), r <= 128.  With flag 2 only info_out is written. */
+int mused_svd_jacobi_small(const double* M, long ldm, int r, double* W_out, double* sigma_out, int* info_out, void* stream);
+
 /* ---- a5-a7: SeqBasedSWFD (swfd submodule; call sites main.py:62,65-67,70) ---------------------- */
 
 /* SeqBasedSWFD(N=, R=, d=, sketch_dim=) */

@@ -136,6 +136,10 @@ _PROTOS = {
     "mused_kth_distance": (_i, [_vp, _l, _i, _l, _i, _vp, _vp, _vp, _l, _vp]),
     "mused_eps_knee_ws_bytes": (_l, [_l]),
     "mused_eps_knee": (_i, [_vp, _l, _vp, _vp, _l, _vp]),
+    "mused_procrustes_ws_bytes": (_l, [_l, _i]),
+    "mused_procrustes": (_i, [_vp, _l, _vp, _l, _l, _i, _vp, _vp, _vp, _vp, _l, _vp]),
+    "mused_procrustes_apply": (_i, [_vp, _l, _l, _i, _vp, _vp, _l, _vp, _l, _l, _vp, _vp, _vp]),
+    "mused_svd_jacobi_small": (_i, [_vp, _l, _i, _vp, _vp, _vp, _vp]),
     "mused_swfd_create": (_i, [_l, _d, _i, _i, _i, C.POINTER(_vp)]),
     "mused_swfd_create_lanes": (_i, [_l, _d, _i, _i, _i, _i, C.POINTER(_vp)]),
     "mused_swfd_lanes": (_i, [_vp]),

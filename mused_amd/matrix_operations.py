@@ -1130,6 +1130,214 @@ def select_eps_on_device(embedding, min_samples, stream=None):
                            "curve": ws[: 8 * n].view(torch.float64)}
 
 
+# ---- orthogonal Procrustes: one window's embedding in the previous window's frame (csrc/procrustes.hip; the rule:
+# mused_amd/procrustes.py) ------------------------------------------------------------------------------------------------
+# calls that orthogonal_procrustes_on_device / align_embedding_on_device answered with SciPy on a host copy of the shared rows
+# although the device was asked: a flagged kernel (ill-conditioned A^T B, sweep cap) or more than 128 columns
+procrustes_fallbacks = 0
+
+
+def _procrustes_count_fallback():
+    global procrustes_fallbacks
+    with _km_fallback_lock:
+        procrustes_fallbacks += 1
+
+
+def _align_host() -> bool:
+    """MUSED_ALIGN (read at every call): "device" (default) or "host" = scipy.linalg.orthogonal_procrustes on host copies."""
+    return os.environ.get("MUSED_ALIGN", "device") == "host"
+
+
+def _procrustes_rows(X):
+    """X as an (m, r) fp64 CUDA tensor with unit column stride and a row pitch >= r (row-offset and column-prefix views stay
+    views; uploads and conversions on the current stream)."""
+    import torch
+
+    if isinstance(X, torch.Tensor):
+        Xd = X if X.is_cuda else X.cuda()
+    else:
+        a = np.asarray(X)
+        if a.dtype.kind not in "fiub":
+            raise ValueError("expected a numeric matrix")
+        Xd = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
+    if Xd.dim() != 2:
+        raise ValueError(f"expected matrix, got shape {tuple(Xd.shape)}")
+    if Xd.shape[0] < 1 or Xd.shape[1] < 1:
+        raise ValueError("expected a matrix with at least one row and one column")
+    if Xd.dtype != torch.float64:
+        Xd = Xd.to(torch.float64)
+    if Xd.stride(1) != 1 or Xd.stride(0) < Xd.shape[1]:
+        Xd = Xd.contiguous()
+    return Xd
+
+
+def _procrustes_scipy(A, B):
+    """SciPy's call on host copies of two operands -> (R, scale) as NumPy; raises SciPy's ValueError for a non-finite entry."""
+    from scipy.linalg import orthogonal_procrustes
+
+    return orthogonal_procrustes(_kdist_to_host(A), _kdist_to_host(B))
+
+
+def _procrustes_raise_nonfinite():
+    from . import procrustes as _pr
+
+    raise ValueError(_pr.NONFINITE_TEXT)
+
+
+def procrustes_launch(Ad, Bd, st):
+    """mused_procrustes enqueued on stream `st` (entered by the caller) for two (m, r) fp64 CUDA operands, r <= 128:
+    (R r x r, out 4 fp64 = {scale, sigma_max, sigma_min, 0}, info 4 int32 = {flags, sweeps, 0, 0}, workspace), all on the
+    device.  Nothing is read."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+
+    m, r = Ad.shape
+    ws = _km_workspace(("procrustes", m, r, Ad.device, st.cuda_stream), _lib.lib().mused_procrustes_ws_bytes(m, r), Ad.device)
+    R = torch.empty((r, r), dtype=torch.float64, device=Ad.device)
+    outf = torch.empty(4, dtype=torch.float64, device=Ad.device)
+    info = torch.empty(4, dtype=torch.int32, device=Ad.device)
+    _lib.call("mused_procrustes", _eng.ptr(Ad), Ad.stride(0), _eng.ptr(Bd), Bd.stride(0), m, r, _eng.ptr(R), _eng.ptr(outf),
+              _eng.ptr(info), _eng.ptr(ws), ws.numel(), C.c_void_p(st.cuda_stream))
+    return R, outf, info, ws
+
+
+def svd_jacobi_small_launch(M, stream=None):
+    """mused_svd_jacobi_small on an (r, r) fp64 CUDA matrix (row pitch >= r), r <= 128: (W = M V r x r, sigma r, info 4 int32 =
+    {flags, sweeps, 0, 0}) on the device; the one-sided Jacobi of the Procrustes kernel alone.  Nothing is read."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+
+    st = _match_stream(stream)
+    with torch.cuda.stream(st):
+        Md = _procrustes_rows(M)
+        r = Md.shape[1]
+        if Md.shape[0] != r:
+            raise ValueError(f"expected a square matrix, got {tuple(Md.shape)}")
+        W = torch.empty((r, r), dtype=torch.float64, device=Md.device)
+        sigma = torch.empty(r, dtype=torch.float64, device=Md.device)
+        info = torch.empty(4, dtype=torch.int32, device=Md.device)
+        _lib.call("mused_svd_jacobi_small", _eng.ptr(Md), Md.stride(0), r, _eng.ptr(W), _eng.ptr(sigma), _eng.ptr(info),
+                  C.c_void_p(st.cuda_stream))
+    return W, sigma, info
+
+
+def _procrustes_pair(A, B):
+    Ad, Bd = _procrustes_rows(A), _procrustes_rows(B)
+    if Ad.shape != Bd.shape:
+        raise ValueError(f"the shapes of A and B differ ({tuple(Ad.shape)} vs {tuple(Bd.shape)})")   # (SciPy's text)
+    return Ad, Bd
+
+
+def orthogonal_procrustes_on_device(A, B, stream=None):
+    """`scipy.linalg.orthogonal_procrustes(A, B)` on the device: (R, scale) as fp64 CUDA tensors (r x r and 0-dim), R the
+    orthogonal matrix (det +-1) that minimises |A R - B|_F, scale the sum of the singular values of A^T B
+    (csrc/procrustes.hip; the rule and its bound: mused_amd/procrustes.py).  A, B: (m, r) NumPy arrays (uploaded) or
+    tensors, taken as fp64.  The call reads the kernel's 16 bytes of flags, so it returns after the stream has finished:
+    a non-finite entry raises SciPy's ValueError; an ill-conditioned A^T B (sigma_min <= 2^-14 sigma_max: m < r, a zero
+    column), the sweep cap or r > 128 is answered by SciPy on a host copy and counted in `procrustes_fallbacks`.
+    MUSED_ALIGN=host: SciPy for every call."""
+    import torch
+
+    from . import procrustes as _pr
+
+    if _align_host():
+        R, scale = _procrustes_scipy(A, B)
+        return torch.from_numpy(np.ascontiguousarray(R)).cuda(), torch.tensor(float(scale), dtype=torch.float64).cuda()
+    st = _match_stream(stream)
+    with torch.cuda.stream(st):
+        Ad, Bd = _procrustes_pair(A, B)
+        flags = -1
+        if Ad.shape[1] <= _pr.MAX_R:
+            R, outf, info, _ = procrustes_launch(Ad, Bd, st)
+            flags = int(info.cpu().numpy()[0])
+            if flags & _pr.FLAG_NONFINITE:
+                _procrustes_raise_nonfinite()
+        if flags != 0:
+            _procrustes_count_fallback()
+            R_h, scale_h = _procrustes_scipy(Ad, Bd)
+            return (torch.from_numpy(np.ascontiguousarray(R_h)).to(Ad.device),
+                    torch.tensor(float(scale_h), dtype=torch.float64, device=Ad.device))
+    return R, outf[0]
+
+
+def align_embedding_on_device(E_new, E_ref, shift, stream=None):
+    """One hopping window's embedding in the previous window's frame: (aligned (W, r) fp64 CUDA tensor = E_new R, R,
+    residual, unaligned) with R = orthogonal_procrustes(A, B)[0] over the rows the windows share, A = E_new[:W - shift] and
+    B = E_ref[shift:]; residual = |A R - B|_F / |B|_F, unaligned = |A - B|_F / |B|_F (Python floats).  The product and the
+    three sums are one pass over E_new on the device (mused_procrustes_apply); what is read is the flags and the sums,
+    40 bytes.  E_new is not modified.  Flags, r > 128 and MUSED_ALIGN=host as for orthogonal_procrustes_on_device: a
+    fallback copies the shared rows to the host for SciPy's R and still multiplies on the device (r <= 128)."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    from . import procrustes as _pr
+
+    if _align_host():
+        out, R, res, un = _align_scipy(_kdist_to_host(E_new), _kdist_to_host(E_ref), shift)
+        return torch.from_numpy(np.ascontiguousarray(out)).cuda(), torch.from_numpy(np.ascontiguousarray(R)).cuda(), res, un
+    st = _match_stream(stream)
+    with torch.cuda.stream(st):
+        En, Er = _procrustes_pair(E_new, E_ref)
+        n, r = En.shape
+        shift = _align_shift(shift, n)
+        m = n - shift
+        A, B = En[:m], Er[shift:]
+        if r > _pr.MAX_R:
+            _procrustes_count_fallback()
+            out, R, res, un = _align_scipy(En.cpu().numpy(), Er.cpu().numpy(), shift)
+            return torch.from_numpy(np.ascontiguousarray(out)).to(En.device), torch.from_numpy(np.ascontiguousarray(R)).to(En.device), res, un
+        R, _, info, ws = procrustes_launch(A, B, st)
+        out = torch.empty((n, r), dtype=torch.float64, device=En.device)
+        sums = torch.empty(3, dtype=torch.float64, device=En.device)
+
+        def apply(R_):
+            _lib.call("mused_procrustes_apply", _eng.ptr(En), En.stride(0), n, r, _eng.ptr(R_), _eng.ptr(out), out.stride(0),
+                      _eng.ptr(B), B.stride(0), m, _eng.ptr(sums), _eng.ptr(ws), C.c_void_p(st.cuda_stream))
+            return torch.cat([info.to(torch.float64), sums]).cpu().numpy()   # ONE read: {flags, sweeps, 0, 0, three sums}
+
+        rec = apply(R)
+        flags = int(rec[0])
+        if flags & _pr.FLAG_NONFINITE:
+            _procrustes_raise_nonfinite()
+        if flags:
+            _procrustes_count_fallback()
+            R = torch.from_numpy(np.ascontiguousarray(_procrustes_scipy(A, B)[0])).to(En.device)
+            rec = apply(R)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        res, un = float(np.sqrt(rec[4] / rec[5])), float(np.sqrt(rec[6] / rec[5]))
+    return out, R, res, un
+
+
+def _align_shift(shift, n):
+    import numbers
+
+    if not isinstance(shift, numbers.Integral) or isinstance(shift, bool) or not 0 < shift < n:
+        raise ValueError(f"shift must be an integer in (0, W = {n}): the windows share W - shift rows, got {shift!r}")
+    return int(shift)
+
+
+def _align_scipy(E_new, E_ref, shift):
+    """align_embedding_on_device on the host with SciPy's R: (E_new R, R, residual, unaligned), NumPy."""
+    E_new = np.asarray(E_new, dtype=np.float64)
+    E_ref = np.asarray(E_ref, dtype=np.float64)
+    if E_new.ndim != 2 or E_new.shape != E_ref.shape:
+        raise ValueError(f"the shapes of A and B differ ({E_new.shape} vs {E_ref.shape})")
+    shift = _align_shift(shift, E_new.shape[0])
+    A, B = E_new[:E_new.shape[0] - shift], E_ref[shift:]
+    R = _procrustes_scipy(A, B)[0]
+    nb = np.linalg.norm(B)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return E_new @ R, R, float(np.linalg.norm(A @ R - B) / nb), float(np.linalg.norm(A - B) / nb)
+
+
 def perform_dbscan_clustering_on_device(emb, eps=0.5, min_samples=5, stream=None):
     """`perform_dbscan_clustering(emb, eps, min_samples)` with the pair work on the device (csrc/dbscan.hip; the rule and
     its rounding margin: mused_amd/dbscan.py): scikit-learn's labels as int64 NumPy, O(n) device memory beside the rows.

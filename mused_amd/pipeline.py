@@ -104,9 +104,26 @@ class StreamPipeline:
                  step_window_ratio=1, engine=None, async_labels=True, feature_sketch=False, stream=None,
                  assume_finite=False, window_slots=1, n_clusters_total=None, eps=0.5, min_samples=5,
                  dbscan_max_rows=None, modality_weights=None, fusion_threshold=None, modality_ks=None,
-                 n_clusters_range=None, internal_scores=False):
+                 n_clusters_range=None, internal_scores=False, align_embeddings=False):
         if approach not in ("sSVDMC", "sSVDMC_hung", "sSVDMC_pot", "sSVDMC_mini", "SWFDMC", "DBSCAN_incr"):
             raise ValueError(f"approach {approach!r} is not on the device hot path")
+        # `align_embeddings` (off by default: nothing below runs then).  The two chained approaches feed every window's
+        # embedding into ONE stream-long clusterer, but each window's coordinates are its own singular vectors.  With the
+        # option window 0 defines the frame and window t is carried onto the ALIGNED window t - 1 by the orthogonal
+        # Procrustes map of the rows the two share (matrix_operations.align_embedding_on_device) -- an isometry of the whole
+        # window, applied on the chain worker immediately before the clusterer takes the embedding.  Per window:
+        # `alignment_residuals` = |A R - B| / |B| and `alignment_unaligned` = |A - B| / |B| over the shared rows, NaN for window 0.
+        self._align = bool(align_embeddings)
+        if self._align:
+            if approach not in ("sSVDMC_mini", "DBSCAN_incr"):
+                raise ValueError(f"align_embeddings: approach {approach!r} clusters every window on its own -- k-means is invariant "
+                                 "under the map, and a sketch is no eigenstep embedding; it serves 'sSVDMC_mini' and 'DBSCAN_incr'")
+            if int(step_window_ratio) <= 1:
+                raise ValueError("align_embeddings: with step_window_ratio = 1 consecutive windows share no rows to align on")
+            if int(window_slots) > 1:
+                raise ValueError("align_embeddings: the alignment is a chain over windows in order; window_slots must be 1")
+        self.alignment_residuals, self.alignment_unaligned = [], []
+        self._align_ref = None    # (the previous window's aligned embedding, the stream row of its first row)
         # WITHOUT GROUND TRUTH (both off by default: nothing below runs then).  `n_clusters_range` = (lo, hi): every k-means
         # window chooses its own k among lo .. hi by the device silhouette (matrix_operations.select_n_clusters_on_device)
         # instead of taking the number of distinct true labels, which may then be None; the k of every window: `chosen_k`.
@@ -413,6 +430,8 @@ class StreamPipeline:
                 reduced_host, sigma_host = reduced_dev.cpu().numpy(), sigma_dev.cpu().numpy()
             WindowEngine.check_rsvd_flags(flags_host)  # raised on the label worker, surfaces in flush()
         t0 = time.perf_counter()
+        if self._align:
+            reduced_dev, reduced_host = self._aligned(reduced_dev, reduced_host, job[11] if len(job) > 11 else None)
         if self._mini:
             clusters = self._minibatch(reduced_dev, reduced_host)
         elif self._incr:
@@ -458,6 +477,33 @@ class StreamPipeline:
         words are all the trace and the matching take), so it is not copied to the pinned buffer; a window that falls back
         fetches it itself (matrix_operations._km_host_copy)."""
         return self._km_seed_device and not self._chained and reduced is not None and reduced.dtype == torch.float64
+
+    def _aligned(self, reduced_dev, reduced_host, lo):
+        """align_embeddings: this window's embedding in the frame of window 0 -> (device tensor, host array), one of them None:
+        the form the clusterer takes (the device tensor unless MUSED_KMEANS=host hands 'sSVDMC_mini' the host copy).  Called in
+        window order on the chain worker, on its stream; `lo` = stream row of the window's first row."""
+        if lo is None:
+            raise ValueError("align_embeddings needs the stream row of every window (process_window(..., lo=...))")
+        on_dev = reduced_dev is not None and reduced_dev.dtype == torch.float64 and (self._incr or self._km_device)
+        cur = reduced_dev if on_dev else np.ascontiguousarray(reduced_host, dtype=np.float64)
+        res = un = float("nan")
+        if self._align_ref is not None:
+            ref, ref_lo = self._align_ref
+            shift = int(lo) - int(ref_lo)
+            if not 0 < shift < self.W:
+                raise ValueError(f"align_embeddings: windows at stream rows {ref_lo} and {lo} share no rows")
+            if on_dev:
+                st = getattr(self._km_local, "stream", None)
+                if st is None:
+                    st = self._km_local.stream = torch.cuda.Stream(priority=-1)
+                reduced_dev.record_stream(st)  # produced on the pipeline's stream, complete (ev), consumed on the worker's
+                cur, _, res, un = mo.align_embedding_on_device(reduced_dev, ref, shift, stream=st)
+            else:
+                cur, _, res, un = mo._align_scipy(cur, ref, shift)
+        self._align_ref = (cur, lo)
+        self.alignment_residuals.append(res)
+        self.alignment_unaligned.append(un)
+        return (cur, None) if on_dev else (None, cur)
 
     def _minibatch(self, reduced_dev, reduced_host):
         """main.py:82-86: clusterer.partial_fit(reduced).predict(reduced) on the stream's one MiniBatchKMeans.  Called in
@@ -613,7 +659,7 @@ class StreamPipeline:
             ev = torch.cuda.Event()
             ev.record()
         # (slot -> hop-state key of this window's deferred flag words: the engine has moved on by the time a worker reads them)
-        return (ev, red_pin, sig_pin, n_clusters, trigger, t_start, flag_pin, reduced, mods, list(eng.slot_keys), eng)
+        return (ev, red_pin, sig_pin, n_clusters, trigger, t_start, flag_pin, reduced, mods, list(eng.slot_keys), eng, lo)
 
     def _submit(self, job):
         """Hand a window to the label workers (async mode)."""
@@ -820,7 +866,7 @@ class StreamPipeline:
 def process_streaming_data(results, data_modalities, modality_types, window_size, reduced_dim, k_basis, n_clusters_total,
                            seed, approach, complete_true_labels, step_window_ratio, noise_rate, label_mode, sorting,
                            eps, min_samples, score=False, modality_weights=None, fusion_threshold=None, modality_ks=None,
-                           n_clusters_range=None, internal_scores=False, partition_scores=False):
+                           n_clusters_range=None, internal_scores=False, partition_scores=False, align_embeddings=False):
     """Same positional parameters as main.py:13.  `modality_weights` (one weight per modality, finite and > 0): fusion by
     weighted sum instead of OR for the approaches that go through the eigenstep ("SWFDMC": ValueError); None: OR.
     `fusion_threshold` (tau): every window's fused matrix is the 0/1 mask of the edges whose agreement sum_m w_m [modality m
@@ -842,7 +888,11 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
     single value.  `partition_scores=True`: `results["partition_scores"]`, the dict of
     metrics_evaluation.compute_partition_metrics (ARI, AMI, V-measure, ..., matched accuracy: scores that ignore how clusters
     are numbered) on the same concatenated labels, and `results["window_partition_scores"]`, the (K, 9) array of
-    metrics_evaluation.partition_windows; ValueError when `complete_true_labels` is None."""
+    metrics_evaluation.partition_windows; ValueError when `complete_true_labels` is None.
+    `align_embeddings=True` ("sSVDMC_mini" and "DBSCAN_incr" with step_window_ratio > 1; ValueError otherwise): every window's
+    embedding is carried into the frame of window 0 by the orthogonal Procrustes map of the rows it shares with the window
+    before it, ahead of the stream's clusterer; `results["alignment_residuals"]` and `results["alignment_unaligned"]`, one
+    entry per window, NaN for the first."""
     if score and complete_true_labels is None:
         raise ValueError("score=True compares against complete_true_labels, which is None")
     if partition_scores and complete_true_labels is None:
@@ -856,7 +906,8 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
                         window_slots=int(os.environ.get("MUSED_WINDOW_SLOTS", "1")), n_clusters_total=n_clusters_total,
                         eps=eps, min_samples=min_samples, dbscan_max_rows=int(incr_rows) if incr_rows else None,
                         modality_weights=modality_weights, fusion_threshold=fusion_threshold, modality_ks=modality_ks,
-                        n_clusters_range=n_clusters_range, internal_scores=internal_scores) as pipe:
+                        n_clusters_range=n_clusters_range, internal_scores=internal_scores,
+                        align_embeddings=align_embeddings) as pipe:
         clusters = pipe.run(data_modalities, None if complete_true_labels is None else np.asarray(complete_true_labels))
     t1 = time.time_ns()
     if score:
@@ -874,6 +925,9 @@ def process_streaming_data(results, data_modalities, modality_types, window_size
         results["chosen_k"] = list(pipe.chosen_k)
     if internal_scores:
         results["internal_scores"] = list(pipe.internal_scores)
+    if align_embeddings:
+        results["alignment_residuals"] = list(pipe.alignment_residuals)
+        results["alignment_unaligned"] = list(pipe.alignment_unaligned)
     if partition_scores:
         _partition_scored(results, clusters, _window_true_labels(complete_true_labels, len(data_modalities[0]), window_size,
                                                                  step_window_ratio), window_size)
