@@ -53,10 +53,10 @@ constexpr long MT_WS_KX_BYTES = 8l * (16 - MT_RREG) * 4 * MT_THREADS;
 struct MatchLds {
   double part[2][MT_WAVES][MT_MAXC];  // column-sum partials, double-buffered over the iterations
   double red[2][MT_WAVES];
-  MatchTables tb;   // steps 1, 2 and 5 (match_labels.h)
-  int row_ok[MT_MAXC], col_ok[MT_MAXC], map_row[MT_MAXC];
-  int any_inf, max_ov, infeasible;
+  ChainLds ch;      // steps 1, 2 and 5, the marks of step 3 and the selection (match_labels.h)
 };
+// the two words mt_chain zeroes before every window: an entry below min_overlap was seen; the largest count that reaches it
+constexpr int MT_ANY_INF = 0, MT_MAX_OV = 1;
 
 __device__ __forceinline__ double wave_allmax(double v) {
 #pragma unroll
@@ -70,7 +70,7 @@ __device__ __forceinline__ double wave_allmin(double v) {
 }
 
 // Steps 3 - 5 of one window for the size class (RPW rows per wave, CPL columns per lane; rows r >= RREG live in kx).
-// Returns the flag word; s.map_row holds the selection when it is 0.  Not inlined: each size class gets its own register
+// Returns the flag word; s.ch.map_row holds the selection when it is 0.  Not inlined: each size class gets its own register
 // allocation (with 16 waves a lane has 128 VGPRs; what hipcc cannot keep of k[][] beside the working set it spills).
 template <int RPW, int CPL, int RREG>
 __device__ __noinline__ int match_solve(MatchLds& s, int P, int N, int min_overlap, const int* __restrict__ ov,
@@ -105,19 +105,16 @@ __device__ __noinline__ int match_solve(MatchLds& s, int P, int N, int min_overl
       if (i < P && j < N) {
         const int cnt = __hip_atomic_load(&ov[i * N + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (cnt >= min_overlap) {
-          s.row_ok[i] = 1;
-          s.col_ok[j] = 1;
+          s.ch.row_ok[i] = 1;
+          s.ch.col_ok[j] = 1;
           mx = max(mx, cnt);
         } else {
-          s.any_inf = 1;
+          s.ch.word[MT_ANY_INF] = 1;
         }
       }
     }
-  if (mx > 0) atomicMax(&s.max_ov, mx);
-  __syncthreads();
-  if (t < MT_MAXC && ((t < P && !s.row_ok[t]) || (t < N && !s.col_ok[t]))) s.infeasible = 1;
-  __syncthreads();
-  if (s.infeasible) {
+  if (mx > 0) atomicMax(&s.ch.word[MT_MAX_OV], mx);
+  if (!mt_feasible(s.ch, P, N)) {
     *feasible_out = 0;
     *iters_out = 0;
     *margin_out = 0.f;
@@ -126,7 +123,8 @@ __device__ __noinline__ int match_solve(MatchLds& s, int P, int N, int min_overl
   *feasible_out = 1;
 
   // cost -> K, the operations of the specification: inf -> 1e9, abs, / max, exp(M / -reg); 0 outside the matrix
-  const double cmax = s.any_inf ? fmax(1e9, (double)s.max_ov) : (double)s.max_ov;
+  const double max_ov = (double)s.ch.word[MT_MAX_OV];
+  const double cmax = s.ch.word[MT_ANY_INF] ? fmax(1e9, max_ov) : max_ov;
   auto k_entry = [&](int r, int c) -> double {
     const int i = r * MT_WAVES + w, j = c * 64 + l;
     if (i >= P || j >= N) return 0.0;
@@ -245,7 +243,7 @@ __device__ __noinline__ int match_solve(MatchLds& s, int P, int N, int min_overl
       const int j = c * 64 + l;
       if (j < N) {
         const double p = (u * kr[c]) * v[c];
-        if (p > thr) atomicMax(&s.map_row[j], i);
+        if (p > thr) atomicMax(&s.ch.map_row[j], i);
         mrg = fmin(mrg, fabs(p - thr) / thr);
         if (plan_out) plan_out[i * N + j] = p;
       }
@@ -272,52 +270,22 @@ __global__ __launch_bounds__(MT_THREADS) void match_pot_chain_kernel(const int* 
                                                                      double* __restrict__ kx) {
   extern __shared__ __attribute__((aligned(16))) unsigned char mt_lds[];
   MatchLds& s = *reinterpret_cast<MatchLds*>(mt_lds);
-  const int t = threadIdx.x;
-  int tw = 0;
-  for (; tw < K_windows; ++tw) {
-    const int* nw = raw + (long)tw * W;
-    const int* pv = tw == 0 ? prev0 : matched + (long)(tw - 1) * W;
-    int* out = matched + (long)tw * W;
-    int* inf = info + tw * MT_INFO;
-    if (pv == nullptr) {   // no previous window: match_clusters returns the new labels as they are
-      const int bad = mt_pass_through(s.tb, nw, out, W);
-      if (t < MT_INFO) inf[t] = t == 6 ? !bad : (t == 4 && bad ? MT_FLAG_RANGE : 0);
-      if (bad) break;
-      continue;
-    }
-    if (t < MT_MAXC) {
-      s.row_ok[t] = 0;
-      s.col_ok[t] = 0;
-      s.map_row[t] = -1;
-    }
-    if (t == 0) s.any_inf = s.max_ov = s.infeasible = 0;
-    int P, N;
-    int flags = mt_label_tables(s.tb, pv, nw, W, &P, &N);
-    int iters = 0, feasible = 0;
+  mt_chain(s.ch, raw, K_windows, W, prev0, matched, info, ov, [&](int tw, int P, int N) {
+    // match_solve is not inlined, and it addresses LDS with ds instructions only if the compiler's constant propagation
+    // across functions, which runs before this lambda is inlined, sees every call site pass the LDS base itself.  A `s`
+    // captured by reference is a load from the closure at that point: match_solve then takes a generic pointer, uses flat
+    // loads and stores for LDS, and the <16, 4> class grows from 16,908 to 18,712 instructions and from 488 to 516 bytes
+    // of scratch.  So the lambda names mt_lds again.
+    MatchLds& s = *reinterpret_cast<MatchLds*>(mt_lds);
+    int iters = 0, feasible = 0, flags;
     float margin = 0.f;
-    if (!flags) {
-      mt_overlap_counts(s.tb, pv, nw, W, P, N, ov);
-      double* po = plan_out ? plan_out + (long)tw * MT_MAXC * MT_MAXC : nullptr;
-      if (P <= 2 * MT_WAVES && N <= 64) flags = match_solve<2, 1, 2>(s, P, N, min_overlap, ov, kx, po, &iters, &feasible, &margin);
-      else if (P <= 10 * MT_WAVES && N <= 192) flags = match_solve<10, 3, 10>(s, P, N, min_overlap, ov, kx, po, &iters, &feasible, &margin);
-      else flags = match_solve<16, 4, MT_RREG>(s, P, N, min_overlap, ov, kx, po, &iters, &feasible, &margin);
-    }
-    if (t == 0) {
-      inf[0] = P;
-      inf[1] = N;
-      inf[2] = iters;
-      inf[3] = feasible;
-      inf[4] = flags;
-      inf[5] = __float_as_int(margin);
-      inf[6] = flags ? 0 : 1;
-      inf[7] = 0;
-    }
-    if (flags) break;   // uniform: the chain ends at the first flagged window
-    __syncthreads();    // map_row is complete
-    mt_relabel(s.tb, nw, out, W, feasible ? s.map_row : nullptr);
-  }
-  // windows behind a flagged one were not run
-  for (int e = t + (tw + 1) * MT_INFO; e < K_windows * MT_INFO; e += MT_THREADS) info[e] = 0;
+    double* po = plan_out ? plan_out + (long)tw * MT_MAXC * MT_MAXC : nullptr;
+    if (P <= 2 * MT_WAVES && N <= 64) flags = match_solve<2, 1, 2>(s, P, N, min_overlap, ov, kx, po, &iters, &feasible, &margin);
+    else if (P <= 10 * MT_WAVES && N <= 192) flags = match_solve<10, 3, 10>(s, P, N, min_overlap, ov, kx, po, &iters, &feasible, &margin);
+    else flags = match_solve<16, 4, MT_RREG>(s, P, N, min_overlap, ov, kx, po, &iters, &feasible, &margin);
+    if (!flags) __syncthreads();   // map_row is complete
+    return ChainSolved{iters, feasible, flags, __float_as_int(margin)};
+  });
 }
 
 }  // namespace mused

@@ -1,7 +1,7 @@
 // The passes of a label-chain window that do not depend on how the assignment is found, shared by the Sinkhorn chain
 // (match.hip) and the Hungarian chain (match_hung.hip): the distinct label values of prev / new and their ranks, the
-// P x N positional overlap counts, and the relabel.  One workgroup of MT_THREADS threads calls every function here
-// from uniform control flow.
+// P x N positional overlap counts, the relabel, and the loop over the windows of a launch with its info words (mt_chain).
+// One workgroup of MT_THREADS threads calls every function here from uniform control flow.
 #pragma once
 #include "internal.h"
 
@@ -13,6 +13,7 @@ constexpr int MT_LABELS = 1024;   // label values the histogram covers (the proj
 constexpr int MT_MAXC = 256;      // largest P, N
 constexpr int MT_INFO = 8;        // ints of info_out per window
 constexpr int MT_FLAG_RANGE = 4, MT_FLAG_SIZE = 8;
+constexpr int MT_LOG_MAX_W = 31;  // the entries admit K_windows * W < 2^31 rows
 
 static_assert(MT_THREADS == MT_LABELS, "one thread per label value in the rank pass");
 
@@ -111,6 +112,83 @@ __device__ __forceinline__ void mt_relabel(const MatchTables& tb, const int* __r
   }
   __threadfence();
   __syncthreads();   // the next window reads `out` and reuses the LDS tables
+}
+
+// ---- the chain: one workgroup walks the windows of a launch ----------------------------------------------------------------
+// What both chain kernels keep in LDS besides their solver's state.
+struct ChainLds {
+  MatchTables tb;
+  int row_ok[MT_MAXC], col_ok[MT_MAXC];   // step 3: the row / the column keeps a finite entry
+  int map_row[MT_MAXC];                   // the solver's result: column j takes the previous value of row map_row[j], or -1
+  int infeasible;
+  int word[2];                            // the solver's own: zero when it is called
+};
+
+// Step 3's test, every row and every column keeps a finite entry (matrix_operations.py:176-178), on the marks the caller
+// has written to row_ok / col_ok.
+__device__ __forceinline__ bool mt_feasible(ChainLds& s, int P, int N) {
+  const int t = threadIdx.x;
+  __syncthreads();
+  if (t < MT_MAXC && ((t < P && !s.row_ok[t]) || (t < N && !s.col_ok[t]))) s.infeasible = 1;
+  __syncthreads();
+  return !s.infeasible;
+}
+
+// What a solver reports of one window: info words 2 (its iteration or step count), 3, 4 and 5.
+struct ChainSolved {
+  int count, feasible, flags, word5;
+};
+
+// The chain matched_t = match(matched_{t-1}, raw_t), t = 0 .. K_windows - 1, and its contract with the host (_match_chain in
+// matrix_operations.py reads words 3, 4 and 6; the wide chain of match_wide.hip writes the same eight words):
+//   info[t] = { P, N, the solver's count, feasible, flags, the solver's word, done = !flags, 0 }
+// A window without a previous one passes through.  The chain ends at the first flagged window, which is not written; the
+// info of the windows behind it is zero.  solve(tw, P, N) is called by every thread once the label tables and the overlap
+// counts ov[i * N + j] of window tw stand, with row_ok / col_ok / word zero and map_row -1; it returns a ChainSolved,
+// uniform over the workgroup, and -- when that is feasible and unflagged -- map_row filled, behind a workgroup barrier.
+template <typename Solve>
+__device__ __forceinline__ void mt_chain(ChainLds& s, const int* __restrict__ raw, int K_windows, int W,
+                                         const int* __restrict__ prev0, int* __restrict__ matched, int* __restrict__ info,
+                                         int* __restrict__ ov, Solve solve) {
+  const int t = threadIdx.x;
+  int tw = 0;
+  for (; tw < K_windows; ++tw) {
+    const int* nw = raw + (long)tw * W;
+    const int* pv = tw == 0 ? prev0 : matched + (long)(tw - 1) * W;
+    int* out = matched + (long)tw * W;
+    int* inf = info + tw * MT_INFO;
+    if (pv == nullptr) {   // no previous window: match_clusters returns the new labels as they are
+      const int bad = mt_pass_through(s.tb, nw, out, W);
+      if (t < MT_INFO) inf[t] = t == 6 ? !bad : (t == 4 && bad ? MT_FLAG_RANGE : 0);
+      if (bad) break;
+      continue;
+    }
+    if (t < MT_MAXC) {
+      s.row_ok[t] = 0;
+      s.col_ok[t] = 0;
+      s.map_row[t] = -1;
+    }
+    if (t == 0) s.infeasible = s.word[0] = s.word[1] = 0;
+    int P, N;
+    ChainSolved r = {0, 0, mt_label_tables(s.tb, pv, nw, W, &P, &N), 0};
+    if (!r.flags) {
+      mt_overlap_counts(s.tb, pv, nw, W, P, N, ov);
+      r = solve(tw, P, N);
+    }
+    if (t == 0) {
+      inf[0] = P;
+      inf[1] = N;
+      inf[2] = r.count;
+      inf[3] = r.feasible;
+      inf[4] = r.flags;
+      inf[5] = r.word5;
+      inf[6] = r.flags ? 0 : 1;
+      inf[7] = 0;
+    }
+    if (r.flags) break;   // uniform
+    mt_relabel(s.tb, nw, out, W, r.feasible ? s.map_row : nullptr);
+  }
+  for (int e = t + (tw + 1) * MT_INFO; e < K_windows * MT_INFO; e += MT_THREADS) info[e] = 0;
 }
 
 }  // namespace mused

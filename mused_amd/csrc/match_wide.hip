@@ -22,26 +22,11 @@
 //                         the info words, the end-of-chain mark
 //   7. mw_relabel_kernel  a matched new label takes the previous value of its row, any other keeps its own
 //
-// Step 6, the solver.  Shortest augmenting paths as lsap: nr <= nc (the transpose when P > N), `remaining` in SciPy's
-// reversed initial order with its swap-removal (the removed column is parked behind position nrem, which SciPy never reads
-// again: positions [nrem, nc) are exactly the scanned columns SC, and their owners the scanned rows SR, so neither set
-// needs an array).  One Dijkstra step: thread t owns positions t, t + 256, ... of `remaining`, updates sp / path of its
-// columns from the global cost row and forms one 64-bit key; the minimum over the workgroup is SciPy's choice.  Four waves,
-// one per SIMD, two barriers per step: a scan of 4,096 positions is 16 per thread, and at the usual few hundred to a
-// thousand labels 2-5, where one wave would walk 64 per lane (every one an LDS read and a dependent global load) and 16
-// waves would only make the barrier dearer.  u, v, sp (int64) and remaining, path, row4col, col4row (uint16) live in LDS.
-//
-// The key, RE-DERIVED for 4,096 positions (match_hung.hip's 2^52 + 9 tie bits holds for 256 only):
-//     ((sp + 2^48) << 13) | (assigned ? 4096 + position : 4095 - position)
-// The tie field is 13 bits: the lowest value wins; among equal values an unassigned column before an assigned one; among
-// unassigned ones the LARGEST position, among assigned ones the SMALLEST.  The bound needs W <= 2^20, which the entry
-// enforces: costs lie in [-2^20, 0].  An unassigned column has v = 0, the row being inserted has u = 0 and matched edges
-// are tight, so the duals telescope along an alternating path: minVal of a step is the ORIGINAL cost of a path of at most
-// 2 nr - 1 < 2^13 edges, |minVal| < 2^13 2^20 = 2^33.  minVal does not decrease over the steps of a row and the sp of every
-// scanned column lies between the first and the last minVal, so the dual update moves a u_i or v_j by less than 2^34 per
-// row and |u|, |v| < 2^12 2^34 = 2^46 after all rows.  A finite sp = minVal + cost - u - v has
-// |sp| < 2^33 + 2^20 + 2^47 < 2^48: 0 < sp + 2^48 < 2^49, the key stays below 2^62 and below the all-ones "no finite entry".
-// "inf" is a sentinel that is tested BEFORE anything is added to it.
+// Step 6, the solver (lsap.h) on the workgroup: thread t owns positions t, t + 256, ... of `remaining` and reads the counts
+// of its columns from the global cost row.  Four waves, one per SIMD, two barriers per step: a scan of 4,096 positions is 16
+// per thread, and at the usual few hundred to a thousand labels 2-5, where one wave would walk 64 per lane (every one an LDS
+// read and a dependent global load) and 16 waves would only make the barrier dearer.  The solver's key bound needs
+// W <= MW_MAX_W, which the entry enforces.
 //
 // Step budget: the solver takes about 2 min(P, N) steps on ordinary label pairs and min(P, N)^2 at worst; one workgroup
 // must not run for seconds, so a window whose solve would take more than max_steps steps (0: 32 min(P, N)) is flagged.
@@ -50,6 +35,7 @@
 //   8 P or N beyond 4,096 (the info word of that side then holds 4,097);  16 the feasibility test passed but no complete
 //   assignment exists (SciPy raises ValueError there);  32 the step budget is spent.  There is no range flag.
 #include "internal.h"
+#include "lsap.h"
 
 namespace mused {
 
@@ -59,18 +45,12 @@ constexpr int MW_HT_BITS = 14;
 constexpr int MW_INFO = 8;                 // ints of info_out per window
 constexpr int MW_THREADS = 256;            // of the grid kernels and of the solver
 constexpr int MW_SORT_THREADS = 1024;
-constexpr int MW_FLAG_SIZE = 8, MW_FLAG_ASSIGN = 16, MW_FLAG_STEPS = 32;
+constexpr int MW_FLAG_SIZE = 8;            // beside LSAP_FLAG_ASSIGN and LSAP_FLAG_STEPS
 constexpr int MW_MAX_W = 1 << 20;
-constexpr long long MW_INF = 0x7fffffffffffffffll;
 constexpr unsigned long long MW_NOKEY = ~0ull;
-constexpr long long MW_BIAS = 1ll << 48;
-constexpr int MW_TIE_BITS = 13;
-constexpr unsigned MW_NONE = 0xffffu;      // "no row / no column" in the uint16 tables
 constexpr unsigned long long MW_OCC = 1ull << 32;
 
 static_assert(MW_HT == 1 << MW_HT_BITS && MW_HT >= 4 * MW_MAXC, "hash set size");
-static_assert(MW_MAXC == 1 << (MW_TIE_BITS - 1), "13 tie bits cover 4,096 positions");
-static_assert(MW_MAXC < (int)MW_NONE, "uint16 tables");
 
 struct WideCtl {
   int stop;        // the chain has ended: every later kernel of the call returns at once
@@ -81,7 +61,7 @@ struct WideCtl {
   int pad;
 };
 
-// the workspace, carved by byte offsets (all multiples of 256)
+// the workspace: every array starts on a multiple of 256 bytes
 struct WideWs {
   WideCtl* ctl;
   unsigned long long* ht;   // 2 x MW_HT
@@ -93,31 +73,23 @@ struct WideWs {
   int* ov;                  // min(W, MW_MAXC)^2 overlap counts, solver orientation
 };
 
-__host__ __device__ inline long mw_align(long b) { return (b + 255) & ~255l; }
+constexpr size_t MW_CTL_BYTES = 256;   // the control block's share of the workspace, cleared by one memset per call
+static_assert(sizeof(WideCtl) <= MW_CTL_BYTES, "the control block is the first 256 bytes");
 
-static long mw_ws_bytes(int W) {
-  const long m = W < MW_MAXC ? W : MW_MAXC;
-  return 256 + 8l * 2 * MW_HT + 4l * 6 * MW_MAXC + mw_align(4l * W) + mw_align(4l * m * m);
-}
-
-static WideWs mw_carve(void* ws, int W) {
-  char* p = (char*)ws;
+// Carves the workspace of a call at window length W, the control block first; a null `ws` only sizes (*bytes).
+static WideWs mw_carve(void* ws, int W, size_t* bytes) {
+  WsCarver c{static_cast<char*>(ws)};
+  const size_t m = W < MW_MAXC ? W : MW_MAXC;
   WideWs w;
-  w.ctl = (WideCtl*)p;
-  p += 256;
-  w.ht = (unsigned long long*)p;
-  p += 8l * 2 * MW_HT;
-  w.val = (int*)p;
-  p += 4l * 2 * MW_MAXC;
-  w.ok = (int*)p;
-  p += 4l * 2 * MW_MAXC;
-  w.map_has = (int*)p;
-  p += 4l * MW_MAXC;
-  w.map_val = (int*)p;
-  p += 4l * MW_MAXC;
-  w.rank_n = (int*)p;
-  p += mw_align(4l * W);
-  w.ov = (int*)p;
+  w.ctl = c.take<WideCtl>(1);
+  w.ht = c.take<unsigned long long>(2 * MW_HT);
+  w.val = c.take<int>(2 * MW_MAXC);
+  w.ok = c.take<int>(2 * MW_MAXC);
+  w.map_has = c.take<int>(MW_MAXC);
+  w.map_val = c.take<int>(MW_MAXC);
+  w.rank_n = c.take<int>(W);
+  w.ov = c.take<int>(m * m);
+  *bytes = c.off;
   return w;
 }
 
@@ -259,119 +231,9 @@ __global__ __launch_bounds__(MW_THREADS) void mw_count_kernel(WideWs w, const in
 
 // ---- 6 ----
 struct WideLds {
-  long long u[MW_MAXC], v[MW_MAXC], sp[MW_MAXC];
-  unsigned short remaining[MW_MAXC], path[MW_MAXC], row4col[MW_MAXC], col4row[MW_MAXC];
-  unsigned long long wmin[MW_THREADS / 64];
-  int sel_j, sel_owner, bad;
+  LsapLds<MW_THREADS, MW_MAXC> ls;
+  int bad;
 };
-
-__device__ __forceinline__ unsigned long long mw_wave_min(unsigned long long k) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = __shfl_xor(k, o);
-    k = other < k ? other : k;
-  }
-  return k;
-}
-
-// Solver row i, column j: cost -ov[i * nc + j] when that count >= min_overlap, else inf.  Uniform control flow over the
-// workgroup.  Leaves col4row[0 .. nr); returns 0, MW_FLAG_ASSIGN or MW_FLAG_STEPS; *steps_out = Dijkstra steps taken.
-__device__ __forceinline__ int mw_solve(WideLds& s, int nr, int nc, int min_overlap, const int* __restrict__ ov, long max_steps,
-                                        int* steps_out) {
-  const int t = threadIdx.x;
-  for (int p = t; p < nc; p += MW_THREADS) {
-    s.u[p] = 0;
-    s.v[p] = 0;
-    s.col4row[p] = MW_NONE;
-    s.row4col[p] = MW_NONE;
-    s.path[p] = MW_NONE;
-  }
-  long steps = 0;
-  for (int cur = 0; cur < nr; ++cur) {
-    for (int p = t; p < nc; p += MW_THREADS) {
-      s.remaining[p] = (unsigned short)(nc - 1 - p);   // the reversed order is SciPy's
-      s.sp[p] = MW_INF;
-    }
-    __syncthreads();
-    long long minVal = 0;
-    int i = cur, nrem = nc, sink = -1;
-    while (sink < 0) {
-      if (steps >= max_steps) {
-        *steps_out = (int)steps;
-        return MW_FLAG_STEPS;
-      }
-      ++steps;
-      const long long ui = s.u[i];
-      const int* __restrict__ row = ov + (long)i * nc;
-      unsigned long long key = MW_NOKEY;
-      for (int it = t; it < nrem; it += MW_THREADS) {
-        const int j = s.remaining[it];
-        const int cnt = row[j];
-        long long spj = s.sp[j];
-        if (cnt >= min_overlap) {   // a finite cost: only then is anything added
-          const long long r = minVal - (long long)cnt - ui - s.v[j];
-          if (r < spj) {
-            s.path[j] = (unsigned short)i;
-            s.sp[j] = r;
-            spj = r;
-          }
-        }
-        if (spj != MW_INF) {
-          const unsigned tie = s.row4col[j] == MW_NONE ? (unsigned)(MW_MAXC - 1 - it) : (unsigned)(MW_MAXC + it);
-          const unsigned long long k = ((unsigned long long)(spj + MW_BIAS) << MW_TIE_BITS) | tie;
-          key = k < key ? k : key;
-        }
-      }
-      key = mw_wave_min(key);
-      if ((t & 63) == 0) s.wmin[t >> 6] = key;
-      __syncthreads();
-#pragma unroll
-      for (int wv = 0; wv < MW_THREADS / 64; ++wv) key = s.wmin[wv] < key ? s.wmin[wv] : key;
-      if (key == MW_NOKEY) {   // lowest == inf: no complete assignment
-        *steps_out = (int)steps;
-        return MW_FLAG_ASSIGN;
-      }
-      minVal = (long long)(key >> MW_TIE_BITS) - MW_BIAS;
-      const int tie = (int)(key & (unsigned long long)(2 * MW_MAXC - 1));
-      const int index = tie >= MW_MAXC ? tie - MW_MAXC : MW_MAXC - 1 - tie;
-      --nrem;
-      if ((index & (MW_THREADS - 1)) == t) {   // the thread that owns the chosen position parks its column behind nrem
-        const int j = s.remaining[index];
-        s.remaining[index] = s.remaining[nrem];
-        s.remaining[nrem] = (unsigned short)j;
-        s.sel_j = j;
-        s.sel_owner = s.row4col[j];
-      }
-      __syncthreads();
-      const int j = s.sel_j, owner = s.sel_owner;
-      if (owner == (int)MW_NONE) sink = j;
-      else i = owner;
-    }
-    // dual updates over the scanned columns remaining[nrem .. nc) and their owners, then the augmentation from the sink
-    for (int p = nrem + t; p < nc; p += MW_THREADS) {
-      const int j = s.remaining[p];
-      const long long d = minVal - s.sp[j];
-      s.v[j] -= d;
-      if (j != sink) s.u[s.row4col[j]] += d;   // the scanned rows other than cur: col4row[row] == j
-    }
-    if (t == 0) s.u[cur] += minVal;
-    __syncthreads();
-    if (t == 0) {
-      int j = sink;
-      for (int n = 0; n < nr; ++n) {   // a path visits a row once: at most nr edges end at `cur`
-        const int r = s.path[j];
-        s.row4col[j] = (unsigned short)r;
-        const int nx = s.col4row[r];
-        s.col4row[r] = (unsigned short)j;
-        j = nx;
-        if (r == cur) break;
-      }
-    }
-    __syncthreads();
-  }
-  *steps_out = (int)steps;
-  return 0;
-}
 
 __global__ __launch_bounds__(MW_THREADS) void mw_solve_kernel(WideWs w, int min_overlap, long max_steps, int* __restrict__ inf,
                                                               int* __restrict__ asg) {
@@ -395,10 +257,13 @@ __global__ __launch_bounds__(MW_THREADS) void mw_solve_kernel(WideWs w, int min_
     if (feasible) {
       const bool tr = P > N;   // SciPy works on the transpose when there are more rows than columns
       const int nr = tr ? N : P, nc = tr ? P : N;
-      flags = mw_solve(s, nr, nc, min_overlap, w.ov, max_steps > 0 ? max_steps : 32l * nr, &steps);
+      const int* __restrict__ ov = w.ov;   // solver row i is contiguous: mw_count_kernel stored the transpose when P > N
+      flags = lsap_solve<MW_THREADS, MW_MAXC, lsap_log2(MW_MAX_W)>(
+          s.ls, nr, nc, min_overlap, [=](int i, int j) { return ov[(long)i * nc + j]; }, max_steps > 0 ? max_steps : 32l * nr,
+          &steps);
       if (!flags)
         for (int r = t; r < nr; r += MW_THREADS) {
-          const int c = s.col4row[r];
+          const int c = s.ls.col4row[r];
           const int row = tr ? c : r, col = tr ? r : c;   // of the P x N matrix
           w.map_has[col] = 1;
           w.map_val[col] = w.val[row];
@@ -441,7 +306,12 @@ using namespace mused;
 
 extern "C" {
 
-long mused_match_hung_wide_ws_bytes(int W) { return W < 1 || W > MW_MAX_W ? -1 : mw_ws_bytes(W); }
+long mused_match_hung_wide_ws_bytes(int W) {
+  if (W < 1 || W > MW_MAX_W) return -1;
+  size_t bytes;
+  mw_carve(nullptr, W, &bytes);
+  return (long)bytes;
+}
 
 int mused_match_hung_wide_chain(const int* raw, int K_windows, int W, const int* prev0, int min_overlap, long max_steps,
                                 int* matched_out, int* info_out, int* assign_out, void* ws, long ws_bytes, void* stream) {
@@ -449,14 +319,15 @@ int mused_match_hung_wide_chain(const int* raw, int K_windows, int W, const int*
   MUSED_REQUIRE(W >= 1 && W <= MW_MAX_W, "mused_match_hung_wide_chain: W must lie in [1, 2^20] (the solver's key bound)");
   MUSED_REQUIRE((long)K_windows * W < (1l << 31) && K_windows < (1 << 18) && max_steps >= 0,
                 "mused_match_hung_wide_chain: K_windows * W must stay below 2^31, K_windows below 2^18, max_steps >= 0");
-  MUSED_REQUIRE(ws_bytes >= mw_ws_bytes(W) && ((size_t)ws & 255) == 0,
+  size_t need;
+  const WideWs w = mw_carve(ws, W, &need);
+  MUSED_REQUIRE(ws_bytes >= (long)need && ((size_t)ws & 255) == 0,
                 "mused_match_hung_wide_chain: workspace too small or not 256-byte aligned");
   static LdsOptIn opt;
   const hipError_t aerr = allow_dynamic_lds(opt, reinterpret_cast<const void*>(mw_solve_kernel), sizeof(WideLds));
   MUSED_CHECK_HIP(aerr);
   hipStream_t st = (hipStream_t)stream;
-  const WideWs w = mw_carve(ws, W);
-  MUSED_CHECK_HIP(hipMemsetAsync(w.ctl, 0, 256, st));
+  MUSED_CHECK_HIP(hipMemsetAsync(w.ctl, 0, MW_CTL_BYTES, st));
   MUSED_CHECK_HIP(hipMemsetAsync(info_out, 0, sizeof(int) * (size_t)K_windows * MW_INFO, st));
   if (assign_out) MUSED_CHECK_HIP(hipMemsetAsync(assign_out, 0xff, sizeof(int) * (size_t)K_windows * MW_MAXC, st));
   const int gw = cdiv(W, MW_THREADS);

@@ -1,5 +1,5 @@
 // Wave-level data movement on fp64 values without the LDS crossbar: DPP moves and v_permlane{16,32}_swap (gfx950).
-// Shared by the Jacobi kernels (eig.hip) and the tridiagonalisation solver (trd.hip).
+// Shared by the Jacobi kernels (eig.hip), the tridiagonalisation solver (trd.hip) and the label matching (match*.hip).
 #pragma once
 #include "common.h"
 
@@ -60,6 +60,16 @@ __device__ __forceinline__ double wave_allsum(double v) {
   v = v + xchg16(v);
   v = v + xchg32(v);
   return v;
+}
+
+// minimum of a 64-bit key over the 64 lanes, result in every lane (the assignment solver's selection, lsap.h)
+__device__ __forceinline__ unsigned long long wave_allmin_u64(unsigned long long k) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(k, o);
+    k = other < k ? other : k;
+  }
+  return k;
 }
 
 }  // namespace mused

@@ -722,36 +722,49 @@ def _match_entry(method):
         raise ValueError("Invalid method. Choose 'hungarian' or 'pot'.") from None
 
 
-def match_chain_launch(raw_dev, prev_dev, min_overlap, stream=None, want_plan=False, method="pot"):
-    """One mused_match_pot_chain (method "pot") or mused_match_hung_chain ("hungarian") launch over raw_dev (K x W int32
-    CUDA) against prev_dev (W int32 CUDA or None) -> (matched K x W int32 CUDA, info K x 8 int32 NumPy, and with want_plan
-    the diagnostic output, else None: plans K x 65536 fp64 CUDA for "pot", assign K x 256 int32 CUDA -- the column of each
-    row of the P x N cost matrix or -1 -- for "hungarian").  Synchronises the stream."""
+def _match_launch(kind, entry, ws_bytes, diag, raw_dev, prev_dev, min_overlap, stream, extra=()):
+    """One call of a chain entry over raw_dev (K x W int32 CUDA) against prev_dev (W int32 CUDA or None) -> (matched K x W
+    int32 CUDA, info K x 8 int32 NumPy, the diagnostic output K x diag[0] of dtype name diag[1] on the device -- allocated by
+    torch's diag[2], "empty" where the entry fills it itself -- or None for diag None).  The workspace is cached per (device,
+    stream, kind) and only grows; ws_bytes is its size for this call, or a callable for a size that never changes, asked
+    when nothing is cached.  `extra` are the entry's arguments between min_overlap and matched_out.  Synchronises the
+    stream."""
     import ctypes as C
 
     import torch
 
     from . import _lib
 
-    entry, ws_entry, diag_len, diag_dtype = _match_entry(method)
     K, W = raw_dev.shape
     dev = raw_dev.device
     st = stream if stream is not None else torch.cuda.current_stream()
     with torch.cuda.stream(st):
-        ws = _MATCH_WS.get((dev, st.cuda_stream, method))
-        if ws is None:
+        key = (dev, st.cuda_stream, kind)
+        ws = _MATCH_WS.get(key)
+        if ws is None or (not callable(ws_bytes) and ws.numel() < ws_bytes):
             if len(_MATCH_WS) > 16:
                 _MATCH_WS.clear()
-            ws = _MATCH_WS[(dev, st.cuda_stream, method)] = torch.empty(int(getattr(_lib.lib(), ws_entry)()), dtype=torch.uint8,
-                                                                        device=dev)
+            ws = _MATCH_WS[key] = torch.empty(int(ws_bytes()) if callable(ws_bytes) else ws_bytes, dtype=torch.uint8, device=dev)
         matched = torch.empty((K, W), dtype=torch.int32, device=dev)
         info = torch.empty((K, 8), dtype=torch.int32, device=dev)
-        plans = torch.zeros((K, diag_len), dtype=getattr(torch, diag_dtype), device=dev) if want_plan else None
-        _lib.call(entry, _eng.ptr(raw_dev), K, W, _eng.ptr(prev_dev) if prev_dev is not None else None,
-                  int(min_overlap), _eng.ptr(matched), _eng.ptr(info), _eng.ptr(plans) if want_plan else None, _eng.ptr(ws),
-                  ws.numel(), C.c_void_p(st.cuda_stream))
+        out = getattr(torch, diag[2])((K, diag[0]), dtype=getattr(torch, diag[1]), device=dev) if diag else None
+        _lib.call(entry, _eng.ptr(raw_dev), K, W, _eng.ptr(prev_dev) if prev_dev is not None else None, int(min_overlap), *extra,
+                  _eng.ptr(matched), _eng.ptr(info), _eng.ptr(out) if diag else None, _eng.ptr(ws), ws.numel(),
+                  C.c_void_p(st.cuda_stream))
         info_h = info.cpu().numpy()
-    return matched, info_h, plans
+    return matched, info_h, out
+
+
+def match_chain_launch(raw_dev, prev_dev, min_overlap, stream=None, want_plan=False, method="pot"):
+    """One mused_match_pot_chain (method "pot") or mused_match_hung_chain ("hungarian") launch over raw_dev (K x W int32
+    CUDA) against prev_dev (W int32 CUDA or None) -> (matched K x W int32 CUDA, info K x 8 int32 NumPy, and with want_plan
+    the diagnostic output, else None: plans K x 65536 fp64 CUDA for "pot", assign K x 256 int32 CUDA -- the column of each
+    row of the P x N cost matrix or -1 -- for "hungarian").  Synchronises the stream."""
+    from . import _lib
+
+    entry, ws_entry, diag_len, diag_dtype = _match_entry(method)
+    return _match_launch(method, entry, getattr(_lib.lib(), ws_entry), (diag_len, diag_dtype, "zeros") if want_plan else None,
+                         raw_dev, prev_dev, min_overlap, stream)
 
 
 MATCH_WIDE_MAXC = 4096   # distinct labels a side the wide Hungarian chain takes (csrc/match_wide.hip)
@@ -763,33 +776,15 @@ def match_wide_launch(raw_dev, prev_dev, min_overlap, stream=None, want_assign=F
     over raw_dev (K x W int32 CUDA, the TRUE label values) against prev_dev (W int32 CUDA or None) -> (matched K x W int32
     CUDA, info K x 8 int32 NumPy, and with want_assign the K x 4096 int32 CUDA columns of each row or -1, else None).
     max_steps: the solver's step budget per window (0: 32 min(P, N)).  Synchronises the stream."""
-    import ctypes as C
-
-    import torch
-
     from . import _lib
 
-    K, W = raw_dev.shape
-    dev = raw_dev.device
-    st = stream if stream is not None else torch.cuda.current_stream()
-    with torch.cuda.stream(st):
-        need = int(_lib.lib().mused_match_hung_wide_ws_bytes(int(W)))
-        if need < 0:
-            raise ValueError(f"match_wide_launch: W = {W} outside [1, 2^20]")
-        key = (dev, st.cuda_stream, "hungarian_wide")
-        ws = _MATCH_WS.get(key)
-        if ws is None or ws.numel() < need:
-            if len(_MATCH_WS) > 16:
-                _MATCH_WS.clear()
-            ws = _MATCH_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-        matched = torch.empty((K, W), dtype=torch.int32, device=dev)
-        info = torch.empty((K, 8), dtype=torch.int32, device=dev)
-        assign = torch.empty((K, MATCH_WIDE_MAXC), dtype=torch.int32, device=dev) if want_assign else None
-        _lib.call("mused_match_hung_wide_chain", _eng.ptr(raw_dev), K, W, _eng.ptr(prev_dev) if prev_dev is not None else None,
-                  int(min_overlap), int(max_steps), _eng.ptr(matched), _eng.ptr(info), _eng.ptr(assign) if want_assign else None,
-                  _eng.ptr(ws), ws.numel(), C.c_void_p(st.cuda_stream))
-        info_h = info.cpu().numpy()
-    return matched, info_h, assign
+    W = int(raw_dev.shape[1])
+    need = int(_lib.lib().mused_match_hung_wide_ws_bytes(W))
+    if need < 0:
+        raise ValueError(f"match_wide_launch: W = {W} outside [1, 2^20]")
+    return _match_launch("hungarian_wide", "mused_match_hung_wide_chain", need,
+                         (MATCH_WIDE_MAXC, "int32", "empty") if want_assign else None, raw_dev, prev_dev, min_overlap, stream,
+                         extra=(int(max_steps),))
 
 
 def _labels_to_device_wide(x, device):

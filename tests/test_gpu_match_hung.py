@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, regen_inputs
-from test_match_hung_host import MIN_OVERLAP, SEEDS, TUPLES, host_pair
+from test_match_hung_host import MIN_OVERLAP, SEEDS, TIE_SEEDS, TIE_SHAPES, TUPLES, host_pair, host_tie
 from test_match_pot_host import drift_chain
 
 pytestmark = pytest.mark.gpu
@@ -15,7 +15,8 @@ torch = pytest.importorskip("torch")
 from mused_amd import distributed as mdist  # noqa: E402
 from mused_amd import matrix_operations as mo  # noqa: E402
 
-CASES = [(s,) + t for t in TUPLES for s in SEEDS]
+# (seed, W, kp, kn) of the drifting pairs, then ("tie", seed, P, N) of the two-valued cost tables
+CASES = [(s,) + t for t in TUPLES for s in SEEDS] + [("tie", s) + t for t in TIE_SHAPES for s in TIE_SEEDS]
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -55,7 +56,7 @@ def table_chain(seed=1, W=6000, k=150, windows=6):
 
 @pytest.mark.parametrize("c", CASES, ids=lambda c: "-".join(str(x) for x in c))
 def test_pair_against_scipy_and_the_specification(c):
-    h = host_pair(*c)
+    h = host_tie(*c[1:]) if c[0] == "tie" else host_pair(*c)
     matched, info, assign = launch(h["new"], h["prev"])
     P, N, steps, feasible, flags, _, done, _ = (int(x) for x in info[0])
     print(f"case {c}: P {P} N {N} steps {steps} (specification {h['spec'][2]}) feasible {feasible} flags {flags}")

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 from scipy.optimize import linear_sum_assignment
 
-from test_match_hung_host import TUPLES, pair
+from test_match_hung_host import TIE_WIDE_SHAPES, TUPLES, host_tie, pair, tie_pair
 from test_match_pot_host import drift_chain
 from test_match_wide_host import I32_MAX, I32_MIN, MIN_OVERLAP, dbscan_like, spec_chain, spec_pair, wide_chain, wide_pair
 
@@ -74,9 +74,9 @@ def check_against_specification(prev, new):
 
 # ---- wide equals narrow where both apply -------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("t", TUPLES, ids=lambda t: "-".join(str(x) for x in t))
+@pytest.mark.parametrize("t", TUPLES + [("tie", 65, 64), ("tie", 256, 256)], ids=lambda t: "-".join(str(x) for x in t))
 def test_equals_the_narrow_chain_on_its_table(t):
-    prev, new = pair(1, *t)
+    prev, new = tie_pair(0, *t[1:]) if t[0] == "tie" else pair(1, *t)
     m_n, i_n, a_n = narrow(new, prev)
     m_w, i_w, a_w = wide(new, prev)
     assert int(i_n[0, 6]) == 1 and np.array_equal(i_w[:, [0, 1, 2, 3, 4, 6]], i_n[:, [0, 1, 2, 3, 4, 6]])
@@ -94,9 +94,16 @@ def test_equals_the_narrow_chain_on_a_drifting_chain():
 
 # ---- beyond the narrow limits, against match_labels ------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("c", [(0, 264, 40, 8), (1, 264, 40, 8), (0, 1040, 40, 8)], ids=lambda c: "-".join(str(x) for x in c))
+def tie_spec(P, N):
+    """spec_pair's keys for the two-valued cost table of seed 0."""
+    h = host_tie(0, P, N)
+    return dict(h, steps=h["spec"][2], rows=h["scipy"][0], cols=h["scipy"][1])
+
+
+@pytest.mark.parametrize("c", [(0, 264, 40, 8), (1, 264, 40, 8), (0, 1040, 40, 8)] + [("tie",) + s for s in TIE_WIDE_SHAPES],
+                         ids=lambda c: "-".join(str(x) for x in c))
 def test_generator_pair_against_the_specification(c):
-    h = spec_pair(*c)
+    h = tie_spec(*c[1:]) if c[0] == "tie" else spec_pair(*c)
     matched, info, assign = wide(h["new"], h["prev"])
     print(f"case {c}: device info {info[0].tolist()}, specification steps {h['steps']}")
     assert info[0].tolist() == [h["P"], h["N"], h["steps"], 1, 0, 0, 1, 0]
@@ -105,7 +112,8 @@ def test_generator_pair_against_the_specification(c):
     e[h["rows"]] = h["cols"]
     assert np.array_equal(assign[0], e)
     before = mo.match_fallbacks
-    out = mo.match_clusters_on_device(h["prev"], h["new"], MIN_OVERLAP, method="hungarian", wide=True)
+    out = mo.match_clusters_on_device(h["prev"], h["new"], MIN_OVERLAP, method="hungarian",
+                                      wide="only" if c[0] == "tie" else True)
     assert mo.match_fallbacks == before and np.array_equal(np.asarray(out), h["labels"])
 
 

@@ -33,6 +33,35 @@ def pair(seed, W, kp, kn):
     return prev, new
 
 
+# (P, N) of the two-valued cost tables: the narrow chain's (lane boundary, counts read from the workspace beyond 24,576
+# entries, capacity in both orientations) and the ones beyond it (a position's owner wraps at 256 and 512 threads)
+TIE_SHAPES = [(1, 1), (1, 7), (7, 1), (2, 2), (64, 64), (65, 64), (64, 65), (160, 160), (256, 256), (256, 255)]
+TIE_SEEDS = (0, 1)
+TIE_WIDE_SHAPES = [(257, 257), (300, 290), (513, 513), (512, 520)]
+TIE_STEPS = {(64, 64): 110, (65, 64): 103, (64, 65): 136, (160, 160): 280, (256, 256): 476, (256, 255): 482, (257, 257): 510,
+             (300, 290): 504, (513, 513): 1070}   # Dijkstra steps of the specification at seed 0
+
+
+def tie_pair(seed, P, N):
+    """Labels whose P x N overlap counts take two values only, 6 on about two entries a row and 3 elsewhere (every entry
+    is finite at min_overlap = 3): almost every selection of the solver is decided by its tie rule."""
+    C = np.where(np.random.default_rng(seed).random((P, N)) < 2 / max(P, N), 6, 3)
+    i, j = np.nonzero(C)
+    return np.repeat(i, C[i, j]), np.repeat(j, C[i, j])
+
+
+@functools.lru_cache(maxsize=None)
+def host_tie(seed, P, N):
+    """host_pair's dict for tie_pair(seed, P, N), from one contingency pass (hungarian.match_labels is held to match_clusters
+    by tests/test_match_wide_host.py; the host's own P x N loop would take minutes at 256 x 256 and W = 200,000)."""
+    prev, new = tie_pair(seed, P, N)
+    up, un, _, cnt = hg.overlap_counts(prev, new)
+    cost = hg.costs_of(cnt, MIN_OVERLAP)
+    return dict(prev=prev, new=new, P=len(up), N=len(un), cost=cost, feasible=hg.is_feasible(cost),
+                scipy=linear_sum_assignment(cost), spec=hg.lsap(cost),
+                labels=np.asarray(hg.match_labels(prev, new, MIN_OVERLAP)[0]))
+
+
 @functools.lru_cache(maxsize=None)
 def host_pair(seed, W, kp, kn):
     """dict(prev, new, P, N, cost, feasible (match_clusters' own test), scipy (rows, cols), spec (rows, cols, steps),
@@ -91,6 +120,24 @@ def test_label_pair_table():
     # sizes on both sides of the kernel's limits and orientations: P < N, P > N, 256 x 256
     shapes = {(h["P"], h["N"]) for h in hs}
     assert (256, 256) in shapes and any(p < n for p, n in shapes) and any(p > n for p, n in shapes)
+
+
+def test_two_valued_tables_against_scipy():
+    """The specification returns SciPy's assignment where ties decide nearly every step, every pair is feasible, paths are
+    walked (the step counts of seed 0 are pinned: the device tests compare with them), and W stays below the wide chain's 2^20."""
+    for P, N in TIE_SHAPES + TIE_WIDE_SHAPES:
+        for seed in TIE_SEEDS if (P, N) in TIE_SHAPES else (0,):
+            h = host_tie(seed, P, N)
+            assert (h["P"], h["N"]) == (P, N) and h["feasible"] and set(np.unique(-h["cost"])) <= {3.0, 6.0}
+            rows, cols, steps = h["spec"]
+            assert np.array_equal(rows, h["scipy"][0]) and np.array_equal(cols, h["scipy"][1])
+            assert min(P, N) <= steps <= 32 * min(P, N)   # the wide chain's default budget
+            if seed == 0 and (P, N) in TIE_STEPS:
+                assert steps == TIE_STEPS[(P, N)] > min(P, N)
+            up, un = np.unique(h["prev"]), np.unique(h["new"])
+            table = dict(zip(un[cols].tolist(), up[rows].tolist()))
+            assert np.array_equal(h["labels"], [table.get(c, c) for c in h["new"].tolist()])
+    assert max(len(host_tie(0, P, N)["new"]) for P, N in TIE_WIDE_SHAPES) == 801801 < 1 << 20
 
 
 def test_transposed_output_is_sorted_by_row():
