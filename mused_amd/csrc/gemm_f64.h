@@ -78,6 +78,20 @@ struct GemmArgs {
   int tail_split_stride;
   int tail_pend;
   const double* tail_zero;
+  // Optional fill source of a symmetric launch with a tail (the Gram of sketch buffers): P P^T of the tail rows of every lane,
+  // formed beforehand -- lane (z / tail_per) at fill + (z / tail_per) * fill_stride, leading dimension fill_ld >= tail_pend,
+  // only its tail_pend x tail_pend corner is read.  A tile (tm, tn), tm <= tn, with 128 tm >= nk holds nothing but entries of
+  // it and +0.0: C[i][j] = PP[i - nk][j - nk] for i, j < nk + tail_pend, +0.0 elsewhere.  Such a tile runs no K loop: the
+  // workgroup copies it (and its mirror) through epi.put.  The copied doubles are the ones the K loop gives -- an entry of
+  // the MFMA's K chain does not depend on where in a tile it is computed (tests/test_gpu_swfd_ppt.py) -- for finite
+  // operands: a zero row times a row with an infinity is NaN when computed and +0.0 when copied.
+  const double* fill;
+  long fill_stride;
+  int fill_ld;
+  // Second batch level (GRP instantiations of the kernel only): entry z reads its operands at
+  // (z % grp_per) * strideA + (z / grp_per) * grp_stride -- row blocks of several lanes read in place.
+  int grp_per;
+  long grp_stride;
 };
 
 // the split of one batch entry (TAIL kernels): rows [nk, nend) come from `tail`, rows from nend on are zero
@@ -547,8 +561,24 @@ inline int gemm_sym_diag_enabled() {
   return on;
 }
 
+// A tile that is copied (GemmArgs::fill): rows [r0, r0 + 128) x columns [c0, c0 + 128) of entry z, r0 and c0 >= nk.  A thread
+// owns one column and every second row: a wave's load and its store each cover 512 contiguous bytes of one row.
+template <typename Epi>
+__device__ __forceinline__ void gemm_fill_tile(const GemmArgs& g, const Epi& epi, int z, const double* __restrict__ pp, int nk,
+                                               int nend, int r0, int c0) {
+  const int c = c0 + (threadIdx.x & 127);
+  if (c >= g.N) return;
+  const bool cin = c < nend;
+  const int rlim = min(g.M, r0 + GEMM_BM);
+#pragma unroll 8
+  for (int r = r0 + (threadIdx.x >> 7); r < rlim; r += 2) {
+    const double v = (cin && r < nend) ? pp[(long)(r - nk) * g.fill_ld + (c - nk)] : 0.0;
+    epi.put(z, r, c, epi.value(r, c, v));
+  }
+}
+
 // Epilogue concept:  void operator()(int batch, int row, int col, double v) const
-template <typename TA, typename TB, bool A_KC, bool B_KC, bool VEC, typename Epi, bool TAIL = false>
+template <typename TA, typename TB, bool A_KC, bool B_KC, bool VEC, typename Epi, bool TAIL = false, bool GRP = false>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_f64_kernel(GemmArgs g, Epi epi) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
 
@@ -598,8 +628,14 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_f64_kernel(GemmArgs g, E
     k_lo = z * g.kchunk;
     k_hi = min(g.K, k_lo + g.kchunk);
   } else {
-    A += (long)zb * g.strideA;
-    B += (long)zb * g.strideB;
+    if constexpr (GRP) {
+      const int grp = zb / g.grp_per;
+      A += (long)(zb - grp * g.grp_per) * g.strideA + (long)grp * g.grp_stride;
+      B += (long)(zb - grp * g.grp_per) * g.strideB + (long)grp * g.grp_stride;
+    } else {
+      A += (long)zb * g.strideA;
+      B += (long)zb * g.strideB;
+    }
     if (g.bsplit) {
       k_lo = (z - zb * g.bsplit) * g.kchunk;
       k_hi = min(g.K, k_lo + g.kchunk);
@@ -614,6 +650,15 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_f64_kernel(GemmArgs g, E
     sp.nend = sp.nk + g.tail_pend;
     sp.tail = g.tail + (long)(zb / g.tail_per) * g.tail_stride;
     sp.zero = g.tail_zero;
+    if constexpr (A_KC && B_KC) {
+      // a tile of pending rows and zero rows only: copied from the lane's P P^T (uniform over the workgroup; tm <= tn)
+      if (g.fill && g.sym && m0 >= sp.nk) {
+        const double* pp = g.fill + (long)(zb / g.tail_per) * g.fill_stride;
+        gemm_fill_tile(g, epi, z, pp, sp.nk, sp.nend, m0, n0);
+        if (mirror) gemm_fill_tile(g, epi, z, pp, sp.nk, sp.nend, n0, m0);
+        return;
+      }
+    }
   }
 
   if constexpr (std::is_same<TA, TB>::value && A_KC == B_KC) {
@@ -701,18 +746,18 @@ struct EpiStore {
   }
 };
 
-template <typename TA, typename TB, bool A_KC, bool B_KC, bool VEC, typename Epi, bool TAIL = false>
+template <typename TA, typename TB, bool A_KC, bool B_KC, bool VEC, typename Epi, bool TAIL = false, bool GRP = false>
 int gemm_f64_prepare_t() {
   // > 64 KiB of dynamic LDS needs the attribute once per kernel; done outside stream capture.  Several host
   // threads drive the library (sketch groups + the main path): one-time, thread-safe.
   static LdsOptIn opt;
-  auto k = gemm_f64_kernel<TA, TB, A_KC, B_KC, VEC, Epi, TAIL>;
+  auto k = gemm_f64_kernel<TA, TB, A_KC, B_KC, VEC, Epi, TAIL, GRP>;
   const hipError_t err = allow_dynamic_lds(opt, reinterpret_cast<const void*>(k), GEMM_LDS_BYTES);
   MUSED_CHECK_HIP(err);
   return MUSED_OK;
 }
 
-template <typename TA, typename TB, bool A_KC, bool B_KC, typename Epi, bool TAIL = false>
+template <typename TA, typename TB, bool A_KC, bool B_KC, typename Epi, bool TAIL = false, bool GRP = false>
 int gemm_f64_launch_t(GemmArgs g, int batch, Epi epi, bool vec, hipStream_t stream) {
   g.tiles_m = cdiv(g.M, GEMM_BM);
   g.tiles_n = cdiv(g.N, GEMM_BN);
@@ -721,12 +766,12 @@ int gemm_f64_launch_t(GemmArgs g, int batch, Epi epi, bool vec, hipStream_t stre
   dim3 grid(g.sym ? g.tiles_n * (g.tiles_n + 1) / 2 : g.tiles_m * g.tiles_n, 1, batch);
   int rc;
   if (vec) {
-    if ((rc = gemm_f64_prepare_t<TA, TB, A_KC, B_KC, true, Epi, TAIL>())) return rc;
-    hipLaunchKernelGGL((gemm_f64_kernel<TA, TB, A_KC, B_KC, true, Epi, TAIL>), grid, dim3(GEMM_THREADS), GEMM_LDS_BYTES,
+    if ((rc = gemm_f64_prepare_t<TA, TB, A_KC, B_KC, true, Epi, TAIL, GRP>())) return rc;
+    hipLaunchKernelGGL((gemm_f64_kernel<TA, TB, A_KC, B_KC, true, Epi, TAIL, GRP>), grid, dim3(GEMM_THREADS), GEMM_LDS_BYTES,
                        stream, g, epi);
   } else {
-    if ((rc = gemm_f64_prepare_t<TA, TB, A_KC, B_KC, false, Epi, TAIL>())) return rc;
-    hipLaunchKernelGGL((gemm_f64_kernel<TA, TB, A_KC, B_KC, false, Epi, TAIL>), grid, dim3(GEMM_THREADS), GEMM_LDS_BYTES,
+    if ((rc = gemm_f64_prepare_t<TA, TB, A_KC, B_KC, false, Epi, TAIL, GRP>())) return rc;
+    hipLaunchKernelGGL((gemm_f64_kernel<TA, TB, A_KC, B_KC, false, Epi, TAIL, GRP>), grid, dim3(GEMM_THREADS), GEMM_LDS_BYTES,
                        stream, g, epi);
   }
   MUSED_LAUNCH_CHECK();

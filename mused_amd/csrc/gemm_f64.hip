@@ -26,6 +26,10 @@ int gemm_f64_prepare_all() {
 #define PREP(a, b, v) rc |= gemm_f64_prepare_t<double, double, a, b, v, EpiStore, true>()
   PREP(true, true, true); PREP(true, true, false); PREP(true, false, true); PREP(true, false, false);
 #undef PREP
+  rc |= gemm_f64_prepare_t<double, double, true, true, true, EpiStore, false, true>();
+  rc |= gemm_f64_prepare_t<double, double, true, true, false, EpiStore, false, true>();
+  rc |= gemm_f64_prepare_t<float, float, true, true, true, EpiStore, false, true>();
+  rc |= gemm_f64_prepare_t<float, float, true, true, false, EpiStore, false, true>();
   return rc ? MUSED_ERR_HIP : MUSED_OK;
 }
 
@@ -36,6 +40,10 @@ static int gemm_set_tail(GemmArgs& g, const GemmTail& t, bool a_kc, bool b_kc, l
   g.tail = t.rows; g.tail_stride = t.lane_stride; g.tail_per = t.per_lane;
   g.tail_split = t.split; g.tail_split_stride = t.split_stride; g.tail_pend = t.pend; g.tail_zero = t.zero_row;
   if (g.sym && t.plain_diag) g.sym = 3;
+  if (t.fill) {
+    MUSED_REQUIRE(g.sym && !g.bsplit && !g.splitk && t.fill_ld >= t.pend, "gemm_f64: a fill source needs a Gram launch that is not split over K");
+    g.fill = t.fill; g.fill_stride = t.fill_stride; g.fill_ld = t.fill_ld;
+  }
   vec = vec && vec_ok<double>(t.rows, ld, t.lane_stride) && vec_ok<double>(t.zero_row, ld, 0);
   return MUSED_OK;
 }
@@ -62,6 +70,24 @@ int gemm_f64(bool a_kc, bool b_kc, const double* A, long lda, long strideA, cons
   if (a_kc && !b_kc) return gemm_f64_launch_t<double, double, true, false>(g, batch, epi, vec, stream);
   if (!a_kc && b_kc) return gemm_f64_launch_t<double, double, false, true>(g, batch, epi, vec, stream);
   return gemm_f64_launch_t<double, double, false, false>(g, batch, epi, vec, stream);
+}
+
+int gemm_gram_rows(const void* A, bool f32, long lda, long strideA, int per_group, long group_stride, double* C, long ldc,
+                   long strideC, int M, int K, int batch, int plain_diag, hipStream_t stream) {
+  MUSED_REQUIRE(per_group >= 1 && ldc >= M, "gemm_gram_rows: bad arguments");
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A = A; g.B = A; g.lda = lda; g.ldb = lda; g.strideA = strideA; g.strideB = strideA;
+  g.M = M; g.N = M; g.K = K;
+  g.sym = plain_diag ? 3 : 1;
+  g.grp_per = per_group; g.grp_stride = group_stride;
+  EpiStore epi{C, ldc, strideC, 1.0};
+  if (f32) {
+    const bool vec = vec_ok<float>(A, lda, strideA) && group_stride % 4 == 0;
+    return gemm_f64_launch_t<float, float, true, true, EpiStore, false, true>(g, batch, epi, vec, stream);
+  }
+  const bool vec = vec_ok<double>(A, lda, strideA) && group_stride % 2 == 0;
+  return gemm_f64_launch_t<double, double, true, true, EpiStore, false, true>(g, batch, epi, vec, stream);
 }
 
 int gemm_f64_splitk(bool a_kc, bool b_kc, const double* A, long lda, const double* B, long ldb, double* partial,
@@ -210,6 +236,25 @@ int mused_debug_gemm_f64_batched_tail(int a_kc, int b_kc, const double* A, long 
                                           nsplit, (hipStream_t)stream, nullptr, list, &t);
   if (rc != MUSED_OK) return rc;
   return mused::gemm_batched_splitk_reduce(partial, nsplit, (long)M * N, C, batch, nullptr, (hipStream_t)stream, list);
+}
+
+// The Gram launch with a tail and a fill source (GemmTail::fill): tiles of tail rows and zero rows are copied from P P^T.
+int mused_debug_gemm_f64_batched_tail_fill(const double* A, long lda, long strideA, double* C, long ldc, long strideC, int n, int K,
+                                           int batch, const int* list, const double* tail, long tail_stride, int per_lane,
+                                           const int* split, int split_stride, int pend, const double* zero_row, int plain_diag,
+                                           const double* fill, long fill_stride, int fill_ld, void* stream) {
+  MUSED_REQUIRE(A && C && tail && split && fill && batch >= 1, "mused_debug_gemm_f64_batched_tail_fill: bad arguments");
+  const mused::GemmTail t{tail, tail_stride, per_lane, split, split_stride, pend, zero_row, plain_diag, fill, fill_stride, fill_ld};
+  return mused::gemm_f64(true, true, A, lda, strideA, A, lda, strideA, C, ldc, strideC, n, n, K, batch, 1.0, (hipStream_t)stream,
+                         nullptr, list, nullptr, &t);
+}
+
+// P P^T of row blocks read in place (gemm_gram_rows; dtype MUSED_F32 or MUSED_F64).
+int mused_debug_gemm_gram_rows(const void* A, int dtype, long lda, long strideA, int per_group, long group_stride, double* C,
+                               long ldc, long strideC, int M, int K, int batch, int plain_diag, void* stream) {
+  MUSED_REQUIRE(A && C && batch >= 1 && (dtype == MUSED_F32 || dtype == MUSED_F64), "mused_debug_gemm_gram_rows: bad arguments");
+  return mused::gemm_gram_rows(A, dtype == MUSED_F32, lda, strideA, per_group, group_stride, C, ldc, strideC, M, K, batch,
+                               plain_diag, (hipStream_t)stream);
 }
 
 int mused_gemm_f64_splitk(int a_kc, int b_kc, const double* A, long lda, const double* B, long ldb, double* partial,

@@ -72,11 +72,22 @@ struct GemmTail {
   int pend;
   const double* zero_row;
   int plain_diag;  // 1: the diagonal tiles of this (Gram) launch run the ordinary main loop, as under MUSED_GEMM_SYM_DIAG=0 (tests)
+  // optional, Gram launches that are not split over K: P P^T of every lane's tail rows (lane at fill + lane * fill_stride, leading
+  // dimension fill_ld >= pend), from gemm_gram_rows on those rows.  Tiles that hold only tail rows and zero rows are copied
+  // from it instead of computed (GemmArgs::fill): the same bits for finite operands.
+  const double* fill;
+  long fill_stride;
+  int fill_ld;
 };
 int gemm_f64(bool a_kc, bool b_kc, const double* A, long lda, long strideA, const double* B, long ldb,
              long strideB, double* C, long ldc, long strideC, int M, int N, int K, int batch, double alpha,
              hipStream_t stream, const int* rep = nullptr, const int* list = nullptr, const int* kact = nullptr,
              const GemmTail* tail = nullptr);
+// Gram products of row blocks read in place, fp32 (widened exactly) or fp64 rows: C[z] = P_z P_z^T (M x M, K = the row length) for
+// z = group * per_group + e, P_z = the M rows at A + e * strideA + group * group_stride (elements), row pitch lda.  The tile
+// order, K order and MFMA sequence of the symmetric launch of gemm_f64 (plain_diag as in GemmTail).
+int gemm_gram_rows(const void* A, bool f32, long lda, long strideA, int per_group, long group_stride, double* C, long ldc,
+                   long strideC, int M, int K, int batch, int plain_diag, hipStream_t stream);
 // rep (device, batch ints, optional): entry z is computed only when rep[z] == z (duplicates are skipped)
 // list (device, 1 + batch ints, optional, instead of rep): the entries to compute, compacted -- list[0] of them, list[1 ..];
 //   workgroup z of the batch takes entry list[1 + z], so the workgroups with nothing to do are dispatched last

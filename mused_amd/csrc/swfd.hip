@@ -17,6 +17,7 @@
 // Control flow is data independent (the rotation schedule depends only on the row counter),
 // all data-dependent decisions (dumps, expiry, level choice) stay on the device: no host sync
 // anywhere on the update or query path.
+#include <type_traits>
 #include <vector>
 
 #include "internal.h"
@@ -87,6 +88,12 @@ struct Swfd {
   int pre_chunk;        // blocks per batch (0: off)
   double *pre_in, *pre_out, *pre_gram;  // [chunk][lanes][l][d] fp64 rows in / out, [chunk][lanes][l][l] Gram matrices
   EigPlan* eigp;        // order 2l, batch chunk * lanes, fixed sweeps, no sort
+  // P P^T AHEAD OF THE ROTATIONS (round 11; shared mode, gram_split == 1, fp32 / fp64 rows; MUSED_SWFD_PPT=0: off).  Rows 128 and
+  // up of a sketch's Gram matrix are pending rows and zero rows whenever nk <= 128, and all 2L sketches of a lane hold the same
+  // pending rows: P P^T of every complete block of an append call is formed once per lane, `ppt_chunk` blocks per launch
+  // (swfd_append_t), and the Gram launch of the block's rotation copies the tiles that hold nothing else (GemmArgs::fill).
+  int ppt_chunk;        // blocks per launch (0: off)
+  double* ppt;          // [chunk][lanes][l][l]
 };
 
 // sketch index = lane * 2L + kind * L + level  (kind 0 = MAIN, 1 = AUX)
@@ -535,8 +542,10 @@ __global__ void swfd_settle_shared_kernel(const double* __restrict__ T, const in
 // One rotation of all sketches.  (next, nxt): the first nxt rows of the block that follows in the same append call (row pitch
 // ldx, lanes lane_stride apart), which the settle kernel puts behind the kept rows; nxt = 0: none.  Leaves pend = 0: the
 // caller counts the nxt rows when its loop reaches them.
+// ppt: P P^T of the pending rows of every lane ([lanes][l][l], see Swfd::ppt), or null.
 template <typename Src>
-static int swfd_rotate_all(Swfd* h, hipStream_t st, const Src* next, long ldx, long lane_stride, int nxt) {
+static int swfd_rotate_all(Swfd* h, hipStream_t st, const Src* next, long ldx, long lane_stride, int nxt,
+                           const double* ppt = nullptr) {
   const int S = h->S, n2 = h->n2, d = h->d, ell = h->ell;
   int rc;
   if (h->rep)
@@ -546,7 +555,8 @@ static int swfd_rotate_all(Swfd* h, hipStream_t st, const Src* next, long ldx, l
   else
     hipLaunchKernelGGL(swfd_set_now_kernel, dim3(1), dim3(1), 0, st, h->now_dev, (long long)h->i);
   // shared mode: rows [nk, nk + pend) of every operand built from a sketch buffer are the lane's pendbuf rows
-  const GemmTail gram_tail{h->pendbuf, (long)ell * d, 2 * h->L, h->meta, 4, h->pend, h->pendbuf + (long)h->lanes * ell * d, 0};
+  const GemmTail gram_tail{h->pendbuf, (long)ell * d, 2 * h->L, h->meta, 4, h->pend, h->pendbuf + (long)h->lanes * ell * d, 0,
+                           ppt, (long)ell * ell, ell};
   const GemmTail rot_tail{h->pendbuf, (long)ell * d, 2 * h->L, h->nk0, 1, h->pend, h->pendbuf + (long)h->lanes * ell * d, 0};
   if (h->gram_split > 1) {
     const int kchunk = ((d + h->gram_split - 1) / h->gram_split + 15) / 16 * 16;
@@ -667,6 +677,9 @@ static int swfd_append_t(Swfd* h, const T* X, long ldx, long lane_stride, long m
   PreBlocks pb;
   int pre_n = 0, pre_next = 0;
   int placed = 0;  // rows of the block at r that the last rotation of this call has already put into the buffers
+  // blocks of this call whose P P^T lies in h->ppt: entries [ppt_next, ppt_n) of the chunk belong to the blocks from r on
+  int ppt_n = 0, ppt_next = 0;
+  constexpr bool ppt_rows = std::is_same<T, float>::value || std::is_same<T, double>::value;
   while (r < m) {
     if (h->i > 0 && h->i % h->N == 0 && h->restart_mark != h->i) {
       // first row of a new epoch (pend == 0 here: the epoch-end rotation has run)
@@ -678,6 +691,29 @@ static int swfd_append_t(Swfd* h, const T* X, long ldx, long lane_stride, long m
     long until = h->ell - (in_epoch % h->ell);
     if (h->N - in_epoch < until) until = h->N - in_epoch;
     const long take = (m - r) < until ? (m - r) : until;
+    const double* ppt = nullptr;
+    if (ppt_rows && h->ppt_chunk > 0 && h->pend == 0 && take == until) {
+      // a complete block: P P^T of it and of the complete blocks of the same length that follow in this call, all lanes, in
+      // one launch on the caller's rows (the workspace is reused in stream order: the rotations of the last chunk are queued)
+      if (ppt_next >= ppt_n) {
+        ppt_n = ppt_next = 0;
+        long rr = r, ii = h->i;
+        while (ppt_n < h->ppt_chunk && rr < m) {
+          const long ie = ii % h->N;
+          long u = h->ell - (ie % h->ell);
+          if (h->N - ie < u) u = h->N - ie;
+          if (u != take || m - rr < u) break;  // the short block at an epoch's end starts a chunk of its own; the call ends here
+          ++ppt_n;
+          rr += u;
+          ii += u;
+        }
+        if ((rc = gemm_gram_rows(X + r * ldx, std::is_same<T, float>::value, ldx, lane_stride, h->lanes, take * ldx, h->ppt,
+                                 h->ell, (long)h->ell * h->ell, (int)take, h->d, ppt_n * h->lanes, 0, st)))
+          return rc;
+      }
+      ppt = h->ppt + (long)ppt_next * h->lanes * h->ell * h->ell;
+      ++ppt_next;
+    }
     bool from_pre = false;
     if (h->pre_chunk > 0 && h->pend == 0 && take == until) {
       // a complete block: rotate it (and the complete blocks that follow in this call, a batch at a time) beforehand
@@ -732,7 +768,7 @@ static int swfd_append_t(Swfd* h, const T* X, long ldx, long lane_stride, long m
         if (h->N - ie < u) u = h->N - ie;
         nxt = (m - r) < u ? (m - r) : u;
       }
-      if ((rc = swfd_rotate_all<T>(h, st, nxt ? X + r * ldx : nullptr, ldx, lane_stride, (int)nxt))) return rc;
+      if ((rc = swfd_rotate_all<T>(h, st, nxt ? X + r * ldx : nullptr, ldx, lane_stride, (int)nxt, ppt))) return rc;
       placed = (int)nxt;
     }
   }
@@ -1073,6 +1109,23 @@ static int swfd_create_impl(Swfd* h, long N, double R, int d, int ell, int sweep
       (void)hipFree(h->nk0); h->nk0 = nullptr;
     }
   }
+  {
+    // MUSED_SWFD_PPT=0: every Gram tile is computed.  The workspace holds up to 16 blocks and at most 32 MB
+    // (MUSED_SWFD_PPT_CHUNK=n: fewer blocks per launch).  A Gram matrix of one tile (2 l <= 128) is copied only where a sketch
+    // holds no kept row at all, and the launch ahead costs more than that saves (l = 50: -1.9 %): off
+    // unless MUSED_SWFD_PPT=1 asks for it.
+    const char* pp = getenv("MUSED_SWFD_PPT");
+    const size_t per_block = (size_t)lanes * ell * ell * 8;
+    size_t c = ((size_t)32 << 20) / per_block;
+    c = c > 16 ? 16 : c;
+    const char* pc = getenv("MUSED_SWFD_PPT_CHUNK");
+    if (pc && atoi(pc) >= 1 && (size_t)atoi(pc) < c) c = (size_t)atoi(pc);
+    const bool want = pp ? pp[0] != '0' : h->n2 > 128;
+    if (h->shared && h->gram_split == 1 && want && c >= 1) {
+      MUSED_CHECK_HIP(hipMalloc((void**)&h->ppt, c * per_block));
+      h->ppt_chunk = (int)c;
+    }
+  }
   return MUSED_OK;
 }
 
@@ -1087,7 +1140,7 @@ int mused_swfd_destroy(void* handle) {
   void* bufs[] = {h->buf, h->queue, h->qt, h->meta, h->dropped, h->theta, h->T, h->Wc, h->plan,
                   h->keep_src, h->now_dev, h->stack, h->Wq, h->Bout, h->sig_out, h->qinfo, h->qsel,
                   h->rep, h->pre_in, h->pre_out, h->pre_gram, h->status, h->gpart, h->list, h->offs, h->kact, h->ostat, h->used,
-                  h->pendbuf, h->froze, h->nk0};
+                  h->pendbuf, h->froze, h->nk0, h->ppt};
   for (void* b : bufs) (void)hipFree(b);
   if (h->status_host) (void)hipHostFree(h->status_host);
   delete h;
@@ -1175,6 +1228,9 @@ int mused_swfd_debug_used(void* handle, int* used_out) {
   MUSED_CHECK_HIP(hipMemcpy(used_out, h->used, 4 * (size_t)h->S, hipMemcpyDeviceToHost));
   return 1;
 }
+
+// Diagnostic (not part of the declared ABI): blocks per P P^T launch (Swfd::ppt_chunk); 0: every Gram tile is computed.
+int mused_swfd_debug_ppt(void* handle) { return handle ? ((Swfd*)handle)->ppt_chunk : MUSED_ERR_ARG; }
 
 // Diagnostic (not part of the declared ABI): 1 when the handle keeps its pending rows once per lane (Swfd::shared), else 0.
 int mused_swfd_debug_shared(void* handle) { return handle ? (((Swfd*)handle)->shared ? 1 : 0) : MUSED_ERR_ARG; }
